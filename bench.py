@@ -3,7 +3,7 @@
 postnet; CBHG vocoder excluded) on BASELINE.json configs[1]: GST on, batch 32 per GPU, 128-token
 utterances, Step_Reduction 2, Max_Step 1000, LJSpeech 80-mel hyper-parameters, fp32.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N>1 under a launcher: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...;
      N>1 WITHOUT a launcher: this process starts the N rank processes itself -- before anything touches the GPU -- and exits with
      their status.  A --gpus that disagrees with the launcher's WORLD_SIZE is an error, never a silent 1-rank run.)
@@ -12,6 +12,12 @@ A "step" is one Inference_Step over one synthetic batch per rank (inputs residen
 random-init of the reference architecture, randomness from the on-device Philox generator).
 Utterances shard over ranks with no data-path collective; the only exchange is the final RCCL
 gather of the mels to rank 0, which is inside the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the line.  --full adds
+what takes runs of its own: the per-kernel decode-step timings and the roofline (an event-bracketed graph, replayed
+by the last timed step), the postnet alone, the bf16 drift against fp32 (--mixed), the several-batches-in-flight
+figure and the CPU baseline.  --dump-outputs DIR writes what the last timed step returned (mel, stop, alignment) as
+float32 .npy files; the inputs and seeds depend only on the arguments, so two builds can be compared file by file.
 """
 import argparse
 import ctypes
@@ -39,6 +45,7 @@ MFMA_PEAK_TFLOPS = {"f32": 157.3, "bf16": 2500.0}      # dense MFMA peaks (same 
 MFMA_SUSTAINED_TFLOPS = {"f32": 132.0, "bf16": 1650.0}
 BATCH_PER_GPU = 32
 PROFILE_EVERY = 20             # bracket every 20th decode step's LSTM launches with HIP events
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: above this, a fixed seeded sample of utterance rows is written
 
 
 def host_cpu_info():
@@ -315,6 +322,30 @@ def serving_throughput(hp, w, holder, tok, mels, lens, device_index, B, Tv, Tref
                     "resident weights); `value` is the better of the two".format(streams, B, streams, streams, B * streams)}
 
 
+def dump_outputs(path, arrays, max_bytes=DUMP_MAX_BYTES):
+    """``--dump-outputs``: each array as ``path/<name>.npy`` in float32.  Above ``max_bytes`` in all, every array keeps the same
+    fraction of its rows (utterances), chosen by a fixed seed, so that the files stay comparable from run to run."""
+    os.makedirs(path, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > max_bytes:
+            keep = max(1, int(a.shape[0] * max_bytes / total))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+            print("bench.py: {}.npy holds {} of {} rows (seeded sample: the outputs exceed {} MB)".format(
+                name, keep, host[name].shape[0], max_bytes >> 20), file=sys.stderr, flush=True)
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def finish_line(line, lib_message, fallback_taken, fallback_note):
+    """Rank 0: the library's last message and whether a fallback was taken go on the line, which is printed."""
+    line["library_message"] = lib_message
+    line["fallback_taken"] = fallback_taken
+    if fallback_note:
+        line["fallback_note"] = fallback_note
+    print(json.dumps(line), flush=True)
+
+
 def dry_run(args, overlap):
     """``--dry-run``: the N-rank control flow of this file on CPU ranks -- the launcher environment (or the self-spawned ranks), a gloo
     process group, ``gdist.run_steps`` with the chosen gather ordering around a stand-in for ``Inference_Step`` (a tensor that carries
@@ -381,8 +412,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-serving", action="store_true", help="skip the several-batches-in-flight measurement (N = 1 only)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: per-kernel decode-step timings and "
+                    "the roofline, the postnet alone, the bf16 drift (--mixed), the serving figure and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned (mel, stop, alignment) "
+                    "as DIR/<name>.npy, float32; above 64 MB in all, a fixed seeded sample of utterance rows")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-serving", action="store_true", help="--full: skip the several-batches-in-flight measurement (N = 1 only)")
     ap.add_argument("--mixed", action="store_true", help="Use_Mixed_Precision: bf16 GEMM operands, fp32 accumulation (BASELINE "
                     "configs[4]); NOT the headline metric -- dtype is then reported as bf16")
     ap.add_argument("--batch-per-gpu", type=int, default=BATCH_PER_GPU, help="utterances per GPU (default 32 = the headline "
@@ -396,7 +431,7 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help="CPU ranks, gloo, a stand-in for the model: exercises the launcher, the process group, the "
                     "step / gather ordering, the give-up all-reduce and the line's assembly without a GPU (tests/test_host.py); the line carries "
                     "dry_run: true and no measurement")
-    ap.add_argument("--cpu-seconds", type=float, default=25.0, help="wall-time budget of the bounded CPU-baseline sample (both thread counts)")
+    ap.add_argument("--cpu-seconds", type=float, default=25.0, help="--full: wall-time budget of the bounded CPU-baseline sample (both thread counts)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
@@ -435,26 +470,32 @@ def main():
     mels = torch.as_tensor(inputs["mels_for_gst"]).to(dev)
     lens = torch.as_tensor(inputs["mel_lengths_for_gst"]).to(dev)
     n_total = B * world
+    last_i = args.warmup + args.steps - 1
+    kept = {}                                      # the last timed step's local stop / alignment (--dump-outputs)
 
     def one_step(i):
         # dropout / noise streams are indexed by the LOCAL utterance index: fold the rank into the seed so that shards
         # do not draw identical randomness
         mel, stop, _, align = model.Inference_Step(tok, None, None, mels, lens, seed=(1000 + i) * world + rank)
+        if i == last_i:
+            kept["stop"], kept["alignment"] = stop, align
         # the gather runs on RCCL's stream behind this batch's compute; its result is claimed one step later, so that the
         # next batch's kernels are enqueued behind this batch's COMPUTE, not behind its gather (N = 1: no collective at all)
         return gdist.gather_to_root(mel, n_total=n_total, async_op=True)
 
-    # Two cached graphs: the plain one, and one whose decode launches are bracketed by event-record nodes on every
+    # --full: two cached graphs, the plain one and one whose decode launches are bracketed by event-record nodes on every
     # PROFILE_EVERY-th step.  Only the LAST timed step replays the bracketed graph (each bracket costs ~2.5 us, 200 of
-    # them ~2 % of a step), so the kernel timings come from inside the timed region at 1/K of that cost.
+    # them ~2 % of a step), so the kernel timings come from inside the timed region at 1/K of that cost.  A plain run
+    # replays the plain graph only.
     def set_prof(on):
         model.ctx.check(lib.gsttaco_set_profiling(handle, PROFILE_EVERY if on else 0))
 
     def timed_run():
         """Warm-up + the timed region; returns the elapsed seconds (the clock stops after every gather has completed)."""
-        set_prof(True)
-        one_step(-1).result()                      # capture + first replay of the bracketed graph (untimed, extra)
-        set_prof(False)
+        if args.full:
+            set_prof(True)
+            one_step(-1).result()                  # capture + first replay of the bracketed graph (untimed, extra)
+            set_prof(False)
         for i in range(args.warmup):
             one_step(i).result()
         if args.warmup == 0:
@@ -466,7 +507,7 @@ def main():
         t0 = time.perf_counter()
 
         def timed_step(i):
-            if i == args.warmup + args.steps - 1:
+            if args.full and i == last_i:
                 set_prof(True)
             return one_step(i)
         # (gather ordering: gdist.run_steps -- N > 1 claims batch i's gather before batch i + 1 is enqueued unless --overlap-gather 1)
@@ -507,6 +548,44 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    line = None
+    if rank == 0:
+        assert out is not None and tuple(out.shape) == (n_total, model.dims.steps * model.dims.r, model.dims.mel)
+        assert bool(torch.isfinite(out).all())
+        if args.dump_outputs:
+            # what rank 0's caller of the timed path received in the last timed step: the gathered mels, its own stop logits and alignments
+            dump_outputs(args.dump_outputs, {"mel": out, "stop": kept["stop"], "alignment": kept["alignment"]})
+        frames = n_total * model.dims.max_step * args.steps
+        line = {
+            "metric": "mel-frames/s", "value": frames / elapsed, "unit": "mel-frames/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "bf16" if args.mixed else "f32", "data": "synthetic",
+            # what the dtype's arithmetic runs on: since round 6 the fp32 path's Winograd-domain GEMMs (postnet, encoder) and tall plain GEMMs run on the
+            # bf16 matrix pipe as split-bf16 x6 (three bf16 planes per fp32 operand, six plane products, fp32 accumulation: the fp32 MFMA
+            # chain's accuracy -- tools/split_bf16.hip, profiles/r06_split_bf16.txt); everything else of the fp32 path on fp32 MFMA / VALU
+            "arith": ("bf16 operands, fp32 accumulate (Use_Mixed_Precision)" if args.mixed else
+                      "fp32; the decode step on fp32 MFMA / VALU; the tall GEMMs around it (five-tap Conv1D layers of the postnet and the encoder as Winograd, "
+                      "BiLSTM input halves, Value projection) as split-bf16 x6 on the bf16 matrix pipe, fp32 accumulate"
+                      if os.environ.get("GSTTACO_WINO_SPLIT", "1") != "0" else "fp32"),
+            "config": {"workload": ("" if args.batch_per_gpu == BATCH_PER_GPU and not args.mixed else "NOT THE HEADLINE CONFIGURATION -- ") +
+                                   "BASELINE configs[1]: GST on, batch {} per GPU, 128-token utterances, ".format(args.batch_per_gpu) +
+                                   "Step_Reduction 2, Max_Step 1000, LJSpeech 80-mel hparams; whole Inference_Step "
+                                   "(encoder+GST+decode+postnet, vocoder excluded)",
+                       "global_batch": n_total, "tokens": Tv, "ref_frames": Tref1 - 1,
+                       "parallelism": "utterance-sharded x{} + final RCCL gather".format(world),
+                       "gather": ("none (one rank)" if world == 1 else "overlapped with the next batch's compute (--overlap-gather 1)" if overlap else
+                                  "claimed before the next batch is enqueued (safe by construction: a persistent decode launch never meets a resident receive kernel)")},
+        }
+    if not args.full:
+        if rank == 0:
+            finish_line(line, lib_message, fallback_taken, fallback_note)
+        if world > 1:
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
+        return 0
+
+    # --full from here on.
     # per-kernel timing of the decode step: HIP event-record nodes inside the replayed graph (on the stream the
     # kernels run on), every PROFILE_EVERY-th decode step of the last timed replay
     big = B > 32            # batches above 32 rows run the multi-chunk kernels (weights resident over the chunks)
@@ -609,9 +688,6 @@ def main():
                             "`frac_direct_equivalent` the direct form's (can exceed 1 for a Winograd kernel)"}
 
     if rank == 0:
-        assert out is not None and tuple(out.shape) == (n_total, model.dims.steps * model.dims.r, model.dims.mel)
-        assert bool(torch.isfinite(out).all())
-        frames = n_total * model.dims.max_step * args.steps
         dom = max(prof, key=lambda k: prof[k][0])          # dominant = largest share of the decode step
         ms1, cnt1, bytes1 = prof[dom]
         achieved_in_run = (bytes1 / (ms1 * 1e-3)) / 1e9 if ms1 > 0 else 0.0
@@ -654,26 +730,7 @@ def main():
         else:
             achieved, peak, unit = bytes1 / (dur_us * 1e-6) / 1e9, HBM_PEAK_GBS, "GB/s"
             achieved_raw = achieved_in_run
-        line = {
-            "metric": "mel-frames/s", "value": frames / elapsed, "unit": "mel-frames/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "bf16" if args.mixed else "f32", "data": "synthetic",
-            # what the dtype's arithmetic runs on: since round 6 the fp32 path's Winograd-domain GEMMs (postnet, encoder) and tall plain GEMMs run on the
-            # bf16 matrix pipe as split-bf16 x6 (three bf16 planes per fp32 operand, six plane products, fp32 accumulation: the fp32 MFMA
-            # chain's accuracy -- tools/split_bf16.hip, profiles/r06_split_bf16.txt); everything else of the fp32 path on fp32 MFMA / VALU
-            "arith": ("bf16 operands, fp32 accumulate (Use_Mixed_Precision)" if args.mixed else
-                      "fp32; the decode step on fp32 MFMA / VALU; the tall GEMMs around it (five-tap Conv1D layers of the postnet and the encoder as Winograd, "
-                      "BiLSTM input halves, Value projection) as split-bf16 x6 on the bf16 matrix pipe, fp32 accumulate"
-                      if os.environ.get("GSTTACO_WINO_SPLIT", "1") != "0" else "fp32"),
-            "config": {"workload": ("" if args.batch_per_gpu == BATCH_PER_GPU and not args.mixed else "NOT THE HEADLINE CONFIGURATION -- ") +
-                                   "BASELINE configs[1]: GST on, batch {} per GPU, 128-token utterances, ".format(args.batch_per_gpu) +
-                                   "Step_Reduction 2, Max_Step 1000, LJSpeech 80-mel hparams; whole Inference_Step "
-                                   "(encoder+GST+decode+postnet, vocoder excluded)",
-                       "global_batch": n_total, "tokens": Tv, "ref_frames": Tref1 - 1,
-                       "parallelism": "utterance-sharded x{} + final RCCL gather".format(world),
-                       "gather": ("none (one rank)" if world == 1 else "overlapped with the next batch's compute (--overlap-gather 1)" if overlap else
-                                  "claimed before the next batch is enqueued (safe by construction: a persistent decode launch never meets a resident receive kernel)")},
+        line.update({
             "roofline": {"bound": step_bound, "kernel": KNAMES[dom],
                          "achieved": achieved, "peak": peak, "unit": unit, "frac": achieved / peak,
                          "frac_basis": ("measured live in this run: HIP event-record nodes inside the replayed graph around the ONE persistent launch of the last timed "
@@ -730,7 +787,7 @@ def main():
                                                                       "compulsory_bytes_per_launch": persistent_compulsory_bytes(model.dims, B, Tv, args.mixed, n_steps_dec)}
                                                                      if persistent else {}))
                                                      for k in prof}}},
-        }
+        })
         if args.mixed:
             # what the mode costs in accuracy, MEASURED on this run's inputs: the same batch, weights and seed (same keep decisions and noise)
             # through an fp32 context; mel max-abs / mean-abs difference after the postnet, on the +-4 mel range.  (BASELINE configs[4]'s
@@ -756,11 +813,7 @@ def main():
             line["serving"] = serving_throughput(hp, w, holder, tok, mels, lens, local_rank, B, Tv, Tref1)
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(hp, w, inputs, args.cpu_seconds)
-        line["library_message"] = lib_message
-        line["fallback_taken"] = fallback_taken
-        if fallback_note:
-            line["fallback_note"] = fallback_note
-        print(json.dumps(line), flush=True)
+        finish_line(line, lib_message, fallback_taken, fallback_note)
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()

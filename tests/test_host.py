@@ -293,6 +293,30 @@ def test_bench_prices_the_decode_step_at_the_surveys_bytes():
     assert w < comp < 500 * total / 50
 
 
+def test_bench_dump_outputs_writes_float32_and_a_seeded_sample_above_the_cap(tmp_path):
+    """`bench.py --dump-outputs DIR`: each array as DIR/<name>.npy in float32 with its values; above the size cap every array keeps
+    the same fraction of its rows, the same rows from call to call, and the files stay within the cap."""
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(0)
+    arrays = {"mel": torch.randn(16, 10, 4, generator=g), "stop": torch.randn(16, 5, generator=g, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    for name, v in arrays.items():
+        a = np.load(tmp_path / "all" / (name + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, v.float().numpy())
+    cap = (16 * 10 * 4 + 16 * 5) * 4 // 2
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays, max_bytes=cap)
+    got = {name: np.load(tmp_path / "a" / (name + ".npy")) for name in arrays}
+    assert sum(a.nbytes for a in got.values()) <= cap and got["mel"].shape[0] == got["stop"].shape[0] == 8
+    full = arrays["mel"].numpy()
+    rows = [i for r in got["mel"] for i in range(16) if np.array_equal(full[i], r)]
+    assert rows == sorted(set(rows)) and len(rows) == 8
+    np.testing.assert_array_equal(got["stop"], arrays["stop"].float().numpy()[rows])
+    for name in arrays:
+        assert np.array_equal(got[name], np.load(tmp_path / "b" / (name + ".npy")))
+
+
 def test_run_steps_claims_each_gather_before_the_next_batch_unless_told_to_overlap():
     """N > 1 default of bench.py (gst_tacotron_amd.distributed.run_steps): batch i's gather is claimed BEFORE batch i + 1 is enqueued,
     so a persistent decode launch (256 workgroups that must all be resident) is stream-ordered behind the previous gather and can

@@ -4,7 +4,7 @@
 N=$1; ARGS=$2; shift 2
 for i in $(seq 1 $N); do
   for cfg in "$@"; do
-    env $cfg python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-serving $ARGS 2>/dev/null | python -c "
+    env $cfg python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-serving $ARGS 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 k = d['roofline']['decode_step']['kernels']

@@ -7,7 +7,7 @@ run() { # label, env..., -- bench args
     local label=$1; shift
     local envs=()
     while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-    env "${envs[@]}" python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-serving "$@" 2>/dev/null | python -c "
+    env "${envs[@]}" python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-serving "$@" 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 k = d['roofline']['decode_step']['kernels']

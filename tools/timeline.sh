@@ -4,7 +4,7 @@
 TAG=${1:-t}; shift
 cd "${GRAFT_REPO_ROOT:-.}"; export TMPDIR=/tmp
 OUT=gpurun_out/timeline_$TAG; rm -rf "$OUT"; mkdir -p "$OUT"
-rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d "$OUT/trace" -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-serving "$@" > "$OUT/bench.log" 2>&1
+rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d "$OUT/trace" -- python3 bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-serving "$@" > "$OUT/bench.log" 2>&1
 python3 - "$OUT" "$TAG" <<'PY'
 import csv, glob, os, sys
 out, tag = sys.argv[1], sys.argv[2]
