@@ -50,11 +50,7 @@ def _stale(target, deps):
 LAST_BUILD = {"compiled": [], "linked": False, "mode": "not run"}     # what the last build() call actually did (reported by __graft_entry__.build)
 
 
-def build(force=False, verbose=False, debug=False):
-    """debug=True adds -DGSTTACO_DEBUG: the experiment knobs are compiled in.  Never the default."""
-    global FLAGS
-    if debug and "-DGSTTACO_DEBUG" not in FLAGS:
-        FLAGS = FLAGS + ["-DGSTTACO_DEBUG"]
+def build(force=False, verbose=False):
     os.makedirs(LIBDIR, exist_ok=True)
     hdrs = _headers()
     if _flags_changed():
@@ -109,4 +105,4 @@ def describe():
 
 
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv, verbose=True, debug="--debug" in sys.argv))
+    print(build(force="--force" in sys.argv, verbose=True))

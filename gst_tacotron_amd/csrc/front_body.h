@@ -74,9 +74,8 @@ __device__ __forceinline__ void gemv_store(const GemvPlan& p, int N, const float
 // Jobs are groups of up to WT adjacent tiles of one layer sharing one pass over that layer's state (skinny_body.h).
 template <int LEAN>
 __device__ __forceinline__ void front_worker(const DecFrontArgs& P, float* smem, const int slot) {
-    const int wt = P.worker_tiles == 1 ? 1 : WT;
-    const int j0 = (P.rec_end[0] - P.rec_begin[0] + wt - 1) / wt;
-    const int total = j0 + (P.rec_end[1] - P.rec_begin[1] + wt - 1) / wt;
+    const int j0 = (P.rec_end[0] - P.rec_begin[0] + WT - 1) / WT;
+    const int total = j0 + (P.rec_end[1] - P.rec_begin[1] + WT - 1) / WT;
     const int mchunks = (P.B + 31) / 32;
     const int wslot = slot == 0 ? 8 : ((int)blockIdx.x == (int)gridDim.x - 1 ? 10 : -1);   // diagnostics
     if (P.dbg && wslot >= 0 && threadIdx.x == 0) P.dbg[wslot] = __builtin_amdgcn_s_memrealtime();
@@ -86,8 +85,8 @@ __device__ __forceinline__ void front_worker(const DecFrontArgs& P, float* smem,
         // [pf, pf + ne); utterance workgroups that have finished their chain take pieces of `y` chunks of jobs [pf + ne, total).
         auto run = [&](const int job, const int c0, const int c1) {
             const int layer = job < j0 ? 0 : 1;
-            const int tile = P.rec_begin[layer] + (layer == 0 ? job : job - j0) * wt;
-            const int ntile = min(wt, P.rec_end[layer] - tile);
+            const int tile = P.rec_begin[layer] + (layer == 0 ? job : job - j0) * WT;
+            const int ntile = min(WT, P.rec_end[layer] - tile);
             if (LEAN == 2) gt_lean_partial_mc<FT / 64, 2, WT, true>(P.lrec[layer], tile, ntile, c0, c1, smem);
             else gt_lean_partial_mc<FT / 64, 4, WT>(P.lrec[layer], tile, ntile, c0, c1, smem);
             __syncthreads();
@@ -109,8 +108,8 @@ __device__ __forceinline__ void front_worker(const DecFrontArgs& P, float* smem,
     } else {
         for (int job = slot; job < total; job += P.n_workers) {
             const int layer = job < j0 ? 0 : 1;
-            const int tile = P.rec_begin[layer] + (layer == 0 ? job : job - j0) * wt;
-            const int ntile = min(wt, P.rec_end[layer] - tile);
+            const int tile = P.rec_begin[layer] + (layer == 0 ? job : job - j0) * WT;
+            const int ntile = min(WT, P.rec_end[layer] - tile);
             for (int mc = 0; mc < mchunks; ++mc) {
                 if (LEAN == 2) gt_lean_partial<FT / 64, 2, WT, true>(P.lrec[layer], tile, ntile, mc, smem);
                 else if (LEAN == 1) gt_lean_partial<FT / 64, 4, WT>(P.lrec[layer], tile, ntile, mc, smem);

@@ -116,9 +116,7 @@ struct gsttaco_ctx {
     // EXPERIMENTS round 3, item 2b)
     hipStream_t side_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int gst_fork = 1;            // GSTTACO_GST_FORK (default 1 since round 6): 1 = forked inside the captured encoder graph, 2 = its own graph on the side stream beside the
-                                 // encoder's convolution graph, joined in front of the BiLSTM graph
-    int enc_part = 0;            // (mode 2) which part of the encoder segment is being enqueued: 0 all, 1 up to the hoisted GEMM, 2 the BiLSTM
+    bool gst_fork = true;        // GSTTACO_GST_FORK (default 1 since round 6): the GST branch forked inside the captured encoder graph
     bool masks_lazy = false;     // the last decode did not write the keep-mask tensor (hashed decisions): gsttaco_debug_randomness regenerates it
 
     // weights on device
@@ -149,7 +147,6 @@ struct gsttaco_ctx {
     bool persist_decode = true;  // the whole decode loop as ONE persistent launch where it applies (GSTTACO_PERSIST_DECODE=0: launches)
     bool persist_now = false;    // ... for the call being enqueued (one live context, as fuse12_now)
     int persist_rows = 128;      // ... for batches up to this many rows (GSTTACO_PERSIST_ROWS; 32: the one-group kernel only)
-    int persist_split16 = 0;     // GSTTACO_PERSIST_SPLIT16=1: 17..32 rows as two groups of 16 through the group kernel (experiment)
     int persist_slots = 0;       // workgroups of gt_persist_decode_kernel the device holds at once
     uint64_t n_persist_decodes = 0;      // persistent decode launches enqueued (eagerly or into a captured graph)
     float* w_xa2 = nullptr; uint2* w_z0g = nullptr; float* w_hpart = nullptr; uint32_t* w_pctl = nullptr;    // its workspace
@@ -157,12 +154,6 @@ struct gsttaco_ctx {
     int fuse12_slots[3] = {0, 0, 0};    // workgroups of gt_lstm12_kernel / gt_lstm12_mc_kernel fp32 / bf16 the device holds at once (occupancy x CUs)
     bool counted = false;        // this context is included in g_live_contexts
     uint64_t n_persist_enqueued = 0;     // persistent BiLSTM launches enqueued (eagerly or into a captured graph)
-    bool split_rec = true;       // recurrent halves of the decode LSTMs computed beside the front end / projection (GSTTACO_DEBUG: SPLIT_REC=0)
-    int keep_x_weights = 1;
-    int co_tiles = -1;           // layer-2 recurrent tiles computed beside the projection (the rest beside the front end); -1 = by batch size
-    int worker_tiles = 2;        // tiles per worker job in the front launch (2: pairs sharing one activation pass)
-    int co_worker_tiles = 1;     // the same for the projection launch's workers
-    int proj_both_m = 0;         // projection launch at 17..32 rows: one workgroup per tile over both M-tiles (GSTTACO_PROJ_BOTH_M, debug builds)
     int wino = 4;                // Winograd for the 5-tap Conv1D layers that fill the chip: 4 = F(4,5) where its grid fills the chip and F(2,5)
                                  // otherwise, 2 = F(2,5) only, 0 = implicit GEMM only (GSTTACO_WINO)
     bool wino_x3 = false;        // GSTTACO_WINO_SPLIT=3: the postnet's split kernel with two planes and three products (~2^-16; NOT fp32-accurate)
@@ -171,20 +162,17 @@ struct gsttaco_ctx {
     int enc_wino = 2;            // the text encoder's five-tap layers behind the token gather on the split-bf16 Winograd kernel (GSTTACO_ENC_WINO)
     bool pad_dec = true;         // a decoder smaller than the reference's is zero-padded up to it (pad_decoder; GSTTACO_PAD_DECODER=0: its own sizes)
     bool bilstm_persist = true;  // one persistent launch per BiLSTM instead of one per time step (GSTTACO_BILSTM_PERSIST=0: per step)
-    bool keep_hash = true;       // throughput mode: hashed keep decisions, dropped weight rows not requested (GSTTACO_DEBUG: KEEP_HASH=0)
     bool fuse12 = true;          // both decode LSTM cells in one launch with an in-kernel hand-off (GSTTACO_FUSED_LSTM=0: two launches)
     bool fuse12_now = false;     // ... for the call being enqueued: fuse12 and this is the process's only live context
     uint32_t* w_arrive = nullptr;    // [steps_max][8 x 32] arrival counters of the fused launch, zeroed at the start of every decode
     int debug_drop_member = -1;  // fault injection (gsttaco_debug_raise_handoff_error): a member of the next persistent launches never shows up
     mutable std::string warn;    // last warning (a recovered condition): readable through gsttaco_last_error until the next error
     bool lean = true;            // lean_body.h kernels for the decode shapes they cover (GSTTACO_LEAN=0: general kernels only)
-    double sched_unit[2] = {5.8, 3.4}, sched_chain = 9.5;     // plan_front_jobs cost model (us): fp32 / bf16 unit, chain
 
     float *pw0 = nullptr, *pb0 = nullptr, *pw1 = nullptr, *pb1 = nullptr, *pwq = nullptr, *pbq = nullptr;  // plain layouts (fused front)
     bool fused_front = true;
     int front_mode = 2;         // GSTTACO_FUSED_FRONT: 0 = four-kernel front end, 1 = the general fused kernel, 2 = + the lean utterance path
-    bool fuse_prenet0 = true;   // prenet-0 pre-activations computed by the previous step's projection launch (GSTTACO_DEBUG: FUSE_PRENET0=0)
-    PackedLinear proj_z;        // projection columns | padding to a tile | (Wp_last . W0) columns
+    PackedLinear proj_z;        // projection columns | padding to a tile | (Wp_last . W0) columns: prenet 0 rides in the projection launch
     int z_col0 = 0;
     float* w_z0 = nullptr;
     float *val_enc_w = nullptr, *val_bias = nullptr, *att_v = nullptr, *att_sb = nullptr;
@@ -515,10 +503,6 @@ hipError_t launch_skinny(gsttaco_ctx* c, int epi, SkinnyArgs a0, const SkinnyArg
     return gt_launch_skinny(epi, a0, a1, ntiles, s, tag);
 }
 
-hipError_t launch_skinny_co(gsttaco_ctx* c, SkinnyArgs m, int ntiles, SkinnyArgs co, int co_begin, int co_end, hipStream_t s) {
-    return gt_launch_skinny_co(m, ntiles, co, co_begin, co_end, c->co_worker_tiles, s);
-}
-
 // Fold inference BatchNorm into y = x*scale + shift (Appendix A.4).
 void fold_bn(const gsttaco_ctx* c, const std::string& prefix, std::vector<float>& scale, std::vector<float>& shift) {
     const auto& g = T(c, prefix + ".bn.gamma").data;
@@ -811,9 +795,8 @@ int enqueue_lean_bilstm(gsttaco_ctx* c, hipStream_t s, const gsttaco_ctx::LeanBi
     a.out = L.z; a.ldo = 8 * H;
     a.B = B; a.T = Tn; a.Cin = L.C; a.N = 8 * H; a.taps = 1; a.pad_before = 0; a.act = ACT_NONE;
     a.gemm_s = L.xw_s; a.wino_npad = L.xw_npad;         // (round 6: on the bf16 matrix pipe as split-bf16 x6 where the grid allows)
-    if (c->enc_part != 2) HIPCHECK(c, launch_conv(c, a, s));
+    HIPCHECK(c, launch_conv(c, a, s));
     if (join) HIPCHECK(c, hipStreamWaitEvent(s, join, 0));
-    if (c->enc_part == 1) return 0;
     // One persistent launch for the whole sequence, one (direction, 16 utterances) group per XCD (skinny_gemm.hip
     // gt_bilstm_persist_kernel; same arithmetic, bitwise the same outputs); GSTTACO_BILSTM_PERSIST=0 keeps the launch per step.
     if (L.ph && c->bilstm_persist && gt_bilstm_persist_supported(H, std::min(B, 64), c->n_cu)) {
@@ -859,9 +842,6 @@ int enqueue_encoder(gsttaco_ctx* c, hipStream_t s, int B, int Tv, bool masked, i
     const float* x = c->d_emb;
     const int32_t* tok = c->w_tokens;
     int cur = 0;
-    if (c->enc_part == 2) {         // (the convolutions ran in their own graph: their output is where n_enc_conv layers leave it)
-        if (g.n_enc_conv > 0) { x = c->w_act[(g.n_enc_conv - 1) & 1]; tok = nullptr; }
-    } else
     if (gst_Tref1 > 0) {
         HIPCHECK(c, hipEventRecord(c->ev_fork, s));
         HIPCHECK(c, hipStreamWaitEvent(c->side_stream, c->ev_fork, 0));
@@ -877,15 +857,15 @@ int enqueue_encoder(gsttaco_ctx* c, hipStream_t s, int B, int Tv, bool masked, i
     struct JoinGuard {      // an error return between the fork and the join below still joins the side stream
         gsttaco_ctx* c; hipStream_t s; bool armed;
         ~JoinGuard() { if (armed) (void)hipStreamWaitEvent(s, c->ev_join, 0); }
-    } join_guard{c, s, gst_Tref1 > 0 && c->enc_part == 0};
+    } join_guard{c, s, gst_Tref1 > 0};
     // (round 6) the embedding lookup as rows in memory when the first convolution can then take the Winograd kernel on the bf16 pipe
     // (it resolves the lookup inside its gather only as an implicit GEMM: 140 us against ~90 for lookup + Winograd at 4 096 rows)
-    if (c->enc_part != 2 && g.n_enc_conv > 0 && c->enc_wino && c->enc_conv[0].wino_s && tok && c->enc_conv[0].cin == g.emb &&
+    if (g.n_enc_conv > 0 && c->enc_wino && c->enc_conv[0].wino_s && tok && c->enc_conv[0].cin == g.emb &&
         (B * ((Tv + 1) / 2) + 63) / 64 * ((c->enc_conv[0].cout + 127) / 128) >= 100) {
         HIPCHECK(c, gt_launch_embed_rows(c->d_emb, tok, c->w_act[1], B * Tv, g.emb, s));
         x = c->w_act[1]; tok = nullptr;
     }
-    for (int i = 0; i < g.n_enc_conv && c->enc_part != 2; ++i) {
+    for (int i = 0; i < g.n_enc_conv; ++i) {
         const ConvLayer& L = c->enc_conv[i];
         ConvGemmArgs a{};
         a.x = x; a.tokens = tok; a.w = L.w; a.scale = L.scale; a.shift = L.shift;
@@ -912,10 +892,10 @@ int enqueue_encoder(gsttaco_ctx* c, hipStream_t s, int B, int Tv, bool masked, i
     // (joining BEHIND the BiLSTM instead measured 10.83-10.86 against 10.85-10.89 ms per Inference_Step: not worth GST kernels lingering
     // beside a launch that needs its members co-resident)
     const bool lean_enc = lean_bilstm_usable(c, c->enc_lean, B);
-    const bool join_here = gst_Tref1 > 0 && c->enc_part == 0;
+    const bool join_here = gst_Tref1 > 0;
     // (the lean BiLSTM joins behind its hoisted GEMM, see enqueue_lean_bilstm; the guard covers its error returns in front of that)
     if (join_here && !lean_enc) { join_guard.armed = false; HIPCHECK(c, hipStreamWaitEvent(s, c->ev_join, 0)); }
-    if (c->enc_part != 2) HIPCHECK(c, gt_launch_zero(c->w_cenc, (size_t)2 * B * H, s));
+    HIPCHECK(c, gt_launch_zero(c->w_cenc, (size_t)2 * B * H, s));
     if (lean_enc) {
         const int rl = enqueue_lean_bilstm(c, s, c->enc_lean, x, B, Tv, c->w_cenc, c->w_enc, tlen, join_here ? c->ev_join : nullptr);
         if (!rl) join_guard.armed = false;          // (joined inside)
@@ -1018,8 +998,8 @@ int enqueue_value_proj(gsttaco_ctx* c, hipStream_t s, int B, int Tv) {
 // workgroup's prenet / attention chain (measured on MI355X with in-kernel stamps: 5.8 / 3.4 us per unit in fp32 / bf16 -- fp32
 // MFMA-bound at the ~2.0 GHz the chip sustains, bf16 bound by the CU's load pipe -- and 9.5 us per chain).
 struct FrontSched { int pf, ne, e, y, utt; };
-FrontSched plan_front_jobs(const gsttaco_ctx* c, int jobs, int chunks, int n_workers, int B, bool bf16) {
-    const double unit = c->sched_unit[bf16 ? 1 : 0], chain = c->sched_chain;
+FrontSched plan_front_jobs(int jobs, int chunks, int n_workers, int B, bool bf16) {
+    const double unit = bf16 ? 3.4 : 5.8, chain = 9.5;
     FrontSched best{jobs, 0, 0, 0, 0};
     double best_t = 1e30;
     for (int y = 0; y <= chunks; ++y) {
@@ -1040,351 +1020,371 @@ FrontSched plan_front_jobs(const gsttaco_ctx* c, int jobs, int chunks, int n_wor
     return best;
 }
 
-// the fused front end (dec_front.hip; dec_front_lsa.hip for the LSA extension, whose operands share its LDS) takes this shape
-static bool front_fits(const gsttaco_ctx* c, int Tv) {
+// Every launch-form question of one decode, answered in one place: enqueue_decode launches what the plan says, and
+// gsttaco_decode_plan, gsttaco_lstm_launch_bytes and masks_lazy report it.  `persist` and `fuse12` also depend on the per-call
+// persist_now / fuse12_now (run_cached), so they mean something only while a decode is being enqueued; no other field does.
+struct DecodePlan {
+    bool persist = false;         // the whole loop as ONE persistent launch (persist_decode.hip) ...
+    bool persist_bf16 = false;    // ... its bf16 kernel (mixed precision)
+    bool fused = false;           // fused front launch (dec_front.hip; dec_front_lsa.hip for LSA), whose worker workgroups compute the
+                                  // recurrent halves of both decode LSTMs; else the four-kernel front end and whole LSTM GEMMs
+    bool lean_front = false;      // ... its lean utterance path (front_lean.h)
+    int n_workers = 0;            // ... its worker workgroups: one per CU the utterance workgroups leave free (a quarter of the chip at least)
+    int lean_rec = 0;             // ... their body: 0 general, 1 lean fp32, 2 lean bf16
+    bool z0 = false;              // prenet-0 pre-activations computed by the previous step's projection launch (proj_z)
+    int fuse12 = 0;               // both LSTM cells in one launch: 0 no, 1 gt_lstm12_kernel (fp32, <= 32 rows), 2 the multi-chunk form
+    bool lean_x[2] = {false, false};  // otherwise LSTM layer l's input half on the lean kernel (gt_launch_lstm_x)
+    int co_tiles = 0;             // layer-2 recurrent tiles computed beside the projection (the rest beside the front end)
+    bool lean_proj = false;       // ... that projection launch on the lean kernel (gt_launch_proj_lean), else gt_launch_skinny_co
+    bool mirror = false;          // bf16 mirrors of the blocked activations (mixed precision above 32 rows)
+    bool hashed = false;          // keep decisions hashed from the seed (throughput mode at the reference's rate 0.5) ...
+    bool masks_unused = false;    // ... and no launch reads the keep-mask tensor
+};
+
+DecodePlan plan_decode(const gsttaco_ctx* c, int B, int Tv, bool injected_mask) {
     const gsttaco_config& g = c->cfg;
     const bool lsa = g.att_type == GSTTACO_ATT_LSA;
-    return gt_dec_front_supported(g.mel_dim, c->P0, c->P1, c->att, Tv, lsa ? g.loc_filters : 0, lsa ? g.loc_kernel : 0);
-}
-
-// throughput mode at the reference's dropout rate on a fused front end: nobody reads the keep-mask tensor (see enqueue_decode)
-bool masks_unused(const gsttaco_ctx* c, int Tv, bool injected) {
-    const gsttaco_config& g = c->cfg;
-    return !injected && g.prenet_rate == 0.5f && c->keep_hash && c->fused_front && front_fits(c, Tv);
-}
-
-int enqueue_decode(gsttaco_ctx* c, hipStream_t s, int B, int Tv, int steps, bool has_mask, bool has_noise, bool masked) {
-    const int32_t* tlen = masked ? c->w_tok_len : nullptr;
-    const gsttaco_config& g = c->cfg;
-    const int mel = g.mel_dim, r = c->r, P0 = c->P0, P1 = c->P1, att = c->att, H1 = c->H1, H2 = c->H2;
-    const int XA = P1 + att;
-    const int MT = (B + 15) / 16;
-    const size_t BLK = (size_t)MT * 256;        // floats per k-block of a blocked activation buffer
-    const int64_t ld_pre = (int64_t)steps * r * mel;
-    // ---- the whole loop as ONE persistent launch (persist_decode.hip): fp32, batch <= 128 (above 32 rows: groups of 32 through one set of
-    // resident weights), T_v <= 256, the reference's decoder sizes, SMA / BMA -- while this is the process's only live context (its
-    // hand-offs need every workgroup resident).  Bitwise the launches below (GPU test), which stay the path for every other shape, for
-    // several contexts, and after a give-up.  It keeps its state in registers and initialises it itself: none of the launch path's
-    // zero-fill launches (and their boundaries) is enqueued for it.
-    // (mixed precision: the bf16 kernel -- every GEMM pack bf16, the activation mirrors allocated, one group of up to 64 rows)
-    const int n_bf16 = c->lstm_x[0].bf16 + c->lstm_x[1].bf16 + c->lstm_h[0].bf16 + c->lstm_h[1].bf16 + c->proj_z.bf16;
-    const bool persist_bf16 = n_bf16 == 5 && c->w_xa_h && c->w_xa2_h && c->w_h1_h[0] && c->w_h2_h[0];
-    // (ONE effective value for the host's eligibility check and the launcher's kernel choice: the experiment's two groups of 16 never
-    // apply to LSA or mixed precision, which always take their one-group kernels)
-    const int split16_eff = (c->persist_split16 && g.att_type != GSTTACO_ATT_LSA && !persist_bf16) ? 1 : 0;
-    const bool persist_base = c->persist_now && c->fused_front && c->split_rec && c->lean && c->keep_x_weights && c->front_mode >= 2 &&
-                              (n_bf16 == 0 || persist_bf16) && c->proj_z.wp != nullptr && c->proj.nkb >= 32 &&
-                              c->worker_tiles == 2 && c->co_worker_tiles == 1 &&
-                              // (the LSA extension: the one-group fp32 kernel's LSA chain, up to 128 tokens -- else the launch path)
-                              (g.att_type != GSTTACO_ATT_LSA || (n_bf16 == 0 && c->loc_pack && gt_persist_decode_lsa_fits(B, Tv, g.loc_filters, g.loc_kernel))) &&
-                              front_fits(c, Tv) && c->lstm_x[0].nkb == 24 && c->lstm_x[1].nkb == 64 && c->lstm_h[0].nkb == 64 &&
-                              c->lstm_h[1].nkb == 64 && B <= c->persist_rows && (B <= 16 || !split16_eff || c->w_stash) && (B <= 32 || c->w_stash) &&
-                              gt_persist_decode_supported(mel, r, P0, P1, att, H1, H2, B, Tv, c->proj_z.ntiles, c->proj_z.nkb, c->persist_slots, split16_eff,
-                                                          persist_bf16 ? 1 : 0);
-    if (!persist_base) {
-        HIPCHECK(c, gt_launch_zero(c->w_h1[1], (size_t)MT * 16 * H1, s));
-        HIPCHECK(c, gt_launch_zero(c->w_h2[1], (size_t)MT * 16 * H2, s));
-        HIPCHECK(c, gt_launch_zero(c->w_c1, (size_t)B * H1, s));
-        HIPCHECK(c, gt_launch_zero(c->w_c2, (size_t)B * H2, s));
-    }
+    const PackedLinear *X = c->lstm_x, *R = c->lstm_h;
+    DecodePlan p;
+    p.fused = c->fused_front && gt_dec_front_supported(g.mel_dim, c->P0, c->P1, c->att, Tv, lsa ? g.loc_filters : 0, lsa ? g.loc_kernel : 0);
+    p.hashed = !injected_mask && g.prenet_rate == 0.5f;
+    // (at rate 0.5 every fused front end derives the keep decisions from the seed itself (gt_keep_word): the tensor is not generated
+    // -- 32 MB and most of a 30 us launch per call at the headline shape --, gsttaco_debug_randomness regenerates it when asked)
+    p.masks_unused = p.hashed && p.fused;
+    if (!p.fused) return p;
+    p.lean_front = c->front_mode >= 2;
+    p.n_workers = B < c->n_cu * 3 / 4 ? c->n_cu - B : c->n_cu / 4;
+    p.lean_rec = (c->lean && R[0].bf16 == R[1].bf16 && R[0].nkb == 64 && R[1].nkb == 64) ? (R[0].bf16 ? 2 : 1) : 0;
+    p.z0 = c->proj_z.wp != nullptr;
+    for (int l = 0; l < 2; ++l) p.lean_x[l] = c->lean && gt_lstm_x_supported(X[l].nkb);
+    // (batches above 32 rows: every launch is throughput-bound, the front launch most of all, and the projection launch has ~150 CUs
+    // to spare: it takes half of layer 2's recurrent tiles instead of a quarter.  The persistent kernels sum these tiles in the same
+    // order -- persist_decode.hip pd_rec2, persist_groups.h pd_g_rec_all, persist_bf16.h -- which keeps the two paths bitwise equal)
+    if (c->proj.nkb >= 32) p.co_tiles = std::min(R[1].ntiles, B > 32 ? 128 : 64);
+    p.lean_proj = c->lean && c->proj_z.bf16 == R[1].bf16 && gt_proj_lean_supported(c->proj_z.nkb, R[1].nkb) &&
+                  c->H2 / 16 + c->att / 16 == c->proj_z.nkb && (c->H2 / 16) % 2 == 0;
     // Mixed precision above 32 rows: the producers of the blocked activations (front launch: prenet output + context; LSTM launches:
     // h1, h2) also write bf16 MIRRORS, which the bf16 multi-chunk GEMM bodies read instead -- half the activation bytes through
     // each CU's load pipe, which is what bounds those launches (EXPERIMENTS round 4), and no conversion per consumer.  Only when
-    // every producer and consumer of the step is one that knows about mirrors (lean paths below).
-    const bool mirror = B > 32 && c->w_xa_h != nullptr && c->fused_front && c->split_rec && c->lean && c->keep_x_weights &&
-                        front_fits(c, Tv) &&
-                        gt_lstm_x_supported(c->lstm_x[0].nkb) && gt_lstm_x_supported(c->lstm_x[1].nkb) && c->lstm_h[0].nkb == 64 && c->lstm_h[1].nkb == 64;
-    if (mirror && !persist_base) {
-        HIPCHECK(c, gt_launch_zero(reinterpret_cast<float*>(c->w_h1_h[1]), (size_t)MT * 16 * H1 / 2, s));
-        HIPCHECK(c, gt_launch_zero(reinterpret_cast<float*>(c->w_h2_h[1]), (size_t)MT * 16 * H2 / 2, s));
+    // every producer and consumer of the step is one that knows about mirrors.
+    p.mirror = B > 32 && c->w_xa_h != nullptr && p.lean_x[0] && p.lean_x[1] && R[0].nkb == 64 && R[1].nkb == 64;
+    // both LSTM cells in one launch (skinny_gemm.hip gt_lstm12_kernel: fp32, batch <= 32; above: the multi-chunk form, fp32 or bf16),
+    // while this is the process's one live context
+    if (c->fuse12_now && c->lean && X[0].bf16 == X[1].bf16) {
+        if (gt_lstm12_mc_supported(X[0].nkb, X[1].nkb, c->H1, c->H2, B, c->fuse12_slots[X[0].bf16 ? 2 : 1])) p.fuse12 = 2;
+        else if (!X[0].bf16 && gt_lstm12_supported(X[0].nkb, X[1].nkb, c->H1, c->H2, B, c->fuse12_slots[0])) p.fuse12 = 1;
     }
-    if (g.att_type == GSTTACO_ATT_LSA) HIPCHECK(c, gt_launch_zero(c->w_lsa_state, (size_t)B * Tv, s));   // Layers.py:356
-    // both LSTM cells in one launch (skinny_gemm.hip gt_lstm12_kernel): fp32 lean shapes, batch <= 32, one live context
-    // (batch <= 32: fp32; above: the multi-chunk form, fp32 or bf16)
-    const bool fuse_base = c->fuse12_now && c->fused_front && c->split_rec && c->lean && c->keep_x_weights && c->lstm_x[0].bf16 == c->lstm_x[1].bf16 &&
-                           front_fits(c, Tv);
-    const bool fuse12_small = fuse_base && !c->lstm_x[0].bf16 && gt_lstm12_supported(c->lstm_x[0].nkb, c->lstm_x[1].nkb, H1, H2, B, c->fuse12_slots[0]);
-    const bool fuse12_mc = fuse_base && gt_lstm12_mc_supported(c->lstm_x[0].nkb, c->lstm_x[1].nkb, H1, H2, B, c->fuse12_slots[c->lstm_x[0].bf16 ? 2 : 1]);
-    const bool fuse12 = fuse12_small || fuse12_mc;
-    if (fuse12 && !persist_base) HIPCHECK(c, gt_launch_zero(reinterpret_cast<float*>(c->w_arrive), (size_t)steps * GT_L12_NSH * 32, s));
-    const float drop_scale = g.prenet_rate > 0.f ? 1.0f / (1.0f - g.prenet_rate) : 1.f;
-    const size_t mask_step = (size_t)B * (P0 + P1);
-    // throughput mode: the whole decode's dropout masks and sigmoid noise are generated up front (same Philox streams the
-    // step kernels would draw) into the buffers injected tensors use, so no step spends time on random numbers
-    const bool injected_mask = has_mask;
-    {
-        float* fm = (!has_mask && g.prenet_rate > 0.f) ? c->w_masks : nullptr;
-        float* fn = (!has_noise && g.sigmoid_noise > 0.f && g.att_type != GSTTACO_ATT_LSA) ? c->w_noise : nullptr;
-        // At the reference's rate 0.5 every fused front end derives the keep decisions from the seed itself (gt_keep_word) and never
-        // reads the mask tensor: it is not generated (32 MB and most of a 30 us launch per call at the headline shape).
-        // gsttaco_debug_randomness regenerates it from the seed when a test asks for it.
-        if (fm && masks_unused(c, Tv, false)) fm = nullptr;
-        if (fm || fn) HIPCHECK(c, gt_launch_rng_fill(c->w_seed, fm, fn, steps, B, P0, P1, Tv, g.prenet_rate, s));
-        if (fm) has_mask = true;
-        if (fn) has_noise = true;
-    }
-    int nprof[5] = {0, 0, 0, 0, 0};
-    auto prof_begin = [&](int which) -> int {
-        const size_t need = (size_t)2 * (nprof[which] + 1);
-        while (c->prof_ev[which].size() < need) {
+    // The whole loop as ONE persistent launch: fp32, batch <= 128 (above 32 rows: groups of 32 through one set of resident weights),
+    // T_v <= 256, the reference's decoder sizes, SMA / BMA / LSA -- while this is the process's only live context (its hand-offs need
+    // every workgroup resident).  Mixed precision: the bf16 kernel -- every GEMM pack bf16, the activation mirrors allocated, one
+    // group of up to 64 rows.
+    const int n_bf16 = X[0].bf16 + X[1].bf16 + R[0].bf16 + R[1].bf16 + c->proj_z.bf16;
+    const bool bf16 = n_bf16 == 5 && c->w_xa_h && c->w_xa2_h && c->w_h1_h[0] && c->w_h2_h[0];
+    p.persist = c->persist_now && c->lean && p.lean_front && p.z0 && (n_bf16 == 0 || bf16) && c->proj.nkb >= 32 &&
+                // (the LSA extension: the one-group fp32 kernel's LSA chain, up to 128 tokens -- else the launch path)
+                (!lsa || (n_bf16 == 0 && c->loc_pack && gt_persist_decode_lsa_fits(B, Tv, g.loc_filters, g.loc_kernel))) &&
+                X[0].nkb == 24 && X[1].nkb == 64 && R[0].nkb == 64 && R[1].nkb == 64 && B <= c->persist_rows && (B <= 32 || c->w_stash) &&
+                gt_persist_decode_supported(g.mel_dim, c->r, c->P0, c->P1, c->att, c->H1, c->H2, B, Tv, c->proj_z.ntiles, c->proj_z.nkb,
+                                            c->persist_slots, bf16 ? 1 : 0);
+    p.persist_bf16 = p.persist && bf16;
+    return p;
+}
+
+// Event brackets around the decode launches that gsttaco_set_profiling times (gsttaco_ctx::prof_ev): enqueue() runs between the two
+// events of the next bracket `which` when `on`, and alone otherwise.
+struct ProfBrackets {
+    gsttaco_ctx* c;
+    hipStream_t s;
+    int n[5] = {0, 0, 0, 0, 0};
+    template <class F> int run(bool on, int which, F&& enqueue) {
+        if (!on) return enqueue();
+        while (c->prof_ev[which].size() < (size_t)2 * (n[which] + 1)) {
             hipEvent_t e;
             HIPCHECK(c, hipEventCreate(&e));
             c->prof_ev[which].push_back(e);
         }
-        return record_event(c, c->prof_ev[which][2 * nprof[which]], s);
-    };
-    auto prof_end = [&](int which) -> int {
-        int rce = record_event(c, c->prof_ev[which][2 * nprof[which] + 1], s);
-        nprof[which]++;
-        return rce;
-    };
-    // layer-2 recurrent tiles co-scheduled with the (11-workgroup) projection kernel: one tile per otherwise idle CU
-    // (batches above 32 rows: every launch is throughput-bound, the front launch most of all, and the projection launch has
-    // ~150 CUs to spare: it takes half of layer 2's recurrent tiles instead of a quarter)
-    const int co_tiles = std::max(0, std::min(c->lstm_h[1].ntiles, c->co_tiles >= 0 ? c->co_tiles : (B > 32 ? 128 : 64)));
-    {
-        // (randomness: hashed keep decisions, or the masks / noise in the buffers -- injected, or generated above -- always one of them)
-        const bool hashed = !injected_mask && g.prenet_rate == 0.5f && c->keep_hash;
-        if (persist_base) {
-            const bool lsa_p = g.att_type == GSTTACO_ATT_LSA;        // (LSA: softmax, no sigmoid noise)
-            if (!((g.prenet_rate == 0.f || hashed || has_mask) && (g.sigmoid_noise == 0.f || has_noise || lsa_p)))
-                return fail(c, GSTTACO_E_INVALID, "internal: the persistent decode launch was chosen without its randomness");
-            PersistDecodeArgs a{};
-            a.w1x = c->lstm_x[0].wp; a.w1h = c->lstm_h[0].wp; a.b1h = c->lstm_h[0].bias;
-            a.w2x = c->lstm_x[1].wp; a.w2h = c->lstm_h[1].wp; a.b2h = c->lstm_h[1].bias;
-            a.wp = c->proj_z.wp; a.bp = c->proj_z.bias; a.pj_tiles = c->proj_z.ntiles;
-            a.n_out = c->proj_out; a.n_split = mel * r; a.z_col0 = c->z_col0;
-            a.W1 = c->pw1; a.b1 = c->pb1; a.Wq = c->pwq; a.bq = c->pbq; a.av = c->att_v; a.score_bias = c->att_sb;
-            a.pm = c->w_pm;
-            a.noise = (g.sigmoid_noise > 0.f && !lsa_p) ? c->w_noise : nullptr;
-            a.masks = (g.prenet_rate > 0.f && !hashed) ? c->w_masks : nullptr;
-            a.seed_ptr = c->w_seed; a.tok_len = tlen;
-            a.drop_rate = g.prenet_rate; a.drop_scale = drop_scale; a.sigmoid_noise = lsa_p ? 0.f : g.sigmoid_noise;
-            a.keep_hash = hashed ? 1 : 0; a.att_type = g.att_type;
-            a.loc_pack = c->loc_pack; a.loc_f = g.loc_filters; a.loc_k = g.loc_kernel; a.lsa_cumulate = g.lsa_cumulate; a.lsa_smoothing = g.lsa_smoothing;
-            a.xa[0] = c->w_xa; a.xa[1] = c->w_xa2;
-            a.h1[0] = c->w_h1[0]; a.h1[1] = c->w_h1[1]; a.h2[0] = c->w_h2[0]; a.h2[1] = c->w_h2[1];
-            a.stash = c->w_stash;
-            a.bf16 = persist_bf16 ? 1 : 0;
-            a.xah[0] = c->w_xa_h; a.xah[1] = c->w_xa2_h;
-            a.h1h[0] = c->w_h1_h[0]; a.h1h[1] = c->w_h1_h[1]; a.h2h[0] = c->w_h2_h[0]; a.h2h[1] = c->w_h2_h[1];
-            a.z0g = c->w_z0g; a.hpart = c->w_hpart; a.ctl = c->w_pctl; a.err = c->w_err + 2;        // (its own give-up word)
-            a.pre = c->w_pre; a.ld_pre = ld_pre; a.stop = c->w_stop; a.align = c->w_align; a.ld_align = (int64_t)steps * Tv;
-            a.B = B; a.MT = MT; a.Tv = Tv; a.steps = steps; a.co_tiles = co_tiles;
-            a.expect_extra = c->debug_drop_member >= 0 ? 1 : 0;
-            a.dbg = c->stamps ? c->w_dbg : nullptr;
-            const bool prof = c->prof_every > 0;
-            if (prof) { int rce = prof_begin(2); if (rce) return rce; }
-            HIPCHECK(c, gt_launch_persist_decode(a, c->pb0, split16_eff, s));
-            if (prof) { int rce = prof_end(2); if (rce) return rce; }
-            ++c->n_persist_decodes;
-            if (c->prof_every > 0)
-                for (int i = 0; i < 5; ++i) c->prof_count[i] = nprof[i];
-            return 0;
-        }
+        int rc = record_event(c, c->prof_ev[which][2 * n[which]], s);
+        if (!rc) rc = enqueue();
+        if (rc) return rc;
+        rc = record_event(c, c->prof_ev[which][2 * n[which] + 1], s);
+        ++n[which];
+        return rc;
     }
-    for (int t = 0; t < steps; ++t) {
-        const int p = t & 1;
-        SkinnyArgs k;
-        const float* frame_ptr = t == 0 ? c->w_zero : c->w_pre + ((size_t)(t - 1) * r + (r - 1)) * mel;
-        const int64_t frame_ld = t == 0 ? 0 : ld_pre;
-        const float* mask0 = has_mask ? c->w_masks + (size_t)t * mask_step : nullptr;
-        const float* mask1 = has_mask ? c->w_masks + (size_t)t * mask_step + (size_t)B * P0 : nullptr;
-        const bool prof = c->prof_every > 0 && (t % c->prof_every) == 0;
-        // (the four-kernel path below: GSTTACO_FUSED_FRONT=0, or a shape the fused kernel's LDS does not hold)
-        const bool lsa = g.att_type == GSTTACO_ATT_LSA;
-        const bool fused = c->fused_front && front_fits(c, Tv);
-        const bool split = fused && c->split_rec;
-        const bool use_z0 = split && c->proj_z.wp != nullptr;        // prenet-0 rides in the projection launch
-        float* xa_t = c->w_xa;
-        if (fused) {
-            // 1-4 fused: prenet x2, query projection, score / alignment / context (dec_front.hip)
-            DecFrontArgs f{};
-            f.frame = frame_ptr; f.ldframe = frame_ld;
-            f.z0 = (use_z0 && t > 0) ? c->w_z0 : nullptr;
-            f.w0 = c->pw0; f.b0 = c->pb0; f.w1 = c->pw1; f.b1 = c->pb1; f.wq = c->pwq; f.bq = c->pbq;
-            f.mask0 = mask0; f.mask1 = mask1;
-            if (!injected_mask && g.prenet_rate == 0.5f && c->keep_hash) {
-                // throughput mode: the kernel derives the same decisions gt_rng_fill_kernel wrote to w_masks from the seed
-                // itself (gt_keep_word) and, at the reference's sizes, skips the weight rows they zero
-                f.mask0 = f.mask1 = nullptr;
-                f.keep_hash = (P0 == 256 && P1 == 256 && att == 128) ? 1 : 0;
-            }
-            f.drop_rate = g.prenet_rate; f.drop_scale = drop_scale; f.seed_ptr = c->w_seed; f.rng_step = (uint32_t)t;
-            f.pm = c->w_pm; f.v = c->att_v; f.score_bias = c->att_sb;
-            f.prev = t == 0 ? nullptr : c->w_align + (size_t)(t - 1) * Tv; f.ldprev = (int64_t)steps * Tv;
-            if (lsa) {      // the state buffer (zeroed above) in place of the previous alignment; softmax, no noise
-                f.prev = c->w_lsa_state; f.ldprev = Tv;
-                f.loc_pack = c->loc_pack;
-                f.lsa_state = c->w_lsa_state; f.loc_k = g.loc_kernel; f.loc_f = g.loc_filters;
-                f.lsa_cumulate = g.lsa_cumulate; f.lsa_smoothing = g.lsa_smoothing;
-            }
-            f.noise = (has_noise && !lsa) ? c->w_noise + (size_t)t * B * Tv : nullptr; f.ldnoise = Tv;
-            f.align = c->w_align + (size_t)t * Tv; f.ldalign = (int64_t)steps * Tv;
-            f.xa = xa_t; f.MT = MT;
-            f.xah = mirror ? c->w_xa_h : nullptr;
-            f.B = B; f.Tv = Tv; f.mel = mel; f.P0 = P0; f.P1 = P1; f.A = att; f.type = g.att_type;
-            f.sigmoid_noise = lsa ? 0.f : g.sigmoid_noise;
-            f.tok_len = tlen;
-            f.dbg = (c->stamps && t == steps / 2) ? c->w_dbg : nullptr;
-            f.lean_front = c->front_mode >= 2 ? 1 : 0;
-            if (split) {
-                for (int layer = 0; layer < 2; ++layer) {
-                    SkinnyArgs& rk = f.rec[layer];
-                    const PackedLinear& L = c->lstm_h[layer];
-                    const int H = layer == 0 ? H1 : H2;
-                    rk.wp = L.wp; rk.bf16 = L.bf16; rk.bias = L.bias; rk.nkb = L.nkb;
-                    rk.seg[0] = SkinnySeg{layer == 0 ? c->w_h1[p ^ 1] : c->w_h2[p ^ 1], 0, H / 16, 1};
-                    rk.M = B; rk.N = H; rk.MT = MT;
-                    rk.keep_weights = 1;                    // default cache policy (see lean_body.h gt_lean_partial)
-                    rk.partial_out = c->w_part[layer];
-                    f.rec_begin[layer] = 0; f.rec_end[layer] = L.ntiles;
-                }
-                // one worker workgroup per compute unit the utterance workgroups leave free (a quarter of the chip at least)
-                f.n_workers = B < c->n_cu * 3 / 4 ? c->n_cu - B : c->n_cu / 4;
-                f.worker_tiles = c->worker_tiles;
-                f.lean_rec = (c->lean && f.rec[0].bf16 == f.rec[1].bf16 && f.rec[0].nkb == 64 && f.rec[1].nkb == 64) ? (f.rec[0].bf16 ? 2 : 1) : 0;
-                for (int layer = 0; layer < 2; ++layer) {
-                    f.lrec[layer] = LeanPartialArgs{f.rec[layer].wp, f.rec[layer].bias, f.rec[layer].seg[0].ptr, f.rec[layer].partial_out, MT};
-                    if (mirror && f.lean_rec == 2) f.lrec[layer].xh = layer == 0 ? c->w_h1_h[p ^ 1] : c->w_h2_h[p ^ 1];
-                }
-                // from step 1 on, the projection kernel of the previous step already did layer-2 tiles [0, co_tiles)
-                if (t > 0 && c->proj.nkb >= 32) f.rec_begin[1] = co_tiles;
-                {
-                    const int wt = f.worker_tiles == 1 ? 1 : 2;
-                    const int jobs = (f.rec_end[0] - f.rec_begin[0] + wt - 1) / wt + (f.rec_end[1] - f.rec_begin[1] + wt - 1) / wt;
-                    f.sched_pf = jobs;
-                    if (f.lean_rec != 0 && B > 32) {
-                        const FrontSched fs = plan_front_jobs(c, jobs, (B + 31) / 32, f.n_workers, B, f.lean_rec == 2);
-                        f.sched_pf = fs.pf; f.sched_ne = fs.ne; f.sched_e = fs.e; f.sched_y = fs.y; f.utt_jobs = fs.utt;
-                    }
-                }
-            }
-            if (prof) { int rce = prof_begin(2); if (rce) return rce; }
-            HIPCHECK(c, gt_launch_dec_front(f, s));
-            if (prof) { int rce = prof_end(2); if (rce) return rce; }
-        } else {
-        // 1. prenet layer 0 on the last emitted frame (Taco2.py:186: decodings[:, -1]; zeros at t=0)
-        memset(&k, 0, sizeof(k));
-        k.wp = c->prenet0.wp; k.bf16 = c->prenet0.bf16; k.bias = c->prenet0.bias;
-        k.seg[0] = SkinnySeg{frame_ptr, frame_ld, mel / 16, 0};
-        k.nkb = c->prenet0.nkb; k.M = B; k.N = P0; k.n_split = P0; k.MT = MT;
-        k.out = c->w_p1; k.ldo = P0;
-        k.mask = mask0; k.ldm = P0;
-        k.drop_rate = g.prenet_rate; k.drop_scale = drop_scale;
-        k.seed_ptr = c->w_seed; k.rng_step = (uint32_t)t; k.rng_stream = 0x1000u;
-        HIPCHECK(c, launch_skinny(c, EPI_RELU_DROP, k, nullptr, c->prenet0.ntiles, s));
-        // 2. prenet layer 1 -> xa[:, 0:P1]
-        memset(&k, 0, sizeof(k));
-        k.wp = c->prenet1.wp; k.bf16 = c->prenet1.bf16; k.bias = c->prenet1.bias;
-        k.seg[0] = SkinnySeg{c->w_p1, P0, P0 / 16, 0};
-        k.nkb = c->prenet1.nkb; k.M = B; k.N = P1; k.n_split = P1; k.MT = MT;
-        k.out = xa_t; k.out_blocked = 1;
-        k.mask = mask1; k.ldm = P1;
-        k.drop_rate = g.prenet_rate; k.drop_scale = drop_scale;
-        k.seed_ptr = c->w_seed; k.rng_step = (uint32_t)t; k.rng_stream = 0x1001u;
-        HIPCHECK(c, launch_skinny(c, EPI_RELU_DROP, k, nullptr, c->prenet1.ntiles, s));
-        // 3. attention query projection (Steps.py:122)
-        memset(&k, 0, sizeof(k));
-        k.wp = c->query.wp; k.bf16 = c->query.bf16; k.bias = c->query.bias;
-        k.seg[0] = SkinnySeg{xa_t, 0, P1 / 16, 1};
-        k.nkb = c->query.nkb; k.M = B; k.N = att; k.n_split = att; k.MT = MT;
-        k.out = c->w_q; k.ldo = att;
-        HIPCHECK(c, launch_skinny(c, EPI_LINEAR, k, nullptr, c->query.ntiles, s));
-        // 4. score / monotonic alignment / context -> xa[:, P1:P1+att]
-        AttnStepArgs a{};
-        a.q = c->w_q; a.ldq = att; a.pm = c->w_pm; a.v = c->att_v; a.score_bias = c->att_sb;
-        a.prev = t == 0 ? nullptr : c->w_align + (size_t)(t - 1) * Tv; a.ldprev = (int64_t)steps * Tv;
-        a.noise = has_noise ? c->w_noise + (size_t)t * B * Tv : nullptr; a.ldnoise = Tv;
-        a.align = c->w_align + (size_t)t * Tv; a.ldalign = (int64_t)steps * Tv;
-        a.ctx = xa_t + (size_t)(P1 / 16) * BLK; a.ldctx = 0; a.ctx_mt = MT;
-        a.B = B; a.Tv = Tv; a.A = att; a.type = g.att_type; a.sigmoid_noise = g.sigmoid_noise;
-        a.seed_ptr = c->w_seed; a.rng_step = (uint32_t)t; a.tok_len = tlen;
-        a.loc_cw = c->loc_cw; a.loc_cb = c->loc_cb; a.loc_dw = c->loc_dw; a.loc_db = c->loc_db; a.att_bias = c->att_bias;
-        a.lsa_state = c->w_lsa_state; a.loc_k = g.loc_kernel; a.loc_f = g.loc_filters;
-        a.lsa_cumulate = g.lsa_cumulate; a.lsa_smoothing = g.lsa_smoothing;
-        HIPCHECK(c, gt_launch_attn_step(a, s));
-        }
-        // 5/6. the two LSTM cells (StackedRNNCells, Taco2.py:111)
-        if (fuse12) {
-            Lstm12Args fa{};
-            for (int layer = 0; layer < 2; ++layer) {
-                const PackedLinear& L = c->lstm_x[layer];
-                float** hb = layer == 0 ? c->w_h1 : c->w_h2;
-                unsigned long long* dbg = (c->stamps && t == steps / 2) ? c->w_dbg + 16 * (1 + layer) : nullptr;
-                (layer == 0 ? fa.l1 : fa.l2) = LstmXArgs{L.wp, layer == 0 ? xa_t : c->w_h1[p], c->w_part[layer], layer == 0 ? c->w_c1 : c->w_c2, hb[p],
-                                                         nullptr, dbg, B, MT, layer == 0 ? H1 : H2, 0, L.nkb};
-                if (mirror) {
-                    (layer == 0 ? fa.l1 : fa.l2).xh = layer == 0 ? c->w_xa_h : c->w_h1_h[p];
-                    (layer == 0 ? fa.l1 : fa.l2).hh = layer == 0 ? c->w_h1_h[p] : c->w_h2_h[p];
-                }
-            }
-            fa.arrive = c->w_arrive + (size_t)t * GT_L12_NSH * 32;
-            fa.err = c->w_err;
-            fa.expect = (uint32_t)(fuse12_mc ? gt_lstm12_mc_grid(H1) : (H1 + 3) / 4) + (c->debug_drop_member >= 0 ? 1u : 0u);
-            if (prof) { int rce = prof_begin(0); if (rce) return rce; }
-            if (fuse12_mc) HIPCHECK(c, gt_launch_lstm12_mc(fa, c->lstm_x[0].bf16 != 0, s));
-            else
-            HIPCHECK(c, gt_launch_lstm12(fa, s));
-            if (prof) { int rce = prof_end(0); if (rce) return rce; }
-        } else
+};
+
+// One decode being enqueued: what the parts below share
+struct DecodeCall {
+    gsttaco_ctx* c;
+    hipStream_t s;
+    DecodePlan P;
+    int B, Tv, steps, MT;
+    bool has_mask, has_noise;       // the buffers hold keep masks / noise (injected, or generated up front)
+    const int32_t* tlen;            // masked mode: token lengths, or NULL
+    float drop_scale;
+    int64_t ld_pre;                 // row stride of the pre-postnet frames
+    ProfBrackets prof;
+    const float* frame(int t) const {       // the last frame step t - 1 emitted (Taco2.py:186: decodings[:, -1]; zeros at t = 0)
+        return t == 0 ? c->w_zero : c->w_pre + ((size_t)(t - 1) * c->r + (c->r - 1)) * c->cfg.mel_dim;
+    }
+    const float* mask(int t, int layer) const {
+        return has_mask ? c->w_masks + (size_t)t * B * (c->P0 + c->P1) + (layer ? (size_t)B * c->P0 : 0) : nullptr;
+    }
+    unsigned long long* stamps(int t, int slot) const { return (c->stamps && t == steps / 2) ? c->w_dbg + slot : nullptr; }
+};
+
+// The whole loop as ONE persistent launch.  Bitwise the launches below (GPU test), which stay the path for every other shape, for
+// several contexts, and after a give-up.  It keeps its state in registers and initialises it itself: none of the launch path's
+// zero-fill launches (and their boundaries) is enqueued for it.
+int enqueue_decode_persist(DecodeCall& d) {
+    gsttaco_ctx* c = d.c;
+    const gsttaco_config& g = c->cfg;
+    const bool lsa = g.att_type == GSTTACO_ATT_LSA;        // (LSA: softmax, no sigmoid noise)
+    // (randomness: hashed keep decisions, or the masks / noise in the buffers -- injected, or generated up front -- always one of them)
+    if (!((g.prenet_rate == 0.f || d.P.hashed || d.has_mask) && (g.sigmoid_noise == 0.f || d.has_noise || lsa)))
+        return fail(c, GSTTACO_E_INVALID, "internal: the persistent decode launch was chosen without its randomness");
+    PersistDecodeArgs a{};
+    a.w1x = c->lstm_x[0].wp; a.w1h = c->lstm_h[0].wp; a.b1h = c->lstm_h[0].bias;
+    a.w2x = c->lstm_x[1].wp; a.w2h = c->lstm_h[1].wp; a.b2h = c->lstm_h[1].bias;
+    a.wp = c->proj_z.wp; a.bp = c->proj_z.bias; a.pj_tiles = c->proj_z.ntiles;
+    a.n_out = c->proj_out; a.n_split = g.mel_dim * c->r; a.z_col0 = c->z_col0;
+    a.W1 = c->pw1; a.b1 = c->pb1; a.Wq = c->pwq; a.bq = c->pbq; a.av = c->att_v; a.score_bias = c->att_sb;
+    a.pm = c->w_pm;
+    a.noise = (g.sigmoid_noise > 0.f && !lsa) ? c->w_noise : nullptr;
+    a.masks = (g.prenet_rate > 0.f && !d.P.hashed) ? c->w_masks : nullptr;
+    a.seed_ptr = c->w_seed; a.tok_len = d.tlen;
+    a.drop_rate = g.prenet_rate; a.drop_scale = d.drop_scale; a.sigmoid_noise = lsa ? 0.f : g.sigmoid_noise;
+    a.keep_hash = d.P.hashed ? 1 : 0; a.att_type = g.att_type;
+    a.loc_pack = c->loc_pack; a.loc_f = g.loc_filters; a.loc_k = g.loc_kernel; a.lsa_cumulate = g.lsa_cumulate; a.lsa_smoothing = g.lsa_smoothing;
+    a.xa[0] = c->w_xa; a.xa[1] = c->w_xa2;
+    a.h1[0] = c->w_h1[0]; a.h1[1] = c->w_h1[1]; a.h2[0] = c->w_h2[0]; a.h2[1] = c->w_h2[1];
+    a.stash = c->w_stash;
+    a.bf16 = d.P.persist_bf16 ? 1 : 0;
+    a.xah[0] = c->w_xa_h; a.xah[1] = c->w_xa2_h;
+    a.h1h[0] = c->w_h1_h[0]; a.h1h[1] = c->w_h1_h[1]; a.h2h[0] = c->w_h2_h[0]; a.h2h[1] = c->w_h2_h[1];
+    a.z0g = c->w_z0g; a.hpart = c->w_hpart; a.ctl = c->w_pctl; a.err = c->w_err + 2;        // (its own give-up word)
+    a.pre = c->w_pre; a.ld_pre = d.ld_pre; a.stop = c->w_stop; a.align = c->w_align; a.ld_align = (int64_t)d.steps * d.Tv;
+    a.B = d.B; a.MT = d.MT; a.Tv = d.Tv; a.steps = d.steps; a.co_tiles = d.P.co_tiles;
+    a.expect_extra = c->debug_drop_member >= 0 ? 1 : 0;
+    a.dbg = c->stamps ? c->w_dbg : nullptr;
+    const int rc = d.prof.run(c->prof_every > 0, 2, [&] { HIPCHECK(c, gt_launch_persist_decode(a, c->pb0, d.s)); return 0; });
+    if (!rc) ++c->n_persist_decodes;
+    return rc;
+}
+
+// 1-4 of step t fused: prenet x2, query projection, score / alignment / context (dec_front.hip); its worker workgroups compute the
+// recurrent halves h_{t-1} . W_h + b of both LSTM layers (those of layer 2's tiles [0, co_tiles) from step 1 on: the previous
+// step's projection launch did them)
+int enqueue_front_fused(DecodeCall& d, int t, bool on) {
+    gsttaco_ctx* c = d.c;
+    const gsttaco_config& g = c->cfg;
+    const DecodePlan& P = d.P;
+    const int B = d.B, Tv = d.Tv, MT = d.MT, p = t & 1;
+    const bool lsa = g.att_type == GSTTACO_ATT_LSA;
+    DecFrontArgs f{};
+    f.frame = d.frame(t); f.ldframe = t == 0 ? 0 : d.ld_pre;
+    f.z0 = (P.z0 && t > 0) ? c->w_z0 : nullptr;
+    f.w0 = c->pw0; f.b0 = c->pb0; f.w1 = c->pw1; f.b1 = c->pb1; f.wq = c->pwq; f.bq = c->pbq;
+    f.mask0 = d.mask(t, 0); f.mask1 = d.mask(t, 1);
+    if (P.hashed) {
+        // throughput mode: the kernel derives the same decisions gt_rng_fill_kernel would write to w_masks from the seed
+        // itself (gt_keep_word) and, at the reference's sizes, skips the weight rows they zero
+        f.mask0 = f.mask1 = nullptr;
+        f.keep_hash = (c->P0 == 256 && c->P1 == 256 && c->att == 128) ? 1 : 0;
+    }
+    f.drop_rate = g.prenet_rate; f.drop_scale = d.drop_scale; f.seed_ptr = c->w_seed; f.rng_step = (uint32_t)t;
+    f.pm = c->w_pm; f.v = c->att_v; f.score_bias = c->att_sb;
+    f.prev = t == 0 ? nullptr : c->w_align + (size_t)(t - 1) * Tv; f.ldprev = (int64_t)d.steps * Tv;
+    if (lsa) {      // the state buffer (zeroed up front) in place of the previous alignment; softmax, no noise
+        f.prev = c->w_lsa_state; f.ldprev = Tv;
+        f.loc_pack = c->loc_pack;
+        f.lsa_state = c->w_lsa_state; f.loc_k = g.loc_kernel; f.loc_f = g.loc_filters;
+        f.lsa_cumulate = g.lsa_cumulate; f.lsa_smoothing = g.lsa_smoothing;
+    }
+    f.noise = (d.has_noise && !lsa) ? c->w_noise + (size_t)t * B * Tv : nullptr; f.ldnoise = Tv;
+    f.align = c->w_align + (size_t)t * Tv; f.ldalign = (int64_t)d.steps * Tv;
+    f.xa = c->w_xa; f.MT = MT;
+    f.xah = P.mirror ? c->w_xa_h : nullptr;
+    f.B = B; f.Tv = Tv; f.mel = g.mel_dim; f.P0 = c->P0; f.P1 = c->P1; f.A = c->att; f.type = g.att_type;
+    f.sigmoid_noise = lsa ? 0.f : g.sigmoid_noise;
+    f.tok_len = d.tlen;
+    f.dbg = d.stamps(t, 0);
+    f.lean_front = P.lean_front ? 1 : 0;
+    for (int layer = 0; layer < 2; ++layer) {
+        SkinnyArgs& rk = f.rec[layer];
+        const PackedLinear& L = c->lstm_h[layer];
+        const int H = layer == 0 ? c->H1 : c->H2;
+        rk.wp = L.wp; rk.bf16 = L.bf16; rk.bias = L.bias; rk.nkb = L.nkb;
+        rk.seg[0] = SkinnySeg{layer == 0 ? c->w_h1[p ^ 1] : c->w_h2[p ^ 1], 0, H / 16, 1};
+        rk.M = B; rk.N = H; rk.MT = MT;
+        rk.keep_weights = 1;                    // default cache policy (see lean_body.h gt_lean_partial)
+        rk.partial_out = c->w_part[layer];
+        f.rec_begin[layer] = 0; f.rec_end[layer] = L.ntiles;
+        f.lrec[layer] = LeanPartialArgs{rk.wp, rk.bias, rk.seg[0].ptr, rk.partial_out, MT};
+        if (P.mirror && P.lean_rec == 2) f.lrec[layer].xh = layer == 0 ? c->w_h1_h[p ^ 1] : c->w_h2_h[p ^ 1];
+    }
+    f.n_workers = P.n_workers;
+    f.lean_rec = P.lean_rec;
+    if (t > 0) f.rec_begin[1] = P.co_tiles;
+    constexpr int wt = 2;           // tiles per worker job (front_body.h WT: pairs sharing one pass over the activations)
+    const int jobs = (f.rec_end[0] - f.rec_begin[0] + wt - 1) / wt + (f.rec_end[1] - f.rec_begin[1] + wt - 1) / wt;
+    f.sched_pf = jobs;
+    if (P.lean_rec != 0 && B > 32) {
+        const FrontSched fs = plan_front_jobs(jobs, (B + 31) / 32, f.n_workers, B, P.lean_rec == 2);
+        f.sched_pf = fs.pf; f.sched_ne = fs.ne; f.sched_e = fs.e; f.sched_y = fs.y; f.utt_jobs = fs.utt;
+    }
+    return d.prof.run(on, 2, [&] { HIPCHECK(c, gt_launch_dec_front(f, d.s)); return 0; });
+}
+
+// 1-4 of step t as four kernels (GSTTACO_FUSED_FRONT=0, or a shape the fused kernel's LDS does not hold)
+int enqueue_front_kernels(DecodeCall& d, int t) {
+    gsttaco_ctx* c = d.c;
+    const gsttaco_config& g = c->cfg;
+    const int B = d.B, Tv = d.Tv, MT = d.MT, P0 = c->P0, P1 = c->P1, att = c->att, mel = g.mel_dim;
+    hipStream_t s = d.s;
+    float* xa_t = c->w_xa;
+    SkinnyArgs k;
+    // 1. prenet layer 0 on the last emitted frame
+    memset(&k, 0, sizeof(k));
+    k.wp = c->prenet0.wp; k.bf16 = c->prenet0.bf16; k.bias = c->prenet0.bias;
+    k.seg[0] = SkinnySeg{d.frame(t), t == 0 ? 0 : d.ld_pre, mel / 16, 0};
+    k.nkb = c->prenet0.nkb; k.M = B; k.N = P0; k.n_split = P0; k.MT = MT;
+    k.out = c->w_p1; k.ldo = P0;
+    k.mask = d.mask(t, 0); k.ldm = P0;
+    k.drop_rate = g.prenet_rate; k.drop_scale = d.drop_scale;
+    k.seed_ptr = c->w_seed; k.rng_step = (uint32_t)t; k.rng_stream = 0x1000u;
+    HIPCHECK(c, launch_skinny(c, EPI_RELU_DROP, k, nullptr, c->prenet0.ntiles, s));
+    // 2. prenet layer 1 -> xa[:, 0:P1]
+    memset(&k, 0, sizeof(k));
+    k.wp = c->prenet1.wp; k.bf16 = c->prenet1.bf16; k.bias = c->prenet1.bias;
+    k.seg[0] = SkinnySeg{c->w_p1, P0, P0 / 16, 0};
+    k.nkb = c->prenet1.nkb; k.M = B; k.N = P1; k.n_split = P1; k.MT = MT;
+    k.out = xa_t; k.out_blocked = 1;
+    k.mask = d.mask(t, 1); k.ldm = P1;
+    k.drop_rate = g.prenet_rate; k.drop_scale = d.drop_scale;
+    k.seed_ptr = c->w_seed; k.rng_step = (uint32_t)t; k.rng_stream = 0x1001u;
+    HIPCHECK(c, launch_skinny(c, EPI_RELU_DROP, k, nullptr, c->prenet1.ntiles, s));
+    // 3. attention query projection (Steps.py:122)
+    memset(&k, 0, sizeof(k));
+    k.wp = c->query.wp; k.bf16 = c->query.bf16; k.bias = c->query.bias;
+    k.seg[0] = SkinnySeg{xa_t, 0, P1 / 16, 1};
+    k.nkb = c->query.nkb; k.M = B; k.N = att; k.n_split = att; k.MT = MT;
+    k.out = c->w_q; k.ldo = att;
+    HIPCHECK(c, launch_skinny(c, EPI_LINEAR, k, nullptr, c->query.ntiles, s));
+    // 4. score / monotonic alignment / context -> xa[:, P1:P1+att]
+    AttnStepArgs a{};
+    a.q = c->w_q; a.ldq = att; a.pm = c->w_pm; a.v = c->att_v; a.score_bias = c->att_sb;
+    a.prev = t == 0 ? nullptr : c->w_align + (size_t)(t - 1) * Tv; a.ldprev = (int64_t)d.steps * Tv;
+    a.noise = d.has_noise ? c->w_noise + (size_t)t * B * Tv : nullptr; a.ldnoise = Tv;
+    a.align = c->w_align + (size_t)t * Tv; a.ldalign = (int64_t)d.steps * Tv;
+    a.ctx = xa_t + (size_t)(P1 / 16) * MT * 256; a.ldctx = 0; a.ctx_mt = MT;
+    a.B = B; a.Tv = Tv; a.A = att; a.type = g.att_type; a.sigmoid_noise = g.sigmoid_noise;
+    a.seed_ptr = c->w_seed; a.rng_step = (uint32_t)t; a.tok_len = d.tlen;
+    a.loc_cw = c->loc_cw; a.loc_cb = c->loc_cb; a.loc_dw = c->loc_dw; a.loc_db = c->loc_db; a.att_bias = c->att_bias;
+    a.lsa_state = c->w_lsa_state; a.loc_k = g.loc_kernel; a.loc_f = g.loc_filters;
+    a.lsa_cumulate = g.lsa_cumulate; a.lsa_smoothing = g.lsa_smoothing;
+    HIPCHECK(c, gt_launch_attn_step(a, s));
+    return 0;
+}
+
+// 5/6. the two LSTM cells of step t (StackedRNNCells, Taco2.py:111): one fused launch, or one launch per cell -- the input half on
+// top of the recurrent half the front launch's workers computed (fused front), or the whole GEMM
+int enqueue_lstm_cells(DecodeCall& d, int t, bool on) {
+    gsttaco_ctx* c = d.c;
+    const DecodePlan& P = d.P;
+    const int B = d.B, MT = d.MT, H1 = c->H1, H2 = c->H2, p = t & 1;
+    float* xa_t = c->w_xa;
+    if (P.fuse12) {
+        Lstm12Args fa{};
         for (int layer = 0; layer < 2; ++layer) {
-            memset(&k, 0, sizeof(k));
-            const int H = layer == 0 ? H1 : H2;
+            const PackedLinear& L = c->lstm_x[layer];
             float** hb = layer == 0 ? c->w_h1 : c->w_h2;
-            if (split) {
-                // only the half that depends on this step's inputs; + partial_in (recurrent half + bias)
-                const PackedLinear& L = c->lstm_x[layer];
-                k.wp = L.wp; k.bf16 = L.bf16; k.bias = L.bias; k.nkb = L.nkb;
-                if (layer == 0) k.seg[0] = SkinnySeg{xa_t, 0, XA / 16, 1};
-                else k.seg[0] = SkinnySeg{c->w_h1[p], 0, H1 / 16, 1};
-                k.partial_in = c->w_part[layer];
-                k.keep_weights = c->keep_x_weights;
-            } else {
-                const PackedLinear& L = layer == 0 ? c->lstm0 : c->lstm1;
-                k.wp = L.wp; k.bf16 = L.bf16; k.bias = L.bias; k.nkb = L.nkb;
-                if (layer == 0) {
-                    k.seg[0] = SkinnySeg{xa_t, 0, XA / 16, 1};
-                    k.seg[1] = SkinnySeg{c->w_h1[p ^ 1], 0, H1 / 16, 1};
-                } else {
-                    k.seg[0] = SkinnySeg{c->w_h1[p], 0, H1 / 16, 1};
-                    k.seg[1] = SkinnySeg{c->w_h2[p ^ 1], 0, H2 / 16, 1};
-                }
+            LstmXArgs& la = layer == 0 ? fa.l1 : fa.l2;
+            la = LstmXArgs{L.wp, layer == 0 ? xa_t : c->w_h1[p], c->w_part[layer], layer == 0 ? c->w_c1 : c->w_c2, hb[p],
+                           nullptr, d.stamps(t, 16 * (1 + layer)), B, MT, layer == 0 ? H1 : H2, 0, L.nkb};
+            if (P.mirror) {
+                la.xh = layer == 0 ? c->w_xa_h : c->w_h1_h[p];
+                la.hh = layer == 0 ? c->w_h1_h[p] : c->w_h2_h[p];
             }
-            k.N = H; k.c = layer == 0 ? c->w_c1 : c->w_c2; k.h = hb[p]; k.out_blocked = 1;
-            k.M = B; k.MT = MT;
-            k.dbg = (c->stamps && t == steps / 2) ? c->w_dbg + 16 * (1 + layer) : nullptr;
-            if (prof) { int rce = prof_begin(layer); if (rce) return rce; }
-            if (split && c->lean && c->keep_x_weights && gt_lstm_x_supported(k.nkb)) {
+        }
+        fa.arrive = c->w_arrive + (size_t)t * GT_L12_NSH * 32;
+        fa.err = c->w_err;
+        fa.expect = (uint32_t)(P.fuse12 == 2 ? gt_lstm12_mc_grid(H1) : (H1 + 3) / 4) + (c->debug_drop_member >= 0 ? 1u : 0u);
+        return d.prof.run(on, 0, [&] {
+            if (P.fuse12 == 2) HIPCHECK(c, gt_launch_lstm12_mc(fa, c->lstm_x[0].bf16 != 0, d.s));
+            else HIPCHECK(c, gt_launch_lstm12(fa, d.s));
+            return 0;
+        });
+    }
+    const int XA = c->P1 + c->att;
+    for (int layer = 0; layer < 2; ++layer) {
+        SkinnyArgs k;
+        memset(&k, 0, sizeof(k));
+        const int H = layer == 0 ? H1 : H2;
+        float** hb = layer == 0 ? c->w_h1 : c->w_h2;
+        if (P.fused) {
+            // only the half that depends on this step's inputs; + partial_in (recurrent half + bias)
+            const PackedLinear& L = c->lstm_x[layer];
+            k.wp = L.wp; k.bf16 = L.bf16; k.bias = L.bias; k.nkb = L.nkb;
+            if (layer == 0) k.seg[0] = SkinnySeg{xa_t, 0, XA / 16, 1};
+            else k.seg[0] = SkinnySeg{c->w_h1[p], 0, H1 / 16, 1};
+            k.partial_in = c->w_part[layer];
+            k.keep_weights = 1;
+        } else {
+            const PackedLinear& L = layer == 0 ? c->lstm0 : c->lstm1;
+            k.wp = L.wp; k.bf16 = L.bf16; k.bias = L.bias; k.nkb = L.nkb;
+            if (layer == 0) {
+                k.seg[0] = SkinnySeg{xa_t, 0, XA / 16, 1};
+                k.seg[1] = SkinnySeg{c->w_h1[p ^ 1], 0, H1 / 16, 1};
+            } else {
+                k.seg[0] = SkinnySeg{c->w_h1[p], 0, H1 / 16, 1};
+                k.seg[1] = SkinnySeg{c->w_h2[p ^ 1], 0, H2 / 16, 1};
+            }
+        }
+        k.N = H; k.c = layer == 0 ? c->w_c1 : c->w_c2; k.h = hb[p]; k.out_blocked = 1;
+        k.M = B; k.MT = MT;
+        k.dbg = d.stamps(t, 16 * (1 + layer));
+        const int tag = layer == 0 ? TAG_DEC_LSTM1 : TAG_DEC_LSTM2;
+        const int rc = d.prof.run(on, layer, [&] {
+            if (P.lean_x[layer]) {
                 LstmXArgs la{k.wp, k.seg[0].ptr, k.partial_in, k.c, k.h, nullptr, k.dbg, B, MT, H, 0, k.nkb};
-                if (mirror) {
+                if (P.mirror) {
                     la.xh = layer == 0 ? c->w_xa_h : c->w_h1_h[p];
                     la.hh = layer == 0 ? c->w_h1_h[p] : c->w_h2_h[p];
                 }
-                HIPCHECK(c, gt_launch_lstm_x(la, k.nkb, layer == 0 ? TAG_DEC_LSTM1 : TAG_DEC_LSTM2, k.bf16 != 0, s));
+                HIPCHECK(c, gt_launch_lstm_x(la, k.nkb, tag, k.bf16 != 0, d.s));
             } else
-            HIPCHECK(c, launch_skinny(c, EPI_LSTM, k, nullptr, (H + 3) / 4, s, layer == 0 ? TAG_DEC_LSTM1 : TAG_DEC_LSTM2));
-            if (prof) { int rce = prof_end(layer); if (rce) return rce; }
-        }
-        // 7. projection [h2, ctx] -> r mel frames + stop logit, written in place (Taco2.py:112-118,194-205)
-        if (prof) {     // empty bracket
-            int rce = prof_begin(4); if (rce) return rce;
-            rce = prof_end(4); if (rce) return rce;
-        }
-        memset(&k, 0, sizeof(k));
-        const PackedLinear& PJ = (use_z0 && t + 1 < steps) ? c->proj_z : c->proj;
-        k.wp = PJ.wp; k.bf16 = PJ.bf16; k.bias = PJ.bias;
-        k.seg[0] = SkinnySeg{c->w_h2[p], 0, H2 / 16, 1};
-        k.seg[1] = SkinnySeg{xa_t + (size_t)(P1 / 16) * BLK, 0, att / 16, 1};
-        k.nkb = PJ.nkb; k.M = B; k.N = c->proj_out; k.n_split = mel * r; k.MT = MT;
-        if (&PJ == &c->proj_z) {
-            k.N = c->z_col0 + P0; k.n_valid2 = c->proj_out; k.col3 = c->z_col0;
-            k.out3 = c->w_z0; k.ldo3 = P0;
-        }
-        k.out = c->w_pre + (size_t)t * r * mel; k.ldo = ld_pre;
-        k.out2 = c->w_stop + t; k.ldo2 = steps;
-        if (prof) { int rce = prof_begin(3); if (rce) return rce; }
-        if (split && t + 1 < steps && c->proj.nkb >= 32) {
+                HIPCHECK(c, launch_skinny(c, EPI_LSTM, k, nullptr, (H + 3) / 4, d.s, tag));
+            return 0;
+        });
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// 7. projection [h2, ctx] -> r mel frames + stop logit, written in place (Taco2.py:112-118,194-205); + the next step's prenet-0
+// pre-activations (proj_z) and, beside it, layer 2's recurrent tiles [0, co_tiles) for the next step
+int enqueue_projection(DecodeCall& d, int t, bool on) {
+    gsttaco_ctx* c = d.c;
+    const DecodePlan& P = d.P;
+    const int B = d.B, MT = d.MT, H2 = c->H2, P1 = c->P1, att = c->att, mel = c->cfg.mel_dim, r = c->r, p = t & 1;
+    float* xa_t = c->w_xa;
+    int rc = d.prof.run(on, 4, [] { return 0; });          // empty bracket
+    if (rc) return rc;
+    SkinnyArgs k;
+    memset(&k, 0, sizeof(k));
+    const PackedLinear& PJ = (P.z0 && t + 1 < d.steps) ? c->proj_z : c->proj;
+    k.wp = PJ.wp; k.bf16 = PJ.bf16; k.bias = PJ.bias;
+    k.seg[0] = SkinnySeg{c->w_h2[p], 0, H2 / 16, 1};
+    k.seg[1] = SkinnySeg{xa_t + (size_t)(P1 / 16) * MT * 256, 0, att / 16, 1};
+    k.nkb = PJ.nkb; k.M = B; k.N = c->proj_out; k.n_split = mel * r; k.MT = MT;
+    if (&PJ == &c->proj_z) {
+        k.N = c->z_col0 + c->P0; k.n_valid2 = c->proj_out; k.col3 = c->z_col0;
+        k.out3 = c->w_z0; k.ldo3 = c->P0;
+    }
+    k.out = c->w_pre + (size_t)t * r * mel; k.ldo = d.ld_pre;
+    k.out2 = c->w_stop + t; k.ldo2 = d.steps;
+    return d.prof.run(on, 3, [&] {
+        if (P.co_tiles > 0 && t + 1 < d.steps) {
             // co-scheduled workers: recurrent half of layer 2 for the NEXT step, h2_t . W_h + b (tiles [0, co_tiles))
             SkinnyArgs rk;
             memset(&rk, 0, sizeof(rk));
@@ -1394,24 +1394,57 @@ int enqueue_decode(gsttaco_ctx* c, hipStream_t s, int B, int Tv, int steps, bool
             rk.M = B; rk.N = H2; rk.MT = MT;
             rk.keep_weights = 1;
             rk.partial_out = c->w_part[1];
-            if (c->lean && k.bf16 == rk.bf16 && gt_proj_lean_supported(k.nkb, rk.nkb) && k.seg[0].nkb + k.seg[1].nkb == k.nkb &&
-                k.seg[0].nkb % 2 == 0) {
+            if (P.lean_proj) {
                 ProjArgs pa{k.wp, k.bias, k.seg[0].ptr, k.seg[1].ptr, k.seg[0].nkb, B, MT, k.N, k.n_split, k.n_valid2, k.col3,
-                            k.out, k.ldo, k.out2, k.ldo2, k.out3, k.ldo3,
-                            (c->stamps && t == steps / 2) ? c->w_dbg + 40 : nullptr};
-                if (mirror) { pa.xah = c->w_h2_h[p]; pa.xbh = c->w_xa_h + (size_t)(P1 / 32) * MT * 512; }
-                pa.both_m = (c->proj_both_m && B > 16 && B <= 32) ? 1 : 0;
-                HIPCHECK(c, gt_launch_proj_lean(pa, PJ.ntiles, rk.wp, rk.bias, rk.seg[0].ptr, rk.partial_out, 0, co_tiles,
-                                                c->co_worker_tiles, k.bf16 != 0, s));
+                            k.out, k.ldo, k.out2, k.ldo2, k.out3, k.ldo3, d.stamps(t, 40)};
+                if (P.mirror) { pa.xah = c->w_h2_h[p]; pa.xbh = c->w_xa_h + (size_t)(P1 / 32) * MT * 512; }
+                HIPCHECK(c, gt_launch_proj_lean(pa, PJ.ntiles, rk.wp, rk.bias, rk.seg[0].ptr, rk.partial_out, 0, P.co_tiles, k.bf16 != 0, d.s));
             } else
-            HIPCHECK(c, launch_skinny_co(c, k, PJ.ntiles, rk, 0, co_tiles, s));
-        } else {
-            HIPCHECK(c, launch_skinny(c, EPI_LINEAR, k, nullptr, PJ.ntiles, s));
+                HIPCHECK(c, gt_launch_skinny_co(k, PJ.ntiles, rk, 0, P.co_tiles, d.s));
+        } else
+            HIPCHECK(c, launch_skinny(c, EPI_LINEAR, k, nullptr, PJ.ntiles, d.s));
+        return 0;
+    });
+}
+
+int enqueue_decode(gsttaco_ctx* c, hipStream_t s, int B, int Tv, int steps, bool has_mask, bool has_noise, bool masked) {
+    const gsttaco_config& g = c->cfg;
+    const int MT = (B + 15) / 16;
+    DecodeCall d{c, s, plan_decode(c, B, Tv, has_mask), B, Tv, steps, MT, has_mask, has_noise, masked ? c->w_tok_len : nullptr,
+                 g.prenet_rate > 0.f ? 1.0f / (1.0f - g.prenet_rate) : 1.f, (int64_t)steps * c->r * g.mel_dim, ProfBrackets{c, s}};
+    const DecodePlan& P = d.P;
+    if (!P.persist) {
+        HIPCHECK(c, gt_launch_zero(c->w_h1[1], (size_t)MT * 16 * c->H1, s));
+        HIPCHECK(c, gt_launch_zero(c->w_h2[1], (size_t)MT * 16 * c->H2, s));
+        HIPCHECK(c, gt_launch_zero(c->w_c1, (size_t)B * c->H1, s));
+        HIPCHECK(c, gt_launch_zero(c->w_c2, (size_t)B * c->H2, s));
+        if (P.mirror) {
+            HIPCHECK(c, gt_launch_zero(reinterpret_cast<float*>(c->w_h1_h[1]), (size_t)MT * 16 * c->H1 / 2, s));
+            HIPCHECK(c, gt_launch_zero(reinterpret_cast<float*>(c->w_h2_h[1]), (size_t)MT * 16 * c->H2 / 2, s));
         }
-        if (prof) { int rce = prof_end(3); if (rce) return rce; }
     }
+    if (g.att_type == GSTTACO_ATT_LSA) HIPCHECK(c, gt_launch_zero(c->w_lsa_state, (size_t)B * Tv, s));   // Layers.py:356
+    if (P.fuse12 && !P.persist) HIPCHECK(c, gt_launch_zero(reinterpret_cast<float*>(c->w_arrive), (size_t)steps * GT_L12_NSH * 32, s));
+    // throughput mode: the whole decode's dropout masks and sigmoid noise are generated up front (same Philox streams the
+    // step kernels would draw) into the buffers injected tensors use, so no step spends time on random numbers
+    float* fm = (!has_mask && g.prenet_rate > 0.f && !P.masks_unused) ? c->w_masks : nullptr;
+    float* fn = (!has_noise && g.sigmoid_noise > 0.f && g.att_type != GSTTACO_ATT_LSA) ? c->w_noise : nullptr;
+    if (fm || fn) HIPCHECK(c, gt_launch_rng_fill(c->w_seed, fm, fn, steps, B, c->P0, c->P1, Tv, g.prenet_rate, s));
+    if (fm) d.has_mask = true;
+    if (fn) d.has_noise = true;
+    int rc = 0;
+    if (P.persist)
+        rc = enqueue_decode_persist(d);
+    else
+        for (int t = 0; t < steps && !rc; ++t) {
+            const bool on = c->prof_every > 0 && (t % c->prof_every) == 0;      // (bracketed steps)
+            rc = P.fused ? enqueue_front_fused(d, t, on) : enqueue_front_kernels(d, t);
+            if (!rc) rc = enqueue_lstm_cells(d, t, on);
+            if (!rc) rc = enqueue_projection(d, t, on);
+        }
+    if (rc) return rc;
     if (c->prof_every > 0)      // an un-bracketed capture must not forget the brackets of an earlier, bracketed graph
-        for (int i = 0; i < 5; ++i) c->prof_count[i] = nprof[i];
+        for (int i = 0; i < 5; ++i) c->prof_count[i] = d.prof.n[i];
     return 0;
 }
 
@@ -1877,7 +1910,7 @@ int gsttaco_create(const gsttaco_config* cfg, gsttaco_ctx** out) {
     c->proj_out = g.mel_dim * g.step_reduction + 1;
     c->conv_c = g.enc_filters[g.n_enc_conv - 1];
     c->P0 = g.prenet[0]; c->P1 = g.prenet[1]; c->H1 = g.dec_rnn[0]; c->H2 = g.dec_rnn[1]; c->att = g.att_size;
-    // The environment is read ONCE, here (INTEGRATION.md section 6 documents these nine; GSTTACO_LIB is the Python binding's).
+    // The environment is read ONCE, here (INTEGRATION.md section 6 documents these; GSTTACO_LIB is the Python binding's).
     auto env_int = [](const char* name, int dflt) { const char* e = getenv(name); return e && *e ? atoi(e) : dflt; };
     c->use_graph = env_int("GSTTACO_GRAPH", 1) != 0;
     c->graph_cache_max = std::max(0, env_int("GSTTACO_GRAPH_CACHE", c->graph_cache_max));
@@ -1889,11 +1922,10 @@ int gsttaco_create(const gsttaco_config* cfg, gsttaco_ctx** out) {
     c->fuse12 = env_int("GSTTACO_FUSED_LSTM", 1) != 0;
     c->persist_decode = env_int("GSTTACO_PERSIST_DECODE", 1) != 0;
     c->persist_rows = env_int("GSTTACO_PERSIST_ROWS", 128);
-    c->persist_split16 = env_int("GSTTACO_PERSIST_SPLIT16", 0) != 0 ? 1 : 0;
     // (round 6: the encoder's convolutions run on the Winograd split kernel's 128 workgroups = half the chip, and the GST branch -- 0.24 ms of
     // small launches -- now does hide beside them: 10.75 -> 10.5 ms per Inference_Step at the headline shape; when they filled the chip
     // the fork measured neutral, EXPERIMENTS round 5 item 6)
-    c->gst_fork = std::min(2, std::max(0, env_int("GSTTACO_GST_FORK", 1)));
+    c->gst_fork = env_int("GSTTACO_GST_FORK", 1) > 0;      // (0 or 1; the retired 2, a graph of its own for the GST branch, means 1)
     c->wino = env_int("GSTTACO_WINO", 4);
     if (c->wino != 0 && c->wino != 2) c->wino = 4;      // {0, 2, 4}; any other non-zero value (the old boolean's 1 included) means the default
     c->wino_split = env_int("GSTTACO_WINO_SPLIT", 1) != 0;
@@ -1902,21 +1934,6 @@ int gsttaco_create(const gsttaco_config* cfg, gsttaco_ctx** out) {
     if (c->enc_wino != 0 && c->enc_wino != 4) c->enc_wino = 2;
     c->pad_dec = env_int("GSTTACO_PAD_DECODER", 1) != 0;
     c->stamps = env_int("GSTTACO_STAMPS", 0) == 1;
-#ifdef GSTTACO_DEBUG
-    // experiment knobs, compiled only into -DGSTTACO_DEBUG builds (python -m gst_tacotron_amd.build --debug)
-    c->split_rec = env_int("GSTTACO_SPLIT_REC", 1) != 0;
-    c->fuse_prenet0 = env_int("GSTTACO_FUSE_PRENET0", 1) != 0;
-    c->keep_x_weights = env_int("GSTTACO_KEEP_X", 1);
-    c->co_tiles = env_int("GSTTACO_CO_TILES", -1);
-    c->worker_tiles = env_int("GSTTACO_WORKER_TILES", 2);
-    c->co_worker_tiles = env_int("GSTTACO_CO_WORKER_TILES", 1);
-    c->proj_both_m = env_int("GSTTACO_PROJ_BOTH_M", 0);
-    c->keep_hash = env_int("GSTTACO_KEEP_HASH", 1) != 0;
-    if (const char* e = getenv("GSTTACO_SCHED")) {      // "unit_fp32,unit_bf16,chain" in microseconds (cost model of plan_front_jobs)
-        double a = 0, b = 0, d = 0;
-        if (sscanf(e, "%lf,%lf,%lf", &a, &b, &d) == 3 && a > 0 && b > 0 && d >= 0) { c->sched_unit[0] = a; c->sched_unit[1] = b; c->sched_chain = d; }
-    }
-#endif
     build_manifest(c);
     c->counted = true;
     g_live_contexts.fetch_add(1);
@@ -2116,32 +2133,29 @@ int gsttaco_finalize_weights(gsttaco_ctx* c) {
         }
         const HostTensor &pk = T(c, "decoder.projection.kernel"), &pb = T(c, "decoder.projection.bias");
         if ((rc = pack_linear(c, &c->proj, {{pk.data.data(), (int)pk.shape[0]}}, c->proj_out, pb.data.data(), 0))) return rc;
-        if (c->fuse_prenet0) {
-            // The projection and the first prenet Dense are both linear and nothing sits between them at inference
-            // (Taco2.py:186 feeds decodings[:, -1] straight into the prenet): frame.W0 + b0 = [h2|ctx].(Wp_last.W0) +
-            // (bp_last.W0 + b0), Wp_last = the projection columns of the last of the r frames.  The fused columns ride in the
-            // projection launch, so the next step's front kernel starts at prenet 1 with 80 KB less to pull.
-            const HostTensor &k0 = T(c, "decoder.prenet0.kernel"), &b0 = T(c, "decoder.prenet0.bias");
-            const int K = (int)pk.shape[0], N0 = c->proj_out, mel = g.mel_dim, P0 = c->P0, last = (c->r - 1) * mel;
-            c->z_col0 = (N0 + 15) / 16 * 16;
-            const int NE = c->z_col0 + P0;
-            std::vector<float> we((size_t)K * NE, 0.f), be(NE, 0.f);
-            for (int k = 0; k < K; ++k) {
-                for (int n = 0; n < N0; ++n) we[(size_t)k * NE + n] = pk.data[(size_t)k * N0 + n];
-                for (int cc = 0; cc < P0; ++cc) {
-                    double a = 0.0;
-                    for (int j = 0; j < mel; ++j) a += (double)pk.data[(size_t)k * N0 + last + j] * (double)k0.data[(size_t)j * P0 + cc];
-                    we[(size_t)k * NE + c->z_col0 + cc] = (float)a;
-                }
-            }
-            for (int n = 0; n < N0; ++n) be[n] = pb.data[n];
+        // The projection and the first prenet Dense are both linear and nothing sits between them at inference
+        // (Taco2.py:186 feeds decodings[:, -1] straight into the prenet): frame.W0 + b0 = [h2|ctx].(Wp_last.W0) +
+        // (bp_last.W0 + b0), Wp_last = the projection columns of the last of the r frames.  The fused columns ride in the
+        // projection launch, so the next step's front kernel starts at prenet 1 with 80 KB less to pull.
+        const int K = (int)pk.shape[0], N0 = c->proj_out, mel = g.mel_dim, P0 = c->P0, last = (c->r - 1) * mel;
+        c->z_col0 = (N0 + 15) / 16 * 16;
+        const int NE = c->z_col0 + P0;
+        std::vector<float> we((size_t)K * NE, 0.f), be(NE, 0.f);
+        for (int k = 0; k < K; ++k) {
+            for (int n = 0; n < N0; ++n) we[(size_t)k * NE + n] = pk.data[(size_t)k * N0 + n];
             for (int cc = 0; cc < P0; ++cc) {
-                double a = b0.data[cc];
-                for (int j = 0; j < mel; ++j) a += (double)pb.data[last + j] * (double)k0.data[(size_t)j * P0 + cc];
-                be[c->z_col0 + cc] = (float)a;
+                double a = 0.0;
+                for (int j = 0; j < mel; ++j) a += (double)pk.data[(size_t)k * N0 + last + j] * (double)k0.data[(size_t)j * P0 + cc];
+                we[(size_t)k * NE + c->z_col0 + cc] = (float)a;
             }
-            if ((rc = pack_linear(c, &c->proj_z, {{we.data(), K}}, NE, be.data(), 0))) return rc;
         }
+        for (int n = 0; n < N0; ++n) be[n] = pb.data[n];
+        for (int cc = 0; cc < P0; ++cc) {
+            double a = b0.data[cc];
+            for (int j = 0; j < mel; ++j) a += (double)pb.data[last + j] * (double)k0.data[(size_t)j * P0 + cc];
+            be[c->z_col0 + cc] = (float)a;
+        }
+        if ((rc = pack_linear(c, &c->proj_z, {{we.data(), K}}, NE, be.data(), 0))) return rc;
     }
     // ---- postnet
     c->post_conv.resize(g.n_post);
@@ -2284,7 +2298,7 @@ int gsttaco_finalize_weights(gsttaco_ctx* c) {
     HIPCHECK(c, hipMemset(c->w_xa2, 0, Bp * (c->P1 + c->att) * sizeof(float)));
     if ((rc = dev_alloc(c, (void**)&c->w_z0g, std::max<size_t>(32, B) * 256 * sizeof(uint2)))) return rc;
     if ((rc = fa(&c->w_hpart, (size_t)2 * 64 * 1024))) return rc;         // (fp32 kernel: [2][32 tiles][512]; bf16 kernel: [2][64 tiles][1024])
-    if (B > 16 && (rc = fa(&c->w_stash, (size_t)256 * 16 * 512))) return rc;      // (the group kernels: batches above 32 rows, or 17..32 as two groups of 16)
+    if (B > 32 && (rc = fa(&c->w_stash, (size_t)256 * 16 * 512))) return rc;      // (the group kernels: batches above 32 rows)
     if ((rc = dev_alloc(c, (void**)&c->w_pctl, gt_persist_decode_ctl_words() * sizeof(uint32_t)))) return rc;
     // the give-up words of the in-kernel hand-offs live in host-mapped memory: the device raises them with a system-scope
     // atomic (failure path only), the host reads them without a synchronisation at the start of the next call
@@ -2397,7 +2411,7 @@ int gsttaco_decode(gsttaco_ctx* c, const float* enc, const float* gst, const int
     if (c->cfg.gst_use)
         HIPCHECK(c, hipMemcpyAsync(c->w_gst, gst, (size_t)B * c->cfg.gst_att * 4, hipMemcpyDeviceToDevice, s));
     if ((rc = stage_randomness(c, s, mask, noise, seed, B, Tv, steps))) return rc;
-    c->masks_lazy = masks_unused(c, Tv, mask != nullptr);       // (per CALL: a replayed graph does not pass through enqueue_decode)
+    c->masks_lazy = plan_decode(c, B, Tv, mask != nullptr).masks_unused;      // (per CALL: a replayed graph does not pass through enqueue_decode)
     const bool masked = token_lengths != nullptr;
     if (masked) HIPCHECK(c, hipMemcpyAsync(c->w_tok_len, token_lengths, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
     GraphKey key{3, B, Tv, 0, steps, mask != nullptr, noise != nullptr, c->prof_every, masked};
@@ -2542,34 +2556,14 @@ int gsttaco_inference_step(gsttaco_ctx* c, const int32_t* tokens, const int32_t*
     else if (mask)
         HIPCHECK(c, hipMemcpyAsync(c->w_masks, mask, (size_t)steps * B * (c->P0 + c->P1) * 4, hipMemcpyDeviceToDevice, s));
     if (noise) HIPCHECK(c, hipMemcpyAsync(c->w_noise, noise, (size_t)steps * B * Tv * 4, hipMemcpyDeviceToDevice, s));
-    c->masks_lazy = masks_unused(c, Tv, mask != nullptr);       // (per CALL: a replayed graph does not pass through enqueue_decode)
+    c->masks_lazy = plan_decode(c, B, Tv, mask != nullptr).masks_unused;      // (per CALL: a replayed graph does not pass through enqueue_decode)
     // Three graph segments: the encoder and the vocoder each contain a persistent BiLSTM launch and are chained process-wide
     // (run_cached, g_persist_event); the segment between them -- GST, value projection, the decode loop, the postnet: 95 % of the
     // call -- overlaps freely with other contexts' work.  The encoder / vocoder segments share their cached graphs with
     // gsttaco_encode / gsttaco_vocoder.
-    const bool fork = gst && c->gst_fork != 0;
-    const bool lean_enc = lean_bilstm_usable(c, c->enc_lean, B);
-    if (fork && c->gst_fork == 2 && lean_enc) {
-        // three graphs: GST on the side stream beside the convolutions' graph, joined in front of the BiLSTM's
-        HIPCHECK(c, hipEventRecord(c->ev_fork, s));
-        HIPCHECK(c, hipStreamWaitEvent(c->side_stream, c->ev_fork, 0));
-        GraphKey kg{8, B, 0, Tref1, 0, 0, 0, 0, 0};
-        if ((rc = run_cached(c, c->side_stream, kg, [&](hipStream_t st) { return enqueue_gst(c, st, B, Tref1); }))) return rc;
-        HIPCHECK(c, hipEventRecord(c->ev_join, c->side_stream));
-        GraphKey k6{6, B, Tv, 0, 0, 0, 0, 0, masked}, k7{7, B, Tv, 0, 0, 0, 0, 0, masked};
-        c->enc_part = 1;
-        rc = run_cached(c, s, k6, [&](hipStream_t st) { return enqueue_encoder(c, st, B, Tv, masked); });
-        c->enc_part = 0;
-        if (rc) return rc;
-        HIPCHECK(c, hipStreamWaitEvent(s, c->ev_join, 0));
-        c->enc_part = 2;
-        rc = run_cached(c, s, k7, [&](hipStream_t st) { return enqueue_encoder(c, st, B, Tv, masked); }, true);
-        c->enc_part = 0;
-        if (rc) return rc;
-    } else {
+    const bool fork = gst && c->gst_fork;
     GraphKey kenc{fork ? 9 : 1, B, Tv, fork ? Tref1 : 0, 0, 0, 0, 0, masked};
     if ((rc = run_cached(c, s, kenc, [&](hipStream_t st) { return enqueue_encoder(c, st, B, Tv, masked, fork ? Tref1 : 0); }, true))) return rc;
-    }
     GraphKey key{0, B, Tv, Tref1, steps, mask != nullptr, noise != nullptr, c->prof_every, masked};
     rc = run_cached(c, s, key, [&](hipStream_t st) {
         int r2 = 0;
@@ -2603,7 +2597,7 @@ int gsttaco_synchronize(gsttaco_ctx* c, void* stream) {
     if (!c) return GSTTACO_E_INVALID;
     HIPCHECK(c, hipStreamSynchronize((hipStream_t)stream));
     // (the GST fork's side stream is joined into `stream` by every call that forks; after an error return in between it may not be)
-    if (c->gst_fork != 0 && c->side_stream && !c->capturing) HIPCHECK(c, hipStreamSynchronize(c->side_stream));
+    if (c->gst_fork && c->side_stream && !c->capturing) HIPCHECK(c, hipStreamSynchronize(c->side_stream));
     note_give_up(c);
     if (c->gave_up) {
         // the ONLY place the give-up words are cleared: behind the synchronisation, nothing of this context polls them any more
@@ -2744,11 +2738,10 @@ int gsttaco_debug_raise_handoff_error(gsttaco_ctx* c, uint32_t bits) {
 
 int gsttaco_decode_plan(const gsttaco_ctx* c, int Tv, int32_t plan[3]) {
     if (!c || !plan || Tv < 1) return GSTTACO_E_INVALID;
-    const bool fused = c->fused_front && front_fits(c, Tv);
-    const bool split = fused && c->split_rec;
-    plan[0] = fused ? 1 : 0;
-    plan[1] = (split && c->proj_z.wp != nullptr) ? 1 : 0;
-    plan[2] = (split && c->lean && c->keep_x_weights && gt_lstm_x_supported(c->lstm_x[0].nkb) && gt_lstm_x_supported(c->lstm_x[1].nkb)) ? 1 : 0;
+    const DecodePlan p = plan_decode(c, c->cfg.max_batch, Tv, false);      // (these three answers do not depend on the batch)
+    plan[0] = p.fused ? 1 : 0;
+    plan[1] = p.z0 ? 1 : 0;
+    plan[2] = (p.lean_x[0] && p.lean_x[1]) ? 1 : 0;
     return 0;
 }
 
@@ -2757,14 +2750,14 @@ int64_t gsttaco_lstm_launch_bytes(const gsttaco_ctx* c, int which, int B) {
     // Algorithmic bytes of one launch at batch B and T_v = max_tokens: every weight once, every activation row once
     // in and once out (the re-reads of the shared activations by every workgroup are NOT algorithmic).
     const int64_t P0 = c->P0, P1 = c->P1, A = c->att, H1 = c->H1, H2 = c->H2, mel = c->cfg.mel_dim, Tv = c->cfg.max_tokens;
-    const bool fused = c->fused_front && c->split_rec;
+    const DecodePlan p = plan_decode(c, B, (int)Tv, false);
+    const bool fused = p.fused;         // (the recurrent halves ride beside the front launch)
     // weight bytes by the dtype the packs hold: bf16 under Use_Mixed_Precision for the LSTM / projection GEMMs (biases, activations,
     // partial sums and the prenet / query weights stay fp32)
     const int64_t wb = c->lstm_x[0].bf16 ? 2 : 4;
     auto gemm = [&](int64_t K, int64_t N, int64_t extra_row_floats) { return wb * K * N + 4 * N + 4 * (int64_t)B * (K + extra_row_floats); };
     const int64_t ntile2 = (H2 + 3) / 4;
-    int64_t co_tiles = std::max<int64_t>(0, std::min<int64_t>(ntile2, c->co_tiles >= 0 ? c->co_tiles : (B > 32 ? 128 : 64)));   // same rule as enqueue_decode
-    if (c->proj.nkb < 32) co_tiles = 0;
+    const int64_t co_tiles = p.co_tiles;
     const int64_t rec_tile = wb * H2 * 16 + 4 * 16 + 4 * (int64_t)B * 16;      // one layer-2 recurrent tile: weights + bias + its partial sums
     switch (which) {
         case 0:     // LSTM layer 1: x-half only when the recurrent half runs in the front launch

@@ -77,9 +77,8 @@ enum { TAG_GENERIC = 0, TAG_DEC_LSTM1 = 1, TAG_DEC_LSTM2 = 2, TAG_ENC_BILSTM = 3
 hipError_t gt_launch_skinny(int epi, const SkinnyArgs& a0, const SkinnyArgs* a1, int ntiles, hipStream_t stream,
                             int tag = TAG_GENERIC);
 // EPI_LINEAR main GEMM (tiles [0, ntiles)) plus co-scheduled worker workgroups in the same launch that compute tiles
-// [co_begin, co_end) of an independent EPI_PARTIAL GEMM `co` on CUs the small main grid leaves idle.
-hipError_t gt_launch_skinny_co(const SkinnyArgs& main_args, int ntiles, const SkinnyArgs& co, int co_begin, int co_end,
-                               int tiles_per_worker, hipStream_t stream);
+// [co_begin, co_end) of an independent EPI_PARTIAL GEMM `co` on CUs the small main grid leaves idle, one tile per worker.
+hipError_t gt_launch_skinny_co(const SkinnyArgs& main_args, int ntiles, const SkinnyArgs& co, int co_begin, int co_end, hipStream_t stream);
 
 // ---- lean decode-step kernels (lean_body.h): fp32, blocked operands, compile-time K; the host falls back to the
 // general kernels above for any other shape or precision.
@@ -169,12 +168,10 @@ struct ProjArgs {
     float* out3; int64_t ldo3;
     unsigned long long* dbg;                        // diagnostic stamps (8 slots) or NULL
     const uint16_t* xah = nullptr; const uint16_t* xbh = nullptr;   // bf16 mirrors of xa / xb or NULL (gt_proj_mc_kernel<true>)
-    int both_m = 0;     // batches of 17..32 rows: ONE workgroup per tile multiplies both 16-row M-tiles (the tile's weights leave the
-                        // memory side once) instead of one workgroup per (tile, M-tile)
 };
 bool gt_proj_lean_supported(int nkb_main, int nkb_co);
 hipError_t gt_launch_proj_lean(const ProjArgs& m, int ntiles, const float* co_wp, const float* co_bias, const float* co_x,
-                               float* co_out, int co_begin, int co_end, int tiles_per_worker, bool bf16, hipStream_t stream);
+                               float* co_out, int co_begin, int co_end, bool bf16, hipStream_t stream);
 
 // ---------------------------------------------------------------- gemm_conv.hip
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2 };
@@ -303,7 +300,6 @@ struct DecFrontArgs {
     // done (a job = a pair of tiles over every 32-row chunk of the batch; at 128 rows in fp32 it outlasts the chain).
     // Otherwise sched_pf = all jobs, the rest 0.
     int utt_jobs, sched_pf, sched_ne, sched_e, sched_y;
-    int worker_tiles;               // tiles per worker job: 1, or 0/2 = pairs sharing one pass over the activations
     LeanPartialArgs lrec[2];        // the same two GEMMs for the lean body (fp32, K = 1024); used when lean_rec != 0
     int lean_rec;                   // 0: general body, 1: lean fp32, 2: lean bf16
     int keep_hash;                  // throughput mode at dropout rate 0.5 and the reference's prenet / attention sizes: rows of
@@ -380,12 +376,12 @@ struct PersistDecodeArgs {
     unsigned long long* dbg;                           // diagnostic stamps [3 roles][32] or NULL (GSTTACO_STAMPS=1)
 };
 size_t gt_persist_decode_ctl_words();
-bool gt_persist_decode_supported(int mel, int r, int P0, int P1, int A, int H1, int H2, int B, int Tv, int pj_tiles, int pj_nkb, int slots, int split16, int bf16);
+bool gt_persist_decode_supported(int mel, int r, int P0, int P1, int A, int H1, int H2, int B, int Tv, int pj_tiles, int pj_nkb, int slots, int bf16);
 int gt_persist_decode_max_batch();
 bool gt_persist_decode_lsa_fits(int B, int Tv, int loc_f, int loc_k);       // the LSA chain: one group, <= 128 tokens, operands beside the memory tile
 hipError_t gt_persist_decode_init();                   // opt in to > 64 KiB dynamic LDS; once, outside stream capture
 int gt_persist_decode_blocks_per_cu();
-hipError_t gt_launch_persist_decode(const PersistDecodeArgs& a, const float* b0, int split16, hipStream_t stream);
+hipError_t gt_launch_persist_decode(const PersistDecodeArgs& a, const float* b0, hipStream_t stream);
 
 // ---------------------------------------------------------------- gst.hip
 struct Conv2dArgs {

@@ -1185,7 +1185,6 @@ bool gt_persist_decode_lsa_fits(int B, int Tv, int loc_f, int loc_k) {
     return B <= 32 && Tv <= 128 && loc_f >= 1 && loc_k >= 1 && pd_lds_floats(128) + pd_lsa_floats(loc_f, loc_k) <= pd_lds_floats(PD_TVMAX, true);   // (the opted-in LDS size)
 }
 
-// `split16`: a batch of 17..32 rows as two groups of 16 (experiment; the default is the one-group kernel with its helper workgroups)
 // the bf16 kernel's LDS: slabs of 64 rows; the chain workgroups' 16 (or, beside more than 128 tokens, 8) + their chain state
 __host__ __device__ constexpr int pdh_chain_floats(int tvp, int nslab) { return nslab * PDH_SLAB + 3 * PD_P + 2 * PD_A + 4 * tvp + tvp * PD_LDV; }
 __host__ __device__ constexpr int pdh_chain_slabs(int) { return 8; }      // (the chain workgroups' recurrent halves are the helpers': cell reductions only)
@@ -1195,27 +1194,25 @@ __host__ __device__ constexpr int pdh_lds_floats(int tvp) {
 constexpr int PDH_TVMAX = 192;
 static_assert(pdh_lds_floats(PDH_TVMAX) * 4 + 64 <= 160 * 1024, "the bf16 kernel's chain state must fit a CU's LDS");
 
-bool gt_persist_decode_supported(int mel, int r, int P0, int P1, int A, int H1, int H2, int B, int Tv, int pj_tiles, int pj_nkb, int slots, int split16, int bf16) {
+bool gt_persist_decode_supported(int mel, int r, int P0, int P1, int A, int H1, int H2, int B, int Tv, int pj_tiles, int pj_nkb, int slots, int bf16) {
     (void)mel; (void)r;
     if (!(P0 == PD_P && P1 == PD_P && A == PD_A && H1 == PD_H && H2 == PD_H && B >= 1 && Tv >= 1 && Tv <= PD_TVMAX && pj_nkb == PD_KBPJ && pj_tiles >= 1 &&
           slots >= PD_NWG))
         return false;
     if (bf16) return B <= PDH_BMAX && Tv <= PDH_TVMAX && 2 * B + pj_tiles * ((B + 15) / 16) <= PD_NWG;     // (a chain and a helper per utterance)
-    if (B <= 32 && !(split16 && B > 16)) return PD_UTT + pj_tiles * ((B + 15) / 16) + PD_HELP <= PD_NWG;
-    return B <= PD_BMAX && B + pj_tiles * (B <= 32 ? 1 : 2) <= PD_NWG;
+    if (B <= 32) return PD_UTT + pj_tiles * ((B + 15) / 16) + PD_HELP <= PD_NWG;
+    return B <= PD_BMAX && B + pj_tiles * 2 <= PD_NWG;
 }
 
 namespace {
 typedef void (*PdKernel)(PersistDecodeArgs);
 // which kernel a batch runs on: the one-group kernel up to 32 rows, groups of 32 rows above (2 up to 64 rows, else 4)
-PdKernel pd_kernel_for(int B, int split16, int* G, int* mtg) {
-    if (B <= 32 && !(split16 && B > 16)) { *G = 1; *mtg = 2; return gt_persist_decode_kernel; }
-    if (B <= 32) { *G = 2; *mtg = 1; return gt_persist_decode_g_kernel<2, 1>; }
-    *mtg = 2; *G = (B + 31) / 32;
-    return B <= 64 ? gt_persist_decode_g_kernel<2, 2> : gt_persist_decode_g_kernel<4, 2>;
+PdKernel pd_kernel_for(int B, int* G) {
+    if (B <= 32) { *G = 1; return gt_persist_decode_kernel; }
+    *G = (B + 31) / 32;
+    return B <= 64 ? gt_persist_decode_g_kernel<2> : gt_persist_decode_g_kernel<4>;
 }
-const PdKernel kPdKernels[] = {gt_persist_decode_kernel, gt_persist_decode_g_kernel<2, 1>, gt_persist_decode_g_kernel<2, 2>, gt_persist_decode_g_kernel<4, 2>,
-                               gt_persist_decode_h_kernel};
+const PdKernel kPdKernels[] = {gt_persist_decode_kernel, gt_persist_decode_g_kernel<2>, gt_persist_decode_g_kernel<4>, gt_persist_decode_h_kernel};
 }  // namespace
 
 hipError_t gt_persist_decode_init() {
@@ -1237,7 +1234,7 @@ int gt_persist_decode_blocks_per_cu() {
     return worst;
 }
 
-hipError_t gt_launch_persist_decode(const PersistDecodeArgs& a_in, const float* b0, int split16, hipStream_t stream) {
+hipError_t gt_launch_persist_decode(const PersistDecodeArgs& a_in, const float* b0, hipStream_t stream) {
     PersistDecodeArgs a = a_in;
     if (a.bf16) {           // mixed precision: one group of up to 64 rows
         a.G = 1;
@@ -1249,10 +1246,8 @@ hipError_t gt_launch_persist_decode(const PersistDecodeArgs& a_in, const float* 
         hipLaunchKernelGGL(gt_persist_decode_h_kernel, dim3(PD_NWG), dim3(PD_NT), (size_t)pdh_lds_floats(a.tvp) * 4, stream, a);
         return hipGetLastError();
     }
-    int mtg = 2;
     const bool lsa = a.att_type == GSTTACO_ATT_LSA;
-    if (lsa) split16 = 0;
-    const PdKernel k = pd_kernel_for(a.B, split16, &a.G, &mtg);
+    const PdKernel k = pd_kernel_for(a.B, &a.G);
     a.tvp = lsa ? 128 : (a.Tv + 63) / 64 * 64;       // (LSA: the 128-token chain only; gt_persist_decode_lsa_fits)
     const bool gk = k != gt_persist_decode_kernel;
     if (lsa && (gk || !gt_persist_decode_lsa_fits(a.B, a.Tv, a.loc_f, a.loc_k))) return hipErrorInvalidValue;

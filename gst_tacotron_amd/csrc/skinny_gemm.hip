@@ -32,12 +32,11 @@ __global__ __launch_bounds__(NW * 64) void gt_skinny_kernel(SkinnyArgs a0, Skinn
     gt_skinny_body<EPI, NW, NT>(A, blockIdx.x, blockIdx.y, lds);
 }
 
-// Projection (EPI_LINEAR, 11 workgroups at 161 columns) co-scheduled with recurrent-half partial GEMM tiles, CT tiles
-// per worker workgroup (CT = 2: one pass over the activations for both, gt_skinny_partial_multi).
-template <int NW, int CT>
-__global__ __launch_bounds__(NW * 64) void gt_skinny_co_kernel(SkinnyArgs main_args, SkinnyArgs co, int n_main, int co_begin, int co_end) {
-    constexpr int kLds = SkinnyLds<NW>::kFloats > SkinnyMultiLds<NW, CT>::kFloats ? SkinnyLds<NW>::kFloats : SkinnyMultiLds<NW, CT>::kFloats;
-    __shared__ __attribute__((aligned(16))) float lds[kLds];
+// Projection (EPI_LINEAR, 11 workgroups at 161 columns) co-scheduled with recurrent-half partial GEMM tiles, one tile per
+// worker workgroup.
+template <int NW>
+__global__ __launch_bounds__(NW * 64) void gt_skinny_co_kernel(SkinnyArgs main_args, SkinnyArgs co, int n_main, int co_begin) {
+    __shared__ __attribute__((aligned(16))) float lds[SkinnyLds<NW>::kFloats];
     const int mchunks = (main_args.M + 31) / 32;
     if ((int)blockIdx.x < n_main) {
         for (int mc = 0; mc < mchunks; ++mc) {
@@ -45,22 +44,17 @@ __global__ __launch_bounds__(NW * 64) void gt_skinny_co_kernel(SkinnyArgs main_a
             __syncthreads();
         }
     } else {
-        const int tile = co_begin + ((int)blockIdx.x - n_main) * CT;
+        const int tile = co_begin + ((int)blockIdx.x - n_main);
         for (int mc = 0; mc < mchunks; ++mc) {
-            if (CT == 1) gt_skinny_body<EPI_PARTIAL, NW, true>(co, tile, mc, lds);
-            else gt_skinny_partial_multi<NW, CT, true>(co, tile, min(CT, co_end - tile), mc, lds);
+            gt_skinny_body<EPI_PARTIAL, NW, true>(co, tile, mc, lds);
             __syncthreads();
         }
     }
 }
 
-hipError_t gt_launch_skinny_co(const SkinnyArgs& main_args, int ntiles, const SkinnyArgs& co, int co_begin, int co_end,
-                               int tiles_per_worker, hipStream_t stream) {
+hipError_t gt_launch_skinny_co(const SkinnyArgs& main_args, int ntiles, const SkinnyArgs& co, int co_begin, int co_end, hipStream_t stream) {
     const int nco = co_end > co_begin ? co_end - co_begin : 0;
-    if (tiles_per_worker == 2)
-        hipLaunchKernelGGL((gt_skinny_co_kernel<8, 2>), dim3(ntiles + (nco + 1) / 2), dim3(512), 0, stream, main_args, co, ntiles, co_begin, co_end);
-    else
-        hipLaunchKernelGGL((gt_skinny_co_kernel<8, 1>), dim3(ntiles + nco), dim3(512), 0, stream, main_args, co, ntiles, co_begin, co_end);
+    hipLaunchKernelGGL((gt_skinny_co_kernel<8>), dim3(ntiles + nco), dim3(512), 0, stream, main_args, co, ntiles, co_begin);
     return hipGetLastError();
 }
 
@@ -492,47 +486,32 @@ __device__ __forceinline__ void gt_pair_map(const int i, const int n, const int 
     mt = r / half;
 }
 
-// Projection (K = 1152 = 8 waves x 9 k-blocks) + co-scheduled layer-2 recurrent tiles (K = 1024 = 8 x 8), CT per worker.
-template <int CT, bool BF16>
-__global__ __launch_bounds__(512) void gt_proj_lean_kernel(ProjArgs P, LeanPartialArgs co, int n_main, int co_begin, int co_end) {
+// Projection (K = 1152 = 8 waves x 9 k-blocks) + co-scheduled layer-2 recurrent tiles (K = 1024 = 8 x 8).
+template <bool BF16>
+__global__ __launch_bounds__(512) void gt_proj_lean_kernel(ProjArgs P, LeanPartialArgs co, int n_main, int co_begin) {
     constexpr int NW = 8;
-    __shared__ __attribute__((aligned(16))) float lds[LeanLds<NW, CT>::kFloats];
-    const int mchunks = (P.M + 31) / 32;
+    __shared__ __attribute__((aligned(16))) float lds[LeanLds<NW, 1>::kFloats];
     if ((int)blockIdx.x >= n_main) {
         const bool st = P.dbg && (int)blockIdx.x == n_main && threadIdx.x == 0;
         if (st) P.dbg[4] = __builtin_amdgcn_s_memrealtime();
-        if (CT == 1) {          // one workgroup per (tile, 16-row M-tile): lighter jobs that end with the projection's own
-            int ct, cm;
-            gt_pair_map((int)blockIdx.x - n_main, (int)gridDim.x - n_main, P.MT, ct, cm);
-            gt_lean_partial<NW, BF16 ? 4 : 8, 1, BF16, true>(co, co_begin + ct, 1, cm, lds);
-        } else {
-            const int tile = co_begin + ((int)blockIdx.x - n_main) * CT;
-            for (int mc = 0; mc < mchunks; ++mc) {
-                gt_lean_partial<NW, BF16 ? 4 : 8, CT, BF16>(co, tile, min(CT, co_end - tile), mc, lds);
-                if (mc + 1 < mchunks) __syncthreads();
-            }
-        }
+        // one workgroup per (tile, 16-row M-tile): lighter jobs that end with the projection's own
+        int ct, cm;
+        gt_pair_map((int)blockIdx.x - n_main, (int)gridDim.x - n_main, P.MT, ct, cm);
+        gt_lean_partial<NW, BF16 ? 4 : 8, 1, BF16, true>(co, co_begin + ct, 1, cm, lds);
         if (st) P.dbg[5] = __builtin_amdgcn_s_memrealtime();
         return;
     }
     GT_STAMP(P.dbg, 0);
-    // main tiles: one workgroup per (tile, 16-row M-tile) -- 27 tiles would leave most CUs idle, so the rows are split; or
-    // (P.both_m) one workgroup per tile and both M-tiles: the same sums per output, the tile's weights requested once
+    // main tiles: one workgroup per (tile, 16-row M-tile) -- 27 tiles would leave most CUs idle, so the rows are split
     int tile, mt;
-    if (P.both_m) { tile = (int)blockIdx.x; mt = 0; }
-    else gt_pair_map((int)blockIdx.x, n_main, P.MT, tile, mt);
+    gt_pair_map((int)blockIdx.x, n_main, P.MT, tile, mt);
     const int col = threadIdx.x & 15;
-    const int row = P.both_m ? (threadIdx.x >> 4) : ((threadIdx.x >> 4) & 15), half = P.both_m ? 0 : (threadIdx.x >> 8);   // one M-tile: waves 0-3 reduce
+    const int row = (threadIdx.x >> 4) & 15, half = threadIdx.x >> 8;       // one M-tile: waves 0-3 reduce
     const int gcol = tile * 16 + col;
     const float bias = P.bias[gcol];
     f32x4 acc0[1] = {f32x4{0.f, 0.f, 0.f, 0.f}}, acc1[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
-    if (P.both_m) {
-        if (BF16) gt_lean_core_bf16<NW, 5, 1, false, false>(P.wp, tile, 1, LeanX{P.xa, P.xb, P.nkb_a}, P.MT, 0, 36, acc0, acc1);
-        else gt_lean_core<NW, 9, 1, false, false>(P.wp, tile, 1, LeanX{P.xa, P.xb, P.nkb_a}, P.MT, 0, acc0, acc1);
-    } else {
-        if (BF16) gt_lean_core_bf16<NW, 5, 1, false, true>(P.wp, tile, 1, LeanX{P.xa, P.xb, P.nkb_a}, P.MT, mt, 36, acc0, acc1);
-        else gt_lean_core<NW, 9, 1, false, true>(P.wp, tile, 1, LeanX{P.xa, P.xb, P.nkb_a}, P.MT, mt, acc0, acc1);
-    }
+    if (BF16) gt_lean_core_bf16<NW, 5, 1, false, true>(P.wp, tile, 1, LeanX{P.xa, P.xb, P.nkb_a}, P.MT, mt, 36, acc0, acc1);
+    else gt_lean_core<NW, 9, 1, false, true>(P.wp, tile, 1, LeanX{P.xa, P.xb, P.nkb_a}, P.MT, mt, acc0, acc1);
     GT_STAMP(P.dbg, 1);
     gt_lean_spill<NW, 1>(lds, acc0, acc1);          // (one M-tile: rows 16..31 of the slab are unused zeros)
     __syncthreads();
@@ -598,7 +577,7 @@ __global__ __launch_bounds__(512) void gt_proj_mc_kernel(ProjArgs P, LeanPartial
 bool gt_proj_lean_supported(int nkb_main, int nkb_co) { return nkb_main == 72 && (nkb_co == 64 || nkb_co == 0); }
 
 hipError_t gt_launch_proj_lean(const ProjArgs& m, int ntiles, const float* co_wp, const float* co_bias, const float* co_x,
-                               float* co_out, int co_begin, int co_end, int tiles_per_worker, bool bf16, hipStream_t stream) {
+                               float* co_out, int co_begin, int co_end, bool bf16, hipStream_t stream) {
     const int nco = co_end > co_begin ? co_end - co_begin : 0;
     LeanPartialArgs co{co_wp, co_bias, co_x, co_out, m.MT};
     if (co_x == m.xa) co.xh = m.xah;          // the workers multiply the same h2 the projection reads: its bf16 mirror, if there is one
@@ -609,15 +588,10 @@ hipError_t gt_launch_proj_lean(const ProjArgs& m, int ntiles, const float* co_wp
         else hipLaunchKernelGGL((gt_proj_mc_kernel<false>), g, dim3(512), 0, stream, m, co, n_mc, co_begin, co_end);
         return hipGetLastError();
     }
-    const int n_main = m.both_m ? ntiles : ntiles * m.MT;
-    const dim3 g2(n_main + (nco + 1) / 2), g1(n_main + nco * m.MT);
-    if (tiles_per_worker == 2) {
-        if (bf16) hipLaunchKernelGGL((gt_proj_lean_kernel<2, true>), g2, dim3(512), 0, stream, m, co, n_main, co_begin, co_end);
-        else hipLaunchKernelGGL((gt_proj_lean_kernel<2, false>), g2, dim3(512), 0, stream, m, co, n_main, co_begin, co_end);
-    } else {
-        if (bf16) hipLaunchKernelGGL((gt_proj_lean_kernel<1, true>), g1, dim3(512), 0, stream, m, co, n_main, co_begin, co_end);
-        else hipLaunchKernelGGL((gt_proj_lean_kernel<1, false>), g1, dim3(512), 0, stream, m, co, n_main, co_begin, co_end);
-    }
+    const int n_main = ntiles * m.MT;
+    const dim3 g(n_main + nco * m.MT);
+    if (bf16) hipLaunchKernelGGL((gt_proj_lean_kernel<true>), g, dim3(512), 0, stream, m, co, n_main, co_begin);
+    else hipLaunchKernelGGL((gt_proj_lean_kernel<false>), g, dim3(512), 0, stream, m, co, n_main, co_begin);
     return hipGetLastError();
 }
 

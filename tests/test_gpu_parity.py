@@ -341,8 +341,6 @@ PERSIST_CASES = [
     # pipe as in dec_front_lsa.hip, the score's channel halves summed as that kernel's two waves sum them): against the launch path's
     # fused front end; filter / tap counts off the MFMA granules; smoothing; masked
     (32, 128, "LSA", "hashed", 100, {}), (11, 90, "LSA", "injected", 100, {}), (20, 128, "LSA/20/9/s", "masked", 60, {}), (7, 33, "LSA/8/7", "nodrop", 100, {}),
-    # 17..32 rows as two groups of 16 (GSTTACO_PERSIST_SPLIT16=1: the measured alternative to the helpers of the one-group kernel)
-    (32, 128, "SMA", "hashed", 100, {"GSTTACO_PERSIST_SPLIT16": "1"}), (23, 70, "BMA", "injected", 100, {"GSTTACO_PERSIST_SPLIT16": "1"}),
 ]
 
 
