@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libgsttaco.so")
 
 MAX_LAYERS = 8
-ABI_VERSION = 12
+ABI_VERSION = 13
 ATT_CODES = {"BMA": 0, "SMA": 1, "LSA": 2}
 
 # every symbol include/gsttaco.h declares
@@ -29,8 +29,38 @@ EXPORTED_SYMBOLS = (
     "gsttaco_mel_frontend", "gsttaco_mel_basis", "gsttaco_griffin_lim", "gsttaco_crc32c",
     "gsttaco_set_profiling", "gsttaco_get_profile", "gsttaco_lstm_launch_bytes", "gsttaco_debug_stamps", "gsttaco_decode_plan", "gsttaco_debug_randomness",
     "gsttaco_set_graph_policy", "gsttaco_graph_cache_size", "gsttaco_debug_handoff_error", "gsttaco_debug_raise_handoff_error", "gsttaco_debug_counters",
-    "gsttaco_synchronize",
+    "gsttaco_synchronize", "gsttaco_debug_conv_prepare", "gsttaco_debug_conv_run",
 )
+
+# GSTTACO_CONV_V_*: the conv/GEMM dispatcher's kernel instantiations (gsttaco_debug_conv_run reports which one ran)
+CONV_V = {
+    "IG_1411": 0, "IG_2212": 1, "IG_2222": 2, "IG_4113": 3, "IG_4112": 4, "IG_4111": 5,
+    "C2D_1411": 6, "C2D_4112": 7, "C2D_4111": 8,
+    "WINO4": 9, "WINO2": 10, "WINO4_S": 11, "WINO2_S": 12, "WINO4_S_X3": 13, "WINO2_S_X3": 14,
+    "GEMM_SPLIT": 15,
+    "C5_RN4": 16, "C5_RN4_XB": 17, "C5_RN4_OB": 18, "C5_RN4_XB_OB": 19,
+    "C5_RN2": 20, "C5_RN2_XB": 21, "C5_RN2_OB": 22, "C5_RN2_XB_OB": 23,
+    "BF16_RM2": 24, "BF16_RM2_XB": 25, "BF16_RM2_OB": 26, "BF16_RM2_XB_OB": 27,
+    "BF16_RM1": 28, "BF16_RM1_XB": 29, "BF16_RM1_OB": 30, "BF16_RM1_XB_OB": 31,
+}
+CONV_V_INVALID = -1
+CONV_V_NAMES = {v: k for k, v in CONV_V.items()}
+# GSTTACO_CONV_FORM_*: the weight forms gsttaco_debug_conv_prepare builds
+CONV_FORM = {"FP32": 1, "BF16": 2, "WINO2": 4, "WINO4": 8, "WINO_SPLIT": 16, "GEMM_SPLIT": 32}
+
+
+class ConvDesc(ctypes.Structure):
+    _fields_ = [("taps", ctypes.c_int32), ("cin", ctypes.c_int32), ("n", ctypes.c_int32), ("ldw", ctypes.c_int32),
+                ("forms", ctypes.c_int32)]
+
+
+class ConvCall(ctypes.Structure):
+    _fields_ = [("forms", ctypes.c_int32), ("B", ctypes.c_int32), ("T", ctypes.c_int32), ("pad_before", ctypes.c_int32),
+                ("act", ctypes.c_int32), ("ldo", ctypes.c_int64),
+                ("pool2", ctypes.c_int32), ("x_bf16", ctypes.c_int32), ("out_bf16", ctypes.c_int32), ("wino_x3", ctypes.c_int32),
+                ("wino_min_wgs", ctypes.c_int32),
+                ("conv2d", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("Wo", ctypes.c_int32), ("kw", ctypes.c_int32),
+                ("stride", ctypes.c_int32), ("pad_h", ctypes.c_int32), ("pad_w", ctypes.c_int32), ("xb", ctypes.c_int64)]
 
 _I32A = ctypes.c_int32 * MAX_LAYERS
 
@@ -126,6 +156,10 @@ def load_library(path=None):
     lib.gsttaco_debug_counters.restype = ctypes.c_int
     lib.gsttaco_synchronize.argtypes = [vp, vp]
     lib.gsttaco_synchronize.restype = ctypes.c_int
+    lib.gsttaco_debug_conv_prepare.argtypes = [vp, ctypes.POINTER(ConvDesc), f32p, f32p, f32p, ctypes.POINTER(ctypes.c_int)]
+    lib.gsttaco_debug_conv_prepare.restype = ctypes.c_int
+    lib.gsttaco_debug_conv_run.argtypes = [vp, i32, ctypes.POINTER(ConvCall), vp, vp, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int), vp]
+    lib.gsttaco_debug_conv_run.restype = ctypes.c_int
     for fn in ("gsttaco_create", "gsttaco_num_weights", "gsttaco_weight_info", "gsttaco_load_weight",
                "gsttaco_finalize_weights", "gsttaco_encode", "gsttaco_gst", "gsttaco_decode", "gsttaco_postnet", "gsttaco_vocoder",
                "gsttaco_inference_step", "gsttaco_set_profiling", "gsttaco_get_profile", "gsttaco_mel_frontend",

@@ -196,7 +196,7 @@ __global__ __launch_bounds__(WT, 2) void gt_conv_wino5s_kernel(ConvGemmArgs A, c
         /* youngest" when it consumes them -- with this step's DMAs already in the queue that wait covered them too (vmcnt(1) in */ \
         /* front of the slice's last transform: a DMA's whole latency, exposed in two or three of eight steps). */ \
         dma_b(bnx, XI2, min((s_) + (XI + 2 >= AL ? 1 : 0), nsl - 1) * WS_BK);                                      \
-        if constexpr (XI == 0) wino_issue_taps<MO>(A, rs_x, voff, first, len, min((s_) + 1, nsl - 1) * WS_BK, (s_) + 1 < nsl, DNXT); \
+        if constexpr (XI == 0) wino_issue_taps<MO>(A, rs_x, voff, first, len, min((s_) + 1, nsl - 1) * WS_BK, (tid & 7) * 4, (s_) + 1 < nsl, DNXT); \
         /* the NEXT step's B planes have landed (requested a step ago; loads complete in order): what may still be in flight is this */ \
         /* step's three DMAs and, at XI == 0 and 1, the next slice's AL tap loads requested behind XI == 0's DMAs */ \
         if constexpr (XI <= 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPL + AL) : "memory");                    \
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(WT, 2) void gt_conv_wino5s_kernel(ConvGemmArgs A, c
     WS_STEP(4, DCUR, DNXT, DCUR, s_)                                                                               \
     if constexpr (AL == 8) { WS_STEP(5, DCUR, DNXT, DCUR, s_) WS_STEP(6 % AL, DCUR, DNXT, DCUR, s_) WS_STEP(7 % AL, DCUR, DNXT, DNXT, s_) } \
     else { WS_STEP(5, DCUR, DNXT, DNXT, s_) }
-    wino_issue_taps<MO>(A, rs_x, voff, first, len, 0, true, dE);
+    wino_issue_taps<MO>(A, rs_x, voff, first, len, 0, (tid & 7) * 4, true, dE);
     dma_b(0, 0, 0);
     dma_b(1, 1, 0);
     int bcur = 0, bnx = 2;                  // B stage of the current step / of the step two ahead (scalar, cycling 0 1 2)

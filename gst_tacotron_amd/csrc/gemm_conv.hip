@@ -15,6 +15,7 @@
 // bank groups); the next slice's global loads are issued before the current slice's MFMAs.
 #include "device_utils.h"
 #include "kernels.h"
+#include "../../include/gsttaco.h"
 #include <stdlib.h>
 
 #define BK 32
@@ -751,8 +752,8 @@ __global__ __launch_bounds__(WT, 2) void gt_conv_wino5_kernel(ConvGemmArgs A, co
 #pragma unroll
         for (int e = 0; e < 16; ++e) M[xi][e] = 0.f;
     const int kh = lane >> 5, l31 = lane & 31;
-    // wino_cin = Cin rounded up to TWO slice widths: U holds zero rows for the padding channels, whose x operand is whatever
-    // follows in memory (the next row's first channels, or zero past the tensor's end: the descriptor covers exactly B*T*Cin)
+    // wino_cin = Cin rounded up to TWO slice widths: U holds zero rows for the padding channels, whose x operand reads as zero
+    // (wino_issue_taps: out-of-range offset, never the next row's channels)
     const int nsl = A.wino_cin / BK;                      // even, >= 4 (gt_conv_wino5_applies)
     int cur = 0;                                          // LDS stage the current step's operands sit in
 
@@ -811,7 +812,7 @@ __global__ __launch_bounds__(WT, 2) void gt_conv_wino5_kernel(ConvGemmArgs A, co
         constexpr int XI1 = (XI + 1) % AL;                                                                         \
         /* (past the last step: a valid address whose data is never used) */                                      \
         wino_issue_b(A, rs_u, vb0, vb1, XI1, min((s_) + (XI + 1 >= AL ? 1 : 0), nsl - 1) * BK, bP0, bP1);          \
-        if constexpr (XI == 0) wino_issue_taps<MO>(A, rs_x, voff, first, len, min((s_) + 1, nsl - 1) * BK, (s_) + 1 < nsl, DNXT); \
+        if constexpr (XI == 0) wino_issue_taps<MO>(A, rs_x, voff, first, len, min((s_) + 1, nsl - 1) * BK, (tid & 7) * 4, (s_) + 1 < nsl, DNXT); \
         WINO_ABL_MMA(M[XI]);                                                                                      \
         if constexpr (XI + 1 < AL) WINO_ABL_STORE(cur ^ 1, wino_xform<MO, XI1>(DCUR), bP0, bP1);                  \
         else WINO_ABL_STORE(cur ^ 1, wino_xform<MO, 0>(DNXT), bP0, bP1);                                          \
@@ -831,7 +832,7 @@ __global__ __launch_bounds__(WT, 2) void gt_conv_wino5_kernel(ConvGemmArgs A, co
 #define WINO_STAMP_STEP() do { } while (0)
 #endif
     // B(g) lives in set g & 1 (ALPHA is even).  Prologue: taps of slice 0, B of steps 0 and 1, operands of step 0 into stage 0.
-    wino_issue_taps<MO>(A, rs_x, voff, first, len, 0, true, dE);
+    wino_issue_taps<MO>(A, rs_x, voff, first, len, 0, (tid & 7) * 4, true, dE);
     wino_issue_b(A, rs_u, vb0, vb1, 0, 0, bP0, bP1);
     store_slice(0, wino_xform<MO, 0>(dE), bP0, bP1);
     __syncthreads();
@@ -882,41 +883,18 @@ bool gt_conv_wino5_applies(const ConvGemmArgs& a) {
            a.wino_cin >= 4 * BK && a.wino_cin >= a.Cin && (a.ldw == 0 || a.ldw == a.N);
 }
 
-hipError_t gt_launch_conv_gemm(const ConvGemmArgs& a, hipStream_t stream) {
+// Which instantiation gt_launch_conv_gemm runs for `a` (GSTTACO_CONV_V_*, include/gsttaco.h), or GSTTACO_CONV_V_INVALID: the launch
+// switches on this, so what it reports is what runs.  (The 2-D mode's batch slicing, inputs of 2 GiB or more: its slices' variant.)
+int gt_conv_gemm_variant(const ConvGemmArgs& a) {
     const int M = a.B * a.T;
-    if (gt_conv5_bf16_applies(a)) {         // five taps sharing one staged input tile (256 frames of one utterance per workgroup)
-        const int tiles_t = (a.T + C5_BM - 1) / C5_BM;
-        const int nx8 = (a.B * tiles_t + 7) / 8 * 8;         // (1-D grids: frame tiles rounded up to 8 x column blocks, see the kernel)
-        const dim3 g4(nx8 * ((a.N + 255) / 256)), g2(nx8);
-#define GT_C5_LAUNCH(XB, OB)                                                                                                       \
-        do {                                                                                                                       \
-            if (a.N > 128) hipLaunchKernelGGL((gt_conv5_bf16_kernel<4, XB, OB>), g4, dim3(512), c5_lds_bytes<4>(), stream, a);     \
-            else hipLaunchKernelGGL((gt_conv5_bf16_kernel<2, XB, OB>), g2, dim3(512), c5_lds_bytes<2>(), stream, a);               \
-        } while (0)
-        if (a.x_bf16 && a.out_bf16) GT_C5_LAUNCH(true, true);
-        else if (a.x_bf16) GT_C5_LAUNCH(true, false);
-        else if (a.out_bf16) GT_C5_LAUNCH(false, true);
-        else GT_C5_LAUNCH(false, false);
-#undef GT_C5_LAUNCH
-        return hipGetLastError();
-    }
+    const int xo = (a.x_bf16 ? 1 : 0) + (a.out_bf16 ? 2 : 0);     // (the bf16 kernels' XB / OB forms follow their base in the list)
+    if (gt_conv5_bf16_applies(a))           // five taps sharing one staged input tile (256 frames of one utterance per workgroup)
+        return (a.N > 128 ? GSTTACO_CONV_V_C5_RN4 : GSTTACO_CONV_V_C5_RN2) + xo;
     if (a.wt_bf16) {
-        const int nb = (a.N + 127) / 128;
-        const bool big = ((M + 127) / 128) * nb >= 256;
-        const dim3 gb((M + 127) / 128, nb), gs((M + 63) / 64, nb);
-#define GT_CG_LAUNCH(XB, OB)                                                                                              \
-        do {                                                                                                              \
-            if (big) hipLaunchKernelGGL((gt_conv_gemm_bf16_kernel<2, XB, OB>), gb, dim3(256), 0, stream, a);              \
-            else hipLaunchKernelGGL((gt_conv_gemm_bf16_kernel<1, XB, OB>), gs, dim3(256), 0, stream, a);                  \
-        } while (0)
-        if (a.x_bf16 && a.out_bf16) GT_CG_LAUNCH(true, true);
-        else if (a.x_bf16) GT_CG_LAUNCH(true, false);
-        else if (a.out_bf16) GT_CG_LAUNCH(false, true);
-        else GT_CG_LAUNCH(false, false);
-#undef GT_CG_LAUNCH
-        return hipGetLastError();
+        const bool big = ((M + 127) / 128) * ((a.N + 127) / 128) >= 256;
+        return (big ? GSTTACO_CONV_V_BF16_RM2 : GSTTACO_CONV_V_BF16_RM1) + xo;
     }
-    if (gt_gemm_split_applies(a) && ((M + 63) / 64) * ((a.N + 127) / 128) >= 48) return gt_launch_gemm_split(a, stream);
+    if (gt_gemm_split_applies(a) && ((M + 63) / 64) * ((a.N + 127) / 128) >= 48) return GSTTACO_CONV_V_GEMM_SPLIT;
     if (gt_conv_wino5_applies(a)) {
         // worth it when the grid (nearly) fills the chip: the 4096-row encoder convs would leave half of it idle (one round of
         // 128 Winograd workgroups ~275 us against 136 us for the implicit GEMM); 250 workgroups (the 512 -> 80 layer) do pay.
@@ -924,64 +902,92 @@ hipError_t gt_launch_conv_gemm(const ConvGemmArgs& a, hipStream_t stream) {
         const int min_wgs = a.wino_min_wgs > 0 ? a.wino_min_wgs : 240;
         const int nb = (a.N + 127) / 128;
         const int P4 = a.B * ((a.T + 3) / 4), P2 = a.B * ((a.T + 1) / 2);
-        // (1-D grids: 8 XCDs x ceil(row blocks / 8) x column blocks, see the kernel)
-        if (a.wino_u4 && ((P4 + 63) / 64) * nb >= min_wgs) {
-            if (a.wino_s4) return gt_launch_conv_wino5s(a, 4, stream);
-            hipLaunchKernelGGL(gt_conv_wino5_kernel<4>, dim3(8 * (((P4 + 63) / 64 + 7) / 8) * nb), dim3(WT), 0, stream, a, a.wino_u4);
-            return hipGetLastError();
-        }
-        if (((P2 + 63) / 64) * nb >= min_wgs) {
-            if (a.wino_s) return gt_launch_conv_wino5s(a, 2, stream);
-            hipLaunchKernelGGL(gt_conv_wino5_kernel<2>, dim3(8 * (((P2 + 63) / 64 + 7) / 8) * nb), dim3(WT), 0, stream, a, a.wino_u);
-            return hipGetLastError();
-        }
+        if (a.wino_u4 && ((P4 + 63) / 64) * nb >= min_wgs)
+            return a.wino_s4 ? (a.wino_x3 ? GSTTACO_CONV_V_WINO4_S_X3 : GSTTACO_CONV_V_WINO4_S) : GSTTACO_CONV_V_WINO4;
+        if (((P2 + 63) / 64) * nb >= min_wgs)
+            return a.wino_s ? (a.wino_x3 ? GSTTACO_CONV_V_WINO2_S_X3 : GSTTACO_CONV_V_WINO2_S) : GSTTACO_CONV_V_WINO2;
     }
     if (a.conv2d) {
         if ((size_t)a.B * a.xb * 4 >= 0x7FFFFFFFull) {
-            // the 2-D gather addresses the input as ONE buffer resource (< 2 GiB): a larger input goes slice by slice over the batch
-            if ((size_t)a.xb * 4 >= 0x7FFFFFFFull) return hipErrorInvalidValue;        // (one utterance alone is too large)
-            const int per = (int)(0x7FFFFFFEull / ((size_t)a.xb * 4));
-            for (int b0 = 0; b0 < a.B; b0 += per) {
-                ConvGemmArgs s2 = a;
-                s2.B = a.B - b0 < per ? a.B - b0 : per;
-                s2.x = a.x + (size_t)b0 * a.xb;
-                s2.out = a.out + (size_t)b0 * a.T * a.ldo;
-                if (a.res) s2.res = a.res + (size_t)b0 * a.T * a.ldo;
-                if (a.rowbias) s2.rowbias = a.rowbias + (size_t)b0 * a.N;
-                if (a.row_len) s2.row_len = a.row_len + b0;
-                const hipError_t e = gt_launch_conv_gemm(s2, stream);
-                if (e != hipSuccess) return e;
-            }
-            return hipSuccess;
+            if ((size_t)a.xb * 4 >= 0x7FFFFFFFull) return GSTTACO_CONV_V_INVALID;      // (one utterance alone is too large)
+            ConvGemmArgs s2 = a;
+            s2.B = (int)(0x7FFFFFFEull / ((size_t)a.xb * 4));
+            return gt_conv_gemm_variant(s2);
         }
-        if (a.N > 64) hipLaunchKernelGGL((gt_conv_gemm_kernel<1, 4, 1, 1, true>), dim3((M + 31) / 32, (a.N + 127) / 128), dim3(256), 0, stream, a);
-        else if (a.N > 32) hipLaunchKernelGGL((gt_conv_gemm_kernel<4, 1, 1, 2, true>), dim3((M + 127) / 128, 1), dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL((gt_conv_gemm_kernel<4, 1, 1, 1, true>), dim3((M + 127) / 128, 1), dim3(256), 0, stream, a);
-        return hipGetLastError();
+        return a.N > 64 ? GSTTACO_CONV_V_C2D_1411 : a.N > 32 ? GSTTACO_CONV_V_C2D_4112 : GSTTACO_CONV_V_C2D_4111;
     }
     if (a.N > 96) {
-        const int wg128 = ((M + 127) / 128) * ((a.N + 127) / 128);
-        if (wg128 >= 256) {
-            dim3 grid((M + 127) / 128, (a.N + 127) / 128);
-            hipLaunchKernelGGL((gt_conv_gemm_kernel<2, 2, 2, 2>), grid, dim3(256), 0, stream, a);
-        } else if (((M + 63) / 64) * ((a.N + 127) / 128) <= 256) {
-            // few rows (the 4096-row encoder convs): 32 x 128 tiles give two workgroups per CU instead of one wave per SIMD
-            dim3 grid((M + 31) / 32, (a.N + 127) / 128);
-            hipLaunchKernelGGL((gt_conv_gemm_kernel<1, 4, 1, 1>), grid, dim3(256), 0, stream, a);
-        } else {
-            dim3 grid((M + 63) / 64, (a.N + 127) / 128);
-            hipLaunchKernelGGL((gt_conv_gemm_kernel<2, 2, 1, 2>), grid, dim3(256), 0, stream, a);
-        }
-    } else if (a.N > 64) {
-        dim3 grid((M + 127) / 128, 1);
-        hipLaunchKernelGGL((gt_conv_gemm_kernel<4, 1, 1, 3>), grid, dim3(256), 0, stream, a);
-    } else if (a.N > 32) {
-        dim3 grid((M + 127) / 128, 1);
-        hipLaunchKernelGGL((gt_conv_gemm_kernel<4, 1, 1, 2>), grid, dim3(256), 0, stream, a);
-    } else {
-        dim3 grid((M + 127) / 128, 1);
-        hipLaunchKernelGGL((gt_conv_gemm_kernel<4, 1, 1, 1>), grid, dim3(256), 0, stream, a);
+        if (((M + 127) / 128) * ((a.N + 127) / 128) >= 256) return GSTTACO_CONV_V_IG_2222;
+        // few rows (the 4096-row encoder convs): 32 x 128 tiles give two workgroups per CU instead of one wave per SIMD
+        if (((M + 63) / 64) * ((a.N + 127) / 128) <= 256) return GSTTACO_CONV_V_IG_1411;
+        return GSTTACO_CONV_V_IG_2212;
     }
+    return a.N > 64 ? GSTTACO_CONV_V_IG_4113 : a.N > 32 ? GSTTACO_CONV_V_IG_4112 : GSTTACO_CONV_V_IG_4111;
+}
+
+hipError_t gt_launch_conv_gemm(const ConvGemmArgs& a, hipStream_t stream) {
+    const int M = a.B * a.T;
+    if (a.conv2d && (size_t)a.B * a.xb * 4 >= 0x7FFFFFFFull && !gt_conv5_bf16_applies(a) && !a.wt_bf16) {
+        // the 2-D gather addresses the input as ONE buffer resource (< 2 GiB): a larger input goes slice by slice over the batch
+        if ((size_t)a.xb * 4 >= 0x7FFFFFFFull) return hipErrorInvalidValue;        // (one utterance alone is too large)
+        const int per = (int)(0x7FFFFFFEull / ((size_t)a.xb * 4));
+        for (int b0 = 0; b0 < a.B; b0 += per) {
+            ConvGemmArgs s2 = a;
+            s2.B = a.B - b0 < per ? a.B - b0 : per;
+            s2.x = a.x + (size_t)b0 * a.xb;
+            s2.out = a.out + (size_t)b0 * a.T * a.ldo;
+            if (a.res) s2.res = a.res + (size_t)b0 * a.T * a.ldo;
+            if (a.rowbias) s2.rowbias = a.rowbias + (size_t)b0 * a.N;
+            if (a.row_len) s2.row_len = a.row_len + b0;
+            const hipError_t e = gt_launch_conv_gemm(s2, stream);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+    const int tiles_t = (a.T + C5_BM - 1) / C5_BM;
+    const int nx8 = (a.B * tiles_t + 7) / 8 * 8;         // (C5: 1-D grids, frame tiles rounded up to 8 x column blocks, see the kernel)
+    const dim3 c5g4(nx8 * ((a.N + 255) / 256)), c5g2(nx8);
+    const int nb = (a.N + 127) / 128;
+    const dim3 bfg2((M + 127) / 128, nb), bfg1((M + 63) / 64, nb);
+    const int P4 = a.B * ((a.T + 3) / 4), P2 = a.B * ((a.T + 1) / 2);
+    // (Winograd: 1-D grids, 8 XCDs x ceil(row blocks / 8) x column blocks, see the kernel)
+    const dim3 wg4(8 * (((P4 + 63) / 64 + 7) / 8) * nb), wg2(8 * (((P2 + 63) / 64 + 7) / 8) * nb);
+    const dim3 g128((M + 127) / 128, nb), g64((M + 63) / 64, nb), g32((M + 31) / 32, nb), g128x1((M + 127) / 128, 1);
+#define GT_V(V, K, G, LDS) case V: hipLaunchKernelGGL(K, G, dim3(256), LDS, stream, a); break
+    switch (gt_conv_gemm_variant(a)) {
+    case GSTTACO_CONV_V_C5_RN4: hipLaunchKernelGGL((gt_conv5_bf16_kernel<4, false, false>), c5g4, dim3(512), c5_lds_bytes<4>(), stream, a); break;
+    case GSTTACO_CONV_V_C5_RN4_XB: hipLaunchKernelGGL((gt_conv5_bf16_kernel<4, true, false>), c5g4, dim3(512), c5_lds_bytes<4>(), stream, a); break;
+    case GSTTACO_CONV_V_C5_RN4_OB: hipLaunchKernelGGL((gt_conv5_bf16_kernel<4, false, true>), c5g4, dim3(512), c5_lds_bytes<4>(), stream, a); break;
+    case GSTTACO_CONV_V_C5_RN4_XB_OB: hipLaunchKernelGGL((gt_conv5_bf16_kernel<4, true, true>), c5g4, dim3(512), c5_lds_bytes<4>(), stream, a); break;
+    case GSTTACO_CONV_V_C5_RN2: hipLaunchKernelGGL((gt_conv5_bf16_kernel<2, false, false>), c5g2, dim3(512), c5_lds_bytes<2>(), stream, a); break;
+    case GSTTACO_CONV_V_C5_RN2_XB: hipLaunchKernelGGL((gt_conv5_bf16_kernel<2, true, false>), c5g2, dim3(512), c5_lds_bytes<2>(), stream, a); break;
+    case GSTTACO_CONV_V_C5_RN2_OB: hipLaunchKernelGGL((gt_conv5_bf16_kernel<2, false, true>), c5g2, dim3(512), c5_lds_bytes<2>(), stream, a); break;
+    case GSTTACO_CONV_V_C5_RN2_XB_OB: hipLaunchKernelGGL((gt_conv5_bf16_kernel<2, true, true>), c5g2, dim3(512), c5_lds_bytes<2>(), stream, a); break;
+    GT_V(GSTTACO_CONV_V_BF16_RM2, (gt_conv_gemm_bf16_kernel<2, false, false>), bfg2, 0);
+    GT_V(GSTTACO_CONV_V_BF16_RM2_XB, (gt_conv_gemm_bf16_kernel<2, true, false>), bfg2, 0);
+    GT_V(GSTTACO_CONV_V_BF16_RM2_OB, (gt_conv_gemm_bf16_kernel<2, false, true>), bfg2, 0);
+    GT_V(GSTTACO_CONV_V_BF16_RM2_XB_OB, (gt_conv_gemm_bf16_kernel<2, true, true>), bfg2, 0);
+    GT_V(GSTTACO_CONV_V_BF16_RM1, (gt_conv_gemm_bf16_kernel<1, false, false>), bfg1, 0);
+    GT_V(GSTTACO_CONV_V_BF16_RM1_XB, (gt_conv_gemm_bf16_kernel<1, true, false>), bfg1, 0);
+    GT_V(GSTTACO_CONV_V_BF16_RM1_OB, (gt_conv_gemm_bf16_kernel<1, false, true>), bfg1, 0);
+    GT_V(GSTTACO_CONV_V_BF16_RM1_XB_OB, (gt_conv_gemm_bf16_kernel<1, true, true>), bfg1, 0);
+    case GSTTACO_CONV_V_GEMM_SPLIT: return gt_launch_gemm_split(a, stream);
+    case GSTTACO_CONV_V_WINO4_S: case GSTTACO_CONV_V_WINO4_S_X3: return gt_launch_conv_wino5s(a, 4, stream);
+    case GSTTACO_CONV_V_WINO2_S: case GSTTACO_CONV_V_WINO2_S_X3: return gt_launch_conv_wino5s(a, 2, stream);
+    case GSTTACO_CONV_V_WINO4: hipLaunchKernelGGL(gt_conv_wino5_kernel<4>, wg4, dim3(WT), 0, stream, a, a.wino_u4); break;
+    case GSTTACO_CONV_V_WINO2: hipLaunchKernelGGL(gt_conv_wino5_kernel<2>, wg2, dim3(WT), 0, stream, a, a.wino_u); break;
+    GT_V(GSTTACO_CONV_V_C2D_1411, (gt_conv_gemm_kernel<1, 4, 1, 1, true>), g32, 0);
+    GT_V(GSTTACO_CONV_V_C2D_4112, (gt_conv_gemm_kernel<4, 1, 1, 2, true>), g128x1, 0);
+    GT_V(GSTTACO_CONV_V_C2D_4111, (gt_conv_gemm_kernel<4, 1, 1, 1, true>), g128x1, 0);
+    GT_V(GSTTACO_CONV_V_IG_2222, (gt_conv_gemm_kernel<2, 2, 2, 2>), g128, 0);
+    GT_V(GSTTACO_CONV_V_IG_1411, (gt_conv_gemm_kernel<1, 4, 1, 1>), g32, 0);
+    GT_V(GSTTACO_CONV_V_IG_2212, (gt_conv_gemm_kernel<2, 2, 1, 2>), g64, 0);
+    GT_V(GSTTACO_CONV_V_IG_4113, (gt_conv_gemm_kernel<4, 1, 1, 3>), g128x1, 0);
+    GT_V(GSTTACO_CONV_V_IG_4112, (gt_conv_gemm_kernel<4, 1, 1, 2>), g128x1, 0);
+    GT_V(GSTTACO_CONV_V_IG_4111, (gt_conv_gemm_kernel<4, 1, 1, 1>), g128x1, 0);
+    default: return hipErrorInvalidValue;
+    }
+#undef GT_V
     return hipGetLastError();
 }
 

@@ -54,6 +54,10 @@ struct ConvLayer {
     float* scale = nullptr;
     float* shift = nullptr;
     int taps = 0, cin = 0, cout = 0;
+    int ldw = 0;                // row stride of w (0 = cout)
+    void* wt_bf16 = nullptr;    // GSTTACO_CONV_FORM_BF16: the transposed bf16 copy (add_bf16), row stride ldk
+    int ldk = 0;
+    void* gemm_s = nullptr;     // GSTTACO_CONV_FORM_GEMM_SPLIT: w as three bf16 planes [plane][wino_npad][taps*Cin] (taps == 1)
 };
 
 struct GraphKey {
@@ -194,6 +198,8 @@ struct gsttaco_ctx {
     // mixed precision (Use_Mixed_Precision): bf16 transposed copies of the conv-GEMM weights, keyed by the fp32 device pointer
     struct Bf16W { void* wt; int ldk; };
     std::map<const float*, Bf16W> bf16_w;
+    struct DbgConv { ConvLayer L; int forms; };
+    std::vector<DbgConv> dbg_conv;      // gsttaco_debug_conv_prepare's weights (device memory in allocs, freed at destroy)
 
     // audio front / back end, initialised on first use
     bool audio_ready = false;
@@ -476,18 +482,24 @@ inline uint16_t bf16_bits(float f) {
 
 // Mixed precision: registers the bf16 TRANSPOSED copy [ceil(N/256)*256][ldk] (k contiguous, zero padded, ldk =
 // ceil(K/64)*64) of a conv-GEMM weight [K, N] (row stride ldw) under its fp32 device pointer.
-int add_bf16(gsttaco_ctx* c, const float* dev_w, const float* host_w, int K, int N, int ldw) {
-    if (!c->cfg.mixed_precision) return 0;
+int upload_bf16_t(gsttaco_ctx* c, const float* host_w, int K, int N, int ldw, void** dst, int* ldk_out) {
     const int ldk = (K + 63) / 64 * 64, npad = (N + 255) / 256 * 256;     // (column blocks of up to 256: gt_conv5_bf16_kernel)
     std::vector<uint16_t> t((size_t)npad * ldk, 0);
     for (int k = 0; k < K; ++k)
         for (int n = 0; n < N; ++n) t[(size_t)n * ldk + k] = bf16_bits(host_w[(size_t)k * ldw + n]);
-    void* d = nullptr;
-    int rc = dev_alloc(c, &d, t.size() * sizeof(uint16_t));
+    int rc = dev_alloc(c, dst, t.size() * sizeof(uint16_t));
     if (rc) return rc;
-    HIPCHECK(c, hipMemcpy(d, t.data(), t.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    c->bf16_w[dev_w] = gsttaco_ctx::Bf16W{d, ldk};
+    HIPCHECK(c, hipMemcpy(*dst, t.data(), t.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    *ldk_out = ldk;
     return 0;
+}
+int add_bf16(gsttaco_ctx* c, const float* dev_w, const float* host_w, int K, int N, int ldw) {
+    if (!c->cfg.mixed_precision) return 0;
+    void* d = nullptr;
+    int ldk = 0;
+    const int rc = upload_bf16_t(c, host_w, K, N, ldw, &d, &ldk);
+    if (!rc) c->bf16_w[dev_w] = gsttaco_ctx::Bf16W{d, ldk};
+    return rc;
 }
 
 hipError_t launch_conv(gsttaco_ctx* c, ConvGemmArgs a, hipStream_t s) {
@@ -644,42 +656,54 @@ int upload_gemm_split(gsttaco_ctx* c, void** dst, const float* w, int K, int N, 
     return 0;
 }
 
-int upload_conv(gsttaco_ctx* c, ConvLayer* L, const std::string& prefix) {
-    const HostTensor& k = T(c, prefix + ".kernel");
-    L->taps = (int)k.shape[0];
-    L->cin = (int)k.shape[1];
-    L->cout = (int)k.shape[2];
-    std::vector<float> sc, sh;
-    fold_bn(c, prefix, sc, sh);
-    int rc = upload(c, &L->w, k.data.data(), k.data.size());
-    if (!rc) rc = add_bf16(c, L->w, k.data.data(), L->taps * L->cin, L->cout, L->cout);
-    if (!rc) rc = upload(c, &L->scale, sc.data(), sc.size());
-    if (!rc) rc = upload(c, &L->shift, sh.data(), sh.size());
-    if (!rc && c->wino != 0 && L->taps == 5 && L->cin % 4 == 0 && L->cout % 4 == 0) {
-        // U_xi = sum_k G[xi][k] w[k]  (Cook-Toom F(2,5), points 0, +-1, +-1/2, infinity), formed in float64
-        static const double G[6][5] = {{4, 0, 0, 0, 0},
-                                       {2.0 / 3, 2.0 / 3, 2.0 / 3, 2.0 / 3, 2.0 / 3},
-                                       {2.0 / 3, -2.0 / 3, 2.0 / 3, -2.0 / 3, 2.0 / 3},
-                                       {-8.0 / 3, -4.0 / 3, -2.0 / 3, -1.0 / 3, -1.0 / 6},
-                                       {-8.0 / 3, 4.0 / 3, -2.0 / 3, 1.0 / 3, -1.0 / 6},
-                                       {0, 0, 0, 0, 1}};
-        const size_t cn = (size_t)L->cin * L->cout;
-        L->wino_cin = std::max(128, (L->cin + 63) / 64 * 64);   // zero rows for the padding channels (an even number >= 4 of 32-channel slices)
-        const size_t cnp = (size_t)L->wino_cin * L->cout;
-        std::vector<float> u(6 * cnp, 0.f);
-        const bool split = c->wino_split && !c->cfg.mixed_precision;      // (mixed precision runs the bf16 five-tap kernel instead)
+// The device forms (GSTTACO_CONV_FORM_* bits) of one conv / GEMM weight, host w [taps * cin, ldw] with scale / shift [cout] or NULL:
+// finalize (upload_conv) and gsttaco_debug_conv_prepare both build them here.  FP32 is always built; a BF16 form is also registered
+// under the fp32 pointer for launch_conv when the context runs mixed precision.
+int prepare_conv_forms(gsttaco_ctx* c, ConvLayer* L, const float* w, int taps, int cin, int cout, int ldw, const float* sc,
+                       const float* sh, int forms) {
+    L->taps = taps; L->cin = cin; L->cout = cout; L->ldw = ldw == cout ? 0 : ldw;
+    const int K = taps * cin;
+    int rc = upload(c, &L->w, w, (size_t)K * ldw);
+    if (!rc && (forms & GSTTACO_CONV_FORM_BF16)) {
+        rc = upload_bf16_t(c, w, K, cout, ldw, &L->wt_bf16, &L->ldk);
+        if (!rc && c->cfg.mixed_precision) c->bf16_w[L->w] = gsttaco_ctx::Bf16W{L->wt_bf16, L->ldk};
+    }
+    if (!rc && sc) rc = upload(c, &L->scale, sc, cout);
+    if (!rc && sh) rc = upload(c, &L->shift, sh, cout);
+    const bool split = (forms & GSTTACO_CONV_FORM_WINO_SPLIT) != 0;
+    if (!rc && (forms & (GSTTACO_CONV_FORM_WINO2 | GSTTACO_CONV_FORM_WINO4))) {
+        if (taps != 5 || cin % 4 || cout % 4) return fail(c, GSTTACO_E_INVALID, "Winograd forms need taps 5, cin and cout multiples of 4");
+        const size_t cn = (size_t)cin * cout;
+        L->wino_cin = std::max(128, (cin + 63) / 64 * 64);   // zero rows for the padding channels (an even number >= 4 of 32-channel slices)
+        L->wino_npad = (cout + 127) / 128 * 128;
+        const size_t cnp = (size_t)L->wino_cin * cout;
         std::vector<double> ud(split ? 8 * cn : 0);
-        L->wino_npad = (L->cout + 127) / 128 * 128;
-        for (int xi = 0; xi < 6; ++xi)
-            for (size_t i = 0; i < cn; ++i) {
-                double acc = 0.0;
-                for (int tap = 0; tap < 5; ++tap) acc += G[xi][tap] * (double)k.data[(size_t)tap * cn + i];
-                u[xi * cnp + i] = (float)acc;
-                if (split) ud[xi * cn + i] = acc;
-            }
-        rc = upload(c, &L->wino_u, u.data(), u.size());
-        if (!rc && split) rc = upload_wino_split(c, &L->wino_s, ud, 6, L->cin, L->wino_cin, L->cout, L->wino_npad);
-        if (!rc && c->wino >= 4) {
+        // U_xi = sum_k G[xi][k] w[k], formed in float64, [xi][wino_cin][cout]
+        auto transform = [&](const double (*G)[5], int al, float** dst, void** dst_s) {
+            std::vector<float> u(al * cnp, 0.f);
+            for (int xi = 0; xi < al; ++xi)
+                for (int ci = 0; ci < cin; ++ci)
+                    for (int n = 0; n < cout; ++n) {
+                        double acc = 0.0;
+                        for (int tap = 0; tap < 5; ++tap) acc += G[xi][tap] * (double)w[((size_t)tap * cin + ci) * ldw + n];
+                        u[xi * cnp + (size_t)ci * cout + n] = (float)acc;
+                        if (split) ud[xi * cn + (size_t)ci * cout + n] = acc;
+                    }
+            int r = upload(c, dst, u.data(), u.size());
+            if (!r && split) r = upload_wino_split(c, dst_s, ud, al, cin, L->wino_cin, cout, L->wino_npad);
+            return r;
+        };
+        if (forms & GSTTACO_CONV_FORM_WINO2) {
+            // Cook-Toom F(2,5), points 0, +-1, +-1/2, infinity
+            static const double G[6][5] = {{4, 0, 0, 0, 0},
+                                           {2.0 / 3, 2.0 / 3, 2.0 / 3, 2.0 / 3, 2.0 / 3},
+                                           {2.0 / 3, -2.0 / 3, 2.0 / 3, -2.0 / 3, 2.0 / 3},
+                                           {-8.0 / 3, -4.0 / 3, -2.0 / 3, -1.0 / 3, -1.0 / 6},
+                                           {-8.0 / 3, 4.0 / 3, -2.0 / 3, 1.0 / 3, -1.0 / 6},
+                                           {0, 0, 0, 0, 1}};
+            rc = transform(G, 6, &L->wino_u, &L->wino_s);
+        }
+        if (!rc && (forms & GSTTACO_CONV_FORM_WINO4)) {
             // F(4,5), points 0, +-1, +-1/2, +-2, infinity
             static const double G4[8][5] = {{-1, 0, 0, 0, 0},
                                             {-2.0 / 9, -2.0 / 9, -2.0 / 9, -2.0 / 9, -2.0 / 9},
@@ -689,19 +713,28 @@ int upload_conv(gsttaco_ctx* c, ConvLayer* L, const std::string& prefix) {
                                             {1.0 / 90, 1.0 / 45, 2.0 / 45, 4.0 / 45, 8.0 / 45},
                                             {1.0 / 90, -1.0 / 45, 2.0 / 45, -4.0 / 45, 8.0 / 45},
                                             {0, 0, 0, 0, 1}};
-            std::vector<float> u4(8 * cnp, 0.f);
-            for (int xi = 0; xi < 8; ++xi)
-                for (size_t i = 0; i < cn; ++i) {
-                    double acc = 0.0;
-                    for (int tap = 0; tap < 5; ++tap) acc += G4[xi][tap] * (double)k.data[(size_t)tap * cn + i];
-                    u4[xi * cnp + i] = (float)acc;
-                    if (split) ud[xi * cn + i] = acc;
-                }
-            rc = upload(c, &L->wino_u4, u4.data(), u4.size());
-            if (!rc && split) rc = upload_wino_split(c, &L->wino_s4, ud, 8, L->cin, L->wino_cin, L->cout, L->wino_npad);
+            rc = transform(G4, 8, &L->wino_u4, &L->wino_s4);
         }
     }
+    if (!rc && (forms & GSTTACO_CONV_FORM_GEMM_SPLIT)) {
+        if (taps != 1) return fail(c, GSTTACO_E_INVALID, "the plain split-bf16 GEMM form needs taps 1");
+        rc = upload_gemm_split(c, &L->gemm_s, w, K, cout, ldw, &L->wino_npad);
+    }
     return rc;
+}
+
+int upload_conv(gsttaco_ctx* c, ConvLayer* L, const std::string& prefix) {
+    const HostTensor& k = T(c, prefix + ".kernel");
+    const int taps = (int)k.shape[0], cin = (int)k.shape[1], cout = (int)k.shape[2];
+    std::vector<float> sc, sh;
+    fold_bn(c, prefix, sc, sh);
+    int forms = GSTTACO_CONV_FORM_FP32 | (c->cfg.mixed_precision ? GSTTACO_CONV_FORM_BF16 : 0);
+    if (c->wino != 0 && taps == 5 && cin % 4 == 0 && cout % 4 == 0) {
+        forms |= GSTTACO_CONV_FORM_WINO2 | (c->wino >= 4 ? GSTTACO_CONV_FORM_WINO4 : 0);
+        // (mixed precision runs the bf16 five-tap kernel instead)
+        if (c->wino_split && !c->cfg.mixed_precision) forms |= GSTTACO_CONV_FORM_WINO_SPLIT;
+    }
+    return prepare_conv_forms(c, L, k.data.data(), taps, cin, cout, cout, sc.data(), sh.data(), forms);
 }
 
 int same_pad_before(int n_in, int k, int s, int* out_n) {
@@ -2719,6 +2752,52 @@ int gsttaco_debug_counters(const gsttaco_ctx* c, uint64_t out[4]) {
     out[1] = c->bilstm_persist ? 1u : 0u;
     out[2] = c->n_persist_decodes;
     out[3] = c->persist_decode ? 1u : 0u;
+    return 0;
+}
+
+int gsttaco_debug_conv_prepare(gsttaco_ctx* c, const gsttaco_conv_desc* d, const float* w_host, const float* scale_host,
+                               const float* shift_host, int* id) {
+    if (!c || !d || !w_host || !id) return GSTTACO_E_INVALID;
+    if (!c->finalized) return fail(c, GSTTACO_E_WEIGHTS, "weights not finalized (call gsttaco_finalize_weights)");
+    const int ldw = d->ldw ? d->ldw : d->n;
+    if (d->taps < 1 || d->cin < 4 || d->cin % 4 || d->n < 1 || ldw < d->n || ldw % 4 || !(d->forms & GSTTACO_CONV_FORM_FP32) || (d->forms & ~63))
+        return fail(c, GSTTACO_E_INVALID, "gsttaco_debug_conv_prepare: bad descriptor");
+    gsttaco_ctx::DbgConv e{};
+    const int rc = prepare_conv_forms(c, &e.L, w_host, d->taps, d->cin, d->n, ldw, scale_host, shift_host, d->forms);
+    if (rc) return rc;
+    e.forms = d->forms;
+    c->dbg_conv.push_back(e);
+    *id = (int)c->dbg_conv.size() - 1;
+    return 0;
+}
+
+int gsttaco_debug_conv_run(gsttaco_ctx* c, int id, const gsttaco_conv_call* k, const void* x, const int32_t* tokens,
+                           const int32_t* row_len, const float* rowbias, const float* res, void* out, int* variant, void* stream) {
+    if (!c || !k || !x || !out) return GSTTACO_E_INVALID;
+    if (id < 0 || id >= (int)c->dbg_conv.size()) return fail(c, GSTTACO_E_INVALID, "gsttaco_debug_conv_run: unknown weight id");
+    const ConvLayer& L = c->dbg_conv[id].L;
+    const int f = k->forms;
+    if ((f & c->dbg_conv[id].forms) != f || !(f & GSTTACO_CONV_FORM_FP32) || k->B < 1 || k->T < 1 || (k->ldo && k->ldo < L.cout))
+        return fail(c, GSTTACO_E_INVALID, "gsttaco_debug_conv_run: bad call (a form that was not prepared?)");
+    // (what the production call sites fill in, from the caller's fields: no allocation, no synchronisation)
+    ConvGemmArgs a{};
+    a.x = reinterpret_cast<const float*>(x); a.tokens = tokens; a.w = L.w; a.scale = L.scale; a.shift = L.shift;
+    a.rowbias = rowbias; a.res = res; a.row_len = row_len; a.ldw = L.ldw; a.pool2 = k->pool2;
+    if (f & GSTTACO_CONV_FORM_BF16) { a.wt_bf16 = L.wt_bf16; a.ldk = L.ldk; }
+    a.x_bf16 = k->x_bf16; a.out_bf16 = k->out_bf16;
+    const bool split = (f & GSTTACO_CONV_FORM_WINO_SPLIT) != 0;
+    if (f & GSTTACO_CONV_FORM_WINO2) { a.wino_u = L.wino_u; if (split) a.wino_s = L.wino_s; }
+    if (f & GSTTACO_CONV_FORM_WINO4) { a.wino_u4 = L.wino_u4; if (split) a.wino_s4 = L.wino_s4; }
+    if (f & GSTTACO_CONV_FORM_GEMM_SPLIT) a.gemm_s = L.gemm_s;
+    a.wino_cin = L.wino_cin; a.wino_npad = L.wino_npad; a.wino_x3 = k->wino_x3; a.wino_min_wgs = k->wino_min_wgs;
+    a.out = reinterpret_cast<float*>(out); a.ldo = k->ldo ? k->ldo : L.cout;
+    a.B = k->B; a.T = k->T; a.Cin = L.cin; a.N = L.cout; a.taps = L.taps; a.pad_before = k->pad_before; a.act = k->act;
+    a.conv2d = k->conv2d; a.H = k->H; a.W = k->W; a.Wo = k->Wo; a.kw = k->kw; a.stride = k->stride; a.pad_h = k->pad_h; a.pad_w = k->pad_w;
+    a.xb = k->xb;
+    const int v = gt_conv_gemm_variant(a);
+    if (variant) *variant = v;
+    if (v == GSTTACO_CONV_V_INVALID) return fail(c, GSTTACO_E_INVALID, "gsttaco_debug_conv_run: no kernel takes this call");
+    HIPCHECK(c, gt_launch_conv_gemm(a, reinterpret_cast<hipStream_t>(stream)));
     return 0;
 }
 

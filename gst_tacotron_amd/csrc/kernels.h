@@ -220,6 +220,7 @@ struct ConvGemmArgs {
 };
 
 hipError_t gt_launch_conv_gemm(const ConvGemmArgs& a, hipStream_t stream);
+int gt_conv_gemm_variant(const ConvGemmArgs& a);     // the GSTTACO_CONV_V_* the launch runs (include/gsttaco.h)
 hipError_t gt_conv5_bf16_init();           // opt in to >64 KiB dynamic LDS; call once outside stream capture
 // conv_wino_split.hip: the Winograd five-tap kernel on the bf16 pipe (split-bf16 x6); mo = 4 / 2 outputs per tile
 hipError_t gt_conv_wino5s_init();

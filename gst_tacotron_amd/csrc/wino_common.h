@@ -39,14 +39,17 @@ struct Wino {
 // ALPHA transform-domain GEMMs is a combination of the same ALPHA input rows ("taps"), which are loaded raw into d[] ONCE per
 // slice.  Every gather load is an unconditional buffer load: a row outside [0, len) gets an out-of-range offset and reads as
 // zero (SAME padding / masked mode; also a slice past the last one) -- no branches, so the number of loads in flight is known
-// exactly at every later point and the waits the compiler inserts are counted, not vmcnt(0).
+// exactly at every later point and the waits the compiler inserts are counted, not vmcnt(0).  So does a channel quad at or beyond
+// Cin (the padding slices up to wino_cin): its U rows are zero, but the memory behind it is the NEXT row's channels, and an Inf or
+// NaN there would leak into this utterance through 0 * Inf.  cq = this thread's channel offset within the slice (Cin % 4 == 0).
 template <int MO>
 __device__ __forceinline__ void wino_issue_taps(const ConvGemmArgs& A, __amdgpu_buffer_rsrc_t rs_x, const uint32_t voff, const int first, const int len,
-                                                const int c0, const bool live, float4 (&d)[Wino<MO>::ALPHA]) {
+                                                const int c0, const int cq, const bool live, float4 (&d)[Wino<MO>::ALPHA]) {
+    const bool in = live && c0 + cq < A.Cin;
 #pragma unroll
     for (int tap = 0; tap < Wino<MO>::ALPHA; ++tap) {
         const int ts = first + tap;
-        const uint32_t vo = (live && ts >= 0 && ts < len) ? voff + (uint32_t)(tap * A.Cin * 4) : GT_WINO_OOB;
+        const uint32_t vo = (in && ts >= 0 && ts < len) ? voff + (uint32_t)(tap * A.Cin * 4) : GT_WINO_OOB;
         const auto t = __builtin_amdgcn_raw_buffer_load_b128(rs_x, (int)vo, c0 * 4, 0);
         __builtin_memcpy(&d[tap], &t, 16);
     }

@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define GSTTACO_ABI_VERSION 12
+#define GSTTACO_ABI_VERSION 13
 #define GSTTACO_MAX_LAYERS 8
 
 enum {
@@ -298,6 +298,56 @@ int gsttaco_debug_randomness(gsttaco_ctx* ctx, float* host_masks, float* host_no
 int gsttaco_decode_plan(const gsttaco_ctx* ctx, int Tv, int32_t plan[3]);
 /* Algorithmic bytes one launch of decode-LSTM layer `layer` moves at batch B (weights + activations). */
 int64_t gsttaco_lstm_launch_bytes(const gsttaco_ctx* ctx, int layer, int B);
+
+/* Test support: the conv/GEMM dispatcher behind every tall GEMM outside the decode step (encoder convolutions, hoisted BiLSTM
+ * inputs, Value projection, GST Conv2D, postnet, vocoder).  Which kernel instantiation a call runs, as decided by the same
+ * function the dispatcher switches on: IG = fp32 implicit GEMM <WAVES_M, WAVES_N, RM, RN>, C2D = its 2-D (Conv2D) form,
+ * WINO4 / WINO2 = Winograd F(4,5) / F(2,5) on the fp32 pipe, ..._S = the same as split-bf16 x6 (X3: the reduced three-product
+ * knob), GEMM_SPLIT = the plain split-bf16 x6 GEMM, C5 = the bf16 five-tap kernel <RN>, BF16 = the bf16 implicit GEMM <RM>;
+ * _XB / _OB = bf16 activations in / out. */
+enum {
+    GSTTACO_CONV_V_INVALID = -1,
+    GSTTACO_CONV_V_IG_1411 = 0, GSTTACO_CONV_V_IG_2212 = 1, GSTTACO_CONV_V_IG_2222 = 2,
+    GSTTACO_CONV_V_IG_4113 = 3, GSTTACO_CONV_V_IG_4112 = 4, GSTTACO_CONV_V_IG_4111 = 5,
+    GSTTACO_CONV_V_C2D_1411 = 6, GSTTACO_CONV_V_C2D_4112 = 7, GSTTACO_CONV_V_C2D_4111 = 8,
+    GSTTACO_CONV_V_WINO4 = 9, GSTTACO_CONV_V_WINO2 = 10,
+    GSTTACO_CONV_V_WINO4_S = 11, GSTTACO_CONV_V_WINO2_S = 12, GSTTACO_CONV_V_WINO4_S_X3 = 13, GSTTACO_CONV_V_WINO2_S_X3 = 14,
+    GSTTACO_CONV_V_GEMM_SPLIT = 15,
+    GSTTACO_CONV_V_C5_RN4 = 16, GSTTACO_CONV_V_C5_RN4_XB = 17, GSTTACO_CONV_V_C5_RN4_OB = 18, GSTTACO_CONV_V_C5_RN4_XB_OB = 19,
+    GSTTACO_CONV_V_C5_RN2 = 20, GSTTACO_CONV_V_C5_RN2_XB = 21, GSTTACO_CONV_V_C5_RN2_OB = 22, GSTTACO_CONV_V_C5_RN2_XB_OB = 23,
+    GSTTACO_CONV_V_BF16_RM2 = 24, GSTTACO_CONV_V_BF16_RM2_XB = 25, GSTTACO_CONV_V_BF16_RM2_OB = 26, GSTTACO_CONV_V_BF16_RM2_XB_OB = 27,
+    GSTTACO_CONV_V_BF16_RM1 = 28, GSTTACO_CONV_V_BF16_RM1_XB = 29, GSTTACO_CONV_V_BF16_RM1_OB = 30, GSTTACO_CONV_V_BF16_RM1_XB_OB = 31,
+    GSTTACO_CONV_V_COUNT = 32
+};
+/* Weight forms gsttaco_debug_conv_prepare builds (bit set), as finalize builds them for a layer:
+ * FP32 = w [taps*cin, ldw] with scale / shift (always built), BF16 = its transposed bf16 copy (the mixed-precision kernels),
+ * WINO2 / WINO4 = the float64 Winograd transforms U / U4 rounded to fp32 (taps 5), WINO_SPLIT = the three bf16 planes of each
+ * Winograd transform built, GEMM_SPLIT = the three bf16 planes of w (taps 1). */
+enum {
+    GSTTACO_CONV_FORM_FP32 = 1, GSTTACO_CONV_FORM_BF16 = 2, GSTTACO_CONV_FORM_WINO2 = 4, GSTTACO_CONV_FORM_WINO4 = 8,
+    GSTTACO_CONV_FORM_WINO_SPLIT = 16, GSTTACO_CONV_FORM_GEMM_SPLIT = 32
+};
+typedef struct gsttaco_conv_desc {
+    int32_t taps, cin, n, ldw;  /* ldw: row stride of w in floats (0 = n) */
+    int32_t forms;              /* GSTTACO_CONV_FORM_* */
+} gsttaco_conv_desc;
+typedef struct gsttaco_conv_call {
+    int32_t forms;              /* which of the prepared forms the call hands to the dispatcher (a subset of the desc's) */
+    int32_t B, T, pad_before, act;     /* act: 0 none, 1 relu, 2 tanh */
+    int64_t ldo;                /* output row stride (0 = n) */
+    int32_t pool2, x_bf16, out_bf16, wino_x3, wino_min_wgs;
+    int32_t conv2d, H, W, Wo, kw, stride, pad_h, pad_w;     /* 2-D mode: T = Ho * Wo, taps = kh * kw */
+    int64_t xb;                 /* 2-D mode: batch stride of x in floats */
+} gsttaco_conv_call;
+/* Uploads the forms of one conv/GEMM weight (host w [taps*cin, ldw], scale / shift [n] or NULL) as finalize would; the context
+ * owns them until destroy.  *id names them for gsttaco_debug_conv_run.  Synchronous. */
+int gsttaco_debug_conv_prepare(gsttaco_ctx* ctx, const gsttaco_conv_desc* desc, const float* w_host, const float* scale_host,
+                               const float* shift_host, int* id);
+/* One dispatcher call with prepared weights `id` on device buffers (x, tokens, row_len, rowbias, res may be NULL; out is written):
+ * enqueued on `stream` (a hipStream_t, NULL = the default stream) without allocation or synchronisation.  *variant (may be NULL)
+ * receives the GSTTACO_CONV_V_* the call ran. */
+int gsttaco_debug_conv_run(gsttaco_ctx* ctx, int id, const gsttaco_conv_call* call, const void* x, const int32_t* tokens,
+                           const int32_t* row_len, const float* rowbias, const float* res, void* out, int* variant, void* stream);
 
 #ifdef __cplusplus
 }
