@@ -44,20 +44,22 @@ struct PackedLinear {       // skinny-GEMM operand set
     int bf16 = 0;           // the pack holds bf16 weights (mixed precision)
 };
 
+// One conv / Dense weight that goes through gt_launch_conv_gemm, with the device forms (GSTTACO_CONV_FORM_* bits) prepare_conv_forms
+// built for it: a form that was not built is a NULL pointer here.  conv_args turns it into the weight half of a ConvGemmArgs.
 struct ConvLayer {
-    float* wino_u = nullptr;    // Winograd F(2,5) transform of w, [6][wino_cin][Cout], for 5-tap layers (gemm_conv.hip)
-    float* wino_u4 = nullptr;   // F(4,5): [8][wino_cin][Cout]
-    int wino_cin = 0;
-    void *wino_s = nullptr, *wino_s4 = nullptr;     // the same U as three bf16 planes [xi][plane][wino_npad][wino_cin] (conv_wino_split.hip)
-    int wino_npad = 0;
-    float* w = nullptr;     // [taps*Cin, Cout]
-    float* scale = nullptr;
-    float* shift = nullptr;
+    float* w = nullptr;         // FP32 (always): [taps*Cin, Cout], row stride ldw
+    float* scale = nullptr;     // [Cout] or NULL (a Dense: no BatchNorm)
+    float* shift = nullptr;     // [Cout] or NULL (a Dense: its bias)
     int taps = 0, cin = 0, cout = 0;
     int ldw = 0;                // row stride of w (0 = cout)
-    void* wt_bf16 = nullptr;    // GSTTACO_CONV_FORM_BF16: the transposed bf16 copy (add_bf16), row stride ldk
+    void* wt_bf16 = nullptr;    // BF16: the transposed bf16 copy (upload_bf16_t), row stride ldk
     int ldk = 0;
-    void* gemm_s = nullptr;     // GSTTACO_CONV_FORM_GEMM_SPLIT: w as three bf16 planes [plane][wino_npad][taps*Cin] (taps == 1)
+    float* wino_u = nullptr;    // WINO2: the F(2,5) transform of w, [6][wino_cin][Cout], for 5-tap layers (gemm_conv.hip)
+    float* wino_u4 = nullptr;   // WINO4: F(4,5), [8][wino_cin][Cout]
+    int wino_cin = 0;
+    void *wino_s = nullptr, *wino_s4 = nullptr;     // WINO_SPLIT: the same U as three bf16 planes [xi][plane][wino_npad][wino_cin] (conv_wino_split.hip)
+    void* gemm_s = nullptr;     // GEMM_SPLIT: w as three bf16 planes [plane][wino_npad][taps*Cin] (taps == 1)
+    int wino_npad = 0;          // column padding of the planes (wino_s / wino_s4 / gemm_s)
 };
 
 struct GraphKey {
@@ -131,14 +133,13 @@ struct gsttaco_ctx {
     // order), recurrent-only packs, hoisted-GEMM output and ping-pong blocked state in the workspace
     struct LeanBiLstm {
         PackedLinear h[2];
-        float *xw = nullptr, *xb = nullptr;         // [C, 2*4H], [2*4H]
-        void* xw_s = nullptr; int xw_npad = 0;      // xw as three bf16 planes (the hoisted GEMM on the bf16 pipe, split-bf16 x6)
+        ConvLayer x;                                // the hoisted GEMM: [C, 2*4H] + bias [2*4H] (w == NULL: no lean form)
         float *z = nullptr, *hb[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
         float* ph = nullptr;                        // persistent kernel: [8 groups][3 slots] blocked state of 16 rows, tagged in bit 30
         uint32_t* pflags = nullptr;                 // persistent kernel: [8] member counters (right behind ph)
         int H = 0, C = 0;
     } enc_lean, voc_lean;
-    struct { float *w, *scale, *shift; int k, cin, cout, stride; } ref_conv[GSTTACO_MAX_LAYERS]{};
+    struct RefConv { ConvLayer L; int k = 0, stride = 0; } ref_conv[GSTTACO_MAX_LAYERS];     // GST 2-D layers (taps = k*k): the FP32 form only
     float *gru_w = nullptr, *gru_u = nullptr, *gru_b = nullptr, *dense_w = nullptr, *dense_b = nullptr;
     float *mq_w = nullptr, *mq_b = nullptr, *v_tok = nullptr, *ln_g = nullptr, *ln_b = nullptr;
     PackedLinear prenet0, prenet1, query, val_gst, lstm0, lstm1, proj;
@@ -179,25 +180,20 @@ struct gsttaco_ctx {
     PackedLinear proj_z;        // projection columns | padding to a tile | (Wp_last . W0) columns: prenet 0 rides in the projection launch
     int z_col0 = 0;
     float* w_z0 = nullptr;
-    float *val_enc_w = nullptr, *val_bias = nullptr, *att_v = nullptr, *att_sb = nullptr;
-    void* val_enc_s = nullptr; int val_enc_npad = 0;        // val_enc_w as three bf16 planes (split-bf16 x6 GEMM)
+    ConvLayer val_enc;          // the [enc] rows of the Value kernel (+ its bias when no GST row bias carries it)
+    float *att_v = nullptr, *att_sb = nullptr;
     float *loc_cw = nullptr, *loc_cb = nullptr, *loc_dw = nullptr, *loc_db = nullptr, *att_bias = nullptr;   // LSA extension
     float* loc_pack = nullptr;          // the same as the fused front end's LDS image (kernels.h LsaPack)
     float* w_lsa_state = nullptr;
 
     // CBHG vocoder
     std::vector<ConvLayer> voc_bank, voc_proj;
-    float *voc_pd_w = nullptr, *voc_pd_b = nullptr, *voc_hin_w = nullptr, *voc_hin_b = nullptr;
-    std::vector<float*> voc_hw_w, voc_hw_b;      // per highway layer: [S, 2S] = [relu | sigmoid], [2S]
+    ConvLayer voc_pd, voc_hin, voc_dense;       // Dense layers (taps 1); voc_pd / voc_hin: w == NULL where the model has none
+    std::vector<ConvLayer> voc_hw;              // per highway layer: [S, 2S] = [relu | sigmoid], bias [2S]
     PackedLinear voc_bilstm[2];
-    float *voc_dense_w = nullptr, *voc_dense_b = nullptr;
-    int voc_dense_ldw = 0;
     float *w_vbank = nullptr, *w_vbuf[3] = {nullptr, nullptr, nullptr}, *w_vz = nullptr, *w_vrnn = nullptr, *w_vc = nullptr,
           *w_spec = nullptr;
 
-    // mixed precision (Use_Mixed_Precision): bf16 transposed copies of the conv-GEMM weights, keyed by the fp32 device pointer
-    struct Bf16W { void* wt; int ldk; };
-    std::map<const float*, Bf16W> bf16_w;
     struct DbgConv { ConvLayer L; int forms; };
     std::vector<DbgConv> dbg_conv;      // gsttaco_debug_conv_prepare's weights (device memory in allocs, freed at destroy)
 
@@ -480,8 +476,8 @@ inline uint16_t bf16_bits(float f) {
     return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
 }
 
-// Mixed precision: registers the bf16 TRANSPOSED copy [ceil(N/256)*256][ldk] (k contiguous, zero padded, ldk =
-// ceil(K/64)*64) of a conv-GEMM weight [K, N] (row stride ldw) under its fp32 device pointer.
+// The bf16 TRANSPOSED copy [ceil(N/256)*256][ldk] (k contiguous, zero padded, ldk = ceil(K/64)*64) of a conv-GEMM weight
+// [K, N] (row stride ldw)
 int upload_bf16_t(gsttaco_ctx* c, const float* host_w, int K, int N, int ldw, void** dst, int* ldk_out) {
     const int ldk = (K + 63) / 64 * 64, npad = (N + 255) / 256 * 256;     // (column blocks of up to 256: gt_conv5_bf16_kernel)
     std::vector<uint16_t> t((size_t)npad * ldk, 0);
@@ -493,28 +489,6 @@ int upload_bf16_t(gsttaco_ctx* c, const float* host_w, int K, int N, int ldw, vo
     *ldk_out = ldk;
     return 0;
 }
-int add_bf16(gsttaco_ctx* c, const float* dev_w, const float* host_w, int K, int N, int ldw) {
-    if (!c->cfg.mixed_precision) return 0;
-    void* d = nullptr;
-    int ldk = 0;
-    const int rc = upload_bf16_t(c, host_w, K, N, ldw, &d, &ldk);
-    if (!rc) c->bf16_w[dev_w] = gsttaco_ctx::Bf16W{d, ldk};
-    return rc;
-}
-
-hipError_t launch_conv(gsttaco_ctx* c, ConvGemmArgs a, hipStream_t s) {
-    if (c->cfg.mixed_precision) {
-        auto it = c->bf16_w.find(a.w);
-        if (it != c->bf16_w.end()) { a.wt_bf16 = it->second.wt; a.ldk = it->second.ldk; }
-    }
-    return gt_launch_conv_gemm(a, s);
-}
-
-hipError_t launch_skinny(gsttaco_ctx* c, int epi, SkinnyArgs a0, const SkinnyArgs* a1, int ntiles, hipStream_t s, int tag = TAG_GENERIC) {
-    (void)c;
-    return gt_launch_skinny(epi, a0, a1, ntiles, s, tag);
-}
-
 // Fold inference BatchNorm into y = x*scale + shift (Appendix A.4).
 void fold_bn(const gsttaco_ctx* c, const std::string& prefix, std::vector<float>& scale, std::vector<float>& shift) {
     const auto& g = T(c, prefix + ".bn.gamma").data;
@@ -657,17 +631,13 @@ int upload_gemm_split(gsttaco_ctx* c, void** dst, const float* w, int K, int N, 
 }
 
 // The device forms (GSTTACO_CONV_FORM_* bits) of one conv / GEMM weight, host w [taps * cin, ldw] with scale / shift [cout] or NULL:
-// finalize (upload_conv) and gsttaco_debug_conv_prepare both build them here.  FP32 is always built; a BF16 form is also registered
-// under the fp32 pointer for launch_conv when the context runs mixed precision.
+// finalize and gsttaco_debug_conv_prepare both build them here, and nothing else does.  FP32 is always built.
 int prepare_conv_forms(gsttaco_ctx* c, ConvLayer* L, const float* w, int taps, int cin, int cout, int ldw, const float* sc,
                        const float* sh, int forms) {
     L->taps = taps; L->cin = cin; L->cout = cout; L->ldw = ldw == cout ? 0 : ldw;
     const int K = taps * cin;
     int rc = upload(c, &L->w, w, (size_t)K * ldw);
-    if (!rc && (forms & GSTTACO_CONV_FORM_BF16)) {
-        rc = upload_bf16_t(c, w, K, cout, ldw, &L->wt_bf16, &L->ldk);
-        if (!rc && c->cfg.mixed_precision) c->bf16_w[L->w] = gsttaco_ctx::Bf16W{L->wt_bf16, L->ldk};
-    }
+    if (!rc && (forms & GSTTACO_CONV_FORM_BF16)) rc = upload_bf16_t(c, w, K, cout, ldw, &L->wt_bf16, &L->ldk);
     if (!rc && sc) rc = upload(c, &L->scale, sc, cout);
     if (!rc && sh) rc = upload(c, &L->shift, sh, cout);
     const bool split = (forms & GSTTACO_CONV_FORM_WINO_SPLIT) != 0;
@@ -723,18 +693,52 @@ int prepare_conv_forms(gsttaco_ctx* c, ConvLayer* L, const float* w, int taps, i
     return rc;
 }
 
-int upload_conv(gsttaco_ctx* c, ConvLayer* L, const std::string& prefix) {
+// The weight half of a launch's arguments: `forms` is the call site's statement of which of L's forms this call may use (the
+// GSTTACO_CONV_FORM_* bits gsttaco_conv_call::forms carries); a form L does not have stays NULL.  The site then sets what is its own:
+// activations, output, geometry, epilogue.
+ConvGemmArgs conv_args(const ConvLayer& L, int forms) {
+    ConvGemmArgs a{};
+    a.w = L.w; a.scale = L.scale; a.shift = L.shift; a.ldw = L.ldw;
+    a.Cin = L.cin; a.N = L.cout; a.taps = L.taps;
+    if (forms & GSTTACO_CONV_FORM_BF16) { a.wt_bf16 = L.wt_bf16; a.ldk = L.ldk; }
+    const bool split = (forms & GSTTACO_CONV_FORM_WINO_SPLIT) != 0;
+    if (forms & GSTTACO_CONV_FORM_WINO2) { a.wino_u = L.wino_u; if (split) a.wino_s = L.wino_s; }
+    if (forms & GSTTACO_CONV_FORM_WINO4) { a.wino_u4 = L.wino_u4; if (split) a.wino_s4 = L.wino_s4; }
+    if (forms & GSTTACO_CONV_FORM_GEMM_SPLIT) a.gemm_s = L.gemm_s;
+    if (a.wino_u || a.wino_u4) a.wino_cin = L.wino_cin;
+    if (a.wino_s || a.wino_s4 || a.gemm_s) a.wino_npad = L.wino_npad;
+    return a;
+}
+
+// What every call may use: FP32, and the bf16 copy mixed precision builds (a call with wt_bf16 takes a bf16 kernel: gt_conv_gemm_variant)
+constexpr int kFormsPlain = GSTTACO_CONV_FORM_FP32 | GSTTACO_CONV_FORM_BF16;
+constexpr int kFormsWino = GSTTACO_CONV_FORM_WINO2 | GSTTACO_CONV_FORM_WINO4 | GSTTACO_CONV_FORM_WINO_SPLIT;
+
+// A Dense (or any taps-1 GEMM) w [K, N], row stride ldw, bias [N] or NULL.  split: the call site may take the plain split-bf16 GEMM
+// (GSTTACO_WINO_SPLIT; mixed precision runs the bf16 kernel instead; its k loop needs K % 32 == 0).
+int upload_dense(gsttaco_ctx* c, ConvLayer* L, const float* w, int K, int N, int ldw, const float* bias, bool split) {
+    int forms = GSTTACO_CONV_FORM_FP32 | (c->cfg.mixed_precision ? GSTTACO_CONV_FORM_BF16 : 0);
+    if (split && c->wino_split && !c->cfg.mixed_precision && K % 32 == 0) forms |= GSTTACO_CONV_FORM_GEMM_SPLIT;
+    return prepare_conv_forms(c, L, w, 1, K, N, ldw, nullptr, bias, forms);
+}
+
+// A Conv1D + BatchNorm layer by manifest name.  wino: the module's call site can pass the Winograd forms of a five-tap layer (mixed
+// precision runs the bf16 five-tap kernel instead and builds none)
+int upload_conv(gsttaco_ctx* c, ConvLayer* L, const std::string& prefix, bool wino) {
     const HostTensor& k = T(c, prefix + ".kernel");
     const int taps = (int)k.shape[0], cin = (int)k.shape[1], cout = (int)k.shape[2];
     std::vector<float> sc, sh;
     fold_bn(c, prefix, sc, sh);
     int forms = GSTTACO_CONV_FORM_FP32 | (c->cfg.mixed_precision ? GSTTACO_CONV_FORM_BF16 : 0);
-    if (c->wino != 0 && taps == 5 && cin % 4 == 0 && cout % 4 == 0) {
-        forms |= GSTTACO_CONV_FORM_WINO2 | (c->wino >= 4 ? GSTTACO_CONV_FORM_WINO4 : 0);
-        // (mixed precision runs the bf16 five-tap kernel instead)
-        if (c->wino_split && !c->cfg.mixed_precision) forms |= GSTTACO_CONV_FORM_WINO_SPLIT;
-    }
+    if (wino && !c->cfg.mixed_precision && c->wino != 0 && taps == 5 && cin % 4 == 0 && cout % 4 == 0)
+        forms |= GSTTACO_CONV_FORM_WINO2 | (c->wino >= 4 ? GSTTACO_CONV_FORM_WINO4 : 0) | (c->wino_split ? GSTTACO_CONV_FORM_WINO_SPLIT : 0);
     return prepare_conv_forms(c, L, k.data.data(), taps, cin, cout, cout, sc.data(), sh.data(), forms);
+}
+
+// upload tensor `name` as it is
+int upload_tensor(gsttaco_ctx* c, float** dst, const std::string& name) {
+    const HostTensor& t = T(c, name);
+    return upload(c, dst, t.data.data(), t.data.size());
 }
 
 int same_pad_before(int n_in, int k, int s, int* out_n) {
@@ -788,16 +792,12 @@ int build_lean_bilstm(gsttaco_ctx* c, gsttaco_ctx::LeanBiLstm* L, const std::str
         if ((rc = pack_linear(c, &L->h[d], {{u.data.data(), (int)u.shape[0]}}, 4 * H, nullptr, H, c->cfg.mixed_precision != 0))) return rc;
         ++d;
     }
-    if ((rc = upload(c, &L->xw, xw.data(), xw.size()))) return rc;
-    if ((rc = add_bf16(c, L->xw, xw.data(), C, 8 * H, 8 * H))) return rc;
-    if (c->wino_split && !c->cfg.mixed_precision && C % 32 == 0 && (rc = upload_gemm_split(c, &L->xw_s, xw.data(), C, 8 * H, 8 * H, &L->xw_npad))) return rc;
-    if ((rc = upload(c, &L->xb, xb.data(), xb.size()))) return rc;
     L->H = H; L->C = C;
-    return 0;
+    return upload_dense(c, &L->x, xw.data(), C, 8 * H, 8 * H, xb.data(), true);
 }
 
 int alloc_lean_bilstm(gsttaco_ctx* c, gsttaco_ctx::LeanBiLstm* L, size_t B, size_t Tmax) {
-    if (!L->xw) return 0;
+    if (!L->x.w) return 0;
     int rc = 0;
     if ((rc = dev_alloc(c, (void**)&L->z, B * Tmax * 8 * L->H * sizeof(float)))) return rc;
     for (int d = 0; d < 2; ++d)
@@ -812,7 +812,7 @@ int alloc_lean_bilstm(gsttaco_ctx* c, gsttaco_ctx::LeanBiLstm* L, size_t B, size
 }
 
 bool lean_bilstm_usable(const gsttaco_ctx* c, const gsttaco_ctx::LeanBiLstm& L, int B) {
-    if (!L.xw) return false;
+    if (!L.x.w) return false;
     if (!c->cfg.mixed_precision) return true;
     return L.ph && c->bilstm_persist && gt_bilstm_persist_supported(L.H, std::min(B, 64), c->n_cu);
 }
@@ -823,12 +823,11 @@ bool lean_bilstm_usable(const gsttaco_ctx* c, const gsttaco_ctx::LeanBiLstm& L, 
 int enqueue_lean_bilstm(gsttaco_ctx* c, hipStream_t s, const gsttaco_ctx::LeanBiLstm& L, const float* x, int B, int Tn, float* cstate,
                         float* out, const int32_t* row_len, hipEvent_t join = nullptr) {
     const int H = L.H, EO = 2 * H, MT = (B + 15) / 16;
-    ConvGemmArgs a{};
-    a.x = x; a.w = L.xw; a.shift = L.xb;
-    a.out = L.z; a.ldo = 8 * H;
-    a.B = B; a.T = Tn; a.Cin = L.C; a.N = 8 * H; a.taps = 1; a.pad_before = 0; a.act = ACT_NONE;
-    a.gemm_s = L.xw_s; a.wino_npad = L.xw_npad;         // (round 6: on the bf16 matrix pipe as split-bf16 x6 where the grid allows)
-    HIPCHECK(c, launch_conv(c, a, s));
+    // (round 6: on the bf16 matrix pipe as split-bf16 x6 where the grid allows)
+    ConvGemmArgs a = conv_args(L.x, kFormsPlain | GSTTACO_CONV_FORM_GEMM_SPLIT);
+    a.x = x; a.out = L.z; a.ldo = 8 * H;
+    a.B = B; a.T = Tn; a.act = ACT_NONE;
+    HIPCHECK(c, gt_launch_conv_gemm(a, s));
     if (join) HIPCHECK(c, hipStreamWaitEvent(s, join, 0));
     // One persistent launch for the whole sequence, one (direction, 16 utterances) group per XCD (skinny_gemm.hip
     // gt_bilstm_persist_kernel; same arithmetic, bitwise the same outputs); GSTTACO_BILSTM_PERSIST=0 keeps the launch per step.
@@ -861,6 +860,32 @@ int enqueue_lean_bilstm(gsttaco_ctx* c, hipStream_t s, const gsttaco_ctx::LeanBi
         k.row_len = row_len; k.ldz = (int64_t)Tn * 8 * H; k.ldo = (int64_t)Tn * EO;
         k.M = B; k.MT = MT; k.H = H;
         HIPCHECK(c, gt_launch_bilstm_lean(k, s));
+    }
+    return 0;
+}
+
+// The BiLSTM without the lean form: one launch per time step over the whole [x_t | h_prev] GEMM, both directions in grid.z; h is written
+// straight into out.  x: [B, Tn, C]; cstate: [2, B, H] (zeroed by the caller); out: [B, Tn, 2H]; row_len: masked mode, or NULL
+int enqueue_bilstm_steps(gsttaco_ctx* c, hipStream_t s, const PackedLinear* pk, const float* x, int B, int Tn, int C, int H, float* cstate,
+                         float* out, const int32_t* row_len) {
+    const int EO = 2 * H;
+    for (int t = 0; t < Tn; ++t) {
+        SkinnyArgs a[2];
+        for (int d = 0; d < 2; ++d) {
+            const int tt = d == 0 ? t : Tn - 1 - t;
+            const int tp = d == 0 ? tt - 1 : tt + 1;
+            SkinnyArgs& k = a[d];
+            memset(&k, 0, sizeof(k));
+            k.wp = pk[d].wp; k.bf16 = pk[d].bf16; k.bias = pk[d].bias;
+            k.seg[0] = SkinnySeg{x + (size_t)tt * C, (int64_t)Tn * C, C / 16, 0};
+            if (t == 0) k.seg[1] = SkinnySeg{c->w_zero, 0, H / 16, 0};
+            else k.seg[1] = SkinnySeg{out + (size_t)tp * EO + d * H, (int64_t)Tn * EO, H / 16, 0};
+            k.nkb = pk[d].nkb; k.M = B; k.N = H; k.MT = (B + 15) / 16;
+            k.c = cstate + (size_t)d * B * H;
+            k.h = out + (size_t)tt * EO + d * H; k.ldh = (int64_t)Tn * EO;
+            k.row_len = row_len; k.t_index = tt;        // (t_index is read only beside row_len)
+        }
+        HIPCHECK(c, gt_launch_skinny(EPI_LSTM, a[0], &a[1], pk[0].ntiles, s, TAG_ENC_BILSTM));
     }
     return 0;
 }
@@ -900,28 +925,25 @@ int enqueue_encoder(gsttaco_ctx* c, hipStream_t s, int B, int Tv, bool masked, i
     }
     for (int i = 0; i < g.n_enc_conv; ++i) {
         const ConvLayer& L = c->enc_conv[i];
-        ConvGemmArgs a{};
-        a.x = x; a.tokens = tok; a.w = L.w; a.scale = L.scale; a.shift = L.shift;
-        a.out = c->w_act[cur]; a.ldo = L.cout;
-        a.B = B; a.T = Tv; a.Cin = L.cin; a.N = L.cout; a.taps = L.taps;
-        a.pad_before = same_pad_before(Tv, L.taps, 1, nullptr);
-        a.act = ACT_RELU;
-        a.row_len = tlen;
         // (round 6) the five-tap layers behind the token gather as Winograd on the bf16 pipe (conv_wino_split.hip): B x Tv = 4 096 rows are
         // 128 workgroups of F(2,5) -- half the chip, where the fp32 Winograd kernel lost to the implicit GEMM (275 against 136 us) --
         // enc_wino: 0 = implicit GEMM, 2 = F(2,5), 4 = F(4,5) where its grid reaches 60 workgroups
-        if (c->enc_wino && !tok && L.wino_s) {
-            // (F(4,5) where ITS grid fills the chip -- batches of 128 utterances --, else F(2,5) down to 100 workgroups)
-            const bool f4 = c->enc_wino == 4 || ((B * ((Tv + 3) / 4) + 63) / 64) * ((L.cout + 127) / 128) >= 240;
-            a.wino_u = L.wino_u; a.wino_u4 = f4 ? L.wino_u4 : nullptr; a.wino_cin = L.wino_cin;
-            a.wino_s = L.wino_s; a.wino_s4 = f4 ? L.wino_s4 : nullptr; a.wino_npad = L.wino_npad;
-            a.wino_min_wgs = c->enc_wino == 4 ? 60 : 100;
-        }
-        HIPCHECK(c, launch_conv(c, a, s));
+        const bool wino = c->enc_wino && !tok && L.wino_s;
+        // (F(4,5) where ITS grid fills the chip -- batches of 128 utterances --, else F(2,5) down to 100 workgroups)
+        const bool f4 = c->enc_wino == 4 || ((B * ((Tv + 3) / 4) + 63) / 64) * ((L.cout + 127) / 128) >= 240;
+        // (nothing but FP32 / BF16 while the token gather is still in front)
+        ConvGemmArgs a = conv_args(L, kFormsPlain | (wino ? GSTTACO_CONV_FORM_WINO2 | GSTTACO_CONV_FORM_WINO_SPLIT | (f4 ? GSTTACO_CONV_FORM_WINO4 : 0) : 0));
+        if (wino) a.wino_min_wgs = c->enc_wino == 4 ? 60 : 100;
+        a.x = x; a.tokens = tok;
+        a.out = c->w_act[cur]; a.ldo = L.cout;
+        a.B = B; a.T = Tv;
+        a.pad_before = same_pad_before(Tv, L.taps, 1, nullptr);
+        a.act = ACT_RELU;
+        a.row_len = tlen;
+        HIPCHECK(c, gt_launch_conv_gemm(a, s));
         x = c->w_act[cur]; tok = nullptr; cur ^= 1;
     }
-    // BiLSTM: one launch per time step, both directions in grid.z; h is written straight into enc_out.
-    const int H = g.enc_rnn, C = c->conv_c, EO = c->enc_out;
+    const int H = g.enc_rnn;
     // (joining BEHIND the BiLSTM instead measured 10.83-10.86 against 10.85-10.89 ms per Inference_Step: not worth GST kernels lingering
     // beside a launch that needs its members co-resident)
     const bool lean_enc = lean_bilstm_usable(c, c->enc_lean, B);
@@ -934,25 +956,7 @@ int enqueue_encoder(gsttaco_ctx* c, hipStream_t s, int B, int Tv, bool masked, i
         if (!rl) join_guard.armed = false;          // (joined inside)
         return rl;
     }
-    for (int t = 0; t < Tv; ++t) {
-        SkinnyArgs a[2];
-        for (int d = 0; d < 2; ++d) {
-            const int tt = d == 0 ? t : Tv - 1 - t;
-            const int tp = d == 0 ? tt - 1 : tt + 1;
-            SkinnyArgs& k = a[d];
-            memset(&k, 0, sizeof(k));
-            k.wp = c->bilstm[d].wp; k.bf16 = c->bilstm[d].bf16; k.bias = c->bilstm[d].bias;
-            k.seg[0] = SkinnySeg{x + (size_t)tt * C, (int64_t)Tv * C, C / 16, 0};
-            if (t == 0) k.seg[1] = SkinnySeg{c->w_zero, 0, H / 16, 0};
-            else k.seg[1] = SkinnySeg{c->w_enc + (size_t)tp * EO + d * H, (int64_t)Tv * EO, H / 16, 0};
-            k.nkb = c->bilstm[d].nkb; k.M = B; k.N = H; k.MT = (B + 15) / 16;
-            k.c = c->w_cenc + (size_t)d * B * H;
-            k.h = c->w_enc + (size_t)tt * EO + d * H; k.ldh = (int64_t)Tv * EO;
-            k.row_len = tlen; k.t_index = tt;
-        }
-        HIPCHECK(c, launch_skinny(c, EPI_LSTM, a[0], &a[1], c->bilstm[0].ntiles, s, TAG_ENC_BILSTM));
-    }
-    return 0;
+    return enqueue_bilstm_steps(c, s, c->bilstm, x, B, Tv, c->conv_c, H, c->w_cenc, c->w_enc, tlen);
 }
 
 int enqueue_gst(gsttaco_ctx* c, hipStream_t s, int B, int Tref1) {
@@ -962,22 +966,23 @@ int enqueue_gst(gsttaco_ctx* c, hipStream_t s, int B, int Tref1) {
     int64_t xb = (int64_t)Tref1 * g.mel_dim;
     int cur = 0;
     for (int i = 0; i < g.n_ref_conv; ++i) {
+        const ConvLayer& L = c->ref_conv[i].L;
         Conv2dArgs a{};
         a.x = x; a.xb = xb;
-        a.w = c->ref_conv[i].w; a.scale = c->ref_conv[i].scale; a.shift = c->ref_conv[i].shift;
+        a.w = L.w; a.scale = L.scale; a.shift = L.shift;
         a.out = c->w_gconv[cur];
-        a.B = B; a.H = H; a.W = W; a.Cin = c->ref_conv[i].cin; a.Cout = c->ref_conv[i].cout;
+        a.B = B; a.H = H; a.W = W; a.Cin = L.cin; a.Cout = L.cout;
         a.k = c->ref_conv[i].k; a.stride = c->ref_conv[i].stride;
         a.pad_h = same_pad_before(H, a.k, a.stride, &a.Ho);
         a.pad_w = same_pad_before(W, a.k, a.stride, &a.Wo);
         if (a.Cin % 4 == 0 && a.Cin >= 16) {
             // implicit GEMM on the fp32 MFMA path (M = B*Ho*Wo rows, K = 9*Cin): the direct kernel's late layers have a
             // few thousand threads with K = 576..1152 serial loads each (124 us for the last one).  Under Use_Mixed_Precision
-            // too: the GST branch stays fp32 there (gt_launch_conv_gemm directly, not launch_conv's bf16 operands)
-            ConvGemmArgs ga{};
-            ga.x = a.x; ga.xb = a.xb; ga.w = a.w; ga.scale = a.scale; ga.shift = a.shift;
+            // too: the GST branch stays fp32 there (the FP32 form is the only one its layers have)
+            ConvGemmArgs ga = conv_args(L, GSTTACO_CONV_FORM_FP32);
+            ga.x = a.x; ga.xb = a.xb;
             ga.out = a.out; ga.ldo = a.Cout;
-            ga.B = B; ga.T = a.Ho * a.Wo; ga.Cin = a.Cin; ga.N = a.Cout; ga.taps = a.k * a.k; ga.act = ACT_RELU;
+            ga.B = B; ga.T = a.Ho * a.Wo; ga.act = ACT_RELU;
             ga.conv2d = 1; ga.H = H; ga.W = W; ga.Wo = a.Wo; ga.kw = a.k; ga.stride = a.stride; ga.pad_h = a.pad_h; ga.pad_w = a.pad_w;
             HIPCHECK(c, gt_launch_conv_gemm(ga, s));
         } else
@@ -990,7 +995,7 @@ int enqueue_gst(gsttaco_ctx* c, hipStream_t s, int B, int Tref1) {
     t.dense_w = c->dense_w; t.dense_b = c->dense_b;
     t.q_w = c->mq_w; t.q_b = c->mq_b; t.v_tok = c->v_tok; t.ln_g = c->ln_g; t.ln_b = c->ln_b;
     t.gst = c->w_gst;
-    t.B = B; t.T2 = H; t.gru_in = W * c->ref_conv[g.n_ref_conv - 1].cout; t.u = g.ref_rnn;
+    t.B = B; t.T2 = H; t.gru_in = W * c->ref_conv[g.n_ref_conv - 1].L.cout; t.u = g.ref_rnn;
     t.D = g.ref_dense; t.A = g.gst_att; t.ntok = g.n_tokens; t.heads = g.heads;
     t.stride_prod = 1;
     for (int i = 0; i < g.n_ref_conv; ++i) t.stride_prod *= g.ref_strides[i];
@@ -1009,17 +1014,15 @@ int enqueue_value_proj(gsttaco_ctx* c, hipStream_t s, int B, int Tv) {
         k.seg[0] = SkinnySeg{c->w_gst, g.gst_att, g.gst_att / 16, 0};
         k.nkb = c->val_gst.nkb; k.M = B; k.N = c->att; k.n_split = c->att; k.MT = (B + 15) / 16;
         k.out = c->w_rowbias; k.ldo = c->att;
-        HIPCHECK(c, launch_skinny(c, EPI_LINEAR, k, nullptr, c->val_gst.ntiles, s));
+        HIPCHECK(c, gt_launch_skinny(EPI_LINEAR, k, nullptr, c->val_gst.ntiles, s));
         rowbias = c->w_rowbias;
     }
-    ConvGemmArgs a{};
-    a.x = c->w_enc; a.w = c->val_enc_w;
-    a.shift = g.gst_use ? nullptr : c->val_bias;
+    ConvGemmArgs a = conv_args(c->val_enc, kFormsPlain | GSTTACO_CONV_FORM_GEMM_SPLIT);      // (its bias: in the row bias with GST, else its shift)
+    a.x = c->w_enc;
     a.rowbias = rowbias;
     a.out = c->w_pm; a.ldo = c->att;
-    a.B = B; a.T = Tv; a.gemm_s = c->val_enc_s; a.wino_npad = c->val_enc_npad;
-    a.Cin = c->enc_out; a.N = c->att; a.taps = 1; a.pad_before = 0; a.act = ACT_NONE;
-    HIPCHECK(c, launch_conv(c, a, s));
+    a.B = B; a.T = Tv; a.act = ACT_NONE;
+    HIPCHECK(c, gt_launch_conv_gemm(a, s));
     return 0;
 }
 
@@ -1285,7 +1288,7 @@ int enqueue_front_kernels(DecodeCall& d, int t) {
     k.mask = d.mask(t, 0); k.ldm = P0;
     k.drop_rate = g.prenet_rate; k.drop_scale = d.drop_scale;
     k.seed_ptr = c->w_seed; k.rng_step = (uint32_t)t; k.rng_stream = 0x1000u;
-    HIPCHECK(c, launch_skinny(c, EPI_RELU_DROP, k, nullptr, c->prenet0.ntiles, s));
+    HIPCHECK(c, gt_launch_skinny(EPI_RELU_DROP, k, nullptr, c->prenet0.ntiles, s));
     // 2. prenet layer 1 -> xa[:, 0:P1]
     memset(&k, 0, sizeof(k));
     k.wp = c->prenet1.wp; k.bf16 = c->prenet1.bf16; k.bias = c->prenet1.bias;
@@ -1295,14 +1298,14 @@ int enqueue_front_kernels(DecodeCall& d, int t) {
     k.mask = d.mask(t, 1); k.ldm = P1;
     k.drop_rate = g.prenet_rate; k.drop_scale = d.drop_scale;
     k.seed_ptr = c->w_seed; k.rng_step = (uint32_t)t; k.rng_stream = 0x1001u;
-    HIPCHECK(c, launch_skinny(c, EPI_RELU_DROP, k, nullptr, c->prenet1.ntiles, s));
+    HIPCHECK(c, gt_launch_skinny(EPI_RELU_DROP, k, nullptr, c->prenet1.ntiles, s));
     // 3. attention query projection (Steps.py:122)
     memset(&k, 0, sizeof(k));
     k.wp = c->query.wp; k.bf16 = c->query.bf16; k.bias = c->query.bias;
     k.seg[0] = SkinnySeg{xa_t, 0, P1 / 16, 1};
     k.nkb = c->query.nkb; k.M = B; k.N = att; k.n_split = att; k.MT = MT;
     k.out = c->w_q; k.ldo = att;
-    HIPCHECK(c, launch_skinny(c, EPI_LINEAR, k, nullptr, c->query.ntiles, s));
+    HIPCHECK(c, gt_launch_skinny(EPI_LINEAR, k, nullptr, c->query.ntiles, s));
     // 4. score / monotonic alignment / context -> xa[:, P1:P1+att]
     AttnStepArgs a{};
     a.q = c->w_q; a.ldq = att; a.pm = c->w_pm; a.v = c->att_v; a.score_bias = c->att_sb;
@@ -1386,7 +1389,7 @@ int enqueue_lstm_cells(DecodeCall& d, int t, bool on) {
                 }
                 HIPCHECK(c, gt_launch_lstm_x(la, k.nkb, tag, k.bf16 != 0, d.s));
             } else
-                HIPCHECK(c, launch_skinny(c, EPI_LSTM, k, nullptr, (H + 3) / 4, d.s, tag));
+                HIPCHECK(c, gt_launch_skinny(EPI_LSTM, k, nullptr, (H + 3) / 4, d.s, tag));
             return 0;
         });
         if (rc) return rc;
@@ -1435,7 +1438,7 @@ int enqueue_projection(DecodeCall& d, int t, bool on) {
             } else
                 HIPCHECK(c, gt_launch_skinny_co(k, PJ.ntiles, rk, 0, P.co_tiles, d.s));
         } else
-            HIPCHECK(c, launch_skinny(c, EPI_LINEAR, k, nullptr, PJ.ntiles, d.s));
+            HIPCHECK(c, gt_launch_skinny(EPI_LINEAR, k, nullptr, PJ.ntiles, d.s));
         return 0;
     });
 }
@@ -1488,23 +1491,21 @@ int enqueue_postnet(gsttaco_ctx* c, hipStream_t s, int B, int Tf, const float* p
     for (int i = 0; i < g.n_post; ++i) {
         const ConvLayer& L = c->post_conv[i];
         const bool last = i == g.n_post - 1;
-        ConvGemmArgs a{};
-        a.x = x; a.w = L.w; a.scale = L.scale; a.shift = L.shift;
-        a.wino_u = L.wino_u; a.wino_u4 = L.wino_u4; a.wino_cin = L.wino_cin;
-        a.wino_s = L.wino_s; a.wino_s4 = L.wino_s4; a.wino_npad = L.wino_npad; a.wino_x3 = c->wino_x3 ? 1 : 0;
+        ConvGemmArgs a = conv_args(L, kFormsPlain | kFormsWino);       // (everything the layer has)
+        a.x = x; a.wino_x3 = c->wino_x3 ? 1 : 0;
         a.out = last ? out : c->w_post[cur]; a.ldo = L.cout;
         a.res = last ? pre : nullptr;                       // post = postnet(x) + x (Taco2.py:230)
-        a.B = B; a.T = Tf; a.Cin = L.cin; a.N = L.cout; a.taps = L.taps;
+        a.B = B; a.T = Tf;
         a.pad_before = same_pad_before(Tf, L.taps, 1, nullptr);
         a.act = i < g.post_tanh ? ACT_TANH : ACT_NONE;     // tanh on the first post_tanh layers only (F9)
         // mixed precision: the activations BETWEEN the layers are stored as bf16 -- the next layer rounds them to bf16 on its way into
         // LDS anyway, so no result changes and half the bytes move; the residual input and the last layer's output stay fp32
-        if (c->cfg.mixed_precision && c->bf16_w.count(L.w)) {
-            a.x_bf16 = i > 0 && c->bf16_w.count(c->post_conv[i - 1].w) ? 1 : 0;
+        if (a.wt_bf16) {
+            a.x_bf16 = i > 0 && c->post_conv[i - 1].wt_bf16 ? 1 : 0;
             // (a bf16 output row is stored as PAIRS of columns: an even channel count only)
-            a.out_bf16 = !last && L.cout % 2 == 0 && c->bf16_w.count(c->post_conv[i + 1].w) ? 1 : 0;
+            a.out_bf16 = !last && L.cout % 2 == 0 && c->post_conv[i + 1].wt_bf16 ? 1 : 0;
         }
-        HIPCHECK(c, launch_conv(c, a, s));
+        HIPCHECK(c, gt_launch_conv_gemm(a, s));
         x = a.out; cur ^= 1;
     }
     return 0;
@@ -1610,95 +1611,69 @@ int ensure_audio(gsttaco_ctx* c) {
 // mel [B,Tf,mel] -> spectrogram [B,Tf,spec]  (reference Taco2.py:258-260, 366-380)
 int enqueue_vocoder(gsttaco_ctx* c, hipStream_t s, int B, int Tf, const float* mel_in, float* spec) {
     const gsttaco_config& g = c->cfg;
-    const int mel = g.mel_dim, NB = g.bank_count * g.bank_filters;
+    const int NB = g.bank_count * g.bank_filters;
     // conv bank: kernel sizes 1..N on the INPUT, each + BN + ReLU, concatenated on the channel axis (Taco2.py:383-407)
+    // (every GEMM of the vocoder: FP32, BF16 under mixed precision, never Winograd)
     for (int i = 0; i < g.bank_count; ++i) {
         const ConvLayer& L = c->voc_bank[i];
-        ConvGemmArgs a{};
-        a.x = mel_in; a.w = L.w; a.scale = L.scale; a.shift = L.shift;
+        ConvGemmArgs a = conv_args(L, kFormsPlain);
+        a.x = mel_in;
         a.out = c->w_vbank + (size_t)i * g.bank_filters; a.ldo = NB;
-        a.B = B; a.T = Tf; a.Cin = mel; a.N = g.bank_filters; a.taps = L.taps;
+        a.B = B; a.T = Tf;
         a.pad_before = same_pad_before(Tf, L.taps, 1, nullptr);       // even kernels pad asymmetrically (F10)
         a.act = ACT_RELU;
-        HIPCHECK(c, launch_conv(c, a, s));
+        HIPCHECK(c, gt_launch_conv_gemm(a, s));
     }
     // MaxPool1D(2,1,'same') fused into the first projection conv's gather; Conv1D + BN (+ReLU except the last) (Taco2.py:319-340)
     const float* x = c->w_vbank;
-    int cin = NB, cur = 0;
+    int cur = 0;
     for (int i = 0; i < g.n_voc_proj; ++i) {
         const ConvLayer& L = c->voc_proj[i];
-        ConvGemmArgs a{};
-        a.x = x; a.w = L.w; a.scale = L.scale; a.shift = L.shift;
+        ConvGemmArgs a = conv_args(L, kFormsPlain);
+        a.x = x;
         a.out = c->w_vbuf[cur]; a.ldo = L.cout;
-        a.B = B; a.T = Tf; a.Cin = cin; a.N = L.cout; a.taps = L.taps;
+        a.B = B; a.T = Tf;
         a.pad_before = same_pad_before(Tf, L.taps, 1, nullptr);
         a.act = i < g.n_voc_proj - 1 ? ACT_RELU : ACT_NONE;
         a.pool2 = i == 0;
         const bool last = i == g.n_voc_proj - 1;
-        if (last && !c->voc_pd_w) a.res = mel_in;                     // residual directly when no Dense follows (:373)
-        HIPCHECK(c, launch_conv(c, a, s));
-        x = a.out; cin = L.cout; cur ^= 1;
+        if (last && !c->voc_pd.w) a.res = mel_in;                     // residual directly when no Dense follows (:373)
+        HIPCHECK(c, gt_launch_conv_gemm(a, s));
+        x = a.out; cur ^= 1;
     }
-    if (c->voc_pd_w) {                                                // Dense back to mel width + residual (:342-345, 373)
-        ConvGemmArgs a{};
-        a.x = x; a.w = c->voc_pd_w; a.shift = c->voc_pd_b; a.res = mel_in;
-        a.out = c->w_vbuf[cur]; a.ldo = mel;
-        a.B = B; a.T = Tf; a.Cin = cin; a.N = mel; a.taps = 1; a.act = ACT_NONE;
-        HIPCHECK(c, launch_conv(c, a, s));
-        x = a.out; cin = mel; cur ^= 1;
+    // a Dense over the frames: x -> out [B*Tf, L.cout]
+    auto dense = [&](const ConvLayer& L, const float* in, float* out, const float* res) {
+        ConvGemmArgs a = conv_args(L, kFormsPlain);
+        a.x = in; a.res = res;
+        a.out = out; a.ldo = L.cout;
+        a.B = B; a.T = Tf; a.act = ACT_NONE;
+        HIPCHECK(c, gt_launch_conv_gemm(a, s));
+        return 0;
+    };
+    int rc = 0;
+    if (c->voc_pd.w) {                                                // Dense back to mel width + residual (:342-345, 373)
+        if ((rc = dense(c->voc_pd, x, c->w_vbuf[cur], mel_in))) return rc;
+        x = c->w_vbuf[cur]; cur ^= 1;
     }
     const int S = g.highway_size;
-    if (c->voc_hin_w) {                                               // Dense to the highway width (:348-351)
-        ConvGemmArgs a{};
-        a.x = x; a.w = c->voc_hin_w; a.shift = c->voc_hin_b;
-        a.out = c->w_vbuf[cur]; a.ldo = S;
-        a.B = B; a.T = Tf; a.Cin = cin; a.N = S; a.taps = 1; a.act = ACT_NONE;
-        HIPCHECK(c, launch_conv(c, a, s));
-        x = a.out; cin = S; cur ^= 1;
+    if (c->voc_hin.w) {                                               // Dense to the highway width (:348-351)
+        if ((rc = dense(c->voc_hin, x, c->w_vbuf[cur], nullptr))) return rc;
+        x = c->w_vbuf[cur]; cur ^= 1;
     }
     float* hbuf[2] = {c->w_vbuf[cur], c->w_vbuf[2]};
     int hcur = 0;
     for (int i = 0; i < g.highway_count; ++i) {                       // Highwaynet (:409-424)
-        ConvGemmArgs a{};
-        a.x = x; a.w = c->voc_hw_w[i]; a.shift = c->voc_hw_b[i];
-        a.out = c->w_vz; a.ldo = 2 * S;
-        a.B = B; a.T = Tf; a.Cin = S; a.N = 2 * S; a.taps = 1; a.act = ACT_NONE;
-        HIPCHECK(c, launch_conv(c, a, s));
+        if ((rc = dense(c->voc_hw[i], x, c->w_vz, nullptr))) return rc;
         HIPCHECK(c, gt_launch_highway(c->w_vz, x, hbuf[hcur], (int64_t)B * Tf, S, s));
         x = hbuf[hcur]; hcur ^= 1;
     }
-    // Bidirectional LSTM over the Tf frames: one launch per time step, both directions in grid.z (:353-361)
-    const int H = g.voc_rnn, EO = 2 * H;
+    // Bidirectional LSTM over the Tf frames (:353-361)
+    const int H = g.voc_rnn;
     HIPCHECK(c, gt_launch_zero(c->w_vc, (size_t)2 * B * H, s));
-    if (lean_bilstm_usable(c, c->voc_lean, B)) {
-        int rl = enqueue_lean_bilstm(c, s, c->voc_lean, x, B, Tf, c->w_vc, c->w_vrnn, nullptr);
-        if (rl) return rl;
-    } else
-    for (int t = 0; t < Tf; ++t) {
-        SkinnyArgs a[2];
-        for (int d = 0; d < 2; ++d) {
-            const int tt = d == 0 ? t : Tf - 1 - t;
-            const int tp = d == 0 ? tt - 1 : tt + 1;
-            SkinnyArgs& k = a[d];
-            memset(&k, 0, sizeof(k));
-            k.wp = c->voc_bilstm[d].wp; k.bf16 = c->voc_bilstm[d].bf16; k.bias = c->voc_bilstm[d].bias;
-            k.seg[0] = SkinnySeg{x + (size_t)tt * S, (int64_t)Tf * S, S / 16, 0};
-            if (t == 0) k.seg[1] = SkinnySeg{c->w_zero, 0, H / 16, 0};
-            else k.seg[1] = SkinnySeg{c->w_vrnn + (size_t)tp * EO + d * H, (int64_t)Tf * EO, H / 16, 0};
-            k.nkb = c->voc_bilstm[d].nkb; k.M = B; k.N = H; k.MT = (B + 15) / 16;
-            k.c = c->w_vc + (size_t)d * B * H;
-            k.h = c->w_vrnn + (size_t)tt * EO + d * H; k.ldh = (int64_t)Tf * EO;
-        }
-        HIPCHECK(c, launch_skinny(c, EPI_LSTM, a[0], &a[1], c->voc_bilstm[0].ntiles, s, TAG_ENC_BILSTM));
-    }
-    {   // Dense to the linear-spectrogram width (Taco2.py:252-260)
-        ConvGemmArgs a{};
-        a.x = c->w_vrnn; a.w = c->voc_dense_w; a.shift = c->voc_dense_b; a.ldw = c->voc_dense_ldw;
-        a.out = spec; a.ldo = g.spec_dim;
-        a.B = B; a.T = Tf; a.Cin = EO; a.N = g.spec_dim; a.taps = 1; a.act = ACT_NONE;
-        HIPCHECK(c, launch_conv(c, a, s));
-    }
-    return 0;
+    if (lean_bilstm_usable(c, c->voc_lean, B)) rc = enqueue_lean_bilstm(c, s, c->voc_lean, x, B, Tf, c->w_vc, c->w_vrnn, nullptr);
+    else rc = enqueue_bilstm_steps(c, s, c->voc_bilstm, x, B, Tf, S, H, c->w_vc, c->w_vrnn, nullptr);
+    if (rc) return rc;
+    return dense(c->voc_dense, c->w_vrnn, spec, nullptr);             // Dense to the linear-spectrogram width (Taco2.py:252-260)
 }
 
 int check_ready(gsttaco_ctx* c) {
@@ -2022,83 +1997,67 @@ int gsttaco_load_weight(gsttaco_ctx* c, const char* name, const float* host, con
     return 0;
 }
 
-int gsttaco_finalize_weights(gsttaco_ctx* c) {
-    if (!c) return GSTTACO_E_INVALID;
-    if (c->finalized) return 0;
-    for (auto& t : c->tensors)
-        if (!t.loaded) return fail(c, GSTTACO_E_WEIGHTS, "missing weight '" + t.name + "'");
-    const gsttaco_config& g = c->cfg;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= g.device)
-        return fail(c, GSTTACO_E_NO_DEVICE, "no HIP device: the gfx950 kernels are the only compute path (no CPU fallback)");
-    HIPCHECK(c, hipSetDevice(g.device));
-    hipDeviceProp_t prop;
-    HIPCHECK(c, hipGetDeviceProperties(&prop, g.device));
-    if (!strstr(prop.gcnArchName, "gfx950"))
-        return fail(c, GSTTACO_E_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", kernels are built for gfx950 only");
-    HIPCHECK(c, hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking));
-    HIPCHECK(c, hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
-    HIPCHECK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    HIPCHECK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-    if (prop.multiProcessorCount > 0) c->n_cu = prop.multiProcessorCount;
+}  // extern "C"
 
+// ---------------------------------------------------------------------------- gsttaco_finalize_weights, module by module
+namespace {
+
+// the whole [x_t | h_prev] GEMM of both directions (the launch per time step) and, where it applies, the lean form
+int finalize_bilstm(gsttaco_ctx* c, PackedLinear* pk, gsttaco_ctx::LeanBiLstm* lean, const std::string& prefix, int H) {
+    int d = 0, rc = 0;
+    for (const char* dir : {"fwd", "bwd"}) {
+        const std::string p = prefix + "." + dir;
+        const HostTensor &k = T(c, p + ".kernel"), &u = T(c, p + ".recurrent_kernel"), &b = T(c, p + ".bias");
+        if ((rc = pack_linear(c, &pk[d], {{k.data.data(), (int)k.shape[0]}, {u.data.data(), (int)u.shape[0]}}, 4 * H, b.data.data(), H))) return rc;
+        ++d;
+    }
+    return build_lean_bilstm(c, lean, prefix, H);
+}
+
+int finalize_encoder(gsttaco_ctx* c) {
+    const gsttaco_config& g = c->cfg;
+    int rc = upload_tensor(c, &c->d_emb, "encoder.embedding");
+    c->enc_conv.resize(g.n_enc_conv);
+    for (int i = 0; i < g.n_enc_conv && !rc; ++i) rc = upload_conv(c, &c->enc_conv[i], "encoder.conv" + std::to_string(i), true);
+    return rc ? rc : finalize_bilstm(c, c->bilstm, &c->enc_lean, "encoder.bilstm", g.enc_rnn);
+}
+
+int finalize_gst(gsttaco_ctx* c) {
+    const gsttaco_config& g = c->cfg;
     int rc = 0;
-    // ---- encoder
-    {
-        const HostTensor& e = T(c, "encoder.embedding");
-        if ((rc = upload(c, &c->d_emb, e.data.data(), e.data.size()))) return rc;
-        c->enc_conv.resize(g.n_enc_conv);
-        for (int i = 0; i < g.n_enc_conv; ++i)
-            if ((rc = upload_conv(c, &c->enc_conv[i], "encoder.conv" + std::to_string(i)))) return rc;
-        int d = 0;
-        for (const char* dir : {"fwd", "bwd"}) {
-            std::string p = std::string("encoder.bilstm.") + dir;
-            const HostTensor &k = T(c, p + ".kernel"), &u = T(c, p + ".recurrent_kernel"), &b = T(c, p + ".bias");
-            if ((rc = pack_linear(c, &c->bilstm[d], {{k.data.data(), (int)k.shape[0]}, {u.data.data(), (int)u.shape[0]}},
-                                  4 * g.enc_rnn, b.data.data(), g.enc_rnn))) return rc;
-            ++d;
-        }
-        if ((rc = build_lean_bilstm(c, &c->enc_lean, "encoder.bilstm", g.enc_rnn))) return rc;
+    for (int i = 0; i < g.n_ref_conv; ++i) {
+        const std::string p = "gst.ref.conv" + std::to_string(i);
+        const HostTensor& k = T(c, p + ".kernel");      // [k, k, cin, cout] == [taps * cin, cout]
+        std::vector<float> sc, sh;
+        fold_bn(c, p, sc, sh);
+        auto& R = c->ref_conv[i];
+        R.k = (int)k.shape[0]; R.stride = g.ref_strides[i];
+        // (the FP32 form only: the GST branch never runs on bf16 operands, mixed precision or not)
+        if ((rc = prepare_conv_forms(c, &R.L, k.data.data(), R.k * R.k, (int)k.shape[2], (int)k.shape[3], (int)k.shape[3], sc.data(), sh.data(),
+                                     GSTTACO_CONV_FORM_FP32))) return rc;
     }
-    // ---- GST
-    if (g.gst_use) {
-        for (int i = 0; i < g.n_ref_conv; ++i) {
-            std::string p = "gst.ref.conv" + std::to_string(i);
-            const HostTensor& k = T(c, p + ".kernel");
-            std::vector<float> sc, sh;
-            fold_bn(c, p, sc, sh);
-            auto& L = c->ref_conv[i];
-            L.k = (int)k.shape[0]; L.cin = (int)k.shape[2]; L.cout = (int)k.shape[3]; L.stride = g.ref_strides[i];
-            if ((rc = upload(c, &L.w, k.data.data(), k.data.size()))) return rc;
-            if ((rc = upload(c, &L.scale, sc.data(), sc.size()))) return rc;
-            if ((rc = upload(c, &L.shift, sh.data(), sh.size()))) return rc;
+    const std::pair<float**, const char*> plain[] = {
+        {&c->gru_w, "gst.ref.gru.kernel"}, {&c->gru_u, "gst.ref.gru.recurrent_kernel"}, {&c->gru_b, "gst.ref.gru.bias"},
+        {&c->dense_w, "gst.ref.dense.kernel"}, {&c->dense_b, "gst.ref.dense.bias"}, {&c->mq_w, "gst.mha.query.kernel"},
+        {&c->mq_b, "gst.mha.query.bias"}, {&c->ln_g, "gst.mha.ln.gamma"}, {&c->ln_b, "gst.mha.ln.beta"}};
+    for (const auto& t : plain)
+        if ((rc = upload_tensor(c, t.first, t.second))) return rc;
+    // v_tok = tanh(tokens).Wv + bv  (GST.py:100-101, Layers.py:175; batch-invariant)
+    const HostTensor &tok = T(c, "gst.tokens"), &wv = T(c, "gst.mha.value.kernel"), &bv = T(c, "gst.mha.value.bias");
+    std::vector<float> vt((size_t)g.n_tokens * g.gst_att);
+    for (int n = 0; n < g.n_tokens; ++n)
+        for (int a = 0; a < g.gst_att; ++a) {
+            double s = bv.data[a];
+            for (int e = 0; e < g.token_emb; ++e)
+                s += std::tanh((double)tok.data[(size_t)n * g.token_emb + e]) * (double)wv.data[(size_t)e * g.gst_att + a];
+            vt[(size_t)n * g.gst_att + a] = (float)s;
         }
-        auto up = [&](float** dst, const char* name) {
-            const HostTensor& t = T(c, name);
-            return upload(c, dst, t.data.data(), t.data.size());
-        };
-        if ((rc = up(&c->gru_w, "gst.ref.gru.kernel"))) return rc;
-        if ((rc = up(&c->gru_u, "gst.ref.gru.recurrent_kernel"))) return rc;
-        if ((rc = up(&c->gru_b, "gst.ref.gru.bias"))) return rc;
-        if ((rc = up(&c->dense_w, "gst.ref.dense.kernel"))) return rc;
-        if ((rc = up(&c->dense_b, "gst.ref.dense.bias"))) return rc;
-        if ((rc = up(&c->mq_w, "gst.mha.query.kernel"))) return rc;
-        if ((rc = up(&c->mq_b, "gst.mha.query.bias"))) return rc;
-        if ((rc = up(&c->ln_g, "gst.mha.ln.gamma"))) return rc;
-        if ((rc = up(&c->ln_b, "gst.mha.ln.beta"))) return rc;
-        // v_tok = tanh(tokens).Wv + bv  (GST.py:100-101, Layers.py:175; batch-invariant)
-        const HostTensor &tok = T(c, "gst.tokens"), &wv = T(c, "gst.mha.value.kernel"), &bv = T(c, "gst.mha.value.bias");
-        std::vector<float> vt((size_t)g.n_tokens * g.gst_att);
-        for (int n = 0; n < g.n_tokens; ++n)
-            for (int a = 0; a < g.gst_att; ++a) {
-                double s = bv.data[a];
-                for (int e = 0; e < g.token_emb; ++e)
-                    s += std::tanh((double)tok.data[(size_t)n * g.token_emb + e]) * (double)wv.data[(size_t)e * g.gst_att + a];
-                vt[(size_t)n * g.gst_att + a] = (float)s;
-            }
-        if ((rc = upload(c, &c->v_tok, vt.data(), vt.size()))) return rc;
-    }
-    // ---- decoder step
+    return upload(c, &c->v_tok, vt.data(), vt.size());
+}
+
+int finalize_decoder_step(gsttaco_ctx* c) {
+    const gsttaco_config& g = c->cfg;
+    int rc = 0;
     pad_decoder(c);
     {
         const HostTensor &k0 = T(c, "decoder.prenet0.kernel"), &b0 = T(c, "decoder.prenet0.bias");
@@ -2117,21 +2076,15 @@ int gsttaco_finalize_weights(gsttaco_ctx* c) {
         const int goff = g.gst_use ? g.gst_att : 0;     // memory channel order [gst | enc] (GST.py:121-124)
         if (g.gst_use)
             if ((rc = pack_linear(c, &c->val_gst, {{vk.data.data(), g.gst_att}}, c->att, vb.data.data(), 0))) return rc;
-        if ((rc = upload(c, &c->val_enc_w, vk.data.data() + (size_t)goff * c->att, (size_t)c->enc_out * c->att))) return rc;
-        if ((rc = add_bf16(c, c->val_enc_w, vk.data.data() + (size_t)goff * c->att, c->enc_out, c->att, c->att))) return rc;
-        if (c->wino_split && !g.mixed_precision && c->enc_out % 32 == 0 &&
-            (rc = upload_gemm_split(c, &c->val_enc_s, vk.data.data() + (size_t)goff * c->att, c->enc_out, c->att, c->att, &c->val_enc_npad))) return rc;
-        if ((rc = upload(c, &c->val_bias, vb.data.data(), vb.data.size()))) return rc;
+        // (with GST the bias rides in val_gst's row bias: enqueue_value_proj)
+        if ((rc = upload_dense(c, &c->val_enc, vk.data.data() + (size_t)goff * c->att, c->enc_out, c->att, c->att,
+                               g.gst_use ? nullptr : vb.data.data(), true))) return rc;
         if (g.att_type == GSTTACO_ATT_LSA) {
-            auto up = [&](float** dst, const char* name) {
-                const HostTensor& t = T(c, name);
-                return upload(c, dst, t.data.data(), t.data.size());
-            };
-            if ((rc = up(&c->loc_cw, "decoder.attention.location_conv.kernel"))) return rc;
-            if ((rc = up(&c->loc_cb, "decoder.attention.location_conv.bias"))) return rc;
-            if ((rc = up(&c->loc_dw, "decoder.attention.location_dense.kernel"))) return rc;
-            if ((rc = up(&c->loc_db, "decoder.attention.location_dense.bias"))) return rc;
-            if ((rc = up(&c->att_bias, "decoder.attention.bias"))) return rc;
+            if ((rc = upload_tensor(c, &c->loc_cw, "decoder.attention.location_conv.kernel"))) return rc;
+            if ((rc = upload_tensor(c, &c->loc_cb, "decoder.attention.location_conv.bias"))) return rc;
+            if ((rc = upload_tensor(c, &c->loc_dw, "decoder.attention.location_dense.kernel"))) return rc;
+            if ((rc = upload_tensor(c, &c->loc_db, "decoder.attention.location_dense.bias"))) return rc;
+            if ((rc = upload_tensor(c, &c->att_bias, "decoder.attention.bias"))) return rc;
             {   // the same five tensors as the fused front end's LDS image (kernels.h LsaPack)
                 const HostTensor &cw = T(c, "decoder.attention.location_conv.kernel"), &cb = T(c, "decoder.attention.location_conv.bias");
                 const HostTensor &dw = T(c, "decoder.attention.location_dense.kernel"), &db = T(c, "decoder.attention.location_dense.bias");
@@ -2190,74 +2143,62 @@ int gsttaco_finalize_weights(gsttaco_ctx* c) {
         }
         if ((rc = pack_linear(c, &c->proj_z, {{we.data(), K}}, NE, be.data(), 0))) return rc;
     }
-    // ---- postnet
-    c->post_conv.resize(g.n_post);
-    for (int i = 0; i < g.n_post; ++i)
-        if ((rc = upload_conv(c, &c->post_conv[i], "postnet.conv" + std::to_string(i)))) return rc;
+    return 0;
+}
 
-    // ---- CBHG vocoder
-    if (g.voc_use) {
-        c->voc_bank.resize(g.bank_count);
-        for (int i = 0; i < g.bank_count; ++i)
-            if ((rc = upload_conv(c, &c->voc_bank[i], "vocoder.convbank" + std::to_string(i)))) return rc;
-        c->voc_proj.resize(g.n_voc_proj);
-        for (int i = 0; i < g.n_voc_proj; ++i)
-            if ((rc = upload_conv(c, &c->voc_proj[i], "vocoder.proj" + std::to_string(i)))) return rc;
-        auto upn = [&](float** dst, const std::string& name) {
-            const HostTensor& t = T(c, name);
-            int r = upload(c, dst, t.data.data(), t.data.size());
-            if (!r && t.shape.size() == 2) r = add_bf16(c, *dst, t.data.data(), (int)t.shape[0], (int)t.shape[1], (int)t.shape[1]);
-            return r;
-        };
-        if (c->index.count("vocoder.proj_dense.kernel")) {
-            if ((rc = upn(&c->voc_pd_w, "vocoder.proj_dense.kernel"))) return rc;
-            if ((rc = upn(&c->voc_pd_b, "vocoder.proj_dense.bias"))) return rc;
-        }
-        if (c->index.count("vocoder.highway_in.kernel")) {
-            if ((rc = upn(&c->voc_hin_w, "vocoder.highway_in.kernel"))) return rc;
-            if ((rc = upn(&c->voc_hin_b, "vocoder.highway_in.bias"))) return rc;
-        }
-        const int S = g.highway_size;
-        for (int i = 0; i < g.highway_count; ++i) {
-            // one GEMM per layer: columns [0,S) = Dense_Relu, [S,2S) = Dense_Sigmoid (Taco2.py:412-420)
-            const std::string p = "vocoder.highway" + std::to_string(i);
-            const HostTensor &wr = T(c, p + ".relu.kernel"), &br = T(c, p + ".relu.bias");
-            const HostTensor &ws = T(c, p + ".sigmoid.kernel"), &bs = T(c, p + ".sigmoid.bias");
-            std::vector<float> wcat((size_t)S * 2 * S), bcat(2 * S);
-            for (int k = 0; k < S; ++k)
-                for (int n = 0; n < S; ++n) {
-                    wcat[(size_t)k * 2 * S + n] = wr.data[(size_t)k * S + n];
-                    wcat[(size_t)k * 2 * S + S + n] = ws.data[(size_t)k * S + n];
-                }
-            for (int n = 0; n < S; ++n) { bcat[n] = br.data[n]; bcat[S + n] = bs.data[n]; }
-            float *dw = nullptr, *db = nullptr;
-            if ((rc = upload(c, &dw, wcat.data(), wcat.size()))) return rc;
-            if ((rc = add_bf16(c, dw, wcat.data(), S, 2 * S, 2 * S))) return rc;
-            if ((rc = upload(c, &db, bcat.data(), bcat.size()))) return rc;
-            c->voc_hw_w.push_back(dw); c->voc_hw_b.push_back(db);
-        }
-        int d = 0;
-        for (const char* dir : {"fwd", "bwd"}) {
-            std::string p = std::string("vocoder.bilstm.") + dir;
-            const HostTensor &k = T(c, p + ".kernel"), &u = T(c, p + ".recurrent_kernel"), &b = T(c, p + ".bias");
-            if ((rc = pack_linear(c, &c->voc_bilstm[d], {{k.data.data(), (int)k.shape[0]}, {u.data.data(), (int)u.shape[0]}},
-                                  4 * g.voc_rnn, b.data.data(), g.voc_rnn))) return rc;
-            ++d;
-        }
-        if ((rc = build_lean_bilstm(c, &c->voc_lean, "vocoder.bilstm", g.voc_rnn))) return rc;
-        {   // final Dense: rows padded to a multiple of 4 columns so the GEMM can load 16 bytes per lane
-            const HostTensor &k = T(c, "vocoder.dense.kernel"), &b = T(c, "vocoder.dense.bias");
-            const int K = (int)k.shape[0], N = g.spec_dim, ldw = (N + 3) / 4 * 4;
-            std::vector<float> wpad((size_t)K * ldw, 0.f);
-            for (int r = 0; r < K; ++r) memcpy(&wpad[(size_t)r * ldw], &k.data[(size_t)r * N], (size_t)N * sizeof(float));
-            c->voc_dense_ldw = ldw;
-            if ((rc = upload(c, &c->voc_dense_w, wpad.data(), wpad.size()))) return rc;
-            if ((rc = add_bf16(c, c->voc_dense_w, wpad.data(), K, N, ldw))) return rc;
-            if ((rc = upload(c, &c->voc_dense_b, b.data.data(), b.data.size()))) return rc;
-        }
+int finalize_postnet(gsttaco_ctx* c) {
+    int rc = 0;
+    c->post_conv.resize(c->cfg.n_post);
+    for (int i = 0; i < c->cfg.n_post && !rc; ++i) rc = upload_conv(c, &c->post_conv[i], "postnet.conv" + std::to_string(i), true);
+    return rc;
+}
+
+// CBHG vocoder.  No call of enqueue_vocoder passes a Winograd or split form, so none is built (not for its five-tap layers either).
+int finalize_vocoder(gsttaco_ctx* c) {
+    const gsttaco_config& g = c->cfg;
+    int rc = 0;
+    c->voc_bank.resize(g.bank_count);
+    for (int i = 0; i < g.bank_count; ++i)
+        if ((rc = upload_conv(c, &c->voc_bank[i], "vocoder.convbank" + std::to_string(i), false))) return rc;
+    c->voc_proj.resize(g.n_voc_proj);
+    for (int i = 0; i < g.n_voc_proj; ++i)
+        if ((rc = upload_conv(c, &c->voc_proj[i], "vocoder.proj" + std::to_string(i), false))) return rc;
+    // a Dense as the checkpoint holds it: name.kernel [K, N], name.bias [N]
+    auto dense = [&](ConvLayer* L, const std::string& name) {
+        const HostTensor &k = T(c, name + ".kernel"), &b = T(c, name + ".bias");
+        return upload_dense(c, L, k.data.data(), (int)k.shape[0], (int)k.shape[1], (int)k.shape[1], b.data.data(), false);
+    };
+    if (c->index.count("vocoder.proj_dense.kernel") && (rc = dense(&c->voc_pd, "vocoder.proj_dense"))) return rc;
+    if (c->index.count("vocoder.highway_in.kernel") && (rc = dense(&c->voc_hin, "vocoder.highway_in"))) return rc;
+    const int S = g.highway_size;
+    c->voc_hw.resize(g.highway_count);
+    for (int i = 0; i < g.highway_count; ++i) {
+        // one GEMM per layer: columns [0,S) = Dense_Relu, [S,2S) = Dense_Sigmoid (Taco2.py:412-420)
+        const std::string p = "vocoder.highway" + std::to_string(i);
+        const HostTensor &wr = T(c, p + ".relu.kernel"), &br = T(c, p + ".relu.bias");
+        const HostTensor &ws = T(c, p + ".sigmoid.kernel"), &bs = T(c, p + ".sigmoid.bias");
+        std::vector<float> wcat((size_t)S * 2 * S), bcat(2 * S);
+        for (int k = 0; k < S; ++k)
+            for (int n = 0; n < S; ++n) {
+                wcat[(size_t)k * 2 * S + n] = wr.data[(size_t)k * S + n];
+                wcat[(size_t)k * 2 * S + S + n] = ws.data[(size_t)k * S + n];
+            }
+        for (int n = 0; n < S; ++n) { bcat[n] = br.data[n]; bcat[S + n] = bs.data[n]; }
+        if ((rc = upload_dense(c, &c->voc_hw[i], wcat.data(), S, 2 * S, 2 * S, bcat.data(), false))) return rc;
     }
+    if ((rc = finalize_bilstm(c, c->voc_bilstm, &c->voc_lean, "vocoder.bilstm", g.voc_rnn))) return rc;
+    // final Dense: rows padded to a multiple of 4 columns so the GEMM can load 16 bytes per lane
+    const HostTensor &k = T(c, "vocoder.dense.kernel"), &b = T(c, "vocoder.dense.bias");
+    const int K = (int)k.shape[0], N = g.spec_dim, ldw = (N + 3) / 4 * 4;
+    std::vector<float> wpad((size_t)K * ldw, 0.f);
+    for (int r = 0; r < K; ++r) memcpy(&wpad[(size_t)r * ldw], &k.data[(size_t)r * N], (size_t)N * sizeof(float));
+    return upload_dense(c, &c->voc_dense, wpad.data(), K, N, ldw, b.data.data(), false);
+}
 
-    // ---- workspace, sized once for the capacity given at create
+// the workspace, sized once for the capacity given at create
+int alloc_workspace(gsttaco_ctx* c) {
+    const gsttaco_config& g = c->cfg;
+    int rc = 0;
     const size_t B = g.max_batch, Tv = g.max_tokens, S = c->steps_max, Tf = S * c->r, mel = g.mel_dim;
     auto fa = [&](float** p, size_t n) { return dev_alloc(c, (void**)p, n * sizeof(float)); };
     if ((rc = dev_alloc(c, (void**)&c->w_tokens, B * Tv * 4))) return rc;
@@ -2361,6 +2302,31 @@ int gsttaco_finalize_weights(gsttaco_ctx* c) {
         if ((rc = alloc_lean_bilstm(c, &c->voc_lean, B, Tf))) return rc;
         if ((rc = fa(&c->w_spec, B * Tf * g.spec_dim))) return rc;
     }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gsttaco_finalize_weights(gsttaco_ctx* c) {
+    if (!c) return GSTTACO_E_INVALID;
+    if (c->finalized) return 0;
+    for (auto& t : c->tensors)
+        if (!t.loaded) return fail(c, GSTTACO_E_WEIGHTS, "missing weight '" + t.name + "'");
+    const gsttaco_config& g = c->cfg;
+    int rc = ensure_device(c);
+    if (rc) return rc;
+    HIPCHECK(c, hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking));
+    HIPCHECK(c, hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
+    HIPCHECK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+    HIPCHECK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+    if ((rc = finalize_encoder(c))) return rc;
+    if (g.gst_use && (rc = finalize_gst(c))) return rc;
+    if ((rc = finalize_decoder_step(c))) return rc;
+    if ((rc = finalize_postnet(c))) return rc;
+    if (g.voc_use && (rc = finalize_vocoder(c))) return rc;
+    if ((rc = alloc_workspace(c))) return rc;
     HIPCHECK(c, gt_attn_init());
     HIPCHECK(c, gt_dec_front_init());
     HIPCHECK(c, gt_gst_init());
@@ -2779,19 +2745,15 @@ int gsttaco_debug_conv_run(gsttaco_ctx* c, int id, const gsttaco_conv_call* k, c
     const int f = k->forms;
     if ((f & c->dbg_conv[id].forms) != f || !(f & GSTTACO_CONV_FORM_FP32) || k->B < 1 || k->T < 1 || (k->ldo && k->ldo < L.cout))
         return fail(c, GSTTACO_E_INVALID, "gsttaco_debug_conv_run: bad call (a form that was not prepared?)");
-    // (what the production call sites fill in, from the caller's fields: no allocation, no synchronisation)
-    ConvGemmArgs a{};
-    a.x = reinterpret_cast<const float*>(x); a.tokens = tokens; a.w = L.w; a.scale = L.scale; a.shift = L.shift;
-    a.rowbias = rowbias; a.res = res; a.row_len = row_len; a.ldw = L.ldw; a.pool2 = k->pool2;
-    if (f & GSTTACO_CONV_FORM_BF16) { a.wt_bf16 = L.wt_bf16; a.ldk = L.ldk; }
+    // (the weight half through the builder the production call sites use; the call's own half from the caller's fields: no allocation,
+    // no synchronisation)
+    ConvGemmArgs a = conv_args(L, f);
+    a.x = reinterpret_cast<const float*>(x); a.tokens = tokens;
+    a.rowbias = rowbias; a.res = res; a.row_len = row_len; a.pool2 = k->pool2;
     a.x_bf16 = k->x_bf16; a.out_bf16 = k->out_bf16;
-    const bool split = (f & GSTTACO_CONV_FORM_WINO_SPLIT) != 0;
-    if (f & GSTTACO_CONV_FORM_WINO2) { a.wino_u = L.wino_u; if (split) a.wino_s = L.wino_s; }
-    if (f & GSTTACO_CONV_FORM_WINO4) { a.wino_u4 = L.wino_u4; if (split) a.wino_s4 = L.wino_s4; }
-    if (f & GSTTACO_CONV_FORM_GEMM_SPLIT) a.gemm_s = L.gemm_s;
-    a.wino_cin = L.wino_cin; a.wino_npad = L.wino_npad; a.wino_x3 = k->wino_x3; a.wino_min_wgs = k->wino_min_wgs;
+    a.wino_x3 = k->wino_x3; a.wino_min_wgs = k->wino_min_wgs;
     a.out = reinterpret_cast<float*>(out); a.ldo = k->ldo ? k->ldo : L.cout;
-    a.B = k->B; a.T = k->T; a.Cin = L.cin; a.N = L.cout; a.taps = L.taps; a.pad_before = k->pad_before; a.act = k->act;
+    a.B = k->B; a.T = k->T; a.pad_before = k->pad_before; a.act = k->act;
     a.conv2d = k->conv2d; a.H = k->H; a.W = k->W; a.Wo = k->Wo; a.kw = k->kw; a.stride = k->stride; a.pad_h = k->pad_h; a.pad_w = k->pad_w;
     a.xb = k->xb;
     const int v = gt_conv_gemm_variant(a);

@@ -1,8 +1,9 @@
 """GPU: every kernel instantiation of the conv/GEMM dispatcher (gt_launch_conv_gemm) against the float64 reference of its contract
 (oracle/conv_ref.py), through gsttaco_debug_conv_prepare / _run, at the shapes where its variant choice switches.
 
-Each case mirrors one production call site's ConvGemmArgs and names the variant it must run (asserted: a threshold change cannot move
-a case off its kernel silently).  Checks, where they apply:
+Each case is one production call site's call -- its weight forms (`forms`: what the site hands to the host's one argument builder,
+conv_args, which gsttaco_debug_conv_run goes through as well) and its own fields -- and names the variant it must run (asserted: a
+threshold change cannot move a case off its kernel silently).  Checks, where they apply:
   exact      small-integer data (|x|, |w| <= 15, exact scale / shift): every partial sum is exact in fp32 and bf16, so every
              non-Winograd variant must equal the float64 reference BITWISE (act none / relu)
   bound      Gaussian and wide-exponent data: |y - y_ref| <= C 2^-24 m + one rounding for the epilogue (m = the same sum on absolute
