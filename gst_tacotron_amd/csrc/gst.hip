@@ -10,6 +10,7 @@
 // The whole GST path is ~25 MMAC per utterance, run once per batch: these are plain VALU kernels with
 // coalesced channel-fastest accesses; the decode loop is where the time goes.
 #include <algorithm>
+#include <string>
 #include "device_utils.h"
 #include "kernels.h"
 
@@ -214,25 +215,48 @@ __global__ __launch_bounds__(TAIL_THREADS) void gt_gst_tail_kernel(GstTailArgs P
         P.gst[(int64_t)b * P.A + j] = P.ln_g[j] * ((ov[j] - red[0]) * red[1]) + P.ln_b[j];
 }
 
-static size_t tail_lds_bytes(const GstTailArgs& a) {
-    const int G = 3 * a.u;
+#define TAIL_LDS_MAX (160 * 1024)
+
+static size_t tail_lds_bytes(int gru_in, int u, int D, int A, int heads, int ntok) {
+    const int G = 3 * u;
     const size_t KPG = TAIL_THREADS / (G / 4);
     size_t part = (size_t)TAIL_MAXT * KPG * G;
     auto need = [&](int N) { return (size_t)(TAIL_THREADS / (N / 4)) * N; };
-    part = std::max<size_t>({part, need(a.D), need(a.A), (size_t)a.heads * a.ntok});
-    return ((size_t)TAIL_MAXT * a.gru_in + a.u + (size_t)TAIL_MAXT * G + G + a.D + 2 * (size_t)a.A + 64 + part) * sizeof(float);
+    part = std::max<size_t>({part, need(D), need(A), (size_t)heads * ntok});
+    return ((size_t)TAIL_MAXT * gru_in + u + (size_t)TAIL_MAXT * G + G + D + 2 * (size_t)A + 64 + part) * sizeof(float);
+}
+
+// The one statement of what gt_gst_tail_kernel can run: gsttaco_create asks it with the configured sizes, the launch with its arguments.
+bool gt_gst_tail_supported(int gru_in, int u, int D, int A, int heads, int ntok, std::string* why) {
+    auto no = [&](const std::string& m) { if (why) *why = m; return false; };
+    if (gru_in < 1 || u < 1 || D < 1 || A < 1 || heads < 1 || ntok < 1) return no("GST sizes must be positive");
+    const int64_t G = 3 * (int64_t)u;
+    if (G & 3) return no("3 x Reference_Encoder.RNN.Size (" + std::to_string(G) + ") must be a multiple of 4");
+    if (D & 3) return no("Reference_Encoder.Dense.Size (" + std::to_string(D) + ") must be a multiple of 4");
+    if (A & 3) return no("Style_Token.Attention.Size (" + std::to_string(A) + ") must be a multiple of 4");
+    if (gru_in & 3) return no("the reference encoder's GRU input width (" + std::to_string(gru_in) + ") must be a multiple of 4");
+    if (G / 4 > TAIL_THREADS) return no("3 x Reference_Encoder.RNN.Size (" + std::to_string(G) + ") must be at most " + std::to_string(4 * TAIL_THREADS));
+    if (D / 4 > TAIL_THREADS) return no("Reference_Encoder.Dense.Size (" + std::to_string(D) + ") must be at most " + std::to_string(4 * TAIL_THREADS));
+    if (A / 4 > TAIL_THREADS) return no("Style_Token.Attention.Size (" + std::to_string(A) + ") must be at most " + std::to_string(4 * TAIL_THREADS));
+    if (A % heads) return no("Style_Token.Attention.Size must be divisible by Head");
+    if (gru_in > (1 << 24) || (int64_t)heads * ntok > (1 << 24))
+        return no("the reference encoder's GRU input width (" + std::to_string(gru_in) + ") and Head x Style_Token.Size (" +
+                  std::to_string((int64_t)heads * ntok) + ") must be at most 16777216");
+    const size_t lds = tail_lds_bytes(gru_in, u, D, A, heads, ntok);
+    if (lds <= TAIL_LDS_MAX) return true;
+    return no("the style-token kernel needs " + std::to_string(lds) + " bytes of shared memory for GRU input width " +
+              std::to_string(gru_in) + ", Reference_Encoder.RNN.Size " + std::to_string(u) + ", Dense.Size " + std::to_string(D) + ", Attention.Size " +
+              std::to_string(A) + ", Head x Style_Token.Size " + std::to_string((int64_t)heads * ntok) + ": more than the " + std::to_string(TAIL_LDS_MAX) +
+              " (160 KiB) it can have");
 }
 
 hipError_t gt_launch_gst_tail(const GstTailArgs& a, hipStream_t stream) {
-    const int G = 3 * a.u;
-    if ((G & 3) || (a.D & 3) || (a.A & 3) || G / 4 > TAIL_THREADS || a.D / 4 > TAIL_THREADS || a.A / 4 > TAIL_THREADS || (a.gru_in & 3))
-        return hipErrorInvalidValue;
-    const size_t lds = tail_lds_bytes(a);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (!gt_gst_tail_supported(a.gru_in, a.u, a.D, a.A, a.heads, a.ntok, nullptr)) return hipErrorInvalidValue;
+    const size_t lds = tail_lds_bytes(a.gru_in, a.u, a.D, a.A, a.heads, a.ntok);
     hipLaunchKernelGGL(gt_gst_tail_kernel, dim3(a.B), dim3(TAIL_THREADS), lds, stream, a);
     return hipGetLastError();
 }
 
 hipError_t gt_gst_init() {     // opt in to >64 KiB dynamic LDS; call once outside stream capture
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(gt_gst_tail_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(gt_gst_tail_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, TAIL_LDS_MAX);
 }

@@ -273,6 +273,13 @@ void add_bn(gsttaco_ctx* c, const std::string& prefix, int64_t n) {
     for (const char* f : {"gamma", "beta", "moving_mean", "moving_variance"}) add_tensor(c, prefix + ".bn." + f, {n});
 }
 
+// Width of the reference encoder's GRU input: the frequency bins left by the strided convolutions x the last filter count (GST.py:59-62)
+int64_t ref_gru_in(const gsttaco_config& g) {
+    int freq = g.mel_dim;
+    for (int i = 0; i < g.n_ref_conv; ++i) freq = (freq + g.ref_strides[i] - 1) / g.ref_strides[i];
+    return (int64_t)freq * g.ref_filters[g.n_ref_conv - 1];
+}
+
 // Same names/shapes/order as gst_tacotron_amd/weights.py::manifest.
 void build_manifest(gsttaco_ctx* c) {
     const gsttaco_config& g = c->cfg;
@@ -292,15 +299,13 @@ void build_manifest(gsttaco_ctx* c) {
     }
     if (g.gst_use) {
         cin = 1;
-        int freq = g.mel_dim;
         for (int i = 0; i < g.n_ref_conv; ++i) {
             std::string p = "gst.ref.conv" + std::to_string(i);
             add_tensor(c, p + ".kernel", {g.ref_kernels[i], g.ref_kernels[i], cin, g.ref_filters[i]});
             add_bn(c, p, g.ref_filters[i]);
             cin = g.ref_filters[i];
-            freq = (freq + g.ref_strides[i] - 1) / g.ref_strides[i];
         }
-        const int64_t gru_in = (int64_t)freq * cin;
+        const int64_t gru_in = ref_gru_in(g);
         add_tensor(c, "gst.ref.gru.kernel", {gru_in, 3 * (int64_t)g.ref_rnn});
         add_tensor(c, "gst.ref.gru.recurrent_kernel", {g.ref_rnn, 3 * (int64_t)g.ref_rnn});
         add_tensor(c, "gst.ref.gru.bias", {2, 3 * (int64_t)g.ref_rnn});
@@ -1889,6 +1894,11 @@ int gsttaco_create(const gsttaco_config* cfg, gsttaco_ctx** out) {
         if (g.heads < 1 || g.gst_att % g.heads)
             return bad("size must be divisible by num_heads.");   // reference Layers.py:155-156
         if (g.gst_att % 16) return bad("Style_Token.Attention.Size must be a multiple of 16");
+        // (what gt_gst_tail_kernel cannot run is refused here, not at the first gsttaco_gst of a context that has its weights)
+        std::string why;
+        const int64_t gru_in = ref_gru_in(g);
+        if (gru_in > INT32_MAX || !gt_gst_tail_supported((int)gru_in, g.ref_rnn, g.ref_dense, g.gst_att, g.heads, g.n_tokens, &why))
+            return bad(why.empty() ? "the reference encoder's GRU input is too wide" : why.c_str());
     }
     if (g.voc_use) {
         if (g.spec_dim < 1 || g.bank_count < 1 || g.bank_count > 32 || g.bank_filters < 4 || g.bank_filters % 4)

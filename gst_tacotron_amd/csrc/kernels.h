@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string>
 
 // ---------------------------------------------------------------- skinny_gemm.hip
 enum { EPI_LINEAR = 0, EPI_RELU_DROP = 1, EPI_LSTM = 2, EPI_PARTIAL = 3 };
@@ -413,6 +414,9 @@ struct GstTailArgs {
     int B, T2, gru_in, u, D, A, ntok, heads, stride_prod;
 };
 hipError_t gt_launch_gst_tail(const GstTailArgs& a, hipStream_t stream);
+// whether gt_gst_tail_kernel can run these sizes (divisibility, lane counts, its dynamic LDS against 160 KiB); `why` names the limit that fails.
+// gt_launch_gst_tail refuses exactly what this refuses, and gsttaco_create asks it, so a context that exists never fails there.
+bool gt_gst_tail_supported(int gru_in, int u, int D, int A, int heads, int ntok, std::string* why);
 hipError_t gt_gst_init();      // opt in to >64 KiB dynamic LDS; call once outside stream capture
 
 // ---------------------------------------------------------------- audio.hip

@@ -72,6 +72,46 @@ def test_create_rejects_bad_configs(lib):
         hparams.Dims(bad)
 
 
+def test_create_rejects_what_the_style_token_kernel_cannot_run(lib):
+    """gt_gst_tail_kernel's limits (csrc/gst.hip, gt_gst_tail_supported) are create's: a context that exists never fails in gsttaco_gst."""
+    h = ctypes.c_void_p()
+
+    def create(**sizes):
+        cfg = capi.make_config(hparams.load_hp())
+        for k, v in sizes.items():
+            if isinstance(v, list):
+                for i, x in enumerate(v):
+                    getattr(cfg, k)[i] = x
+            else:
+                setattr(cfg, k, v)
+        rc = lib.gsttaco_create(ctypes.byref(cfg), ctypes.byref(h))
+        if rc == 0:
+            lib.gsttaco_destroy(h)
+        return rc, lib.gsttaco_last_error(None).decode()
+
+    assert create()[0] == 0                                                     # the defaults: 147 200 B of shared memory
+    assert create(ref_rnn=256)[0] == 0                                          # 161 536 B: fits
+    assert create(ref_rnn=16, ref_dense=64, gst_att=256, heads=8, n_tokens=33)[0] == 0
+    rc, msg = create(ref_rnn=256, ref_filters=[32, 32, 64, 64, 128, 256])       # GRU input 2 x 256 = 512
+    assert rc == -1 and "169728 bytes of shared memory" in msg and "163840 (160 KiB)" in msg
+    assert "GRU input width 512" in msg and "RNN.Size 256" in msg
+    rc, msg = create(ref_rnn=130)
+    assert rc == -1 and "3 x Reference_Encoder.RNN.Size (390) must be a multiple of 4" in msg
+    rc, msg = create(ref_dense=6)
+    assert rc == -1 and "Reference_Encoder.Dense.Size (6) must be a multiple of 4" in msg
+    rc, msg = create(ref_rnn=1368)                                              # 3u / 4 = 1026 lanes: more than one workgroup
+    assert rc == -1 and "3 x Reference_Encoder.RNN.Size (4104) must be at most 4096" in msg
+    rc, msg = create(ref_dense=4100)
+    assert rc == -1 and "Reference_Encoder.Dense.Size (4100) must be at most 4096" in msg
+    rc, msg = create(n_tokens=12000)                                            # heads x tokens scores live in shared memory too
+    assert rc == -1 and "shared memory" in msg and "Head x Style_Token.Size 48000" in msg
+    # the Python front door reports the same text
+    hp = hparams.load_hp()
+    hp["GST"]["Reference_Encoder"]["Dense"]["Size"] = 6
+    with pytest.raises(capi.GstTacoError, match=r"Dense\.Size \(6\) must be a multiple of 4"):
+        capi.Context(hp, max_batch=2, max_tokens=8, max_ref_frames=9)
+
+
 def test_weight_loading_errors_and_no_cpu_fallback(lib):
     import torch
     hp = synthetic.tiny_hp()
