@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libgsttaco.so")
 
 MAX_LAYERS = 8
-ABI_VERSION = 13
+ABI_VERSION = 14
 ATT_CODES = {"BMA": 0, "SMA": 1, "LSA": 2}
 
 # every symbol include/gsttaco.h declares
@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = (
     "gsttaco_set_profiling", "gsttaco_get_profile", "gsttaco_lstm_launch_bytes", "gsttaco_debug_stamps", "gsttaco_decode_plan", "gsttaco_debug_randomness",
     "gsttaco_set_graph_policy", "gsttaco_graph_cache_size", "gsttaco_debug_handoff_error", "gsttaco_debug_raise_handoff_error", "gsttaco_debug_counters",
     "gsttaco_synchronize", "gsttaco_debug_conv_prepare", "gsttaco_debug_conv_run",
+    "gsttaco_gst_ex", "gsttaco_style_compose", "gsttaco_inference_step_styled",
 )
 
 # GSTTACO_CONV_V_*: the conv/GEMM dispatcher's kernel instantiations (gsttaco_debug_conv_run reports which one ran)
@@ -127,6 +128,9 @@ def load_library(path=None):
     lib.gsttaco_finalize_weights.argtypes = [vp]
     lib.gsttaco_encode.argtypes = [vp, vp, vp, i32, i32, vp, vp]
     lib.gsttaco_gst.argtypes = [vp, vp, vp, i32, i32, vp, vp]
+    lib.gsttaco_gst_ex.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp]
+    lib.gsttaco_style_compose.argtypes = [vp, vp, vp, i32, vp, vp]
+    lib.gsttaco_inference_step_styled.argtypes = [vp, vp, vp, vp, vp, vp, u64, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.gsttaco_decode.argtypes = [vp, vp, vp, vp, vp, vp, u64, i32, i32, i32, vp, vp, vp, vp]
     lib.gsttaco_postnet.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.gsttaco_vocoder.argtypes = [vp, vp, i32, i32, vp, vp]
@@ -163,7 +167,7 @@ def load_library(path=None):
     for fn in ("gsttaco_create", "gsttaco_num_weights", "gsttaco_weight_info", "gsttaco_load_weight",
                "gsttaco_finalize_weights", "gsttaco_encode", "gsttaco_gst", "gsttaco_decode", "gsttaco_postnet", "gsttaco_vocoder",
                "gsttaco_inference_step", "gsttaco_set_profiling", "gsttaco_get_profile", "gsttaco_mel_frontend",
-               "gsttaco_mel_basis", "gsttaco_griffin_lim"):
+               "gsttaco_mel_basis", "gsttaco_griffin_lim", "gsttaco_gst_ex", "gsttaco_style_compose", "gsttaco_inference_step_styled"):
         getattr(lib, fn).restype = ctypes.c_int
     if path is None:
         _lib = lib

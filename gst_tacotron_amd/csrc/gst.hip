@@ -2,6 +2,7 @@
 //
 // gt_conv2d_bn_relu_kernel  <- reference Modules/GST.py:23-31,55-56: Conv2D 3x3 stride 2 padding 'same'
 //     (TF asymmetric pads) no bias + BatchNorm (folded) + ReLU, NHWC = [B, time, freq, C].
+// gt_gst_compose_kernel     <- EXTENSION: the tail's last stage (weights . V, residual, LayerNorm) with the attention weights given
 // gt_gst_tail_kernel        <- GST.py:57-70 (reshape, GRU reset_after, gather at ceil(len/64)-1, Dense tanh)
 //     + GST.py:100-109 / Layers.py:172-214,230-237,280-283 (4-head unscaled attention over tanh(tokens),
 //     residual with the projected query, LayerNorm eps 1e-8).  The token-side projection
@@ -110,6 +111,33 @@ __device__ __forceinline__ float tail_sum(const float* partial, int KP, int N, i
     return z;
 }
 
+// The style-token layer's epilogue, stated once for gt_gst_tail_kernel and gt_gst_compose_kernel: residual with the PROJECTED query
+// (Layers.py:211), then LayerNorm with population variance and eps inside the sqrt (Layers.py:280-283), wave 0 reducing.
+// ov [A] (LDS): the heads' concatenated outputs, entry j written by the thread that owns j in the NT-strided loop below (so the
+// residual needs no barrier in front); q [A]: the query (LDS or global), NULL = 0; red: 2 floats of LDS; out: this utterance's row.
+template <int NT>
+__device__ __forceinline__ void gst_residual_layernorm(float* ov, const float* q, float* red, int A, const float* __restrict__ ln_g,
+                                                       const float* __restrict__ ln_b, float* __restrict__ out) {
+    const int tid = threadIdx.x;
+    if (q)
+        for (int j = tid; j < A; j += NT) ov[j] = ov[j] + q[j];
+    __syncthreads();
+    if (tid < 64) {
+        float m = 0.f;
+        for (int j = tid; j < A; j += 64) m += ov[j];
+        for (int d = 32; d > 0; d >>= 1) m += __shfl_xor(m, d, 64);
+        m /= A;
+        float v = 0.f;
+        for (int j = tid; j < A; j += 64) v += (ov[j] - m) * (ov[j] - m);
+        for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+        v /= A;
+        if (tid == 0) { red[0] = m; red[1] = 1.f / sqrtf(v + 1e-8f); }
+    }
+    __syncthreads();
+    for (int j = tid; j < A; j += NT)
+        out[j] = ln_g[j] * ((ov[j] - red[0]) * red[1]) + ln_b[j];
+}
+
 // one 1024-thread workgroup per utterance.  The GRU's input halves x_t . W + b_i of every needed frame are one pass over W
 // (they do not depend on the state); each recurrent step is then one K = u GEMV split over all lanes.
 __global__ __launch_bounds__(TAIL_THREADS) void gt_gst_tail_kernel(GstTailArgs P) {
@@ -195,24 +223,37 @@ __global__ __launch_bounds__(TAIL_THREADS) void gt_gst_tail_kernel(GstTailArgs P
             den += e;
             num += e * P.v_tok[n * P.A + j];
         }
-        ov[j] = num / den + qv[j];                 // residual adds the PROJECTED query (Layers.py:211)
+        ov[j] = num / den;
+        // exports (style control): the head's normalised weights, by the head's first lane, and the projected query
+        if (P.attn && j == h * dh)
+            for (int n = 0; n < P.ntok; ++n)
+                P.attn[((int64_t)b * P.heads + h) * P.ntok + n] = expf(sc[h * P.ntok + n] - mxs) / den;
+        if (P.query) P.query[(int64_t)b * P.A + j] = qv[j];
     }
+    gst_residual_layernorm<TAIL_THREADS>(ov, qv, red, P.A, P.ln_g, P.ln_b, P.gst + (int64_t)b * P.A);
+}
+
+#define COMPOSE_THREADS 256
+
+// one workgroup per utterance: the utterance's heads x ntok weights staged in LDS (each one a broadcast read), lane j sums
+// w[h(j)][n] . V[n][j] over the tokens (coalesced over j), then the tail's epilogue.
+__global__ __launch_bounds__(COMPOSE_THREADS) void gt_gst_compose_kernel(GstComposeArgs P) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int HN = P.heads * P.ntok, dh = P.A / P.heads;
+    float* ws = sm;                                 // [heads][ntok]
+    float* ov = ws + HN;                            // [A]
+    float* red = ov + P.A;                          // [64]
+    for (int i = tid; i < HN; i += COMPOSE_THREADS) ws[i] = P.weights[(int64_t)b * HN + i];
     __syncthreads();
-    // LayerNorm, population variance, eps inside the sqrt (Layers.py:280-283): wave 0 reduces
-    if (tid < 64) {
-        float m = 0.f;
-        for (int j = tid; j < P.A; j += 64) m += ov[j];
-        for (int d = 32; d > 0; d >>= 1) m += __shfl_xor(m, d, 64);
-        m /= P.A;
-        float v = 0.f;
-        for (int j = tid; j < P.A; j += 64) v += (ov[j] - m) * (ov[j] - m);
-        for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-        v /= P.A;
-        if (tid == 0) { red[0] = m; red[1] = 1.f / sqrtf(v + 1e-8f); }
+    for (int j = tid; j < P.A; j += COMPOSE_THREADS) {
+        const float* wh = ws + (j / dh) * P.ntok;
+        float acc = 0.f;
+        for (int n = 0; n < P.ntok; ++n) acc += wh[n] * P.v_tok[(int64_t)n * P.A + j];
+        ov[j] = acc;
     }
-    __syncthreads();
-    for (int j = tid; j < P.A; j += TAIL_THREADS)
-        P.gst[(int64_t)b * P.A + j] = P.ln_g[j] * ((ov[j] - red[0]) * red[1]) + P.ln_b[j];
+    gst_residual_layernorm<COMPOSE_THREADS>(ov, P.query ? P.query + (int64_t)b * P.A : nullptr, red, P.A, P.ln_g, P.ln_b,
+                                            P.gst + (int64_t)b * P.A);
 }
 
 #define TAIL_LDS_MAX (160 * 1024)
@@ -257,6 +298,19 @@ hipError_t gt_launch_gst_tail(const GstTailArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
+static size_t compose_lds_bytes(int A, int heads, int ntok) { return ((size_t)heads * ntok + A + 64) * sizeof(float); }
+
+hipError_t gt_launch_gst_compose(const GstComposeArgs& a, hipStream_t stream) {
+    if (a.B < 1 || !gt_gst_tail_supported(a.gru_in, a.u, a.D, a.A, a.heads, a.ntok, nullptr)) return hipErrorInvalidValue;
+    // (the tail holds the same scores, two [A] rows and the 64 reduction words, and more: what it fits, this fits)
+    const size_t lds = compose_lds_bytes(a.A, a.heads, a.ntok);
+    if (lds > tail_lds_bytes(a.gru_in, a.u, a.D, a.A, a.heads, a.ntok)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gt_gst_compose_kernel, dim3(a.B), dim3(COMPOSE_THREADS), lds, stream, a);
+    return hipGetLastError();
+}
+
 hipError_t gt_gst_init() {     // opt in to >64 KiB dynamic LDS; call once outside stream capture
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(gt_gst_tail_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, TAIL_LDS_MAX);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gt_gst_tail_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, TAIL_LDS_MAX);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(gt_gst_compose_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, TAIL_LDS_MAX);
 }

@@ -218,6 +218,7 @@ struct gsttaco_ctx {
     bool stamps = false;
     float *w_act[2] = {nullptr, nullptr}, *w_enc = nullptr, *w_cenc = nullptr, *w_zero = nullptr;
     float *w_gconv[2] = {nullptr, nullptr}, *w_gst = nullptr, *w_rowbias = nullptr, *w_pm = nullptr;
+    float *w_gst_attn = nullptr, *w_gst_q = nullptr;    // what the tail exports beside w_gst: token weights [B, heads, n_tokens], query [B, gst_att]
     float *w_p1 = nullptr, *w_xa = nullptr, *w_q = nullptr, *w_h1[2] = {nullptr, nullptr},
           *w_h2[2] = {nullptr, nullptr}, *w_c1 = nullptr, *w_c2 = nullptr;
     // bf16 mirrors of the blocked decoder activations (kernels.h gt_blk_off_h): mixed precision, batches above 32 rows
@@ -1000,6 +1001,7 @@ int enqueue_gst(gsttaco_ctx* c, hipStream_t s, int B, int Tref1) {
     t.dense_w = c->dense_w; t.dense_b = c->dense_b;
     t.q_w = c->mq_w; t.q_b = c->mq_b; t.v_tok = c->v_tok; t.ln_g = c->ln_g; t.ln_b = c->ln_b;
     t.gst = c->w_gst;
+    t.attn = c->w_gst_attn; t.query = c->w_gst_q;       // (always stored: gsttaco_gst_ex copies them out, and no graph key depends on who asks)
     t.B = B; t.T2 = H; t.gru_in = W * c->ref_conv[g.n_ref_conv - 1].L.cout; t.u = g.ref_rnn;
     t.D = g.ref_dense; t.A = g.gst_att; t.ntok = g.n_tokens; t.heads = g.heads;
     t.stride_prod = 1;
@@ -1777,7 +1779,7 @@ int run_cached(gsttaco_ctx* c, hipStream_t stream, const GraphKey& key_in, F bod
         rc = run_cached_inner(c, stream, key_in, body);
         HIPCHECK(c, hipEventRecord(ev, stream));
     }
-    if (!rc && (c->fuse12_now || c->persist_now) && (key_in.kind == 0 || key_in.kind == 3)) {      // the segment held fused / persistent decode launches
+    if (!rc && (c->fuse12_now || c->persist_now) && (key_in.kind == 0 || key_in.kind == 3 || key_in.kind == 10)) {      // the segment held fused / persistent decode launches
         std::lock_guard<std::mutex> lock(g_persist_mu);
         FusedInFlight& f = g_fused_event[c->cfg.device];
         if (!f.ev) HIPCHECK(c, hipEventCreateWithFlags(&f.ev, hipEventDisableTiming));
@@ -2244,6 +2246,8 @@ int alloc_workspace(gsttaco_ctx* c) {
         for (int i = 0; i < 2; ++i)
             if ((rc = fa(&c->w_gconv[i], B * big))) return rc;
         if ((rc = fa(&c->w_gst, B * g.gst_att))) return rc;
+        if ((rc = fa(&c->w_gst_attn, B * (size_t)g.heads * g.n_tokens))) return rc;
+        if ((rc = fa(&c->w_gst_q, B * g.gst_att))) return rc;
         if ((rc = fa(&c->w_rowbias, B * c->att))) return rc;
     }
     if ((rc = fa(&c->w_pm, B * Tv * c->att))) return rc;
@@ -2379,7 +2383,8 @@ int gsttaco_encode(gsttaco_ctx* c, const int32_t* tokens, const int32_t* token_l
     return 0;
 }
 
-int gsttaco_gst(gsttaco_ctx* c, const float* mels, const int32_t* lens, int B, int Tref1, float* gst, void* stream) {
+int gsttaco_gst_ex(gsttaco_ctx* c, const float* mels, const int32_t* lens, int B, int Tref1, float* gst, float* token_weights, float* query,
+                   void* stream) {
     int rc = check_ready(c);
     if (rc) return rc;
     if (!c->cfg.gst_use) return fail(c, GSTTACO_E_INVALID, "GST is not used");     // reference Model.py:258-259
@@ -2392,6 +2397,31 @@ int gsttaco_gst(gsttaco_ctx* c, const float* mels, const int32_t* lens, int B, i
     GraphKey key{2, B, 0, Tref1, 0, 0, 0, 0, 0};
     if ((rc = run_cached(c, s, key, [&](hipStream_t st) { return enqueue_gst(c, st, B, Tref1); }))) return rc;
     HIPCHECK(c, hipMemcpyAsync(gst, c->w_gst, (size_t)B * c->cfg.gst_att * 4, hipMemcpyDeviceToDevice, s));
+    if (token_weights)
+        HIPCHECK(c, hipMemcpyAsync(token_weights, c->w_gst_attn, (size_t)B * c->cfg.heads * c->cfg.n_tokens * 4, hipMemcpyDeviceToDevice, s));
+    if (query) HIPCHECK(c, hipMemcpyAsync(query, c->w_gst_q, (size_t)B * c->cfg.gst_att * 4, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+int gsttaco_gst(gsttaco_ctx* c, const float* mels, const int32_t* lens, int B, int Tref1, float* gst, void* stream) {
+    return gsttaco_gst_ex(c, mels, lens, B, Tref1, gst, nullptr, nullptr, stream);
+}
+
+// EXTENSION (style control): gst = LayerNorm(concat_h(weights[b, h, :] . V[:, h-slice]) + query), the style-token layer's last stage
+// (Layers.py:207-211) with the attention weights given.  One launch, straight from / to the caller's pointers.
+int gsttaco_style_compose(gsttaco_ctx* c, const float* token_weights, const float* query, int B, float* gst, void* stream) {
+    int rc = check_ready(c);
+    if (rc) return rc;
+    const gsttaco_config& g = c->cfg;
+    if (!g.gst_use) return fail(c, GSTTACO_E_INVALID, "GST is not used");
+    if (!token_weights || !gst) return fail(c, GSTTACO_E_INVALID, "null argument");
+    if (B < 1) return fail(c, GSTTACO_E_INVALID, "bad B");
+    if (B > g.max_batch) return fail(c, GSTTACO_E_CAPACITY, "batch exceeds the capacity given at create");
+    GstComposeArgs a{};
+    a.weights = token_weights; a.query = query; a.v_tok = c->v_tok; a.ln_g = c->ln_g; a.ln_b = c->ln_b; a.gst = gst;
+    a.B = B; a.A = g.gst_att; a.ntok = g.n_tokens; a.heads = g.heads;
+    a.gru_in = (int)ref_gru_in(g); a.u = g.ref_rnn; a.D = g.ref_dense;
+    HIPCHECK(c, gt_launch_gst_compose(a, (hipStream_t)stream));
     return 0;
 }
 
@@ -2533,16 +2563,18 @@ int gsttaco_mel_basis(gsttaco_ctx* c, float* host_out) {
     return 0;
 }
 
-int gsttaco_inference_step(gsttaco_ctx* c, const int32_t* tokens, const int32_t* token_lengths, const float* mels_for_gst, const int32_t* mel_lengths,
-                           const float* mask, const float* noise, uint64_t seed, int B, int Tv, int Tref1, int steps,
-                           float* mel, float* stop, float* align, float* pre_mel, float* spectrogram, void* stream) {
-    int rc = check_ready(c);
-    if (rc) return rc;
+}  // extern "C"
+
+namespace {
+
+// gsttaco_inference_step (`style` NULL) and gsttaco_inference_step_styled (`style` [B, gst_att] given: it IS w_gst, the reference encoder
+// and the tail are not run; mels_for_gst / mel_lengths NULL, Tref1 0).  The callers have checked their own arguments.
+int inference_step(gsttaco_ctx* c, const int32_t* tokens, const int32_t* token_lengths, const float* mels_for_gst, const int32_t* mel_lengths,
+                   const float* style, const float* mask, const float* noise, uint64_t seed, int B, int Tv, int Tref1, int steps,
+                   float* mel, float* stop, float* align, float* pre_mel, float* spectrogram, void* stream) {
+    int rc = 0;
     const bool gst = c->cfg.gst_use != 0;
-    if (!tokens || !mel || !stop || !align) return fail(c, GSTTACO_E_INVALID, "null argument");
-    if (gst && (!mels_for_gst || !mel_lengths)) return fail(c, GSTTACO_E_INVALID, "GST is enabled, but no mel information.");
-    if (!gst) Tref1 = 0;
-    if (gst && Tref1 < 2) return fail(c, GSTTACO_E_INVALID, "mels_for_gst needs at least one frame after the prepended zero frame");
+    const bool styled = style != nullptr;
     if (spectrogram && !c->cfg.voc_use) return fail(c, GSTTACO_E_INVALID, "the context was created without Vocoder_Taco1");
     if ((rc = check_shape(c, B, Tv, Tref1, steps))) return rc;
     if (steps == 0) steps = c->steps_max;
@@ -2555,7 +2587,8 @@ int gsttaco_inference_step(gsttaco_ctx* c, const int32_t* tokens, const int32_t*
         GtCopySegs cs{};
         auto seg = [&](const void* src, void* dst, size_t words) { cs.src[cs.n] = src; cs.dst[cs.n] = dst; cs.words[cs.n] = words; ++cs.n; };
         seg(tokens, c->w_tokens, (size_t)B * Tv);
-        if (gst) { seg(mels_for_gst, c->w_mels_in, (size_t)B * Tref1 * meld); seg(mel_lengths, c->w_mel_len, (size_t)B); }
+        if (styled) seg(style, c->w_gst, (size_t)B * c->cfg.gst_att);
+        else if (gst) { seg(mels_for_gst, c->w_mels_in, (size_t)B * Tref1 * meld); seg(mel_lengths, c->w_mel_len, (size_t)B); }
         if (masked) seg(token_lengths, c->w_tok_len, (size_t)B);
         cs.seed = seed; cs.seed_dst = c->w_seed;
         HIPCHECK(c, gt_launch_copy_segments(cs, s));
@@ -2570,13 +2603,16 @@ int gsttaco_inference_step(gsttaco_ctx* c, const int32_t* tokens, const int32_t*
     // (run_cached, g_persist_event); the segment between them -- GST, value projection, the decode loop, the postnet: 95 % of the
     // call -- overlaps freely with other contexts' work.  The encoder / vocoder segments share their cached graphs with
     // gsttaco_encode / gsttaco_vocoder.
-    const bool fork = gst && c->gst_fork;
+    // With the style given the encoder segment is gsttaco_encode's (no fork, no side stream) and the middle one starts at the value
+    // projection (key kind 10).  w_gst was written by this call's input copy on `s`; a forked call in front of it on `s` wrote w_gst on
+    // the side stream and joined it into `s` inside its encoder segment, so the copy is ordered behind that write.
+    const bool fork = gst && !styled && c->gst_fork;
     GraphKey kenc{fork ? 9 : 1, B, Tv, fork ? Tref1 : 0, 0, 0, 0, 0, masked};
     if ((rc = run_cached(c, s, kenc, [&](hipStream_t st) { return enqueue_encoder(c, st, B, Tv, masked, fork ? Tref1 : 0); }, true))) return rc;
-    GraphKey key{0, B, Tv, Tref1, steps, mask != nullptr, noise != nullptr, c->prof_every, masked};
+    GraphKey key{styled ? 10 : 0, B, Tv, Tref1, steps, mask != nullptr, noise != nullptr, c->prof_every, masked};
     rc = run_cached(c, s, key, [&](hipStream_t st) {
         int r2 = 0;
-        if (gst && !fork) r2 = enqueue_gst(c, st, B, Tref1);
+        if (gst && !styled && !fork) r2 = enqueue_gst(c, st, B, Tref1);
         if (!r2) r2 = enqueue_value_proj(c, st, B, Tv);
         if (!r2) r2 = enqueue_decode(c, st, B, Tv, steps, mask != nullptr, noise != nullptr, masked);
         if (!r2) r2 = enqueue_postnet(c, st, B, steps * c->r, c->w_pre, c->w_mel);
@@ -2600,6 +2636,35 @@ int gsttaco_inference_step(gsttaco_ctx* c, const int32_t* tokens, const int32_t*
         HIPCHECK(c, gt_launch_copy_segments(cs, s));
     }
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gsttaco_inference_step(gsttaco_ctx* c, const int32_t* tokens, const int32_t* token_lengths, const float* mels_for_gst, const int32_t* mel_lengths,
+                           const float* mask, const float* noise, uint64_t seed, int B, int Tv, int Tref1, int steps,
+                           float* mel, float* stop, float* align, float* pre_mel, float* spectrogram, void* stream) {
+    int rc = check_ready(c);
+    if (rc) return rc;
+    const bool gst = c->cfg.gst_use != 0;
+    if (!tokens || !mel || !stop || !align) return fail(c, GSTTACO_E_INVALID, "null argument");
+    if (gst && (!mels_for_gst || !mel_lengths)) return fail(c, GSTTACO_E_INVALID, "GST is enabled, but no mel information.");
+    if (!gst) Tref1 = 0;
+    if (gst && Tref1 < 2) return fail(c, GSTTACO_E_INVALID, "mels_for_gst needs at least one frame after the prepended zero frame");
+    return inference_step(c, tokens, token_lengths, mels_for_gst, mel_lengths, nullptr, mask, noise, seed, B, Tv, Tref1, steps,
+                          mel, stop, align, pre_mel, spectrogram, stream);
+}
+
+int gsttaco_inference_step_styled(gsttaco_ctx* c, const int32_t* tokens, const int32_t* token_lengths, const float* style,
+                                  const float* mask, const float* noise, uint64_t seed, int B, int Tv, int steps,
+                                  float* mel, float* stop, float* align, float* pre_mel, float* spectrogram, void* stream) {
+    int rc = check_ready(c);
+    if (rc) return rc;
+    if (!c->cfg.gst_use) return fail(c, GSTTACO_E_INVALID, "GST is not used");
+    if (!tokens || !style || !mel || !stop || !align) return fail(c, GSTTACO_E_INVALID, "null argument");
+    return inference_step(c, tokens, token_lengths, nullptr, nullptr, style, mask, noise, seed, B, Tv, 0, steps,
+                          mel, stop, align, pre_mel, spectrogram, stream);
 }
 
 int gsttaco_synchronize(gsttaco_ctx* c, void* stream) {

@@ -411,6 +411,8 @@ struct GstTailArgs {
     const float* ln_g;      // [A]
     const float* ln_b;      // [A]
     float* gst;             // [B, A]
+    float* attn;            // [B, heads, ntok] the normalised attention weights e / den of every head, or NULL = not stored
+    float* query;           // [B, A] the projected query (the residual term), or NULL = not stored
     int B, T2, gru_in, u, D, A, ntok, heads, stride_prod;
 };
 hipError_t gt_launch_gst_tail(const GstTailArgs& a, hipStream_t stream);
@@ -418,6 +420,20 @@ hipError_t gt_launch_gst_tail(const GstTailArgs& a, hipStream_t stream);
 // gt_launch_gst_tail refuses exactly what this refuses, and gsttaco_create asks it, so a context that exists never fails there.
 bool gt_gst_tail_supported(int gru_in, int u, int D, int A, int heads, int ntok, std::string* why);
 hipError_t gt_gst_init();      // opt in to >64 KiB dynamic LDS; call once outside stream capture
+
+// gst[b] = LayerNorm(concat_h(weights[b, h, :] . v_tok[:, h-slice]) + query[b]): the tail's last stage with the attention weights GIVEN
+// (any real numbers: not normalised, not clipped) instead of computed from a reference.  EXTENSION (style control, DESIGN A14).
+struct GstComposeArgs {
+    const float* weights;   // [B, heads, ntok]
+    const float* query;     // [B, A], or NULL = 0 (tokens alone: outside the training distribution, the residual always carried a query)
+    const float* v_tok;     // [ntok, A]
+    const float* ln_g;      // [A]
+    const float* ln_b;      // [A]
+    float* gst;             // [B, A]
+    int B, A, ntok, heads;
+    int gru_in, u, D;       // the model's other GST sizes: the launch accepts what gt_gst_tail_supported accepts
+};
+hipError_t gt_launch_gst_compose(const GstComposeArgs& a, hipStream_t stream);
 
 // ---------------------------------------------------------------- audio.hip
 struct AudioFrontArgs {

@@ -82,7 +82,8 @@ def shard_bounds(n_items, rank, world):
 
 
 def shard_inputs(inputs, rank, world):
-    """Slice every per-utterance array of an inference pattern dict along axis 0."""
+    """Slice every per-utterance array of an inference pattern dict along axis 0.  ``style_embeddings`` is such a key: give it
+    per utterance, [B, A] -- expand a shared [1, A] style to the batch BEFORE sharding, or rank 0 alone would receive it."""
     n = len(inputs["tokens"])
     lo, hi = shard_bounds(n, rank, world)
     return {k: (v[lo:hi] if v is not None else None) for k, v in inputs.items()}

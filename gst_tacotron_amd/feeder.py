@@ -28,9 +28,12 @@ class Feeder:
         mels, lens = self.mel_frontend(wav_List, top_db)
         return {"mels_for_gst": mels, "mel_lengths_for_gst": lens}
 
-    def Get_Inference_Pattern(self, sentence_List, mel_List_for_GST=None):
+    def Get_Inference_Pattern(self, sentence_List, mel_List_for_GST=None, style_given=False):
         """reference Feeder.py:161-227.  Out-of-vocabulary characters raise KeyError like the
-        reference (Feeder.py:169); bad GST inputs print the reference's message and return None."""
+        reference (Feeder.py:169); bad GST inputs print the reference's message and return None.
+        ``style_given=True`` (extension): the caller supplies the style embedding itself
+        (``Inference_Step(style_embeddings=...)``), so the token pattern is returned without the GST keys and no
+        reference audio is asked for."""
         pattern_Count = len(sentence_List)
         sentence_List = [sentence.upper().strip() for sentence in sentence_List]          # :164
         token_List = [
@@ -47,7 +50,7 @@ class Feeder:
             "token_lengths": np.array([t.shape[0] for t in token_List], dtype=np.int32),
             "initial_mels": np.zeros((pattern_Count, 1, mel_dim), dtype=np.float32),        # :182-185
         }
-        if self.hp["GST"]["Use"]:
+        if self.hp["GST"]["Use"] and not style_given:
             if mel_List_for_GST is None:
                 print("GST is enabled, but no wav information.")                           # :197-199
                 return None

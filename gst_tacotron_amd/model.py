@@ -5,6 +5,7 @@
     .Inference_Step(tokens, token_lengths, initial_mels, mels_for_gst, mel_lengths_for_gst)
     .Inference_GST_Step(mels_for_gst, mel_lengths_for_gst)
     .Inference(sentence_List, mel_List_for_GST)
+    .Style_Compose(token_weights, query)                 (extension: a style from token weights)
 
 Same names, argument order/meaning and error behaviour; the Keras functional model
 behind them (Model.py:145-156) is replaced by the HIP kernels behind include/gsttaco.h.
@@ -17,7 +18,11 @@ PyTorch is used for device memory and streams only.  Differences, all additive:
     reference ignores them at inference (Model.py:249-253, Taco2.py:161; SURVEY F5, F15);
   * the CBHG vocoder output (3rd element of the returned tuple, Vocoder_Taco1) is computed when
     ``with_vocoder=True`` (gsttaco_vocoder); by default it is None, because the north-star metric
-    (mel frames) excludes it.
+    (mel frames) excludes it;
+  * style control: ``Inference_GST_Step(return_attention=True)`` also returns the token weights and the query the
+    reference computes and drops (GST.py:105), ``Style_Compose`` builds an embedding from given token weights, and
+    ``Inference_Step`` / ``Inference`` take ``style_embeddings`` (and ``Inference`` ``style_token_weights``) in place
+    of reference audio.
 """
 import ctypes
 import os
@@ -107,14 +112,18 @@ class GST_Tacotron:
     # ------------------------------------------------------------------ hot path
     def Inference_Step(self, tokens, token_lengths=None, initial_mels=None, mels_for_gst=None,
                        mel_lengths_for_gst=None, prenet_masks=None, attn_noise=None, seed=None,
-                       steps=None, return_pre_mel=False, masked=False, with_vocoder=False):
+                       steps=None, return_pre_mel=False, masked=False, with_vocoder=False, style_embeddings=None):
         """reference Model.py:249-255.  Returns (mel_Logits [B,S*r,mel], stop_Logits [B,S],
         spectrogram_Logits ([B,S*r,Spectrogram_Dim] with ``with_vocoder=True``, else None), alignments [B,S,T_v]) as
         CUDA tensors on the current stream.
         ``masked=True`` (extension): honour ``token_lengths`` so each utterance of a ragged batch equals
         that utterance run alone; the default ignores them like the reference does.
         ``with_vocoder=True`` also runs Vocoder_Taco1 (CBHG) and returns spectrogram_Logits [B,S*r,513]
-        as the third element like the reference; the default returns None there (the north-star metric excludes it)."""
+        as the third element like the reference; the default returns None there (the north-star metric excludes it).
+        ``style_embeddings`` (extension) [batch, Style_Token.Attention.Size], or [1, ...] for one style for the whole batch: the
+        style is given instead of computed from ``mels_for_gst`` (which must then be None); the reference encoder and the style-token
+        layer are skipped, everything downstream is the same code.  With ``Inference_GST_Step``'s output for some mels the results
+        are bitwise those of the call with those mels."""
         self._require_ready()
         d = self.dims
         tok = self._dev(tokens, torch.int32)
@@ -128,9 +137,19 @@ class GST_Tacotron:
             tlen = self._dev(token_lengths, torch.int32)
             if tuple(tlen.shape) != (B,):
                 raise ValueError("token_lengths must be [batch]")
-        mels = lens = None
+        mels = lens = style = None
         Tref1 = 0
-        if d.gst:
+        if style_embeddings is not None:
+            if mels_for_gst is not None or mel_lengths_for_gst is not None:
+                raise ValueError("style_embeddings and mels_for_gst are mutually exclusive")
+            if not d.gst:
+                raise ValueError("GST is not used")
+            style = self._dev(style_embeddings, torch.float32)
+            if style.dim() != 2 or style.shape[0] not in (1, B) or style.shape[1] != d.gst_att:
+                raise ValueError("style_embeddings must be [batch, {0}] or [1, {0}]".format(d.gst_att))
+            if style.shape[0] != B:
+                style = style.expand(B, -1).contiguous()
+        elif d.gst:
             if mels_for_gst is None or mel_lengths_for_gst is None:
                 raise ValueError("GST is enabled, but no mel information.")
             mels = self._dev(mels_for_gst, torch.float32)
@@ -158,10 +177,16 @@ class GST_Tacotron:
             self.seed += 1
             seed = self.seed
         with torch.cuda.device(self.device):
-            self.ctx.check(self.ctx.lib.gsttaco_inference_step(
-                self.ctx.handle, _ptr(tok), _ptr(tlen), _ptr(mels), _ptr(lens), _ptr(masks), _ptr(noise),
-                ctypes.c_uint64(int(seed)), B, Tv, Tref1, S, _ptr(mel), _ptr(stop), _ptr(align), _ptr(pre), _ptr(spec),
-                self._stream()))
+            if style is not None:
+                self.ctx.check(self.ctx.lib.gsttaco_inference_step_styled(
+                    self.ctx.handle, _ptr(tok), _ptr(tlen), _ptr(style), _ptr(masks), _ptr(noise),
+                    ctypes.c_uint64(int(seed)), B, Tv, S, _ptr(mel), _ptr(stop), _ptr(align), _ptr(pre), _ptr(spec),
+                    self._stream()))
+            else:
+                self.ctx.check(self.ctx.lib.gsttaco_inference_step(
+                    self.ctx.handle, _ptr(tok), _ptr(tlen), _ptr(mels), _ptr(lens), _ptr(masks), _ptr(noise),
+                    ctypes.c_uint64(int(seed)), B, Tv, Tref1, S, _ptr(mel), _ptr(stop), _ptr(align), _ptr(pre), _ptr(spec),
+                    self._stream()))
         if return_pre_mel:
             return mel, stop, spec, align, pre
         return mel, stop, spec, align
@@ -177,17 +202,50 @@ class GST_Tacotron:
             self.Export_GST(wav_List, tag_List, gsts, label or datetime.now().strftime("%Y%m%d.%H%M%S"))
         return gsts
 
-    def Inference_GST_Step(self, mels_for_gst, mel_lengths_for_gst):
-        """reference Model.py:257-265"""
+    def Inference_GST_Step(self, mels_for_gst, mel_lengths_for_gst, return_attention=False):
+        """reference Model.py:257-265.  ``return_attention=True`` (extension): returns (gst, style_token_weights [B, Head, Style_Token.Size],
+        style_query [B, Attention.Size]) -- each head's softmax weights over the tokens and the projected query of the residual, which
+        the reference computes and drops (GST.py:105).  ``Style_Compose(style_token_weights, style_query)`` gives ``gst`` back."""
         if not self.hp_Dict["GST"]["Use"]:
             raise NotImplementedError("GST is not used")
         self._require_ready()
+        d = self.dims
         mels = self._dev(mels_for_gst, torch.float32)
         lens = self._dev(mel_lengths_for_gst, torch.int32)
         B, Tref1 = mels.shape[0], mels.shape[1]
-        gst = torch.empty((B, self.dims.gst_att), dtype=torch.float32, device=self.device)
+        gst = torch.empty((B, d.gst_att), dtype=torch.float32, device=self.device)
+        if not return_attention:
+            with torch.cuda.device(self.device):
+                self.ctx.check(self.ctx.lib.gsttaco_gst(self.ctx.handle, _ptr(mels), _ptr(lens), B, Tref1, _ptr(gst), self._stream()))
+            return gst
+        tw = torch.empty((B, d.heads, d.n_tokens), dtype=torch.float32, device=self.device)
+        query = torch.empty((B, d.gst_att), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            self.ctx.check(self.ctx.lib.gsttaco_gst(self.ctx.handle, _ptr(mels), _ptr(lens), B, Tref1, _ptr(gst), self._stream()))
+            self.ctx.check(self.ctx.lib.gsttaco_gst_ex(self.ctx.handle, _ptr(mels), _ptr(lens), B, Tref1, _ptr(gst), _ptr(tw), _ptr(query),
+                                                       self._stream()))
+        return gst, tw, query
+
+    def Style_Compose(self, token_weights, query=None):
+        """Extension (no reference counterpart): the style embedding [B, Attention.Size] of given token weights,
+        LayerNorm(concat_h(token_weights[b, h, :] . V[:, h-slice]) + query) with V = tanh(tokens).Wv + bv -- the last stage of the
+        style-token layer (Layers.py:207-211) with the attention weights chosen by the caller.  ``token_weights`` [B, Head,
+        Style_Token.Size] are any real numbers: not normalised, not clipped.  ``query`` [B, Attention.Size] is the residual term, None = 0.
+        Conditioning on tokens alone (no query) is outside the training distribution of this architecture -- the decoder only ever
+        saw LayerNorm(attention output + query) -- but well defined; all-zero weights with no query give exactly the LayerNorm's beta."""
+        if not self.hp_Dict["GST"]["Use"]:
+            raise NotImplementedError("GST is not used")
+        self._require_ready()
+        d = self.dims
+        tw = self._dev(token_weights, torch.float32)
+        if tw.dim() != 3 or tuple(tw.shape[1:]) != (d.heads, d.n_tokens):
+            raise ValueError("token_weights must be [batch, {}, {}]".format(d.heads, d.n_tokens))
+        B = tw.shape[0]
+        q = self._dev(query, torch.float32)
+        if q is not None and tuple(q.shape) != (B, d.gst_att):
+            raise ValueError("query must be [batch, {}]".format(d.gst_att))
+        gst = torch.empty((B, d.gst_att), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            self.ctx.check(self.ctx.lib.gsttaco_style_compose(self.ctx.handle, _ptr(tw), _ptr(q), B, _ptr(gst), self._stream()))
         return gst
 
     def Mel_Generate(self, wav_List, top_db=60):
@@ -220,12 +278,30 @@ class GST_Tacotron:
             raise ValueError("a reference wav is shorter than n_fft/2 samples after trimming (librosa.stft raises there)")
         return mels[:, :n + 1].contiguous(), mel_len
 
-    def Inference(self, sentence_List, wav_List_for_GST=None, label=None, export=False, **kwargs):
+    def Inference(self, sentence_List, wav_List_for_GST=None, label=None, export=False, style_embeddings=None,
+                  style_token_weights=None, **kwargs):
         """reference Model.py:342-367.  ``wav_List_for_GST`` holds wav paths / 1-D sample arrays like the reference's,
         or precomputed mels [T, Mel_Dim].  The reference always starts its export thread; here ``export=True`` asks for
-        it (it needs the CBHG vocoder and Griffin-Lim, which are off the mel-frame metric) and runs it synchronously."""
+        it (it needs the CBHG vocoder and Griffin-Lim, which are off the mel-frame metric) and runs it synchronously.
+        Extension: instead of reference audio, ``style_embeddings`` [B, A] / [1, A] (see ``Inference_Step``) or
+        ``style_token_weights`` [Head, Style_Token.Size], [1, Head, Size] or [B, Head, Size] -- composed with no query
+        (``Style_Compose``: outside the training distribution, see there) and then used as embeddings."""
         print("Inference running...")
-        pattern_Dict = self.feeder.Get_Inference_Pattern(sentence_List, wav_List_for_GST)
+        styled = style_embeddings is not None or style_token_weights is not None
+        if styled:
+            if wav_List_for_GST is not None or (style_embeddings is not None and style_token_weights is not None):
+                raise ValueError("wav_List_for_GST, style_embeddings and style_token_weights are mutually exclusive")
+            if not self.hp_Dict["GST"]["Use"]:
+                raise ValueError("GST is not used")
+            if style_token_weights is not None:
+                tw = self._dev(style_token_weights, torch.float32)
+                if tw.dim() == 2:
+                    tw = tw.unsqueeze(0)
+                if tw.dim() != 3 or tw.shape[0] not in (1, len(sentence_List)):
+                    raise ValueError("style_token_weights must be [Head, Size], [1, Head, Size] or [batch, Head, Size]")
+                style_embeddings = self.Style_Compose(tw)
+            kwargs["style_embeddings"] = style_embeddings
+        pattern_Dict = self.feeder.Get_Inference_Pattern(sentence_List, wav_List_for_GST, style_given=styled)
         if pattern_Dict is None:
             print("Inference fail.")
             return None

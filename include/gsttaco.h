@@ -13,6 +13,10 @@
  *   gsttaco_encode      <- Modules/Taco2.py:12-51   Encoder.call
  *   gsttaco_gst         <- Modules/GST.py:91-109    Style_Token_Layer.call
  *                          (== GST_Tacotron.Inference_GST_Step, Model.py:257-265)
+ *   gsttaco_gst_ex / gsttaco_style_compose / gsttaco_inference_step_styled
+ *                       <- EXTENSION (style control, DESIGN row A14): the attention weights the reference computes and drops
+ *                          (GST.py:105), the layer's last stage on GIVEN weights (Layers.py:207-211), and Inference_Step on a
+ *                          GIVEN style embedding
  *   gsttaco_decode      <- Modules/Taco2.py:153-228 Decoder.call loop (training=False),
  *                          Decoder_Step :96-120, Prenet :262-283,
  *                          Modules/Attention/Steps.py:107-229 (BMA / SMA)
@@ -44,7 +48,7 @@
 extern "C" {
 #endif
 
-#define GSTTACO_ABI_VERSION 13
+#define GSTTACO_ABI_VERSION 14
 #define GSTTACO_MAX_LAYERS 8
 
 enum {
@@ -164,6 +168,31 @@ int gsttaco_encode(gsttaco_ctx* ctx, const int32_t* tokens, const int32_t* token
 int gsttaco_gst(gsttaco_ctx* ctx, const float* mels_for_gst, const int32_t* mel_lengths,
                 int B, int Tref1, float* gst, void* stream);
 
+/* Style control (EXTENSION, ABI 14).  H = heads, N = n_tokens, A = gst_att, dh = A / H; V = tanh(tokens).Wv + bv [N,A] is
+ * precomputed at finalize.  The reference's layer (Layers.py:172-214) is
+ *     q        = ref.Wq + bq                                                      [B,A]   (ref = reference-encoder output)
+ *     p[b,h,:] = softmax_n( q[b, h*dh:(h+1)*dh] . V[:, h*dh:(h+1)*dh]^T )          [B,H,N]
+ *     gst      = LayerNorm( concat_h( p[b,h,:] . V[:, h-slice] ) + q ; gamma, beta, eps 1e-8 )
+ * and throws p away (GST.py:105).
+ *
+ * gsttaco_gst_ex = gsttaco_gst + what it computed on the way: token_weights [B,heads,n_tokens] = p and query [B,gst_att] = q;
+ * either may be NULL.  gst is bitwise what gsttaco_gst returns. */
+int gsttaco_gst_ex(gsttaco_ctx* ctx, const float* mels_for_gst, const int32_t* mel_lengths, int B, int Tref1,
+                   float* gst, float* token_weights, float* query, void* stream);
+
+/* compose(weights, query) = LayerNorm( concat_h( weights[b,h,:] . V[:, h-slice] ) + query ):
+ * token_weights [B,heads,n_tokens], query [B,gst_att] or NULL (= 0)  ->  gst [B,gst_att].
+ *   - the weights are ANY real numbers: not normalised, not clipped (the GST paper scales and negates them; a caller who wants
+ *     a softmax applies one);
+ *   - compose(p, q) of a reference's exported pair is that reference's embedding up to fp32 rounding (gsttaco_gst divides the
+ *     weighted sum by the softmax denominator once, compose multiplies by the already divided weights);
+ *   - all-zero weights with no query give exactly beta (the LayerNorm input is 0 and 0 / sqrt(0 + 1e-8) = 0);
+ *   - tokens alone (query NULL) are OUTSIDE THE TRAINING DISTRIBUTION of this architecture: the decoder only ever saw
+ *     LayerNorm(attention output + q).  The function is well defined there all the same.
+ * One launch on the caller's stream straight from / to the caller's pointers (like gsttaco_mel_frontend); needs finalized
+ * weights, GST on, B <= max_batch. */
+int gsttaco_style_compose(gsttaco_ctx* ctx, const float* token_weights, const float* query, int B, float* gst, void* stream);
+
 /* enc [B,Tv,2*enc_rnn], gst [B,gst_att] (NULL when GST is off)
  * prenet_mask: keep-masks [steps,2,B,prenet] float32 (1 keep / 0 drop), or NULL = generated on the device from `seed`:
  *              at the reference's rate 0.5 the keep bit of (step, layer, utterance row, column) is bit (column & 31) of a
@@ -229,6 +258,16 @@ int gsttaco_inference_step(gsttaco_ctx* ctx, const int32_t* tokens, const int32_
                            const float* prenet_mask, const float* attn_noise, uint64_t seed,
                            int B, int Tv, int Tref1, int steps,
                            float* mel, float* stop, float* align, float* pre_mel, float* spectrogram, void* stream);
+
+/* gsttaco_inference_step with the style GIVEN (EXTENSION, ABI 14): style [B,gst_att] -- from gsttaco_gst / gsttaco_gst_ex,
+ * gsttaco_style_compose, or arithmetic on such rows -- replaces mels_for_gst / mel_lengths / Tref1; the reference encoder and the
+ * style-token layer are not run.  Everything downstream is the same code and the same decode plan: with style = gsttaco_gst(mels)
+ * the outputs are bitwise those of gsttaco_inference_step(mels).  The encoder segment's cached graph is gsttaco_encode's.
+ * GSTTACO_E_INVALID ("GST is not used") when GST is off, and for a NULL style. */
+int gsttaco_inference_step_styled(gsttaco_ctx* ctx, const int32_t* tokens, const int32_t* token_lengths, const float* style,
+                                  const float* prenet_mask, const float* attn_noise, uint64_t seed,
+                                  int B, int Tv, int steps,
+                                  float* mel, float* stop, float* align, float* pre_mel, float* spectrogram, void* stream);
 
 /* hipGraph cache policy.  Every entry point replays one cached graph executable per (entry, B, Tv, Tref1, steps, flags) key.
  * The cache is LRU-bounded to `max_cached` executables (default 16 -- an Inference_Step replays two or three: encoder segment, GST + decode + postnet, vocoder; GSTTACO_GRAPH_CACHE; 0 = no graphs, everything is
