@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = (
     "gsttaco_set_graph_policy", "gsttaco_graph_cache_size", "gsttaco_debug_handoff_error", "gsttaco_debug_raise_handoff_error", "gsttaco_debug_counters",
     "gsttaco_synchronize", "gsttaco_debug_conv_prepare", "gsttaco_debug_conv_run",
     "gsttaco_gst_ex", "gsttaco_style_compose", "gsttaco_inference_step_styled",
+    "gsttaco_decode_forced", "gsttaco_inference_step_forced", "gsttaco_forced_durations",
 )
 
 # GSTTACO_CONV_V_*: the conv/GEMM dispatcher's kernel instantiations (gsttaco_debug_conv_run reports which one ran)
@@ -132,6 +133,9 @@ def load_library(path=None):
     lib.gsttaco_style_compose.argtypes = [vp, vp, vp, i32, vp, vp]
     lib.gsttaco_inference_step_styled.argtypes = [vp, vp, vp, vp, vp, vp, u64, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.gsttaco_decode.argtypes = [vp, vp, vp, vp, vp, vp, u64, i32, i32, i32, vp, vp, vp, vp]
+    lib.gsttaco_decode_forced.argtypes = [vp, vp, vp, vp, vp, vp, u64, i32, i32, vp, i32, vp, vp, vp, vp]
+    lib.gsttaco_inference_step_forced.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u64, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.gsttaco_forced_durations.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]
     lib.gsttaco_postnet.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.gsttaco_vocoder.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.gsttaco_inference_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
@@ -167,7 +171,8 @@ def load_library(path=None):
     for fn in ("gsttaco_create", "gsttaco_num_weights", "gsttaco_weight_info", "gsttaco_load_weight",
                "gsttaco_finalize_weights", "gsttaco_encode", "gsttaco_gst", "gsttaco_decode", "gsttaco_postnet", "gsttaco_vocoder",
                "gsttaco_inference_step", "gsttaco_set_profiling", "gsttaco_get_profile", "gsttaco_mel_frontend",
-               "gsttaco_mel_basis", "gsttaco_griffin_lim", "gsttaco_gst_ex", "gsttaco_style_compose", "gsttaco_inference_step_styled"):
+               "gsttaco_mel_basis", "gsttaco_griffin_lim", "gsttaco_gst_ex", "gsttaco_style_compose", "gsttaco_inference_step_styled",
+               "gsttaco_decode_forced", "gsttaco_inference_step_forced", "gsttaco_forced_durations"):
         getattr(lib, fn).restype = ctypes.c_int
     if path is None:
         _lib = lib

@@ -180,6 +180,10 @@ struct gsttaco_ctx {
     PackedLinear proj_z;        // projection columns | padding to a tile | (Wp_last . W0) columns: prenet 0 rides in the projection launch
     int z_col0 = 0;
     float* w_z0 = nullptr;
+    // Teacher forcing (gsttaco_decode_forced / gsttaco_inference_step_forced): the consumed frames [S][B][mel] and every step's prenet-0
+    // pre-activations [S][B][P0], allocated by the first forced call (ensure_forced); z0_dense = the plain pw0 / pb0 as a conv/GEMM layer
+    float *w_teach = nullptr, *w_zf = nullptr;
+    ConvLayer z0_dense;
     ConvLayer val_enc;          // the [enc] rows of the Value kernel (+ its bias when no GST row bias carries it)
     float *att_v = nullptr, *att_sb = nullptr;
     float *loc_cw = nullptr, *loc_cb = nullptr, *loc_dw = nullptr, *loc_db = nullptr, *att_bias = nullptr;   // LSA extension
@@ -1084,7 +1088,8 @@ struct DecodePlan {
     bool masks_unused = false;    // ... and no launch reads the keep-mask tensor
 };
 
-DecodePlan plan_decode(const gsttaco_ctx* c, int B, int Tv, bool injected_mask) {
+// `forced`: a teacher-forced decode (DecodeCall::forced): always launches per step -- the persistent kernels feed their own frame back.
+DecodePlan plan_decode(const gsttaco_ctx* c, int B, int Tv, bool injected_mask, bool forced = false) {
     const gsttaco_config& g = c->cfg;
     const bool lsa = g.att_type == GSTTACO_ATT_LSA;
     const PackedLinear *X = c->lstm_x, *R = c->lstm_h;
@@ -1129,6 +1134,7 @@ DecodePlan plan_decode(const gsttaco_ctx* c, int B, int Tv, bool injected_mask) 
                 X[0].nkb == 24 && X[1].nkb == 64 && R[0].nkb == 64 && R[1].nkb == 64 && B <= c->persist_rows && (B <= 32 || c->w_stash) &&
                 gt_persist_decode_supported(g.mel_dim, c->r, c->P0, c->P1, c->att, c->H1, c->H2, B, Tv, c->proj_z.ntiles, c->proj_z.nkb,
                                             c->persist_slots, bf16 ? 1 : 0);
+    if (forced) p.persist = false;
     p.persist_bf16 = p.persist && bf16;
     return p;
 }
@@ -1166,9 +1172,12 @@ struct DecodeCall {
     float drop_scale;
     int64_t ld_pre;                 // row stride of the pre-postnet frames
     ProfBrackets prof;
+    bool forced = false;            // teacher forcing (Taco2.py:185): step t consumes the staged ground-truth frame w_teach[t]
     const float* frame(int t) const {       // the last frame step t - 1 emitted (Taco2.py:186: decodings[:, -1]; zeros at t = 0)
+        if (forced) return c->w_teach + (size_t)t * B * c->cfg.mel_dim;
         return t == 0 ? c->w_zero : c->w_pre + ((size_t)(t - 1) * c->r + (c->r - 1)) * c->cfg.mel_dim;
     }
+    int64_t ldframe(int t) const { return forced ? (int64_t)c->cfg.mel_dim : (t == 0 ? 0 : ld_pre); }
     const float* mask(int t, int layer) const {
         return has_mask ? c->w_masks + (size_t)t * B * (c->P0 + c->P1) + (layer ? (size_t)B * c->P0 : 0) : nullptr;
     }
@@ -1224,8 +1233,10 @@ int enqueue_front_fused(DecodeCall& d, int t, bool on) {
     const int B = d.B, Tv = d.Tv, MT = d.MT, p = t & 1;
     const bool lsa = g.att_type == GSTTACO_ATT_LSA;
     DecFrontArgs f{};
-    f.frame = d.frame(t); f.ldframe = t == 0 ? 0 : d.ld_pre;
+    f.frame = d.frame(t); f.ldframe = d.ldframe(t);
     f.z0 = (P.z0 && t > 0) ? c->w_z0 : nullptr;
+    // (forced: every step's pre-activations were computed up front from the staged frames, step 0 included -- enqueue_forced_z0)
+    if (d.forced) f.z0 = c->w_zf + (size_t)t * B * c->P0;
     f.w0 = c->pw0; f.b0 = c->pb0; f.w1 = c->pw1; f.b1 = c->pb1; f.wq = c->pwq; f.bq = c->pbq;
     f.mask0 = d.mask(t, 0); f.mask1 = d.mask(t, 1);
     if (P.hashed) {
@@ -1289,7 +1300,7 @@ int enqueue_front_kernels(DecodeCall& d, int t) {
     // 1. prenet layer 0 on the last emitted frame
     memset(&k, 0, sizeof(k));
     k.wp = c->prenet0.wp; k.bf16 = c->prenet0.bf16; k.bias = c->prenet0.bias;
-    k.seg[0] = SkinnySeg{d.frame(t), t == 0 ? 0 : d.ld_pre, mel / 16, 0};
+    k.seg[0] = SkinnySeg{d.frame(t), d.ldframe(t), mel / 16, 0};
     k.nkb = c->prenet0.nkb; k.M = B; k.N = P0; k.n_split = P0; k.MT = MT;
     k.out = c->w_p1; k.ldo = P0;
     k.mask = d.mask(t, 0); k.ldm = P0;
@@ -1450,12 +1461,28 @@ int enqueue_projection(DecodeCall& d, int t, bool on) {
     });
 }
 
-int enqueue_decode(gsttaco_ctx* c, hipStream_t s, int B, int Tv, int steps, bool has_mask, bool has_noise, bool masked) {
+// Z0 [S][B][P0] = w_teach [S*B, mel] . W0 + b0: the prenet-0 pre-activations of EVERY forced step in one fp32 GEMM (the implicit-GEMM
+// kernel's v_mfma_f32_32x32x2_f32 chain; fp32 operands under Use_Mixed_Precision too, like the front kernel's own prenet 0)
+int enqueue_forced_z0(gsttaco_ctx* c, hipStream_t s, int B, int steps) {
+    ConvGemmArgs a = conv_args(c->z0_dense, GSTTACO_CONV_FORM_FP32);
+    a.x = c->w_teach;
+    a.out = c->w_zf; a.ldo = c->P0;
+    a.B = 1; a.T = steps * B; a.act = ACT_NONE;
+    HIPCHECK(c, gt_launch_conv_gemm(a, s));
+    return 0;
+}
+
+int enqueue_decode(gsttaco_ctx* c, hipStream_t s, int B, int Tv, int steps, bool has_mask, bool has_noise, bool masked, bool forced = false) {
     const gsttaco_config& g = c->cfg;
     const int MT = (B + 15) / 16;
-    DecodeCall d{c, s, plan_decode(c, B, Tv, has_mask), B, Tv, steps, MT, has_mask, has_noise, masked ? c->w_tok_len : nullptr,
+    DecodeCall d{c, s, plan_decode(c, B, Tv, has_mask, forced), B, Tv, steps, MT, has_mask, has_noise, masked ? c->w_tok_len : nullptr,
                  g.prenet_rate > 0.f ? 1.0f / (1.0f - g.prenet_rate) : 1.f, (int64_t)steps * c->r * g.mel_dim, ProfBrackets{c, s}};
+    d.forced = forced;
     const DecodePlan& P = d.P;
+    if (forced && P.fused) {
+        const int rc0 = enqueue_forced_z0(c, s, B, steps);
+        if (rc0) return rc0;
+    }
     if (!P.persist) {
         HIPCHECK(c, gt_launch_zero(c->w_h1[1], (size_t)MT * 16 * c->H1, s));
         HIPCHECK(c, gt_launch_zero(c->w_h2[1], (size_t)MT * 16 * c->H2, s));
@@ -1698,6 +1725,28 @@ int check_shape(gsttaco_ctx* c, int B, int Tv, int Tref1, int steps) {
     return 0;
 }
 
+// Teacher forcing: the workspace of the staged frames and of every step's prenet-0 pre-activations, sized like the rest of the workspace
+// by the capacity given at create and allocated by the FIRST forced call (outside any capture), so a context that never forces pays
+// nothing; freed with everything else at destroy.
+int ensure_forced(gsttaco_ctx* c) {
+    if (c->w_teach && c->w_zf) return 0;
+    const size_t rows = (size_t)c->cfg.max_batch * c->steps_max;
+    int rc = 0;
+    if (!c->w_teach && (rc = dev_alloc(c, (void**)&c->w_teach, (rows + 16) * c->cfg.mel_dim * sizeof(float)))) return rc;
+    if (!c->w_zf && (rc = dev_alloc(c, (void**)&c->w_zf, rows * c->P0 * sizeof(float)))) return rc;
+    return 0;
+}
+
+// The arguments every forced entry point shares: teacher [B, Tq, mel] -> *S = ceil((Tq - 1) / r) decoder steps
+int check_forced(gsttaco_ctx* c, const float* teacher, int Tq, int B, int Tv, int Tref1, int* S) {
+    if (!teacher) return fail(c, GSTTACO_E_INVALID, "null teacher");
+    if (Tq < 2) return fail(c, GSTTACO_E_INVALID, "teacher needs the go frame and at least one more (Tq >= 2)");
+    const int64_t steps = ((int64_t)Tq - 1 + c->r - 1) / c->r;
+    if (steps > c->steps_max) return fail(c, GSTTACO_E_CAPACITY, "teacher frames exceed Max_Step");
+    *S = (int)steps;
+    return check_shape(c, B, Tv, Tref1, *S);
+}
+
 // Runs `body` either eagerly on `stream` or through a cached hipGraph captured on the internal stream (LRU-bounded,
 // see gsttaco_ctx::graphs).  `persist_segment`: the body may enqueue persistent BiLSTM launches (see g_persist_event).
 template <typename F>
@@ -1779,7 +1828,7 @@ int run_cached(gsttaco_ctx* c, hipStream_t stream, const GraphKey& key_in, F bod
         rc = run_cached_inner(c, stream, key_in, body);
         HIPCHECK(c, hipEventRecord(ev, stream));
     }
-    if (!rc && (c->fuse12_now || c->persist_now) && (key_in.kind == 0 || key_in.kind == 3 || key_in.kind == 10)) {      // the segment held fused / persistent decode launches
+    if (!rc && (c->fuse12_now || c->persist_now) && (key_in.kind == 0 || key_in.kind == 3 || key_in.kind == 10 || key_in.kind == 11 || key_in.kind == 12)) {      // the segment held fused / persistent decode launches
         std::lock_guard<std::mutex> lock(g_persist_mu);
         FusedInFlight& f = g_fused_event[c->cfg.device];
         if (!f.ev) HIPCHECK(c, hipEventCreateWithFlags(&f.ev, hipEventDisableTiming));
@@ -2080,6 +2129,9 @@ int finalize_decoder_step(gsttaco_ctx* c) {
         if ((rc = upload(c, &c->pb0, b0.data.data(), b0.data.size()))) return rc;
         if ((rc = upload(c, &c->pw1, k1.data.data(), k1.data.size()))) return rc;
         if ((rc = upload(c, &c->pb1, b1.data.data(), b1.data.size()))) return rc;
+        // (teacher forcing: prenet 0 over all steps' frames at once is a plain Dense on the plain layouts -- FP32 form, nothing uploaded twice)
+        c->z0_dense.w = c->pw0; c->z0_dense.shift = c->pb0;
+        c->z0_dense.taps = 1; c->z0_dense.cin = g.mel_dim; c->z0_dense.cout = c->P0;
         const HostTensor &qk = T(c, "decoder.attention.query.kernel"), &qb = T(c, "decoder.attention.query.bias");
         if ((rc = upload(c, &c->pwq, qk.data.data(), qk.data.size()))) return rc;
         if ((rc = upload(c, &c->pbq, qb.data.data(), qb.data.size()))) return rc;
@@ -2466,6 +2518,54 @@ int gsttaco_decode(gsttaco_ctx* c, const float* enc, const float* gst, const int
     return 0;
 }
 
+// gsttaco_decode with the reference's OTHER loop branch (Taco2.py:183-187, training=True): step t consumes teacher[:, t * r].  Launches per
+// step (plan_decode `forced`), graph key kind 12.
+int gsttaco_decode_forced(gsttaco_ctx* c, const float* enc, const float* gst, const int32_t* token_lengths, const float* mask,
+                          const float* noise, uint64_t seed, int B, int Tv, const float* teacher, int Tq, float* pre_mel, float* stop,
+                          float* align, void* stream) {
+    int rc = check_ready(c);
+    if (rc) return rc;
+    if (!enc || !pre_mel || !stop || !align || (c->cfg.gst_use && !gst)) return fail(c, GSTTACO_E_INVALID, "null argument");
+    int steps = 0;
+    if ((rc = check_forced(c, teacher, Tq, B, Tv, 0, &steps))) return rc;
+    if ((rc = ensure_forced(c))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHECK(c, hipMemcpyAsync(c->w_enc, enc, (size_t)B * Tv * c->enc_out * 4, hipMemcpyDeviceToDevice, s));
+    if (c->cfg.gst_use)
+        HIPCHECK(c, hipMemcpyAsync(c->w_gst, gst, (size_t)B * c->cfg.gst_att * 4, hipMemcpyDeviceToDevice, s));
+    if ((rc = stage_randomness(c, s, mask, noise, seed, B, Tv, steps))) return rc;
+    HIPCHECK(c, gt_launch_stage_teacher(teacher, c->w_teach, B, Tq, steps, c->r, c->cfg.mel_dim, s));
+    c->masks_lazy = plan_decode(c, B, Tv, mask != nullptr, true).masks_unused;
+    const bool masked = token_lengths != nullptr;
+    if (masked) HIPCHECK(c, hipMemcpyAsync(c->w_tok_len, token_lengths, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+    GraphKey key{12, B, Tv, 0, steps, mask != nullptr, noise != nullptr, c->prof_every, masked};
+    rc = run_cached(c, s, key, [&](hipStream_t st) {
+        int r2 = enqueue_value_proj(c, st, B, Tv);
+        return r2 ? r2 : enqueue_decode(c, st, B, Tv, steps, mask != nullptr, noise != nullptr, masked, true);
+    });
+    if (rc) return rc;
+    const size_t mel = c->cfg.mel_dim;
+    HIPCHECK(c, hipMemcpyAsync(pre_mel, c->w_pre, (size_t)B * steps * c->r * mel * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHECK(c, hipMemcpyAsync(stop, c->w_stop, (size_t)B * steps * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHECK(c, hipMemcpyAsync(align, c->w_align, (size_t)B * steps * Tv * 4, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+// Per-token frame counts of a (forced) alignment: one launch on the caller's stream straight from / to the caller's pointers.  Needs
+// no weights (only Step_Reduction), so it works before finalize.
+int gsttaco_forced_durations(gsttaco_ctx* c, const float* align, const int32_t* token_lengths, const int32_t* mel_lengths, int B, int S,
+                             int Tv, int32_t* durations, void* stream) {
+    if (!c) return GSTTACO_E_INVALID;
+    if (!align || !durations) return fail(c, GSTTACO_E_INVALID, "null argument");
+    if (B < 1 || S < 1 || Tv < 1) return fail(c, GSTTACO_E_INVALID, "bad B / S / Tv");
+    if (S > c->steps_max || B > c->cfg.max_batch || Tv > c->cfg.max_tokens)
+        return fail(c, GSTTACO_E_CAPACITY, "batch / tokens / steps exceed the capacity given at create");
+    int rc = ensure_device(c);
+    if (rc) return rc;
+    HIPCHECK(c, gt_launch_forced_durations(align, token_lengths, mel_lengths, durations, B, S, Tv, c->r, (hipStream_t)stream));
+    return 0;
+}
+
 int gsttaco_postnet(gsttaco_ctx* c, const float* pre_mel, int B, int Tf, float* mel, void* stream) {
     int rc = check_ready(c);
     if (rc) return rc;
@@ -2571,12 +2671,16 @@ namespace {
 // and the tail are not run; mels_for_gst / mel_lengths NULL, Tref1 0).  The callers have checked their own arguments.
 int inference_step(gsttaco_ctx* c, const int32_t* tokens, const int32_t* token_lengths, const float* mels_for_gst, const int32_t* mel_lengths,
                    const float* style, const float* mask, const float* noise, uint64_t seed, int B, int Tv, int Tref1, int steps,
-                   float* mel, float* stop, float* align, float* pre_mel, float* spectrogram, void* stream) {
+                   float* mel, float* stop, float* align, float* pre_mel, float* spectrogram, void* stream,
+                   const float* teacher = nullptr, int Tq = 0, bool forced = false) {
     int rc = 0;
     const bool gst = c->cfg.gst_use != 0;
     const bool styled = style != nullptr;
     if (spectrogram && !c->cfg.voc_use) return fail(c, GSTTACO_E_INVALID, "the context was created without Vocoder_Taco1");
-    if ((rc = check_shape(c, B, Tv, Tref1, steps))) return rc;
+    if (forced) {       // gsttaco_inference_step_forced: the step count follows from the teacher; its workspace exists before any capture
+        if ((rc = check_forced(c, teacher, Tq, B, Tv, Tref1, &steps))) return rc;
+        if ((rc = ensure_forced(c))) return rc;
+    } else if ((rc = check_shape(c, B, Tv, Tref1, steps))) return rc;
     if (steps == 0) steps = c->steps_max;
     hipStream_t s = (hipStream_t)stream;
     const bool voc = spectrogram != nullptr;
@@ -2593,12 +2697,13 @@ int inference_step(gsttaco_ctx* c, const int32_t* tokens, const int32_t* token_l
         cs.seed = seed; cs.seed_dst = c->w_seed;
         HIPCHECK(c, gt_launch_copy_segments(cs, s));
     }
+    if (forced) HIPCHECK(c, gt_launch_stage_teacher(teacher, c->w_teach, B, Tq, steps, c->r, c->cfg.mel_dim, s));      // (the forced graph's input copy)
     if (mask && c->dec_padded)      // (the caller's masks have the caller's prenet sizes: re-laid out for the padded model)
         HIPCHECK(c, gt_launch_relayout_masks(mask, c->w_masks, steps, B, c->P0t, c->P1t, c->P0, c->P1, 1, s));
     else if (mask)
         HIPCHECK(c, hipMemcpyAsync(c->w_masks, mask, (size_t)steps * B * (c->P0 + c->P1) * 4, hipMemcpyDeviceToDevice, s));
     if (noise) HIPCHECK(c, hipMemcpyAsync(c->w_noise, noise, (size_t)steps * B * Tv * 4, hipMemcpyDeviceToDevice, s));
-    c->masks_lazy = plan_decode(c, B, Tv, mask != nullptr).masks_unused;      // (per CALL: a replayed graph does not pass through enqueue_decode)
+    c->masks_lazy = plan_decode(c, B, Tv, mask != nullptr, forced).masks_unused;      // (per CALL: a replayed graph does not pass through enqueue_decode)
     // Three graph segments: the encoder and the vocoder each contain a persistent BiLSTM launch and are chained process-wide
     // (run_cached, g_persist_event); the segment between them -- GST, value projection, the decode loop, the postnet: 95 % of the
     // call -- overlaps freely with other contexts' work.  The encoder / vocoder segments share their cached graphs with
@@ -2609,12 +2714,14 @@ int inference_step(gsttaco_ctx* c, const int32_t* tokens, const int32_t* token_l
     const bool fork = gst && !styled && c->gst_fork;
     GraphKey kenc{fork ? 9 : 1, B, Tv, fork ? Tref1 : 0, 0, 0, 0, 0, masked};
     if ((rc = run_cached(c, s, kenc, [&](hipStream_t st) { return enqueue_encoder(c, st, B, Tv, masked, fork ? Tref1 : 0); }, true))) return rc;
-    GraphKey key{styled ? 10 : 0, B, Tv, Tref1, steps, mask != nullptr, noise != nullptr, c->prof_every, masked};
+    // (a forced call's middle segment has a key kind of its own, 11: with the style given Tref1 is 0, with mels it is >= 2, so the two
+    // bodies never share a key; keys carry the step count, one graph per distinct S)
+    GraphKey key{forced ? 11 : styled ? 10 : 0, B, Tv, Tref1, steps, mask != nullptr, noise != nullptr, c->prof_every, masked};
     rc = run_cached(c, s, key, [&](hipStream_t st) {
         int r2 = 0;
         if (gst && !styled && !fork) r2 = enqueue_gst(c, st, B, Tref1);
         if (!r2) r2 = enqueue_value_proj(c, st, B, Tv);
-        if (!r2) r2 = enqueue_decode(c, st, B, Tv, steps, mask != nullptr, noise != nullptr, masked);
+        if (!r2) r2 = enqueue_decode(c, st, B, Tv, steps, mask != nullptr, noise != nullptr, masked, forced);
         if (!r2) r2 = enqueue_postnet(c, st, B, steps * c->r, c->w_pre, c->w_mel);
         return r2;
     });
@@ -2665,6 +2772,26 @@ int gsttaco_inference_step_styled(gsttaco_ctx* c, const int32_t* tokens, const i
     if (!tokens || !style || !mel || !stop || !align) return fail(c, GSTTACO_E_INVALID, "null argument");
     return inference_step(c, tokens, token_lengths, nullptr, nullptr, style, mask, noise, seed, B, Tv, 0, steps,
                           mel, stop, align, pre_mel, spectrogram, stream);
+}
+
+// gsttaco_inference_step / gsttaco_inference_step_styled with the decoder teacher-forced (Taco2.py:161,185): exactly one style source
+// when GST is on (both ignored when it is off), no `steps` -- S = ceil((Tq - 1) / r).
+int gsttaco_inference_step_forced(gsttaco_ctx* c, const int32_t* tokens, const int32_t* token_lengths, const float* mels_for_gst,
+                                  const int32_t* mel_lengths, const float* style, const float* mask, const float* noise, uint64_t seed,
+                                  int B, int Tv, int Tref1, const float* teacher, int Tq,
+                                  float* mel, float* stop, float* align, float* pre_mel, float* spectrogram, void* stream) {
+    int rc = check_ready(c);
+    if (rc) return rc;
+    const bool gst = c->cfg.gst_use != 0;
+    if (!tokens || !mel || !stop || !align) return fail(c, GSTTACO_E_INVALID, "null argument");
+    if (gst && ((mels_for_gst != nullptr) == (style != nullptr)))
+        return fail(c, GSTTACO_E_INVALID, "exactly one of mels_for_gst and style must be given");
+    if (gst && mels_for_gst && !mel_lengths) return fail(c, GSTTACO_E_INVALID, "GST is enabled, but no mel information.");
+    if (!gst) { mels_for_gst = nullptr; mel_lengths = nullptr; style = nullptr; }
+    if (!gst || style) Tref1 = 0;
+    else if (Tref1 < 2) return fail(c, GSTTACO_E_INVALID, "mels_for_gst needs at least one frame after the prepended zero frame");
+    return inference_step(c, tokens, token_lengths, mels_for_gst, mel_lengths, style, mask, noise, seed, B, Tv, Tref1, 0,
+                          mel, stop, align, pre_mel, spectrogram, stream, teacher, Tq, true);
 }
 
 int gsttaco_synchronize(gsttaco_ctx* c, void* stream) {

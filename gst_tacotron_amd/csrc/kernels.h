@@ -474,3 +474,11 @@ struct GriffinLimArgs {
 hipError_t gt_gl_init();
 hipError_t gt_launch_griffin_lim(GriffinLimArgs a, float* frm_a, float* frm_b, hipStream_t stream);
 
+// ---------------------------------------------------------------- forced.hip
+// Teacher forcing (Taco2.py:161,185): out [S][B][mel] <- teacher[b, t*r, :] of teacher [B, Tq, mel], S = ceil((Tq - 1) / r)
+hipError_t gt_launch_stage_teacher(const float* teacher, float* out, int B, int Tq, int S, int r, int mel, hipStream_t stream);
+// dur [B, Tv] int32 <- frames per token of align [B, S, Tv]: frame f < L_b counts for argmax_{j < n_b} align[b, f / r, j] (lowest
+// index on a tie); n_b = tok_len ? tok_len[b] : Tv, L_b = mel_len ? min(mel_len[b], S*r) : S*r.  One workgroup per utterance.
+hipError_t gt_launch_forced_durations(const float* align, const int32_t* tok_len, const int32_t* mel_len, int32_t* dur, int B, int S,
+                                      int Tv, int r, hipStream_t stream);
+

@@ -86,3 +86,26 @@ class Feeder:
             mels[i, 1:m.shape[0] + 1] = m
         return {"mels_for_gst": mels,
                 "mel_lengths_for_gst": np.array([m.shape[0] for m in mel_List], dtype=np.int32)}
+
+    def Get_Teacher_Pattern(self, sentence_List, mel_List):
+        """Extension (teacher forcing, ``GST_Tacotron.Inference_Step(teacher_mels=...)``): tokens as ``Get_Inference_Pattern`` makes them
+        and the target mels [T, Mel_Dim] in the layout the reference trains on (Feeder.py:103-143): zero-padded to the longest, a zero
+        go frame PREPENDED, padded to a multiple of Step_Reduction, and one more frame appended (the decoder reads ``mels[:, 0:-1:r]``,
+        Taco2.py:161).  Returns tokens, token_lengths, teacher_mels [B, Tq, Mel_Dim] and mel_lengths [B] (excluding the go frame)."""
+        if len(mel_List) != len(sentence_List):
+            raise ValueError("mel_List must hold one mel per sentence")
+        mel_dim, r = self.hp["Sound"]["Mel_Dim"], int(self.hp["Step_Reduction"])
+        mel_List = [np.asarray(m, dtype=np.float32) for m in mel_List]
+        for m in mel_List:
+            if m.ndim != 2 or m.shape[1] != mel_dim or m.shape[0] < 1:
+                raise ValueError("teacher mels must be [T>=1, {}] arrays".format(mel_dim))
+        pattern = self.Get_Inference_Pattern(sentence_List, style_given=True)
+        del pattern["initial_mels"]
+        max_len = max(m.shape[0] for m in mel_List)
+        padded = -(-(max_len + 1) // r) * r                         # Feeder.py:132-133 (go frame included)
+        mels = np.zeros((len(mel_List), padded + 1, mel_dim), dtype=np.float32)      # :134-137 (+1: dropped by 0:-1:r)
+        for i, m in enumerate(mel_List):
+            mels[i, 1:m.shape[0] + 1] = m
+        pattern["teacher_mels"] = mels
+        pattern["mel_lengths"] = np.array([m.shape[0] for m in mel_List], dtype=np.int32)
+        return pattern

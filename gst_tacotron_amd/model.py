@@ -6,6 +6,7 @@
     .Inference_GST_Step(mels_for_gst, mel_lengths_for_gst)
     .Inference(sentence_List, mel_List_for_GST)
     .Style_Compose(token_weights, query)                 (extension: a style from token weights)
+    .Inference_GTA(sentence_List, mel_or_wav_List)       (extension: teacher-forced decoding -- GTA mels, forced durations)
 
 Same names, argument order/meaning and error behaviour; the Keras functional model
 behind them (Model.py:145-156) is replaced by the HIP kernels behind include/gsttaco.h.
@@ -22,7 +23,10 @@ PyTorch is used for device memory and streams only.  Differences, all additive:
   * style control: ``Inference_GST_Step(return_attention=True)`` also returns the token weights and the query the
     reference computes and drops (GST.py:105), ``Style_Compose`` builds an embedding from given token weights, and
     ``Inference_Step`` / ``Inference`` take ``style_embeddings`` (and ``Inference`` ``style_token_weights``) in place
-    of reference audio.
+    of reference audio;
+  * teacher forcing: ``Inference_Step`` / ``decode`` take ``teacher_mels`` -- the decoder then consumes the ground-truth frames like
+    the reference's training=True loop branch (Taco2.py:161,185), with every layer still in inference mode --, ``Forced_Durations``
+    counts frames per token of an alignment and ``Inference_GTA`` wraps both for ground-truth-aligned mels.
 """
 import ctypes
 import os
@@ -112,7 +116,8 @@ class GST_Tacotron:
     # ------------------------------------------------------------------ hot path
     def Inference_Step(self, tokens, token_lengths=None, initial_mels=None, mels_for_gst=None,
                        mel_lengths_for_gst=None, prenet_masks=None, attn_noise=None, seed=None,
-                       steps=None, return_pre_mel=False, masked=False, with_vocoder=False, style_embeddings=None):
+                       steps=None, return_pre_mel=False, masked=False, with_vocoder=False, style_embeddings=None,
+                       teacher_mels=None):
         """reference Model.py:249-255.  Returns (mel_Logits [B,S*r,mel], stop_Logits [B,S],
         spectrogram_Logits ([B,S*r,Spectrogram_Dim] with ``with_vocoder=True``, else None), alignments [B,S,T_v]) as
         CUDA tensors on the current stream.
@@ -123,7 +128,12 @@ class GST_Tacotron:
         ``style_embeddings`` (extension) [batch, Style_Token.Attention.Size], or [1, ...] for one style for the whole batch: the
         style is given instead of computed from ``mels_for_gst`` (which must then be None); the reference encoder and the style-token
         layer are skipped, everything downstream is the same code.  With ``Inference_GST_Step``'s output for some mels the results
-        are bitwise those of the call with those mels."""
+        are bitwise those of the call with those mels.
+        ``teacher_mels`` (extension) [batch, Tq, Mel_Dim] in the reference's ``mels`` layout (Feeder.py:125-139; ``Feeder.Get_Teacher_Pattern``
+        builds it): teacher forcing -- step t consumes ``teacher_mels[:, t * r]`` (frame 0 is the go frame, used as given) instead of
+        the frame it emitted before, as the reference's training=True loop does (Taco2.py:161,185).  S = ceil((Tq - 1) / r) steps;
+        ``steps`` must then be None.  The layers run in inference mode as everywhere here (GTA, not Train_Step's forward), nothing
+        is masked by mel length, the same tuple is returned.  Launch path only; one cached graph per distinct S."""
         self._require_ready()
         d = self.dims
         tok = self._dev(tokens, torch.int32)
@@ -157,7 +167,8 @@ class GST_Tacotron:
             if mels.dim() != 3 or mels.shape[0] != B or mels.shape[2] != d.mel or lens.shape != (B,):
                 raise ValueError("mels_for_gst must be [batch, frames+1, Mel_Dim] with mel_lengths_for_gst [batch]")
             Tref1 = mels.shape[1]
-        S = d.steps if steps is None else int(steps)
+        teacher, Tq = self._teacher(teacher_mels, B, steps)
+        S = (Tq - 1 + d.r - 1) // d.r if teacher is not None else d.steps if steps is None else int(steps)
         masks = self._dev(prenet_masks, torch.float32)
         noise = self._dev(attn_noise, torch.float32)
         if masks is not None and masks.numel() != S * B * sum(d.prenet):
@@ -177,7 +188,12 @@ class GST_Tacotron:
             self.seed += 1
             seed = self.seed
         with torch.cuda.device(self.device):
-            if style is not None:
+            if teacher is not None:
+                self.ctx.check(self.ctx.lib.gsttaco_inference_step_forced(
+                    self.ctx.handle, _ptr(tok), _ptr(tlen), _ptr(mels), _ptr(lens), _ptr(style), _ptr(masks), _ptr(noise),
+                    ctypes.c_uint64(int(seed)), B, Tv, Tref1, _ptr(teacher), Tq, _ptr(mel), _ptr(stop), _ptr(align), _ptr(pre),
+                    _ptr(spec), self._stream()))
+            elif style is not None:
                 self.ctx.check(self.ctx.lib.gsttaco_inference_step_styled(
                     self.ctx.handle, _ptr(tok), _ptr(tlen), _ptr(style), _ptr(masks), _ptr(noise),
                     ctypes.c_uint64(int(seed)), B, Tv, S, _ptr(mel), _ptr(stop), _ptr(align), _ptr(pre), _ptr(spec),
@@ -190,6 +206,67 @@ class GST_Tacotron:
         if return_pre_mel:
             return mel, stop, spec, align, pre
         return mel, stop, spec, align
+
+    def _teacher(self, teacher_mels, B, steps):
+        """(device tensor [B, Tq, Mel_Dim], Tq) of a ``teacher_mels`` argument, or (None, 0)."""
+        if teacher_mels is None:
+            return None, 0
+        if steps is not None:
+            raise ValueError("teacher_mels fixes the step count (ceil((Tq - 1) / Step_Reduction)): steps must be None")
+        t = self._dev(teacher_mels, torch.float32)
+        if t.dim() != 3 or t.shape[0] != B or t.shape[2] != self.dims.mel or t.shape[1] < 2:
+            raise ValueError("teacher_mels must be [batch, Tq >= 2, Mel_Dim] (frame 0 = the go frame)")
+        return t, int(t.shape[1])
+
+    def Forced_Durations(self, alignments, token_lengths=None, mel_lengths=None):
+        """Extension: frames per token of ``alignments`` [B, S, T_v] (as ``Inference_Step`` returns them) -> int32 [B, T_v] on the
+        device.  Frame f of utterance b (f < min(mel_lengths[b], S * r); S * r without ``mel_lengths``) counts for token
+        argmax_{j < token_lengths[b]} alignments[b, f // r, j] (all T_v columns without ``token_lengths``; the lowest index on a tie):
+        rows sum to the length, columns beyond the token length are 0 (``gsttaco_forced_durations``)."""
+        al = self._dev(alignments, torch.float32)
+        if al.dim() != 3:
+            raise ValueError("alignments must be [batch, steps, T_v]")
+        B, S, Tv = al.shape
+        tl = self._dev(token_lengths, torch.int32)
+        ml = self._dev(mel_lengths, torch.int32)
+        for name, v in (("token_lengths", tl), ("mel_lengths", ml)):
+            if v is not None and tuple(v.shape) != (B,):
+                raise ValueError(name + " must be [batch]")
+        dur = torch.empty((B, Tv), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            self.ctx.check(self.ctx.lib.gsttaco_forced_durations(self.ctx.handle, _ptr(al), _ptr(tl), _ptr(ml), B, S, Tv, _ptr(dur),
+                                                                 self._stream()))
+        return dur
+
+    def Inference_GTA(self, sentence_List, mel_or_wav_List, wav_List_for_GST=None, style_embeddings=None, **kwargs):
+        """Extension: ground-truth-aligned (GTA) mels.  ``mel_or_wav_List`` holds one target per sentence: mels [T, Mel_Dim] (as
+        Pattern_Generator stores them) or wav paths / 1-D sample arrays, which go through ``Mel_Generate`` (top_db 15, the value
+        Feeder.py:209 uses for several wavs).  The decoder is teacher-forced on them (``Inference_Step(teacher_mels=...)``; inference-mode
+        layers).  The style comes from ``style_embeddings`` or ``wav_List_for_GST`` when given, else from the target audio itself,
+        as the reference's training model takes it (Model.py:206).
+        Returns (gta_mels: list of [T_i, Mel_Dim] post-net mels trimmed to each target's length, stops [B, S], alignments
+        [B, S, T_v], durations int32 [B, T_v] with each row summing to T_i) after ``synchronize()``."""
+        print("GTA inference running...")
+        targets = list(mel_or_wav_List)
+        if len(targets) != len(sentence_List):
+            raise ValueError("mel_or_wav_List must hold one target per sentence")
+        if not all(self.feeder._is_mel(m) for m in targets):
+            mels, lens = self.Mel_Generate(targets, 15)
+            mels, lens = mels.cpu().numpy(), lens.cpu().numpy()
+            targets = [mels[i, 1:1 + int(lens[i])] for i in range(len(targets))]
+        pattern = self.feeder.Get_Teacher_Pattern(sentence_List, targets)
+        mel_lengths = pattern.pop("mel_lengths")
+        if self.hp_Dict["GST"]["Use"]:
+            if style_embeddings is not None:
+                if wav_List_for_GST is not None:
+                    raise ValueError("wav_List_for_GST and style_embeddings are mutually exclusive")
+                pattern["style_embeddings"] = style_embeddings
+            else:
+                pattern.update(self.feeder.Get_Inference_GST_Pattern(targets if wav_List_for_GST is None else list(wav_List_for_GST)))
+        mel, stop, _, align = self.Inference_Step(**pattern, **kwargs)
+        dur = self.Forced_Durations(align, pattern["token_lengths"], mel_lengths)
+        self.synchronize()
+        return [mel[i, :int(n)] for i, n in enumerate(mel_lengths)], stop, align, dur
 
     def Inference_GST(self, wav_List, tag_List=None, label=None):
         """reference Model.py:427-446: style embeddings [B, Attention.Size] of the wavs; with ``tag_List`` the table
@@ -451,20 +528,27 @@ class GST_Tacotron:
             self.ctx.check(self.ctx.lib.gsttaco_encode(self.ctx.handle, _ptr(tok), _ptr(tlen), B, Tv, _ptr(enc), self._stream()))
         return enc
 
-    def decode(self, enc, gst=None, prenet_masks=None, attn_noise=None, seed=0, steps=None, token_lengths=None):
+    def decode(self, enc, gst=None, prenet_masks=None, attn_noise=None, seed=0, steps=None, token_lengths=None, teacher_mels=None):
+        """``gsttaco_decode``; with ``teacher_mels`` [B, Tq, Mel_Dim] (see ``Inference_Step``) ``gsttaco_decode_forced``."""
         self._require_ready()
         d = self.dims
         enc = self._dev(enc, torch.float32)
         gst = self._dev(gst, torch.float32)
         tlen = self._dev(token_lengths, torch.int32)
         B, Tv = enc.shape[0], enc.shape[1]
-        S = d.steps if steps is None else int(steps)
+        teacher, Tq = self._teacher(teacher_mels, B, steps)
+        S = (Tq - 1 + d.r - 1) // d.r if teacher is not None else d.steps if steps is None else int(steps)
         masks = self._dev(prenet_masks, torch.float32)
         noise = self._dev(attn_noise, torch.float32)
         pre = torch.empty((B, S * d.r, d.mel), dtype=torch.float32, device=self.device)
         stop = torch.empty((B, S), dtype=torch.float32, device=self.device)
         align = torch.empty((B, S, Tv), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
+            if teacher is not None:
+                self.ctx.check(self.ctx.lib.gsttaco_decode_forced(
+                    self.ctx.handle, _ptr(enc), _ptr(gst), _ptr(tlen), _ptr(masks), _ptr(noise), ctypes.c_uint64(int(seed)),
+                    B, Tv, _ptr(teacher), Tq, _ptr(pre), _ptr(stop), _ptr(align), self._stream()))
+                return pre, stop, align
             self.ctx.check(self.ctx.lib.gsttaco_decode(
                 self.ctx.handle, _ptr(enc), _ptr(gst), _ptr(tlen), _ptr(masks), _ptr(noise), ctypes.c_uint64(int(seed)),
                 B, Tv, S, _ptr(pre), _ptr(stop), _ptr(align), self._stream()))

@@ -20,6 +20,9 @@
  *   gsttaco_decode      <- Modules/Taco2.py:153-228 Decoder.call loop (training=False),
  *                          Decoder_Step :96-120, Prenet :262-283,
  *                          Modules/Attention/Steps.py:107-229 (BMA / SMA)
+ *   gsttaco_decode_forced / gsttaco_inference_step_forced / gsttaco_forced_durations
+ *                       <- the same loop's training=True branch (Taco2.py:161,185: step t consumes mels[:, t*r]) for GTA mels and forced
+ *                          alignments; the per-token frame counts are an EXTENSION
  *   gsttaco_postnet     <- Modules/Taco2.py:131-149, 230
  *   gsttaco_vocoder     <- Modules/Taco2.py:234-260 Vocoder_Taco1.call, CBHG :285-380
  *   gsttaco_mel_frontend <- Pattern_Generator.py:39-60 Mel_Generate + Audio.py:29-32,49-55,70-96 melspectrogram
@@ -268,6 +271,42 @@ int gsttaco_inference_step_styled(gsttaco_ctx* ctx, const int32_t* tokens, const
                                   const float* prenet_mask, const float* attn_noise, uint64_t seed,
                                   int B, int Tv, int steps,
                                   float* mel, float* stop, float* align, float* pre_mel, float* spectrogram, void* stream);
+
+/* Teacher-forced decoding (EXTENSION of the inference interface; the reference's own training=True loop branch, Taco2.py:161,183-187,
+ * as Model.py:99-106 wires its Train model): step t consumes the ground-truth frame teacher[:, t*r] in place of the frame step t-1
+ * emitted.  For ground-truth-aligned (GTA) mels -- vocoder training -- and forced alignments / durations.
+ *   teacher : [B, Tq, mel_dim] float32 in the reference's `mels` layout (Feeder.py:125-139): frame 0 is the go frame, USED AS GIVEN (the
+ *             reference feeds zeros), frames 1.. the target, any padding behind it.  Tq >= 2.
+ *   steps   : none -- S = ceil((Tq - 1) / r); outputs pre_mel [B,S*r,mel], stop [B,S], align [B,S,Tv] (S*r may exceed Tq - 1)
+ *   lengths : like the reference, nothing is masked by mel length: every row runs all S steps, rows past an utterance's own length are
+ *             the caller's to trim.  token_lengths (masked mode), injected masks / noise and the seed mean what they mean to
+ *             gsttaco_decode: the dropout and noise of step t are those a free run draws at step t under the same seed.
+ *   layers  : inference mode (BatchNorm statistics, no encoder dropout) as everywhere in this library -- the usual meaning of GTA, not
+ *             Train_Step's forward pass.
+ * Every step's prenet-0 pre-activations come from ONE fp32 GEMM over the staged frames in front of the loop (fp32 operands under
+ * Use_Mixed_Precision too); the loop runs as launches per step -- never as the persistent decode launch, which feeds its own frames
+ * back -- from one cached graph per distinct S: callers whose lengths vary should bucket Tq or use capture_after = 2.  The workspace
+ * (max_batch x Max_Step//r x (mel_dim + prenet[0]) floats) is allocated by the first forced call.
+ * GSTTACO_E_INVALID: NULL teacher, Tq < 2; GSTTACO_E_CAPACITY: S > Max_Step // r, B / Tv beyond the capacity given at create. */
+int gsttaco_decode_forced(gsttaco_ctx* ctx, const float* enc, const float* gst, const int32_t* token_lengths,
+                          const float* prenet_mask, const float* attn_noise, uint64_t seed,
+                          int B, int Tv, const float* teacher, int Tq, float* pre_mel, float* stop, float* align, void* stream);
+
+/* gsttaco_inference_step / gsttaco_inference_step_styled with the decoder teacher-forced.  With GST on the style comes from EXACTLY ONE of
+ * mels_for_gst (+ mel_lengths, Tref1) and style [B,gst_att] -- both or neither: GSTTACO_E_INVALID --; with GST off both are ignored.
+ * The encoder segment replays the cached graph of the unforced calls; the middle segment has a graph key kind of its own. */
+int gsttaco_inference_step_forced(gsttaco_ctx* ctx, const int32_t* tokens, const int32_t* token_lengths,
+                                  const float* mels_for_gst, const int32_t* mel_lengths, const float* style,
+                                  const float* prenet_mask, const float* attn_noise, uint64_t seed,
+                                  int B, int Tv, int Tref1, const float* teacher, int Tq,
+                                  float* mel, float* stop, float* align, float* pre_mel, float* spectrogram, void* stream);
+
+/* Durations from an alignment: align [B,S,Tv] -> durations [B,Tv] int32 (device).  For utterance b with n = token_lengths ?
+ * token_lengths[b] : Tv and L = mel_lengths ? min(mel_lengths[b], S*r) : S*r, every frame f < L adds 1 to token
+ * argmax_{j<n} align[b, f / r, j] (the lowest index on a tie): rows sum to L, columns >= n are 0.  One launch (one workgroup per
+ * utterance) on the caller's stream straight from / to the caller's pointers; needs no weights. */
+int gsttaco_forced_durations(gsttaco_ctx* ctx, const float* align, const int32_t* token_lengths, const int32_t* mel_lengths,
+                             int B, int S, int Tv, int32_t* durations, void* stream);
 
 /* hipGraph cache policy.  Every entry point replays one cached graph executable per (entry, B, Tv, Tref1, steps, flags) key.
  * The cache is LRU-bounded to `max_cached` executables (default 16 -- an Inference_Step replays two or three: encoder segment, GST + decode + postnet, vocoder; GSTTACO_GRAPH_CACHE; 0 = no graphs, everything is
