@@ -16,6 +16,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/gsttaco.h"
@@ -62,14 +63,41 @@ struct ConvLayer {
     int wino_npad = 0;          // column padding of the planes (wino_s / wino_s4 / gemm_s)
 };
 
-struct GraphKey {
-    int kind, B, Tv, Tref1, steps, has_mask, has_noise, prof, masked;
-    int persist = 0;    // captured with the persistent BiLSTM launches enabled (filled in by run_cached)
-    int fuse12 = 0;     // captured with both decode LSTM cells in one launch (only while this is the process's one live context)
-    int persist_dec = 0;    // captured with the whole decode loop as one persistent launch (same condition)
-    bool operator<(const GraphKey& o) const {
-        return memcmp(this, &o, sizeof(GraphKey)) < 0;
+// The three launch forms that need their workgroups co-resident and can give up (note_give_up).  The context holds what it still allows
+// (gsttaco_ctx::allow); run_cached narrows that to what ONE call may take, keys the graph by it and hands it to the segment's body.
+struct LaunchForms {
+    bool fuse12 = false;            // both decode LSTM cells in one launch with an in-kernel hand-off (else two launches)
+    bool bilstm_persist = false;    // one persistent launch per BiLSTM (else one launch per time step)
+    bool persist_decode = false;    // the whole decode loop as ONE persistent launch where it applies (else launches per step)
+};
+
+// What a cached graph segment enqueues.  (The values are only names: nothing outside this file sees them.)
+enum SegKind : int {
+    kSegEncoder = 1, kSegEncoderFork = 9,       // text encoder (gsttaco_encode and Inference_Step share it); with the GST branch forked inside
+    kSegGst = 2, kSegPostnet = 4, kSegVocoder = 5,      // the other phases (gsttaco_vocoder and Inference_Step share the vocoder's)
+    kSegDecode = 3, kSegDecodeForced = 12,      // value projection + decode loop: gsttaco_decode, gsttaco_decode_forced
+    // Inference_Step's middle segment, [GST,] value projection, decode loop, postnet: from mels, with the style given, teacher-forced
+    kSegStep = 0, kSegStepStyled = 10, kSegStepForced = 11,
+};
+// What run_cached needs to know about a kind.  `bilstm`: the segment holds persistent BiLSTM launches and is chained process-wide
+// (g_persist_event); `decode`: it holds the decode loop, whose fused / persistent launches are recorded as in flight (g_fused_event).
+// No default: the compiler names a new kind that does not answer here.
+struct SegTraits { bool bilstm, decode; };
+constexpr SegTraits seg_traits(SegKind k) {
+    switch (k) {
+        case kSegEncoder: case kSegEncoderFork: case kSegVocoder: return {true, false};
+        case kSegStep: case kSegDecode: case kSegStepStyled: case kSegStepForced: case kSegDecodeForced: return {false, true};
+        case kSegGst: case kSegPostnet: break;
     }
+    return {false, false};
+}
+
+struct GraphKey {
+    SegKind kind;
+    int B = 0, Tv = 0, Tref1 = 0, steps = 0, has_mask = 0, has_noise = 0, prof = 0, masked = 0;
+    LaunchForms forms;      // what the call that captured it could take (filled in by run_cached; the call sites name the rest)
+    auto tie() const { return std::tie(kind, B, Tv, Tref1, steps, has_mask, has_noise, prof, masked, forms.fuse12, forms.bilstm_persist, forms.persist_decode); }
+    bool operator<(const GraphKey& o) const { return tie() < o.tie(); }
 };
 
 std::string g_create_error;
@@ -101,10 +129,9 @@ struct gsttaco_ctx {
     std::map<std::string, int> index;
     // Decoder sizes below the ones the persistent decode kernels are written for (prenet 256 / 256, attention 128, LSTM 1024 / 1024) are
     // ZERO-PADDED up to them at finalize (pad_decoder): the padded copies of the decoder's tensors, consulted by T() in front of `tensors`
-    // (whose shapes stay the caller's: gsttaco_weight_info).  dims_true: the caller's P0, P1, att, H1, H2.
+    // (whose shapes stay the caller's: gsttaco_weight_info).  cfg keeps the caller's sizes; P0 .. att below are the padded ones once dec_padded.
     std::map<std::string, HostTensor> padded;
     bool dec_padded = false;
-    int P0t = 0, P1t = 0, attt = 0, H1t = 0, H2t = 0;
     mutable std::string err;
     bool finalized = false;
     bool use_graph = true;
@@ -149,9 +176,9 @@ struct gsttaco_ctx {
     uint32_t* h_err = nullptr;
     uint32_t gave_up = 0;        // sticky: give-ups seen by a later enqueue and not yet reported by gsttaco_synchronize (bit i = word i of h_err)
     bool announce_warn = false;  // the next compute call leaves `warn` in gsttaco_last_error
-    bool persist_decode = true;  // the whole decode loop as ONE persistent launch where it applies (GSTTACO_PERSIST_DECODE=0: launches)
-    bool persist_now = false;    // ... for the call being enqueued (one live context, as fuse12_now)
-    int persist_rows = 128;      // ... for batches up to this many rows (GSTTACO_PERSIST_ROWS; 32: the one-group kernel only)
+    // the launch forms still allowed: GSTTACO_FUSED_LSTM / GSTTACO_BILSTM_PERSIST / GSTTACO_PERSIST_DECODE = 0 or a give-up clear one for good
+    LaunchForms allow{true, true, true};
+    int persist_rows = 128;      // persistent decode: for batches up to this many rows (GSTTACO_PERSIST_ROWS; 32: the one-group kernel only)
     int persist_slots = 0;       // workgroups of gt_persist_decode_kernel the device holds at once
     uint64_t n_persist_decodes = 0;      // persistent decode launches enqueued (eagerly or into a captured graph)
     float* w_xa2 = nullptr; uint2* w_z0g = nullptr; float* w_hpart = nullptr; uint32_t* w_pctl = nullptr;    // its workspace
@@ -166,9 +193,6 @@ struct gsttaco_ctx {
                                  // (conv_wino_split.hip; GSTTACO_WINO_SPLIT=0: the fp32-MFMA Winograd kernel)
     int enc_wino = 2;            // the text encoder's five-tap layers behind the token gather on the split-bf16 Winograd kernel (GSTTACO_ENC_WINO)
     bool pad_dec = true;         // a decoder smaller than the reference's is zero-padded up to it (pad_decoder; GSTTACO_PAD_DECODER=0: its own sizes)
-    bool bilstm_persist = true;  // one persistent launch per BiLSTM instead of one per time step (GSTTACO_BILSTM_PERSIST=0: per step)
-    bool fuse12 = true;          // both decode LSTM cells in one launch with an in-kernel hand-off (GSTTACO_FUSED_LSTM=0: two launches)
-    bool fuse12_now = false;     // ... for the call being enqueued: fuse12 and this is the process's only live context
     uint32_t* w_arrive = nullptr;    // [steps_max][8 x 32] arrival counters of the fused launch, zeroed at the start of every decode
     int debug_drop_member = -1;  // fault injection (gsttaco_debug_raise_handoff_error): a member of the next persistent launches never shows up
     mutable std::string warn;    // last warning (a recovered condition): readable through gsttaco_last_error until the next error
@@ -419,8 +443,8 @@ const HostTensor& T(const gsttaco_ctx* c, const std::string& name) {
 // gate-major (i | f | c~ | o); LSTM 1's input is [prenet | context], the projection's [h2 | context].
 void pad_decoder(gsttaco_ctx* c) {
     const int P0 = 256, P1 = 256, A = 128, H1 = 1024, H2 = 1024;
-    const int p0 = c->P0, p1 = c->P1, a = c->att, h1 = c->H1, h2 = c->H2;
-    c->P0t = p0; c->P1t = p1; c->attt = a; c->H1t = h1; c->H2t = h2;
+    if (c->dec_padded) return;      // (a second finalize after a failed one: the padded tensors and sizes are in place)
+    const int p0 = c->cfg.prenet[0], p1 = c->cfg.prenet[1], a = c->cfg.att_size, h1 = c->cfg.dec_rnn[0], h2 = c->cfg.dec_rnn[1];     // the caller's
     if (!c->pad_dec || p0 > P0 || p1 > P1 || a > A || h1 > H1 || h2 > H2 || (p0 == P0 && p1 == P1 && a == A && h1 == H1 && h2 == H2)) return;
     // dst[rmap(r)][cmap(cc)] = src[r][cc]
     auto embed = [&](const std::string& name, int rows_out, int cols_out, auto rmap, auto cmap) {
@@ -821,16 +845,16 @@ int alloc_lean_bilstm(gsttaco_ctx* c, gsttaco_ctx::LeanBiLstm* L, size_t B, size
     return 0;
 }
 
-bool lean_bilstm_usable(const gsttaco_ctx* c, const gsttaco_ctx::LeanBiLstm& L, int B) {
+bool lean_bilstm_usable(const gsttaco_ctx* c, const LaunchForms& forms, const gsttaco_ctx::LeanBiLstm& L, int B) {
     if (!L.x.w) return false;
     if (!c->cfg.mixed_precision) return true;
-    return L.ph && c->bilstm_persist && gt_bilstm_persist_supported(L.H, std::min(B, 64), c->n_cu);
+    return L.ph && forms.bilstm_persist && gt_bilstm_persist_supported(L.H, std::min(B, 64), c->n_cu);
 }
 
 // x: [B*T, C] rows; cstate: [2, B, H] (zeroed by the caller); out: [B, T, 2H]
 // join: an event the stream waits for BEHIND the hoisted GEMM, in front of the recurrence (the forked GST branch: the GEMM fills the chip
 // for ~80 us and the branch's last small launches finish beside it instead of in front of it)
-int enqueue_lean_bilstm(gsttaco_ctx* c, hipStream_t s, const gsttaco_ctx::LeanBiLstm& L, const float* x, int B, int Tn, float* cstate,
+int enqueue_lean_bilstm(gsttaco_ctx* c, hipStream_t s, const LaunchForms& forms, const gsttaco_ctx::LeanBiLstm& L, const float* x, int B, int Tn, float* cstate,
                         float* out, const int32_t* row_len, hipEvent_t join = nullptr) {
     const int H = L.H, EO = 2 * H, MT = (B + 15) / 16;
     // (round 6: on the bf16 matrix pipe as split-bf16 x6 where the grid allows)
@@ -841,7 +865,7 @@ int enqueue_lean_bilstm(gsttaco_ctx* c, hipStream_t s, const gsttaco_ctx::LeanBi
     if (join) HIPCHECK(c, hipStreamWaitEvent(s, join, 0));
     // One persistent launch for the whole sequence, one (direction, 16 utterances) group per XCD (skinny_gemm.hip
     // gt_bilstm_persist_kernel; same arithmetic, bitwise the same outputs); GSTTACO_BILSTM_PERSIST=0 keeps the launch per step.
-    if (L.ph && c->bilstm_persist && gt_bilstm_persist_supported(H, std::min(B, 64), c->n_cu)) {
+    if (L.ph && forms.bilstm_persist && gt_bilstm_persist_supported(H, std::min(B, 64), c->n_cu)) {
         // one launch per slab of 64 utterances (8 groups = 2 directions x 4 M-tiles fill the 8 XCDs); the recurrences of
         // different utterances are independent, so the slabs simply follow each other on the stream
         for (int r0 = 0; r0 < B; r0 += 64) {
@@ -904,7 +928,7 @@ int enqueue_bilstm_steps(gsttaco_ctx* c, hipStream_t s, const PackedLinear* pk, 
 int enqueue_gst(gsttaco_ctx* c, hipStream_t s, int B, int Tref1);
 
 // gst_Tref1 > 0: the GST branch is forked onto the side stream here and joined in front of the BiLSTM (gsttaco_ctx::gst_fork)
-int enqueue_encoder(gsttaco_ctx* c, hipStream_t s, int B, int Tv, bool masked, int gst_Tref1 = 0) {
+int enqueue_encoder(gsttaco_ctx* c, hipStream_t s, const LaunchForms& forms, int B, int Tv, bool masked, int gst_Tref1 = 0) {
     const int32_t* tlen = masked ? c->w_tok_len : nullptr;      // masked-mode extension
     const gsttaco_config& g = c->cfg;
     const float* x = c->d_emb;
@@ -956,13 +980,13 @@ int enqueue_encoder(gsttaco_ctx* c, hipStream_t s, int B, int Tv, bool masked, i
     const int H = g.enc_rnn;
     // (joining BEHIND the BiLSTM instead measured 10.83-10.86 against 10.85-10.89 ms per Inference_Step: not worth GST kernels lingering
     // beside a launch that needs its members co-resident)
-    const bool lean_enc = lean_bilstm_usable(c, c->enc_lean, B);
+    const bool lean_enc = lean_bilstm_usable(c, forms, c->enc_lean, B);
     const bool join_here = gst_Tref1 > 0;
     // (the lean BiLSTM joins behind its hoisted GEMM, see enqueue_lean_bilstm; the guard covers its error returns in front of that)
     if (join_here && !lean_enc) { join_guard.armed = false; HIPCHECK(c, hipStreamWaitEvent(s, c->ev_join, 0)); }
     HIPCHECK(c, gt_launch_zero(c->w_cenc, (size_t)2 * B * H, s));
     if (lean_enc) {
-        const int rl = enqueue_lean_bilstm(c, s, c->enc_lean, x, B, Tv, c->w_cenc, c->w_enc, tlen, join_here ? c->ev_join : nullptr);
+        const int rl = enqueue_lean_bilstm(c, s, forms, c->enc_lean, x, B, Tv, c->w_cenc, c->w_enc, tlen, join_here ? c->ev_join : nullptr);
         if (!rl) join_guard.armed = false;          // (joined inside)
         return rl;
     }
@@ -1068,8 +1092,8 @@ FrontSched plan_front_jobs(int jobs, int chunks, int n_workers, int B, bool bf16
 }
 
 // Every launch-form question of one decode, answered in one place: enqueue_decode launches what the plan says, and
-// gsttaco_decode_plan, gsttaco_lstm_launch_bytes and masks_lazy report it.  `persist` and `fuse12` also depend on the per-call
-// persist_now / fuse12_now (run_cached), so they mean something only while a decode is being enqueued; no other field does.
+// gsttaco_decode_plan, gsttaco_lstm_launch_bytes and masks_lazy report it.  `forms` is the call's (run_cached); only `persist`,
+// `persist_bf16` and `fuse12` depend on it, and the three reporters read none of those: they pass what the context allows.
 struct DecodePlan {
     bool persist = false;         // the whole loop as ONE persistent launch (persist_decode.hip) ...
     bool persist_bf16 = false;    // ... its bf16 kernel (mixed precision)
@@ -1089,7 +1113,7 @@ struct DecodePlan {
 };
 
 // `forced`: a teacher-forced decode (DecodeCall::forced): always launches per step -- the persistent kernels feed their own frame back.
-DecodePlan plan_decode(const gsttaco_ctx* c, int B, int Tv, bool injected_mask, bool forced = false) {
+DecodePlan plan_decode(const gsttaco_ctx* c, const LaunchForms& forms, int B, int Tv, bool injected_mask, bool forced = false) {
     const gsttaco_config& g = c->cfg;
     const bool lsa = g.att_type == GSTTACO_ATT_LSA;
     const PackedLinear *X = c->lstm_x, *R = c->lstm_h;
@@ -1118,7 +1142,7 @@ DecodePlan plan_decode(const gsttaco_ctx* c, int B, int Tv, bool injected_mask, 
     p.mirror = B > 32 && c->w_xa_h != nullptr && p.lean_x[0] && p.lean_x[1] && R[0].nkb == 64 && R[1].nkb == 64;
     // both LSTM cells in one launch (skinny_gemm.hip gt_lstm12_kernel: fp32, batch <= 32; above: the multi-chunk form, fp32 or bf16),
     // while this is the process's one live context
-    if (c->fuse12_now && c->lean && X[0].bf16 == X[1].bf16) {
+    if (forms.fuse12 && c->lean && X[0].bf16 == X[1].bf16) {
         if (gt_lstm12_mc_supported(X[0].nkb, X[1].nkb, c->H1, c->H2, B, c->fuse12_slots[X[0].bf16 ? 2 : 1])) p.fuse12 = 2;
         else if (!X[0].bf16 && gt_lstm12_supported(X[0].nkb, X[1].nkb, c->H1, c->H2, B, c->fuse12_slots[0])) p.fuse12 = 1;
     }
@@ -1128,7 +1152,7 @@ DecodePlan plan_decode(const gsttaco_ctx* c, int B, int Tv, bool injected_mask, 
     // group of up to 64 rows.
     const int n_bf16 = X[0].bf16 + X[1].bf16 + R[0].bf16 + R[1].bf16 + c->proj_z.bf16;
     const bool bf16 = n_bf16 == 5 && c->w_xa_h && c->w_xa2_h && c->w_h1_h[0] && c->w_h2_h[0];
-    p.persist = c->persist_now && c->lean && p.lean_front && p.z0 && (n_bf16 == 0 || bf16) && c->proj.nkb >= 32 &&
+    p.persist = forms.persist_decode && c->lean && p.lean_front && p.z0 && (n_bf16 == 0 || bf16) && c->proj.nkb >= 32 &&
                 // (the LSA extension: the one-group fp32 kernel's LSA chain, up to 128 tokens -- else the launch path)
                 (!lsa || (n_bf16 == 0 && c->loc_pack && gt_persist_decode_lsa_fits(B, Tv, g.loc_filters, g.loc_kernel))) &&
                 X[0].nkb == 24 && X[1].nkb == 64 && R[0].nkb == 64 && R[1].nkb == 64 && B <= c->persist_rows && (B <= 32 || c->w_stash) &&
@@ -1472,10 +1496,10 @@ int enqueue_forced_z0(gsttaco_ctx* c, hipStream_t s, int B, int steps) {
     return 0;
 }
 
-int enqueue_decode(gsttaco_ctx* c, hipStream_t s, int B, int Tv, int steps, bool has_mask, bool has_noise, bool masked, bool forced = false) {
+int enqueue_decode(gsttaco_ctx* c, hipStream_t s, const LaunchForms& forms, int B, int Tv, int steps, bool has_mask, bool has_noise, bool masked, bool forced) {
     const gsttaco_config& g = c->cfg;
     const int MT = (B + 15) / 16;
-    DecodeCall d{c, s, plan_decode(c, B, Tv, has_mask, forced), B, Tv, steps, MT, has_mask, has_noise, masked ? c->w_tok_len : nullptr,
+    DecodeCall d{c, s, plan_decode(c, forms, B, Tv, has_mask, forced), B, Tv, steps, MT, has_mask, has_noise, masked ? c->w_tok_len : nullptr,
                  g.prenet_rate > 0.f ? 1.0f / (1.0f - g.prenet_rate) : 1.f, (int64_t)steps * c->r * g.mel_dim, ProfBrackets{c, s}};
     d.forced = forced;
     const DecodePlan& P = d.P;
@@ -1643,7 +1667,7 @@ int ensure_audio(gsttaco_ctx* c) {
 }
 
 // mel [B,Tf,mel] -> spectrogram [B,Tf,spec]  (reference Taco2.py:258-260, 366-380)
-int enqueue_vocoder(gsttaco_ctx* c, hipStream_t s, int B, int Tf, const float* mel_in, float* spec) {
+int enqueue_vocoder(gsttaco_ctx* c, hipStream_t s, const LaunchForms& forms, int B, int Tf, const float* mel_in, float* spec) {
     const gsttaco_config& g = c->cfg;
     const int NB = g.bank_count * g.bank_filters;
     // conv bank: kernel sizes 1..N on the INPUT, each + BN + ReLU, concatenated on the channel axis (Taco2.py:383-407)
@@ -1704,7 +1728,7 @@ int enqueue_vocoder(gsttaco_ctx* c, hipStream_t s, int B, int Tf, const float* m
     // Bidirectional LSTM over the Tf frames (:353-361)
     const int H = g.voc_rnn;
     HIPCHECK(c, gt_launch_zero(c->w_vc, (size_t)2 * B * H, s));
-    if (lean_bilstm_usable(c, c->voc_lean, B)) rc = enqueue_lean_bilstm(c, s, c->voc_lean, x, B, Tf, c->w_vc, c->w_vrnn, nullptr);
+    if (lean_bilstm_usable(c, forms, c->voc_lean, B)) rc = enqueue_lean_bilstm(c, s, forms, c->voc_lean, x, B, Tf, c->w_vc, c->w_vrnn, nullptr);
     else rc = enqueue_bilstm_steps(c, s, c->voc_bilstm, x, B, Tf, S, H, c->w_vc, c->w_vrnn, nullptr);
     if (rc) return rc;
     return dense(c->voc_dense, c->w_vrnn, spec, nullptr);             // Dense to the linear-spectrogram width (Taco2.py:252-260)
@@ -1726,8 +1750,8 @@ int check_shape(gsttaco_ctx* c, int B, int Tv, int Tref1, int steps) {
 }
 
 // Teacher forcing: the workspace of the staged frames and of every step's prenet-0 pre-activations, sized like the rest of the workspace
-// by the capacity given at create and allocated by the FIRST forced call (outside any capture), so a context that never forces pays
-// nothing; freed with everything else at destroy.
+// by the capacity given at create and allocated by the FIRST forced call (outside any capture: check_forced), so a context that never
+// forces pays nothing; freed with everything else at destroy.
 int ensure_forced(gsttaco_ctx* c) {
     if (c->w_teach && c->w_zf) return 0;
     const size_t rows = (size_t)c->cfg.max_batch * c->steps_max;
@@ -1737,20 +1761,35 @@ int ensure_forced(gsttaco_ctx* c) {
     return 0;
 }
 
-// The arguments every forced entry point shares: teacher [B, Tq, mel] -> *S = ceil((Tq - 1) / r) decoder steps
+// The arguments every forced entry point shares: teacher [B, Tq, mel] -> *S = ceil((Tq - 1) / r) decoder steps; and their workspace
 int check_forced(gsttaco_ctx* c, const float* teacher, int Tq, int B, int Tv, int Tref1, int* S) {
     if (!teacher) return fail(c, GSTTACO_E_INVALID, "null teacher");
     if (Tq < 2) return fail(c, GSTTACO_E_INVALID, "teacher needs the go frame and at least one more (Tq >= 2)");
     const int64_t steps = ((int64_t)Tq - 1 + c->r - 1) / c->r;
     if (steps > c->steps_max) return fail(c, GSTTACO_E_CAPACITY, "teacher frames exceed Max_Step");
     *S = (int)steps;
-    return check_shape(c, B, Tv, Tref1, *S);
+    const int rc = check_shape(c, B, Tv, Tref1, *S);
+    return rc ? rc : ensure_forced(c);
 }
 
-// Runs `body` either eagerly on `stream` or through a cached hipGraph captured on the internal stream (LRU-bounded,
-// see gsttaco_ctx::graphs).  `persist_segment`: the body may enqueue persistent BiLSTM launches (see g_persist_event).
-template <typename F>
-int run_cached_inner(gsttaco_ctx* c, hipStream_t stream, const GraphKey& key_in, F body);
+// One row per launch form that can give up: its flag, its word of h_err (bit `word` of gave_up) and the warning its fallback leaves.
+// In the order note_give_up visits them, which decides whose warning is left when several gave up at once.
+struct GiveUpForm { bool LaunchForms::*flag; int word; const char* warning; };
+const GiveUpForm kGiveUpForms[3] = {
+    {&LaunchForms::persist_decode, 2,
+     "warning: a hand-off wait of the persistent decode launch gave up in an earlier call (its workgroups were not co-resident: "
+     "is another process or a CU mask sharing this GPU?); that call's outputs were invalid.  This context now runs the decode "
+     "loop as launches per step (bitwise the same results, ~25 % slower)"},
+    {&LaunchForms::fuse12, 0,
+     "warning: the in-kernel hand-off of the fused decode-LSTM launch gave up in an earlier call (its workgroups were not "
+     "co-resident: is another process or a CU mask sharing this GPU?); that call's outputs were invalid.  This context now "
+     "runs the two LSTM cells as two launches (same results, ~4 % slower)"},
+    {&LaunchForms::bilstm_persist, 1,
+     "warning: a hand-off wait of the persistent BiLSTM launch gave up in an earlier call (its members were not co-resident: is "
+     "another process or a CU mask sharing this GPU?); that call's outputs were invalid.  This context now runs its BiLSTMs with "
+     "one launch per time step (bitwise the same results in fp32, within the mixed-precision tolerance under "
+     "Use_Mixed_Precision -- the per-step bf16 kernel sums in a different order; ~0.5 ms slower per call)"},
+};
 
 // A bounded in-kernel wait of an EARLIER enqueue gave up (its workgroups never became co-resident: another process on the GPU,
 // a CU mask, a profiler's kernel): the outputs of the call it belongs to are garbage.  Seen here, at a later enqueue:
@@ -1765,89 +1804,25 @@ void note_give_up(gsttaco_ctx* c) {
     if (!c->h_err) return;
     // (one word per launch form: a kernel polls its own word to leave early once a sibling has given up, so a give-up of the persistent
     // decode launch must not make the fused LSTM launches enqueued behind it abort)
-    if (c->h_err[2]) {
-        c->gave_up |= 4u;
-        if (c->persist_decode) {
-            c->persist_decode = false;
-            c->debug_drop_member = -1;
-            c->warn = "warning: a hand-off wait of the persistent decode launch gave up in an earlier call (its workgroups were not co-resident: "
-                      "is another process or a CU mask sharing this GPU?); that call's outputs were invalid.  This context now runs the decode "
-                      "loop as launches per step (bitwise the same results, ~25 % slower)";
-            c->announce_warn = true;
-        }
-    }
-    if (c->h_err[0]) {
-        c->gave_up |= 1u;
-        if (c->fuse12) {
-            c->fuse12 = false;
-            c->debug_drop_member = -1;
-            c->warn = "warning: the in-kernel hand-off of the fused decode-LSTM launch gave up in an earlier call (its workgroups were not "
-                      "co-resident: is another process or a CU mask sharing this GPU?); that call's outputs were invalid.  This context now "
-                      "runs the two LSTM cells as two launches (same results, ~4 % slower)";
-            c->announce_warn = true;
-        }
-    }
-    if (c->h_err[1]) {
-        c->gave_up |= 2u;
-        if (c->bilstm_persist) {
-            c->bilstm_persist = false;
-            c->debug_drop_member = -1;
-            c->warn = "warning: a hand-off wait of the persistent BiLSTM launch gave up in an earlier call (its members were not co-resident: is "
-                      "another process or a CU mask sharing this GPU?); that call's outputs were invalid.  This context now runs its BiLSTMs with "
-                      "one launch per time step (bitwise the same results in fp32, within the mixed-precision tolerance under "
-                      "Use_Mixed_Precision -- the per-step bf16 kernel sums in a different order; ~0.5 ms slower per call)";
-            c->announce_warn = true;
-        }
+    for (const GiveUpForm& f : kGiveUpForms) {
+        if (!c->h_err[f.word]) continue;
+        c->gave_up |= 1u << f.word;
+        if (!(c->allow.*f.flag)) continue;
+        c->allow.*f.flag = false;
+        c->debug_drop_member = -1;
+        c->warn = f.warning;
+        c->announce_warn = true;
     }
 }
 
-void recover_from_give_up(gsttaco_ctx* c) {
-    note_give_up(c);
-    if (c->announce_warn) { c->err = c->warn; c->announce_warn = false; }
+std::map<GraphKey, gsttaco_ctx::GraphEntry>::iterator lru_graph(gsttaco_ctx* c) {
+    return std::min_element(c->graphs.begin(), c->graphs.end(), [](const auto& a, const auto& b) { return a.second.last_use < b.second.last_use; });
 }
 
+// run_cached with the key complete: the graph cache
 template <typename F>
-int run_cached(gsttaco_ctx* c, hipStream_t stream, const GraphKey& key_in, F body, bool persist_segment = false) {
-    recover_from_give_up(c);
-    // The process-wide mutex guards the two event tables and -- for segments with a persistent BiLSTM launch only -- the order in which
-    // such segments are chained on the GPU.  Every other segment is captured / instantiated / launched OUTSIDE it: several contexts on
-    // several threads do not serialise their host-side enqueue on one lock.
-    {   // another context's fused launches may still be in flight: this segment starts behind them (see g_fused_event)
-        std::lock_guard<std::mutex> lock(g_persist_mu);
-        auto it = g_fused_event.find(c->cfg.device);
-        if (it != g_fused_event.end() && it->second.ev && it->second.owner != c) HIPCHECK(c, hipStreamWaitEvent(stream, it->second.ev, 0));
-    }
-    int rc = 0;
-    if (!(persist_segment && c->bilstm_persist)) {
-        rc = run_cached_inner(c, stream, key_in, body);
-    } else {
-        std::lock_guard<std::mutex> lock(g_persist_mu);        // (wait -> enqueue -> record must not interleave with another context's)
-        hipEvent_t& ev = g_persist_event[c->cfg.device];
-        if (!ev) HIPCHECK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        else HIPCHECK(c, hipStreamWaitEvent(stream, ev, 0));
-        rc = run_cached_inner(c, stream, key_in, body);
-        HIPCHECK(c, hipEventRecord(ev, stream));
-    }
-    if (!rc && (c->fuse12_now || c->persist_now) && (key_in.kind == 0 || key_in.kind == 3 || key_in.kind == 10 || key_in.kind == 11 || key_in.kind == 12)) {      // the segment held fused / persistent decode launches
-        std::lock_guard<std::mutex> lock(g_persist_mu);
-        FusedInFlight& f = g_fused_event[c->cfg.device];
-        if (!f.ev) HIPCHECK(c, hipEventCreateWithFlags(&f.ev, hipEventDisableTiming));
-        HIPCHECK(c, hipEventRecord(f.ev, stream));
-        f.owner = c;
-    }
-    return rc;
-}
-
-template <typename F>
-int run_cached_inner(gsttaco_ctx* c, hipStream_t stream, const GraphKey& key_in, F body) {
-    GraphKey key = key_in;
-    key.persist = c->bilstm_persist ? 1 : 0;
-    // several decode loops in flight could each hold part of the chip and wait for the rest of their fused launch: one live context only
-    c->fuse12_now = c->fuse12 && g_live_contexts.load() <= 1;
-    key.fuse12 = c->fuse12_now ? 1 : 0;
-    c->persist_now = c->persist_decode && g_live_contexts.load() <= 1;
-    key.persist_dec = c->persist_now ? 1 : 0;
-    if (!c->use_graph || c->graph_cache_max < 1) return body(stream);
+int run_cached_inner(gsttaco_ctx* c, hipStream_t stream, const GraphKey& key, F body) {
+    if (!c->use_graph || c->graph_cache_max < 1) return body(stream, key.forms);
     const uint64_t now = ++c->graph_clock;
     auto it = c->graphs.find(key);
     if (it == c->graphs.end()) {
@@ -1861,14 +1836,14 @@ int run_cached_inner(gsttaco_ctx* c, hipStream_t stream, const GraphKey& key_in,
                         if (j->second.second < old->second.second) old = j;
                     c->graph_seen.erase(old);
                 }
-                return body(stream);
+                return body(stream, key.forms);
             }
             c->graph_seen.erase(key);
         }
         hipGraph_t graph = nullptr;
         HIPCHECK(c, hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeRelaxed));
         c->capturing = true;
-        int rc = body(c->cap_stream);
+        int rc = body(c->cap_stream, key.forms);
         c->capturing = false;
         hipError_t e = hipStreamEndCapture(c->cap_stream, &graph);
         if (rc) {
@@ -1881,9 +1856,7 @@ int run_cached_inner(gsttaco_ctx* c, hipStream_t stream, const GraphKey& key_in,
         (void)hipGraphDestroy(graph);
         if (e != hipSuccess) return fail(c, GSTTACO_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
         while ((int)c->graphs.size() >= c->graph_cache_max) {       // evict the least recently used executable
-            auto old = c->graphs.begin();
-            for (auto j = c->graphs.begin(); j != c->graphs.end(); ++j)
-                if (j->second.last_use < old->second.last_use) old = j;
+            auto old = lru_graph(c);
             // an evicted executable may still be running on the stream it was last launched on (the stream is a per-call argument)
             HIPCHECK(c, hipStreamSynchronize(old->second.last_stream));
             (void)hipGraphExecDestroy(old->second.exec);
@@ -1894,6 +1867,92 @@ int run_cached_inner(gsttaco_ctx* c, hipStream_t stream, const GraphKey& key_in,
     it->second.last_use = now;
     it->second.last_stream = stream;
     HIPCHECK(c, hipGraphLaunch(it->second.exec, stream));
+    return 0;
+}
+
+// Runs `body(stream, forms)` either eagerly on `stream` or through a cached hipGraph captured on the internal stream (LRU-bounded,
+// see gsttaco_ctx::graphs).  `forms`: what this call may take, decided once -- what the context allows, the fused decode-LSTM and the
+// persistent decode launch only while this is the process's one live context (several decode loops in flight could each hold part of
+// the chip and wait for the rest of their launch).  It is part of the key, and what is recorded as in flight is what the body was given.
+template <typename F>
+int run_cached(gsttaco_ctx* c, hipStream_t stream, GraphKey key, F body) {
+    note_give_up(c);
+    if (c->announce_warn) { c->err = c->warn; c->announce_warn = false; }
+    const bool alone = g_live_contexts.load() <= 1;
+    const LaunchForms forms{c->allow.fuse12 && alone, c->allow.bilstm_persist, c->allow.persist_decode && alone};
+    key.forms = forms;
+    const SegTraits seg = seg_traits(key.kind);
+    // The process-wide mutex guards the two event tables and -- for segments with a persistent BiLSTM launch only -- the order in which
+    // such segments are chained on the GPU.  Every other segment is captured / instantiated / launched OUTSIDE it: several contexts on
+    // several threads do not serialise their host-side enqueue on one lock.
+    {   // another context's fused launches may still be in flight: this segment starts behind them (see g_fused_event)
+        std::lock_guard<std::mutex> lock(g_persist_mu);
+        auto it = g_fused_event.find(c->cfg.device);
+        if (it != g_fused_event.end() && it->second.ev && it->second.owner != c) HIPCHECK(c, hipStreamWaitEvent(stream, it->second.ev, 0));
+    }
+    int rc = 0;
+    if (!(seg.bilstm && forms.bilstm_persist)) {
+        rc = run_cached_inner(c, stream, key, body);
+    } else {
+        std::lock_guard<std::mutex> lock(g_persist_mu);        // (wait -> enqueue -> record must not interleave with another context's)
+        hipEvent_t& ev = g_persist_event[c->cfg.device];
+        if (!ev) HIPCHECK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        else HIPCHECK(c, hipStreamWaitEvent(stream, ev, 0));
+        rc = run_cached_inner(c, stream, key, body);
+        HIPCHECK(c, hipEventRecord(ev, stream));
+    }
+    if (!rc && seg.decode && (forms.fuse12 || forms.persist_decode)) {      // the segment held fused / persistent decode launches
+        std::lock_guard<std::mutex> lock(g_persist_mu);
+        FusedInFlight& f = g_fused_event[c->cfg.device];
+        if (!f.ev) HIPCHECK(c, hipEventCreateWithFlags(&f.ev, hipEventDisableTiming));
+        HIPCHECK(c, hipEventRecord(f.ev, stream));
+        f.owner = c;
+    }
+    return rc;
+}
+
+void add_seg(GtCopySegs& cs, const void* src, void* dst, size_t words) {
+    cs.src[cs.n] = src; cs.dst[cs.n] = dst; cs.words[cs.n] = words; ++cs.n;
+}
+
+// What every decode stages in front of its graph segment: injected keep masks (in the caller's prenet sizes: re-laid out for a padded
+// decoder) and noise -- parity runs --, the seed unless the caller's own input launch carries it (`seed` NULL), the teacher frames a
+// forced decode consumes (`teacher` NULL: a free run), and masks_lazy for gsttaco_debug_randomness.
+int stage_decode_inputs(gsttaco_ctx* c, hipStream_t s, const float* mask, const float* noise, const uint64_t* seed, const float* teacher,
+                        int Tq, int B, int Tv, int steps) {
+    if (mask && c->dec_padded) HIPCHECK(c, gt_launch_relayout_masks(mask, c->w_masks, steps, B, c->cfg.prenet[0], c->cfg.prenet[1], c->P0, c->P1, 1, s));
+    else if (mask) HIPCHECK(c, hipMemcpyAsync(c->w_masks, mask, (size_t)steps * B * (c->P0 + c->P1) * 4, hipMemcpyDeviceToDevice, s));
+    if (noise) HIPCHECK(c, hipMemcpyAsync(c->w_noise, noise, (size_t)steps * B * Tv * 4, hipMemcpyDeviceToDevice, s));
+    if (seed) HIPCHECK(c, gt_launch_set_seed(c->w_seed, *seed, s));
+    if (teacher) HIPCHECK(c, gt_launch_stage_teacher(teacher, c->w_teach, B, Tq, steps, c->r, c->cfg.mel_dim, s));
+    // (per CALL: a replayed graph does not pass through enqueue_decode; masks_unused does not depend on the launch forms)
+    c->masks_lazy = plan_decode(c, c->allow, B, Tv, mask != nullptr, teacher != nullptr).masks_unused;
+    return 0;
+}
+
+// gsttaco_decode (`teacher` NULL) and gsttaco_decode_forced (the reference's OTHER loop branch, Taco2.py:183-187, training=True: step t
+// consumes teacher[:, t * r]; launches per step, plan_decode `forced`).  The callers have checked their own arguments.
+int decode_call(gsttaco_ctx* c, const float* enc, const float* gst, const int32_t* token_lengths, const float* mask, const float* noise,
+                uint64_t seed, int B, int Tv, int steps, const float* teacher, int Tq, float* pre_mel, float* stop, float* align, void* stream) {
+    int rc = 0;
+    const bool forced = teacher != nullptr;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHECK(c, hipMemcpyAsync(c->w_enc, enc, (size_t)B * Tv * c->enc_out * 4, hipMemcpyDeviceToDevice, s));
+    if (c->cfg.gst_use) HIPCHECK(c, hipMemcpyAsync(c->w_gst, gst, (size_t)B * c->cfg.gst_att * 4, hipMemcpyDeviceToDevice, s));
+    if ((rc = stage_decode_inputs(c, s, mask, noise, &seed, teacher, Tq, B, Tv, steps))) return rc;
+    const bool masked = token_lengths != nullptr;
+    if (masked) HIPCHECK(c, hipMemcpyAsync(c->w_tok_len, token_lengths, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+    const GraphKey key{.kind = forced ? kSegDecodeForced : kSegDecode, .B = B, .Tv = Tv, .steps = steps, .has_mask = mask != nullptr,
+                       .has_noise = noise != nullptr, .prof = c->prof_every, .masked = masked};
+    rc = run_cached(c, s, key, [&](hipStream_t st, const LaunchForms& forms) {
+        int r2 = enqueue_value_proj(c, st, B, Tv);
+        return r2 ? r2 : enqueue_decode(c, st, forms, B, Tv, steps, mask != nullptr, noise != nullptr, masked, forced);
+    });
+    if (rc) return rc;
+    const size_t mel = c->cfg.mel_dim;
+    HIPCHECK(c, hipMemcpyAsync(pre_mel, c->w_pre, (size_t)B * steps * c->r * mel * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHECK(c, hipMemcpyAsync(stop, c->w_stop, (size_t)B * steps * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHECK(c, hipMemcpyAsync(align, c->w_align, (size_t)B * steps * Tv * 4, hipMemcpyDeviceToDevice, s));
     return 0;
 }
 
@@ -1987,9 +2046,9 @@ int gsttaco_create(const gsttaco_config* cfg, gsttaco_ctx** out) {
     c->front_mode = std::min(2, std::max(0, env_int("GSTTACO_FUSED_FRONT", 2)));
     c->fused_front = c->front_mode != 0;
     c->lean = env_int("GSTTACO_LEAN", 1) != 0;
-    c->bilstm_persist = env_int("GSTTACO_BILSTM_PERSIST", 1) != 0;
-    c->fuse12 = env_int("GSTTACO_FUSED_LSTM", 1) != 0;
-    c->persist_decode = env_int("GSTTACO_PERSIST_DECODE", 1) != 0;
+    c->allow.bilstm_persist = env_int("GSTTACO_BILSTM_PERSIST", 1) != 0;
+    c->allow.fuse12 = env_int("GSTTACO_FUSED_LSTM", 1) != 0;
+    c->allow.persist_decode = env_int("GSTTACO_PERSIST_DECODE", 1) != 0;
     c->persist_rows = env_int("GSTTACO_PERSIST_ROWS", 128);
     // (round 6: the encoder's convolutions run on the Winograd split kernel's 128 workgroups = half the chip, and the GST branch -- 0.24 ms of
     // small launches -- now does hide beside them: 10.75 -> 10.5 ms per Inference_Step at the headline shape; when they filled the chip
@@ -2019,8 +2078,6 @@ void gsttaco_destroy(gsttaco_ctx* c) {
     if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-
-
     for (void* p : c->allocs) (void)hipFree(p);
     if (c->h_err) (void)hipHostFree(c->h_err);
     if (c->counted) g_live_contexts.fetch_sub(1);
@@ -2401,15 +2458,15 @@ int gsttaco_finalize_weights(gsttaco_ctx* c) {
     HIPCHECK(c, gt_conv_wino5s_init());
     HIPCHECK(c, gt_persist_decode_init());
     // the persistent BiLSTM's groups need their 32 members each on a CU of their own: exactly one workgroup per CU must fit
-    if (c->bilstm_persist && gt_bilstm_persist_blocks_per_cu() != 1) {
-        c->bilstm_persist = false;
+    if (c->allow.bilstm_persist && gt_bilstm_persist_blocks_per_cu() != 1) {
+        c->allow.bilstm_persist = false;
         c->warn = c->err = "warning: the persistent BiLSTM kernel does not get one workgroup per compute unit on this device; using one launch per time step";
     }
     // the fused decode-LSTM launches hand h1 over in-kernel: their whole grid must be resident (occupancy x CUs of THIS device;
     // a partition with fewer CUs than the grid simply keeps the two-launch form)
     for (int i = 0; i < 3; ++i) c->fuse12_slots[i] = gt_lstm12_blocks_per_cu(i) * c->n_cu;
     c->persist_slots = gt_persist_decode_blocks_per_cu() * c->n_cu;
-    if (c->fuse12 && c->H1 == c->H2 && (c->H1 + 3) / 4 > c->fuse12_slots[0])
+    if (c->allow.fuse12 && c->H1 == c->H2 && (c->H1 + 3) / 4 > c->fuse12_slots[0])
         c->warn = c->err = "warning: this device cannot hold the fused decode-LSTM launch's whole grid at once (" + std::to_string((c->H1 + 3) / 4) +
                            " workgroups, " + std::to_string(c->fuse12_slots[0]) + " resident): the two LSTM cells run as two launches";
     HIPCHECK(c, hipDeviceSynchronize());
@@ -2429,8 +2486,8 @@ int gsttaco_encode(gsttaco_ctx* c, const int32_t* tokens, const int32_t* token_l
     HIPCHECK(c, hipMemcpyAsync(c->w_tokens, tokens, (size_t)B * Tv * 4, hipMemcpyDeviceToDevice, s));
     const bool masked = token_lengths != nullptr;
     if (masked) HIPCHECK(c, hipMemcpyAsync(c->w_tok_len, token_lengths, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
-    GraphKey key{1, B, Tv, 0, 0, 0, 0, 0, masked};
-    if ((rc = run_cached(c, s, key, [&](hipStream_t st) { return enqueue_encoder(c, st, B, Tv, masked); }, true))) return rc;
+    if ((rc = run_cached(c, s, GraphKey{.kind = kSegEncoder, .B = B, .Tv = Tv, .masked = masked},
+                         [&](hipStream_t st, const LaunchForms& forms) { return enqueue_encoder(c, st, forms, B, Tv, masked); }))) return rc;
     HIPCHECK(c, hipMemcpyAsync(enc, c->w_enc, (size_t)B * Tv * c->enc_out * 4, hipMemcpyDeviceToDevice, s));
     return 0;
 }
@@ -2446,8 +2503,8 @@ int gsttaco_gst_ex(gsttaco_ctx* c, const float* mels, const int32_t* lens, int B
     hipStream_t s = (hipStream_t)stream;
     HIPCHECK(c, hipMemcpyAsync(c->w_mels_in, mels, (size_t)B * Tref1 * c->cfg.mel_dim * 4, hipMemcpyDeviceToDevice, s));
     HIPCHECK(c, hipMemcpyAsync(c->w_mel_len, lens, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
-    GraphKey key{2, B, 0, Tref1, 0, 0, 0, 0, 0};
-    if ((rc = run_cached(c, s, key, [&](hipStream_t st) { return enqueue_gst(c, st, B, Tref1); }))) return rc;
+    if ((rc = run_cached(c, s, GraphKey{.kind = kSegGst, .B = B, .Tref1 = Tref1},
+                         [&](hipStream_t st, const LaunchForms&) { return enqueue_gst(c, st, B, Tref1); }))) return rc;
     HIPCHECK(c, hipMemcpyAsync(gst, c->w_gst, (size_t)B * c->cfg.gst_att * 4, hipMemcpyDeviceToDevice, s));
     if (token_weights)
         HIPCHECK(c, hipMemcpyAsync(token_weights, c->w_gst_attn, (size_t)B * c->cfg.heads * c->cfg.n_tokens * 4, hipMemcpyDeviceToDevice, s));
@@ -2477,18 +2534,6 @@ int gsttaco_style_compose(gsttaco_ctx* c, const float* token_weights, const floa
     return 0;
 }
 
-static int stage_randomness(gsttaco_ctx* c, hipStream_t s, const float* mask, const float* noise, uint64_t seed,
-                            int B, int Tv, int steps) {
-    if (mask && c->dec_padded)      // (the caller's masks have the caller's prenet sizes: re-laid out for the padded model)
-        HIPCHECK(c, gt_launch_relayout_masks(mask, c->w_masks, steps, B, c->P0t, c->P1t, c->P0, c->P1, 1, s));
-    else if (mask)
-        HIPCHECK(c, hipMemcpyAsync(c->w_masks, mask, (size_t)steps * B * (c->P0 + c->P1) * 4, hipMemcpyDeviceToDevice, s));
-    if (noise)
-        HIPCHECK(c, hipMemcpyAsync(c->w_noise, noise, (size_t)steps * B * Tv * 4, hipMemcpyDeviceToDevice, s));
-    HIPCHECK(c, gt_launch_set_seed(c->w_seed, seed, s));
-    return 0;
-}
-
 int gsttaco_decode(gsttaco_ctx* c, const float* enc, const float* gst, const int32_t* token_lengths, const float* mask,
                    const float* noise, uint64_t seed, int B, int Tv, int steps, float* pre_mel, float* stop, float* align,
                    void* stream) {
@@ -2497,29 +2542,10 @@ int gsttaco_decode(gsttaco_ctx* c, const float* enc, const float* gst, const int
     if (!enc || !pre_mel || !stop || !align || (c->cfg.gst_use && !gst)) return fail(c, GSTTACO_E_INVALID, "null argument");
     if ((rc = check_shape(c, B, Tv, 0, steps))) return rc;
     if (steps == 0) steps = c->steps_max;
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHECK(c, hipMemcpyAsync(c->w_enc, enc, (size_t)B * Tv * c->enc_out * 4, hipMemcpyDeviceToDevice, s));
-    if (c->cfg.gst_use)
-        HIPCHECK(c, hipMemcpyAsync(c->w_gst, gst, (size_t)B * c->cfg.gst_att * 4, hipMemcpyDeviceToDevice, s));
-    if ((rc = stage_randomness(c, s, mask, noise, seed, B, Tv, steps))) return rc;
-    c->masks_lazy = plan_decode(c, B, Tv, mask != nullptr).masks_unused;      // (per CALL: a replayed graph does not pass through enqueue_decode)
-    const bool masked = token_lengths != nullptr;
-    if (masked) HIPCHECK(c, hipMemcpyAsync(c->w_tok_len, token_lengths, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
-    GraphKey key{3, B, Tv, 0, steps, mask != nullptr, noise != nullptr, c->prof_every, masked};
-    rc = run_cached(c, s, key, [&](hipStream_t st) {
-        int r2 = enqueue_value_proj(c, st, B, Tv);
-        return r2 ? r2 : enqueue_decode(c, st, B, Tv, steps, mask != nullptr, noise != nullptr, masked);
-    });
-    if (rc) return rc;
-    const size_t mel = c->cfg.mel_dim;
-    HIPCHECK(c, hipMemcpyAsync(pre_mel, c->w_pre, (size_t)B * steps * c->r * mel * 4, hipMemcpyDeviceToDevice, s));
-    HIPCHECK(c, hipMemcpyAsync(stop, c->w_stop, (size_t)B * steps * 4, hipMemcpyDeviceToDevice, s));
-    HIPCHECK(c, hipMemcpyAsync(align, c->w_align, (size_t)B * steps * Tv * 4, hipMemcpyDeviceToDevice, s));
-    return 0;
+    return decode_call(c, enc, gst, token_lengths, mask, noise, seed, B, Tv, steps, nullptr, 0, pre_mel, stop, align, stream);
 }
 
-// gsttaco_decode with the reference's OTHER loop branch (Taco2.py:183-187, training=True): step t consumes teacher[:, t * r].  Launches per
-// step (plan_decode `forced`), graph key kind 12.
+// gsttaco_decode teacher-forced: S = ceil((Tq - 1) / r) steps, graph segment kSegDecodeForced
 int gsttaco_decode_forced(gsttaco_ctx* c, const float* enc, const float* gst, const int32_t* token_lengths, const float* mask,
                           const float* noise, uint64_t seed, int B, int Tv, const float* teacher, int Tq, float* pre_mel, float* stop,
                           float* align, void* stream) {
@@ -2528,27 +2554,7 @@ int gsttaco_decode_forced(gsttaco_ctx* c, const float* enc, const float* gst, co
     if (!enc || !pre_mel || !stop || !align || (c->cfg.gst_use && !gst)) return fail(c, GSTTACO_E_INVALID, "null argument");
     int steps = 0;
     if ((rc = check_forced(c, teacher, Tq, B, Tv, 0, &steps))) return rc;
-    if ((rc = ensure_forced(c))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHECK(c, hipMemcpyAsync(c->w_enc, enc, (size_t)B * Tv * c->enc_out * 4, hipMemcpyDeviceToDevice, s));
-    if (c->cfg.gst_use)
-        HIPCHECK(c, hipMemcpyAsync(c->w_gst, gst, (size_t)B * c->cfg.gst_att * 4, hipMemcpyDeviceToDevice, s));
-    if ((rc = stage_randomness(c, s, mask, noise, seed, B, Tv, steps))) return rc;
-    HIPCHECK(c, gt_launch_stage_teacher(teacher, c->w_teach, B, Tq, steps, c->r, c->cfg.mel_dim, s));
-    c->masks_lazy = plan_decode(c, B, Tv, mask != nullptr, true).masks_unused;
-    const bool masked = token_lengths != nullptr;
-    if (masked) HIPCHECK(c, hipMemcpyAsync(c->w_tok_len, token_lengths, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
-    GraphKey key{12, B, Tv, 0, steps, mask != nullptr, noise != nullptr, c->prof_every, masked};
-    rc = run_cached(c, s, key, [&](hipStream_t st) {
-        int r2 = enqueue_value_proj(c, st, B, Tv);
-        return r2 ? r2 : enqueue_decode(c, st, B, Tv, steps, mask != nullptr, noise != nullptr, masked, true);
-    });
-    if (rc) return rc;
-    const size_t mel = c->cfg.mel_dim;
-    HIPCHECK(c, hipMemcpyAsync(pre_mel, c->w_pre, (size_t)B * steps * c->r * mel * 4, hipMemcpyDeviceToDevice, s));
-    HIPCHECK(c, hipMemcpyAsync(stop, c->w_stop, (size_t)B * steps * 4, hipMemcpyDeviceToDevice, s));
-    HIPCHECK(c, hipMemcpyAsync(align, c->w_align, (size_t)B * steps * Tv * 4, hipMemcpyDeviceToDevice, s));
-    return 0;
+    return decode_call(c, enc, gst, token_lengths, mask, noise, seed, B, Tv, steps, teacher, Tq, pre_mel, stop, align, stream);
 }
 
 // Per-token frame counts of a (forced) alignment: one launch on the caller's stream straight from / to the caller's pointers.  Needs
@@ -2575,8 +2581,8 @@ int gsttaco_postnet(gsttaco_ctx* c, const float* pre_mel, int B, int Tf, float* 
     hipStream_t s = (hipStream_t)stream;
     const size_t n = (size_t)B * Tf * c->cfg.mel_dim;
     HIPCHECK(c, hipMemcpyAsync(c->w_pre, pre_mel, n * 4, hipMemcpyDeviceToDevice, s));
-    GraphKey key{4, B, 0, 0, Tf, 0, 0, 0, 0};
-    if ((rc = run_cached(c, s, key, [&](hipStream_t st) { return enqueue_postnet(c, st, B, Tf, c->w_pre, c->w_mel); }))) return rc;
+    if ((rc = run_cached(c, s, GraphKey{.kind = kSegPostnet, .B = B, .steps = Tf},
+                         [&](hipStream_t st, const LaunchForms&) { return enqueue_postnet(c, st, B, Tf, c->w_pre, c->w_mel); }))) return rc;
     HIPCHECK(c, hipMemcpyAsync(mel, c->w_mel, n * 4, hipMemcpyDeviceToDevice, s));
     return 0;
 }
@@ -2590,8 +2596,8 @@ int gsttaco_vocoder(gsttaco_ctx* c, const float* mel, int B, int Tf, float* spec
     if (B > c->cfg.max_batch || Tf > c->steps_max * c->r) return fail(c, GSTTACO_E_CAPACITY, "batch / frames exceed capacity");
     hipStream_t s = (hipStream_t)stream;
     HIPCHECK(c, hipMemcpyAsync(c->w_mel, mel, (size_t)B * Tf * c->cfg.mel_dim * 4, hipMemcpyDeviceToDevice, s));
-    GraphKey key{5, B, 0, 0, Tf, 0, 0, 0, 0};
-    if ((rc = run_cached(c, s, key, [&](hipStream_t st) { return enqueue_vocoder(c, st, B, Tf, c->w_mel, c->w_spec); }, true))) return rc;
+    if ((rc = run_cached(c, s, GraphKey{.kind = kSegVocoder, .B = B, .steps = Tf},
+                         [&](hipStream_t st, const LaunchForms& f) { return enqueue_vocoder(c, st, f, B, Tf, c->w_mel, c->w_spec); }))) return rc;
     HIPCHECK(c, hipMemcpyAsync(spectrogram, c->w_spec, (size_t)B * Tf * c->cfg.spec_dim * 4, hipMemcpyDeviceToDevice, s));
     return 0;
 }
@@ -2677,10 +2683,8 @@ int inference_step(gsttaco_ctx* c, const int32_t* tokens, const int32_t* token_l
     const bool gst = c->cfg.gst_use != 0;
     const bool styled = style != nullptr;
     if (spectrogram && !c->cfg.voc_use) return fail(c, GSTTACO_E_INVALID, "the context was created without Vocoder_Taco1");
-    if (forced) {       // gsttaco_inference_step_forced: the step count follows from the teacher; its workspace exists before any capture
-        if ((rc = check_forced(c, teacher, Tq, B, Tv, Tref1, &steps))) return rc;
-        if ((rc = ensure_forced(c))) return rc;
-    } else if ((rc = check_shape(c, B, Tv, Tref1, steps))) return rc;
+    // (gsttaco_inference_step_forced: the step count follows from the teacher; its workspace exists before any capture)
+    if ((rc = forced ? check_forced(c, teacher, Tq, B, Tv, Tref1, &steps) : check_shape(c, B, Tv, Tref1, steps))) return rc;
     if (steps == 0) steps = c->steps_max;
     hipStream_t s = (hipStream_t)stream;
     const bool voc = spectrogram != nullptr;
@@ -2689,57 +2693,52 @@ int inference_step(gsttaco_ctx* c, const int32_t* tokens, const int32_t* token_l
     const bool masked = token_lengths != nullptr;
     {
         GtCopySegs cs{};
-        auto seg = [&](const void* src, void* dst, size_t words) { cs.src[cs.n] = src; cs.dst[cs.n] = dst; cs.words[cs.n] = words; ++cs.n; };
-        seg(tokens, c->w_tokens, (size_t)B * Tv);
-        if (styled) seg(style, c->w_gst, (size_t)B * c->cfg.gst_att);
-        else if (gst) { seg(mels_for_gst, c->w_mels_in, (size_t)B * Tref1 * meld); seg(mel_lengths, c->w_mel_len, (size_t)B); }
-        if (masked) seg(token_lengths, c->w_tok_len, (size_t)B);
+        add_seg(cs, tokens, c->w_tokens, (size_t)B * Tv);
+        if (styled) add_seg(cs, style, c->w_gst, (size_t)B * c->cfg.gst_att);
+        else if (gst) { add_seg(cs, mels_for_gst, c->w_mels_in, (size_t)B * Tref1 * meld); add_seg(cs, mel_lengths, c->w_mel_len, (size_t)B); }
+        if (masked) add_seg(cs, token_lengths, c->w_tok_len, (size_t)B);
         cs.seed = seed; cs.seed_dst = c->w_seed;
         HIPCHECK(c, gt_launch_copy_segments(cs, s));
     }
-    if (forced) HIPCHECK(c, gt_launch_stage_teacher(teacher, c->w_teach, B, Tq, steps, c->r, c->cfg.mel_dim, s));      // (the forced graph's input copy)
-    if (mask && c->dec_padded)      // (the caller's masks have the caller's prenet sizes: re-laid out for the padded model)
-        HIPCHECK(c, gt_launch_relayout_masks(mask, c->w_masks, steps, B, c->P0t, c->P1t, c->P0, c->P1, 1, s));
-    else if (mask)
-        HIPCHECK(c, hipMemcpyAsync(c->w_masks, mask, (size_t)steps * B * (c->P0 + c->P1) * 4, hipMemcpyDeviceToDevice, s));
-    if (noise) HIPCHECK(c, hipMemcpyAsync(c->w_noise, noise, (size_t)steps * B * Tv * 4, hipMemcpyDeviceToDevice, s));
-    c->masks_lazy = plan_decode(c, B, Tv, mask != nullptr, forced).masks_unused;      // (per CALL: a replayed graph does not pass through enqueue_decode)
+    // (the seed went with the input launch; the teacher frames are the forced graph's input copy)
+    if ((rc = stage_decode_inputs(c, s, mask, noise, nullptr, forced ? teacher : nullptr, Tq, B, Tv, steps))) return rc;
     // Three graph segments: the encoder and the vocoder each contain a persistent BiLSTM launch and are chained process-wide
     // (run_cached, g_persist_event); the segment between them -- GST, value projection, the decode loop, the postnet: 95 % of the
     // call -- overlaps freely with other contexts' work.  The encoder / vocoder segments share their cached graphs with
     // gsttaco_encode / gsttaco_vocoder.
     // With the style given the encoder segment is gsttaco_encode's (no fork, no side stream) and the middle one starts at the value
-    // projection (key kind 10).  w_gst was written by this call's input copy on `s`; a forked call in front of it on `s` wrote w_gst on
+    // projection (kSegStepStyled).  w_gst was written by this call's input copy on `s`; a forked call in front of it on `s` wrote w_gst on
     // the side stream and joined it into `s` inside its encoder segment, so the copy is ordered behind that write.
     const bool fork = gst && !styled && c->gst_fork;
-    GraphKey kenc{fork ? 9 : 1, B, Tv, fork ? Tref1 : 0, 0, 0, 0, 0, masked};
-    if ((rc = run_cached(c, s, kenc, [&](hipStream_t st) { return enqueue_encoder(c, st, B, Tv, masked, fork ? Tref1 : 0); }, true))) return rc;
-    // (a forced call's middle segment has a key kind of its own, 11: with the style given Tref1 is 0, with mels it is >= 2, so the two
+    const int Tfork = fork ? Tref1 : 0;
+    if ((rc = run_cached(c, s, GraphKey{.kind = fork ? kSegEncoderFork : kSegEncoder, .B = B, .Tv = Tv, .Tref1 = Tfork, .masked = masked},
+                         [&](hipStream_t st, const LaunchForms& forms) { return enqueue_encoder(c, st, forms, B, Tv, masked, Tfork); }))) return rc;
+    // (a forced call's middle segment has a kind of its own, kSegStepForced: with the style given Tref1 is 0, with mels it is >= 2, so the two
     // bodies never share a key; keys carry the step count, one graph per distinct S)
-    GraphKey key{forced ? 11 : styled ? 10 : 0, B, Tv, Tref1, steps, mask != nullptr, noise != nullptr, c->prof_every, masked};
-    rc = run_cached(c, s, key, [&](hipStream_t st) {
+    const GraphKey key{.kind = forced ? kSegStepForced : styled ? kSegStepStyled : kSegStep, .B = B, .Tv = Tv, .Tref1 = Tref1, .steps = steps,
+                       .has_mask = mask != nullptr, .has_noise = noise != nullptr, .prof = c->prof_every, .masked = masked};
+    rc = run_cached(c, s, key, [&](hipStream_t st, const LaunchForms& forms) {
         int r2 = 0;
         if (gst && !styled && !fork) r2 = enqueue_gst(c, st, B, Tref1);
         if (!r2) r2 = enqueue_value_proj(c, st, B, Tv);
-        if (!r2) r2 = enqueue_decode(c, st, B, Tv, steps, mask != nullptr, noise != nullptr, masked, forced);
+        if (!r2) r2 = enqueue_decode(c, st, forms, B, Tv, steps, mask != nullptr, noise != nullptr, masked, forced);
         if (!r2) r2 = enqueue_postnet(c, st, B, steps * c->r, c->w_pre, c->w_mel);
         return r2;
     });
     if (rc) return rc;
     if (voc) {                                                                                 // Model.py:126-129
-        GraphKey kvoc{5, B, 0, 0, steps * c->r, 0, 0, 0, 0};
-        if ((rc = run_cached(c, s, kvoc, [&](hipStream_t st) { return enqueue_vocoder(c, st, B, steps * c->r, c->w_mel, c->w_spec); }, true))) return rc;
+        if ((rc = run_cached(c, s, GraphKey{.kind = kSegVocoder, .B = B, .steps = steps * c->r},
+                             [&](hipStream_t st, const LaunchForms& f) { return enqueue_vocoder(c, st, f, B, steps * c->r, c->w_mel, c->w_spec); }))) return rc;
     }
     // outputs out of the workspace the graphs write: ONE launch
     const size_t nf = (size_t)B * steps * c->r * meld;
     {
         GtCopySegs cs{};
-        auto seg = [&](const void* src, void* dst, size_t words) { cs.src[cs.n] = src; cs.dst[cs.n] = dst; cs.words[cs.n] = words; ++cs.n; };
-        seg(c->w_mel, mel, nf);
-        if (pre_mel) seg(c->w_pre, pre_mel, nf);
-        if (voc) seg(c->w_spec, spectrogram, (size_t)B * steps * c->r * c->cfg.spec_dim);
-        seg(c->w_stop, stop, (size_t)B * steps);
-        seg(c->w_align, align, (size_t)B * steps * Tv);
+        add_seg(cs, c->w_mel, mel, nf);
+        if (pre_mel) add_seg(cs, c->w_pre, pre_mel, nf);
+        if (voc) add_seg(cs, c->w_spec, spectrogram, (size_t)B * steps * c->r * c->cfg.spec_dim);
+        add_seg(cs, c->w_stop, stop, (size_t)B * steps);
+        add_seg(cs, c->w_align, align, (size_t)B * steps * Tv);
         HIPCHECK(c, gt_launch_copy_segments(cs, s));
     }
     return 0;
@@ -2817,9 +2816,7 @@ int gsttaco_set_graph_policy(gsttaco_ctx* c, int max_cached, int capture_after) 
     c->graph_cache_max = max_cached;
     c->graph_capture_after = capture_after;
     while ((int)c->graphs.size() > max_cached) {
-        auto old = c->graphs.begin();
-        for (auto j = c->graphs.begin(); j != c->graphs.end(); ++j)
-            if (j->second.last_use < old->second.last_use) old = j;
+        auto old = lru_graph(c);
         HIPCHECK(c, hipDeviceSynchronize());
         (void)hipGraphExecDestroy(old->second.exec);
         c->graphs.erase(old);
@@ -2894,9 +2891,10 @@ int gsttaco_debug_randomness(gsttaco_ctx* c, float* host_masks, float* host_nois
     }
     if (host_masks && c->dec_padded) {          // (in the caller's layout: the columns of the caller's prenet sizes)
         float* tmp = nullptr;
-        const size_t n = (size_t)steps * B * (c->P0t + c->P1t);
+        const int p0 = c->cfg.prenet[0], p1 = c->cfg.prenet[1];
+        const size_t n = (size_t)steps * B * (p0 + p1);
         HIPCHECK(c, hipMalloc((void**)&tmp, n * 4));
-        hipError_t e = gt_launch_relayout_masks(c->w_masks, tmp, steps, B, c->P0t, c->P1t, c->P0, c->P1, 0, nullptr);
+        hipError_t e = gt_launch_relayout_masks(c->w_masks, tmp, steps, B, p0, p1, c->P0, c->P1, 0, nullptr);
         if (e == hipSuccess) e = hipMemcpy(host_masks, tmp, n * 4, hipMemcpyDeviceToHost);
         (void)hipFree(tmp);
         HIPCHECK(c, e);
@@ -2910,16 +2908,17 @@ int gsttaco_debug_handoff_error(gsttaco_ctx* c, uint32_t* host_out) {
     if (!c || !host_out || !c->w_err) return GSTTACO_E_INVALID;
     HIPCHECK(c, hipDeviceSynchronize());
     // pending = raised by a kernel or noted by a later enqueue, and not yet reported by gsttaco_synchronize
-    *host_out = (c->h_err[0] | (c->gave_up & 1u)) | ((c->h_err[1] | ((c->gave_up >> 1) & 1u)) << 8) | ((c->h_err[2] | ((c->gave_up >> 2) & 1u)) << 16);
+    *host_out = 0;
+    for (const GiveUpForm& f : kGiveUpForms) *host_out |= (c->h_err[f.word] | ((c->gave_up >> f.word) & 1u)) << (8 * f.word);
     return 0;
 }
 
 int gsttaco_debug_counters(const gsttaco_ctx* c, uint64_t out[4]) {
     if (!c || !out) return GSTTACO_E_INVALID;
     out[0] = c->n_persist_enqueued;
-    out[1] = c->bilstm_persist ? 1u : 0u;
+    out[1] = c->allow.bilstm_persist ? 1u : 0u;
     out[2] = c->n_persist_decodes;
-    out[3] = c->persist_decode ? 1u : 0u;
+    out[3] = c->allow.persist_decode ? 1u : 0u;
     return 0;
 }
 
@@ -2981,7 +2980,7 @@ int gsttaco_debug_raise_handoff_error(gsttaco_ctx* c, uint32_t bits) {
 
 int gsttaco_decode_plan(const gsttaco_ctx* c, int Tv, int32_t plan[3]) {
     if (!c || !plan || Tv < 1) return GSTTACO_E_INVALID;
-    const DecodePlan p = plan_decode(c, c->cfg.max_batch, Tv, false);      // (these three answers do not depend on the batch)
+    const DecodePlan p = plan_decode(c, c->allow, c->cfg.max_batch, Tv, false);      // (these three answers do not depend on the batch)
     plan[0] = p.fused ? 1 : 0;
     plan[1] = p.z0 ? 1 : 0;
     plan[2] = (p.lean_x[0] && p.lean_x[1]) ? 1 : 0;
@@ -2993,7 +2992,7 @@ int64_t gsttaco_lstm_launch_bytes(const gsttaco_ctx* c, int which, int B) {
     // Algorithmic bytes of one launch at batch B and T_v = max_tokens: every weight once, every activation row once
     // in and once out (the re-reads of the shared activations by every workgroup are NOT algorithmic).
     const int64_t P0 = c->P0, P1 = c->P1, A = c->att, H1 = c->H1, H2 = c->H2, mel = c->cfg.mel_dim, Tv = c->cfg.max_tokens;
-    const DecodePlan p = plan_decode(c, B, (int)Tv, false);
+    const DecodePlan p = plan_decode(c, c->allow, B, (int)Tv, false);
     const bool fused = p.fused;         // (the recurrent halves ride beside the front launch)
     // weight bytes by the dtype the packs hold: bf16 under Use_Mixed_Precision for the LSTM / projection GEMMs (biases, activations,
     // partial sums and the prenet / query weights stay fp32)
