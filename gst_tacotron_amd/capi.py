@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = (
     "gsttaco_synchronize", "gsttaco_debug_conv_prepare", "gsttaco_debug_conv_run",
     "gsttaco_gst_ex", "gsttaco_style_compose", "gsttaco_inference_step_styled",
     "gsttaco_decode_forced", "gsttaco_inference_step_forced", "gsttaco_forced_durations",
+    "gsttaco_fill_randomness", "gsttaco_utterance_report",
 )
 
 # GSTTACO_CONV_V_*: the conv/GEMM dispatcher's kernel instantiations (gsttaco_debug_conv_run reports which one ran)
@@ -136,6 +137,8 @@ def load_library(path=None):
     lib.gsttaco_decode_forced.argtypes = [vp, vp, vp, vp, vp, vp, u64, i32, i32, vp, i32, vp, vp, vp, vp]
     lib.gsttaco_inference_step_forced.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u64, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp]
     lib.gsttaco_forced_durations.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]
+    lib.gsttaco_fill_randomness.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
+    lib.gsttaco_utterance_report.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.gsttaco_postnet.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.gsttaco_vocoder.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.gsttaco_inference_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
@@ -172,7 +175,8 @@ def load_library(path=None):
                "gsttaco_finalize_weights", "gsttaco_encode", "gsttaco_gst", "gsttaco_decode", "gsttaco_postnet", "gsttaco_vocoder",
                "gsttaco_inference_step", "gsttaco_set_profiling", "gsttaco_get_profile", "gsttaco_mel_frontend",
                "gsttaco_mel_basis", "gsttaco_griffin_lim", "gsttaco_gst_ex", "gsttaco_style_compose", "gsttaco_inference_step_styled",
-               "gsttaco_decode_forced", "gsttaco_inference_step_forced", "gsttaco_forced_durations"):
+               "gsttaco_decode_forced", "gsttaco_inference_step_forced", "gsttaco_forced_durations",
+               "gsttaco_fill_randomness", "gsttaco_utterance_report"):
         getattr(lib, fn).restype = ctypes.c_int
     if path is None:
         _lib = lib

@@ -2572,6 +2572,39 @@ int gsttaco_forced_durations(gsttaco_ctx* c, const float* align, const int32_t* 
     return 0;
 }
 
+// Per-utterance seeds: the randomness of a whole decode in the layouts every prenet_mask / attn_noise argument takes, row b drawn from
+// seeds[b] as a batch of one draws its row 0.  One launch on the caller's stream straight into the caller's buffers; needs no weights.
+int gsttaco_fill_randomness(gsttaco_ctx* c, const uint64_t* seeds, int B, int Tv, int steps, float* prenet_mask, float* attn_noise,
+                            void* stream) {
+    if (!c) return GSTTACO_E_INVALID;
+    if (!seeds || (!prenet_mask && !attn_noise)) return fail(c, GSTTACO_E_INVALID, "null argument");
+    if (B < 1 || steps < 1 || Tv < 1) return fail(c, GSTTACO_E_INVALID, "bad B / steps / Tv");
+    if (steps > c->steps_max || B > c->cfg.max_batch || Tv > c->cfg.max_tokens)
+        return fail(c, GSTTACO_E_CAPACITY, "batch / tokens / steps exceed the capacity given at create");
+    // (the caller's, unpadded, sizes: what an injected mask tensor has -- stage_decode_inputs re-lays it out for a padded decoder)
+    const int p0 = c->cfg.prenet[0], p1 = c->cfg.prenet[1];
+    if (prenet_mask && p0 != p1) return fail(c, GSTTACO_E_INVALID, "the injected mask layout [steps][2][B][prenet] needs equal prenet layer sizes");
+    int rc = ensure_device(c);
+    if (rc) return rc;
+    HIPCHECK(c, gt_launch_fill_randomness(seeds, prenet_mask, attn_noise, steps, B, p0, p1, Tv, c->cfg.prenet_rate, (hipStream_t)stream));
+    return 0;
+}
+
+// The synthesis report of a decode's stop logits and alignments (and, when given, its mels): one launch, one workgroup per utterance,
+// straight from / to the caller's pointers.  Needs no weights (only Step_Reduction and Mel_Dim).
+int gsttaco_utterance_report(gsttaco_ctx* c, const float* stop, const float* align, const int32_t* token_lengths, const float* mel, int B,
+                             int S, int Tv, int32_t* report, float* focus, void* stream) {
+    if (!c) return GSTTACO_E_INVALID;
+    if (!stop || !align || !report) return fail(c, GSTTACO_E_INVALID, "null argument");
+    if (B < 1 || S < 1 || Tv < 1) return fail(c, GSTTACO_E_INVALID, "bad B / S / Tv");
+    if (S > c->steps_max || B > c->cfg.max_batch || Tv > c->cfg.max_tokens)
+        return fail(c, GSTTACO_E_CAPACITY, "batch / tokens / steps exceed the capacity given at create");
+    int rc = ensure_device(c);
+    if (rc) return rc;
+    HIPCHECK(c, gt_launch_utterance_report(stop, align, token_lengths, mel, report, focus, B, S, Tv, c->r, c->cfg.mel_dim, (hipStream_t)stream));
+    return 0;
+}
+
 int gsttaco_postnet(gsttaco_ctx* c, const float* pre_mel, int B, int Tf, float* mel, void* stream) {
     int rc = check_ready(c);
     if (rc) return rc;

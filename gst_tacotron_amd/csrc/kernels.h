@@ -482,3 +482,13 @@ hipError_t gt_launch_stage_teacher(const float* teacher, float* out, int B, int 
 hipError_t gt_launch_forced_durations(const float* align, const int32_t* tok_len, const int32_t* mel_len, int32_t* dur, int B, int S,
                                       int Tv, int r, hipStream_t stream);
 
+// ---------------------------------------------------------------- report.hip
+// gt_launch_rng_fill's tensors (masks [steps][B*P0 | B*P1], noise [steps][B][Tv]) with row b drawn from seeds[b] (device [B]) as a
+// batch of one draws its row 0: gt_drop_keep(seeds[b], step, layer, 0, col, ..), gt_philox(seeds[b], position, step, 0, GT_RNG_NOISE)
+hipError_t gt_launch_fill_randomness(const uint64_t* seeds, float* masks, float* noise, int steps, int B, int P0, int P1, int Tv,
+                                     float drop_rate, hipStream_t stream);
+// report [B][8] int32 (stop_step, frames, end_gap, max_jump, back_steps, max_stall, visited, nonfinite: include/gsttaco.h) and focus [B]
+// (or NULL) of stop [B,S], align [B,S,Tv], tok_len [B] or NULL, mel [B,S*r,mel_dim] or NULL.  One workgroup per utterance.
+hipError_t gt_launch_utterance_report(const float* stop, const float* align, const int32_t* tok_len, const float* mel, int32_t* report,
+                                      float* focus, int B, int S, int Tv, int r, int mel_dim, hipStream_t stream);
+

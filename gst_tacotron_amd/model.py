@@ -26,7 +26,11 @@ PyTorch is used for device memory and streams only.  Differences, all additive:
     of reference audio;
   * teacher forcing: ``Inference_Step`` / ``decode`` take ``teacher_mels`` -- the decoder then consumes the ground-truth frames like
     the reference's training=True loop branch (Taco2.py:161,185), with every layer still in inference mode --, ``Forced_Durations``
-    counts frames per token of an alignment and ``Inference_GTA`` wraps both for ground-truth-aligned mels.
+    counts frames per token of an alignment and ``Inference_GTA`` wraps both for ground-truth-aligned mels;
+  * per-utterance seeds and a synthesis report: ``seeds=`` ([batch], one per utterance) in place of ``seed`` makes an utterance's
+    dropout and noise depend on its own seed alone -- not on its row or the batch --, ``Utterance_Report`` says on the device where each
+    utterance stopped and how its attention moved, and ``Inference_Checked`` runs a batch, reads the report and redoes only the
+    rejected rows under new seeds.
 """
 import ctypes
 import os
@@ -35,7 +39,8 @@ from datetime import datetime
 import numpy as np
 import torch
 
-from . import capi, weights as weights_mod
+from . import capi, checked, weights as weights_mod
+from .checked import REPORT_FIELDS  # noqa: F401  -- the columns of Utterance_Report's first result
 from .feeder import Feeder
 from .hparams import Dims, load_hp, load_token_dict
 
@@ -117,7 +122,7 @@ class GST_Tacotron:
     def Inference_Step(self, tokens, token_lengths=None, initial_mels=None, mels_for_gst=None,
                        mel_lengths_for_gst=None, prenet_masks=None, attn_noise=None, seed=None,
                        steps=None, return_pre_mel=False, masked=False, with_vocoder=False, style_embeddings=None,
-                       teacher_mels=None):
+                       teacher_mels=None, seeds=None):
         """reference Model.py:249-255.  Returns (mel_Logits [B,S*r,mel], stop_Logits [B,S],
         spectrogram_Logits ([B,S*r,Spectrogram_Dim] with ``with_vocoder=True``, else None), alignments [B,S,T_v]) as
         CUDA tensors on the current stream.
@@ -133,7 +138,10 @@ class GST_Tacotron:
         builds it): teacher forcing -- step t consumes ``teacher_mels[:, t * r]`` (frame 0 is the go frame, used as given) instead of
         the frame it emitted before, as the reference's training=True loop does (Taco2.py:161,185).  S = ceil((Tq - 1) / r) steps;
         ``steps`` must then be None.  The layers run in inference mode as everywhere here (GTA, not Train_Step's forward), nothing
-        is masked by mel length, the same tuple is returned.  Launch path only; one cached graph per distinct S."""
+        is masked by mel length, the same tuple is returned.  Launch path only; one cached graph per distinct S.
+        ``seeds`` (extension) [batch] integers, taken mod 2^64, in place of ``seed`` / ``prenet_masks`` / ``attn_noise``: utterance b
+        draws the dropout and noise a batch of one draws under ``seed=seeds[b]`` (``Fill_Randomness``, passed on as injected
+        randomness).  With ``masked=True`` its outputs are then those of that call alone, whatever its row and the rest of the batch."""
         self._require_ready()
         d = self.dims
         tok = self._dev(tokens, torch.int32)
@@ -169,6 +177,10 @@ class GST_Tacotron:
             Tref1 = mels.shape[1]
         teacher, Tq = self._teacher(teacher_mels, B, steps)
         S = (Tq - 1 + d.r - 1) // d.r if teacher is not None else d.steps if steps is None else int(steps)
+        if seeds is not None:
+            self._seeds_exclusive(seed, prenet_masks, attn_noise)
+            prenet_masks, attn_noise = self.Fill_Randomness(seeds, S, Tv, batch=B)
+            seed = 0
         masks = self._dev(prenet_masks, torch.float32)
         noise = self._dev(attn_noise, torch.float32)
         if masks is not None and masks.numel() != S * B * sum(d.prenet):
@@ -207,6 +219,59 @@ class GST_Tacotron:
             return mel, stop, spec, align, pre
         return mel, stop, spec, align
 
+    @staticmethod
+    def _seeds_exclusive(seed, prenet_masks, attn_noise):
+        if seed is not None or prenet_masks is not None or attn_noise is not None:
+            raise ValueError("seeds is mutually exclusive with seed, prenet_masks and attn_noise")
+
+    def Fill_Randomness(self, seeds, steps, Tv, batch=None):
+        """Extension: (prenet_masks [steps, 2, B, prenet], attn_noise [steps, B, Tv] -- None unless the attention is SMA) on the device,
+        in the layouts ``Inference_Step(prenet_masks=, attn_noise=)`` takes, with row b drawn from ``seeds[b]`` as a batch of one draws
+        its row 0 under that seed (``gsttaco_fill_randomness``): independent of B, of the row order and of ``Tv``.  ``seeds`` [B]
+        integers, taken mod 2^64.  Works before Restore (no weights involved)."""
+        d = self.dims
+        if torch.is_tensor(seeds):
+            seeds = seeds.cpu().numpy()
+        vals = [int(v) & checked.MASK64 for v in np.asarray(seeds, dtype=object).reshape(-1)]
+        if np.ndim(seeds) != 1 or not vals or (batch is not None and len(vals) != batch):
+            raise ValueError("seeds must be [batch]")
+        if not torch.cuda.is_available():
+            raise capi.GstTacoError(-2, "no HIP device: the gfx950 kernels are the only compute path (no CPU fallback)")
+        B = len(vals)
+        dev_seeds = torch.from_numpy(np.array(vals, dtype=np.uint64).view(np.int64)).to(self.device)      # (the same 64 bits)
+        masks = torch.empty((steps, 2, B, d.prenet[0]), dtype=torch.float32, device=self.device)
+        noise = torch.empty((steps, B, Tv), dtype=torch.float32, device=self.device) if d.att_type == "SMA" else None
+        with torch.cuda.device(self.device):
+            self.ctx.check(self.ctx.lib.gsttaco_fill_randomness(self.ctx.handle, _ptr(dev_seeds), B, int(Tv), int(steps), _ptr(masks),
+                                                                _ptr(noise), self._stream()))
+        return masks, noise
+
+    def Utterance_Report(self, stops, alignments, token_lengths=None, mels=None):
+        """Extension: the synthesis report of ``stops`` [B, S] and ``alignments`` [B, S, T_v] as ``Inference_Step`` returns them ->
+        (report int32 [B, 8], focus float32 [B]) on the device (``gsttaco_utterance_report``).  The columns are ``REPORT_FIELDS``:
+        stop_step (== S: the stop token never fired), frames (what ``Inv_Spectrogram(frames=)`` takes), end_gap (> 0: the attention did
+        not reach the last token), max_jump, back_steps, max_stall, visited, nonfinite; focus is the mean attention maximum over the
+        steps before the stop.  ``token_lengths`` [B] limits each utterance's columns, ``mels`` [B, S * r, Mel_Dim] adds the frames
+        before the stop to the non-finite count.  No thresholds are built in: callers compare the fields themselves."""
+        d = self.dims
+        st = self._dev(stops, torch.float32)
+        al = self._dev(alignments, torch.float32)
+        if al.dim() != 3 or st.dim() != 2 or tuple(st.shape) != tuple(al.shape[:2]):
+            raise ValueError("stops must be [batch, steps] and alignments [batch, steps, T_v]")
+        B, S, Tv = al.shape
+        tl = self._dev(token_lengths, torch.int32)
+        if tl is not None and tuple(tl.shape) != (B,):
+            raise ValueError("token_lengths must be [batch]")
+        ml = self._dev(mels, torch.float32)
+        if ml is not None and tuple(ml.shape) != (B, S * d.r, d.mel):
+            raise ValueError("mels must be [batch, steps * Step_Reduction, Mel_Dim]")
+        report = torch.empty((B, len(REPORT_FIELDS)), dtype=torch.int32, device=self.device)
+        focus = torch.empty((B,), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            self.ctx.check(self.ctx.lib.gsttaco_utterance_report(self.ctx.handle, _ptr(st), _ptr(al), _ptr(tl), _ptr(ml), B, S, Tv,
+                                                                 _ptr(report), _ptr(focus), self._stream()))
+        return report, focus
+
     def _teacher(self, teacher_mels, B, steps):
         """(device tensor [B, Tq, Mel_Dim], Tq) of a ``teacher_mels`` argument, or (None, 0)."""
         if teacher_mels is None:
@@ -238,15 +303,18 @@ class GST_Tacotron:
                                                                  self._stream()))
         return dur
 
-    def Inference_GTA(self, sentence_List, mel_or_wav_List, wav_List_for_GST=None, style_embeddings=None, **kwargs):
+    def Inference_GTA(self, sentence_List, mel_or_wav_List, wav_List_for_GST=None, style_embeddings=None, seeds=None, **kwargs):
         """Extension: ground-truth-aligned (GTA) mels.  ``mel_or_wav_List`` holds one target per sentence: mels [T, Mel_Dim] (as
         Pattern_Generator stores them) or wav paths / 1-D sample arrays, which go through ``Mel_Generate`` (top_db 15, the value
         Feeder.py:209 uses for several wavs).  The decoder is teacher-forced on them (``Inference_Step(teacher_mels=...)``; inference-mode
         layers).  The style comes from ``style_embeddings`` or ``wav_List_for_GST`` when given, else from the target audio itself,
         as the reference's training model takes it (Model.py:206).
         Returns (gta_mels: list of [T_i, Mel_Dim] post-net mels trimmed to each target's length, stops [B, S], alignments
-        [B, S, T_v], durations int32 [B, T_v] with each row summing to T_i) after ``synchronize()``."""
+        [B, S, T_v], durations int32 [B, T_v] with each row summing to T_i) after ``synchronize()``.
+        ``seeds`` [B]: per-utterance seeds (see ``Inference_Step``); the call then runs masked."""
         print("GTA inference running...")
+        if seeds is not None:
+            kwargs["seeds"], kwargs["masked"] = seeds, True
         targets = list(mel_or_wav_List)
         if len(targets) != len(sentence_List):
             raise ValueError("mel_or_wav_List must hold one target per sentence")
@@ -356,14 +424,18 @@ class GST_Tacotron:
         return mels[:, :n + 1].contiguous(), mel_len
 
     def Inference(self, sentence_List, wav_List_for_GST=None, label=None, export=False, style_embeddings=None,
-                  style_token_weights=None, **kwargs):
+                  style_token_weights=None, seeds=None, **kwargs):
         """reference Model.py:342-367.  ``wav_List_for_GST`` holds wav paths / 1-D sample arrays like the reference's,
         or precomputed mels [T, Mel_Dim].  The reference always starts its export thread; here ``export=True`` asks for
         it (it needs the CBHG vocoder and Griffin-Lim, which are off the mel-frame metric) and runs it synchronously.
         Extension: instead of reference audio, ``style_embeddings`` [B, A] / [1, A] (see ``Inference_Step``) or
         ``style_token_weights`` [Head, Style_Token.Size], [1, Head, Size] or [B, Head, Size] -- composed with no query
-        (``Style_Compose``: outside the training distribution, see there) and then used as embeddings."""
+        (``Style_Compose``: outside the training distribution, see there) and then used as embeddings.
+        ``seeds`` [B] (extension): per-utterance seeds (see ``Inference_Step``); the call then runs with ``masked=True`` -- without
+        masking the batch's padding reaches every utterance, which is what the seeds exist to rule out."""
         print("Inference running...")
+        if seeds is not None:
+            kwargs["seeds"], kwargs["masked"] = seeds, True
         styled = style_embeddings is not None or style_token_weights is not None
         if styled:
             if wav_List_for_GST is not None or (style_embeddings is not None and style_token_weights is not None):
@@ -389,6 +461,97 @@ class GST_Tacotron:
         if export:
             self.Export_Inference(sentence_List, out[0], out[1], out[2], out[3],
                                   label or datetime.now().strftime("%Y%m%d.%H%M%S"))
+        return out
+
+    def Inference_Checked(self, sentence_List, wav_List_for_GST=None, style_embeddings=None, style_token_weights=None, seeds=None,
+                          max_attempts=3, accept=None, export=False, label=None, **kwargs):
+        """Extension: ``Inference`` that reads the synthesis report of what it made and redoes only the utterances that failed.
+        Attempt k (0 = the first) of utterance i runs under seed ``(seeds[i] + k * 0x9E3779B97F4A7C15) mod 2^64`` (``seeds`` defaults to
+        consecutive values from the model's counter), masked and with per-utterance seeds, so every returned utterance is the one
+        ``Inference_Step`` gives for that sentence, style and seed ALONE.  After each attempt ``Utterance_Report`` runs and
+        ``accept(report_row, focus, i, k)`` decides; the default accepts when the stop token fired (``stop_step < S``), the attention
+        reached the last token (``end_gap == 0``) and nothing is non-finite -- no thresholds.  Rejected utterances run again as a
+        smaller batch of their own and replace their outputs, until all are accepted or ``max_attempts`` attempts are made (the last
+        attempt's outputs stay; the default ``accept`` on the returned report tells).
+        Returns (mels: list of [frames_i, Mel_Dim] trimmed to the report's ``frames``, report int32 [B, 8], focus [B], attempts int32
+        [B] -- the attempt each row comes from --, stops [B, S], alignments [B, S, T_v] untrimmed; alignments of a re-run batch are
+        zero-padded to the first attempt's T_v).  ``export=True``: the final mels go through the vocoder, ``Inv_Spectrogram`` takes
+        ``frames`` from the report on the device and the wavs are written where ``Export_Inference`` writes them; their paths are
+        appended to the returned tuple.
+        The shrinking batches are new shapes to the graph cache: each is captured at its first use by default.  Callers that run
+        this repeatedly should ``set_graph_policy(capture_after=2)`` so that only batch sizes that come back are captured."""
+        print("Checked inference running...")
+        n = len(sentence_List)
+        for k in ("seed", "prenet_masks", "attn_noise", "masked", "with_vocoder", "return_pre_mel", "teacher_mels"):
+            if k in kwargs:
+                raise ValueError("Inference_Checked sets '{}' itself".format(k))
+        styled = style_embeddings is not None or style_token_weights is not None
+        if styled:
+            if wav_List_for_GST is not None or (style_embeddings is not None and style_token_weights is not None):
+                raise ValueError("wav_List_for_GST, style_embeddings and style_token_weights are mutually exclusive")
+            if not self.hp_Dict["GST"]["Use"]:
+                raise ValueError("GST is not used")
+            if style_token_weights is not None:
+                tw = self._dev(style_token_weights, torch.float32)
+                style_embeddings = self.Style_Compose(tw.unsqueeze(0) if tw.dim() == 2 else tw)
+            style_embeddings = self._dev(style_embeddings, torch.float32)
+            if style_embeddings.dim() != 2 or style_embeddings.shape[0] not in (1, n):
+                raise ValueError("style_embeddings must be [batch, A] or [1, A]")
+        pattern = self.feeder.Get_Inference_Pattern(sentence_List, wav_List_for_GST, style_given=styled)
+        if pattern is None:
+            print("Inference fail.")
+            return None
+        pattern.pop("initial_mels", None)
+        if styled:
+            pattern["style_embeddings"] = style_embeddings
+        if seeds is None:
+            seeds = [self.seed + 1 + i for i in range(n)]
+            self.seed += n
+        seeds = [int(v) for v in (seeds.tolist() if hasattr(seeds, "tolist") else seeds)]
+        if len(seeds) != n:
+            raise ValueError("seeds must hold one seed per sentence")
+        lengths = np.asarray(pattern["token_lengths"])
+        final = {}
+
+        def take(a, rows):
+            if a.shape[0] != n:                 # (one style for the whole batch)
+                return a
+            return a[torch.as_tensor(rows, device=a.device)] if torch.is_tensor(a) else a[np.asarray(rows)]
+
+        def run(rows, row_seeds):
+            sub = {k: take(v, rows) for k, v in pattern.items()}
+            sub["tokens"] = np.ascontiguousarray(sub["tokens"][:, :int(lengths[rows].max())])
+            mel, stop, _, align = self.Inference_Step(**sub, seeds=row_seeds, masked=True, **kwargs)
+            report, focus = self.Utterance_Report(stop, align, sub["token_lengths"], mel)
+            if not final:                       # (attempt 0 is every row: its outputs, in copies of their own, are the store)
+                final.update(mel=mel.clone(), stop=stop.clone(), align=align.clone(), report=report.clone(), focus=focus.clone())
+            else:
+                at = torch.as_tensor(rows, device=self.device)
+                for key, v in (("mel", mel), ("stop", stop), ("report", report), ("focus", focus)):
+                    final[key][at] = v
+                final["align"][at] = 0.0
+                final["align"][at, :, :align.shape[2]] = align
+            self.synchronize()                  # (where a give-up of this attempt surfaces; the report is read on the host next)
+            return report.cpu().numpy(), focus.cpu().numpy()
+
+        S = self.dims.steps if kwargs.get("steps") is None else int(kwargs["steps"])
+        attempts, _ = checked.run_checked(seeds, max_attempts, run, accept or checked.default_accept(S))
+        frames = final["report"][:, 1].cpu().numpy()
+        out = ([final["mel"][i, :int(frames[i])] for i in range(n)], final["report"], final["focus"],
+               torch.as_tensor(attempts, dtype=torch.int32), final["stop"], final["align"])
+        if export:
+            from . import export as export_mod
+            spec = self.vocoder(final["mel"])
+            wav, lens = self.Inv_Spectrogram(spec, frames=final["report"][:, 1].contiguous())
+            wav, lens = wav.cpu().numpy(), lens.cpu().numpy()
+            root = self.hp_Dict["Inference_Path"]
+            os.makedirs(os.path.join(root, "Wav"), exist_ok=True)
+            label = label or datetime.now().strftime("%Y%m%d.%H%M%S")
+            paths = []
+            for i in range(n):
+                paths.append(os.path.join(root, "Wav", "{}.IDX_{}.WAV".format(label, i)))
+                export_mod.write_wav(paths[-1], wav[i, :lens[i]], self.dims.sample_rate)
+            out = out + (paths,)
         return out
 
     def Inv_Spectrogram(self, spectrograms, frames=None, iters=None, power=1.5, ref_level_db=20.0, init_phase=None, seed=0):
@@ -528,8 +691,10 @@ class GST_Tacotron:
             self.ctx.check(self.ctx.lib.gsttaco_encode(self.ctx.handle, _ptr(tok), _ptr(tlen), B, Tv, _ptr(enc), self._stream()))
         return enc
 
-    def decode(self, enc, gst=None, prenet_masks=None, attn_noise=None, seed=0, steps=None, token_lengths=None, teacher_mels=None):
-        """``gsttaco_decode``; with ``teacher_mels`` [B, Tq, Mel_Dim] (see ``Inference_Step``) ``gsttaco_decode_forced``."""
+    def decode(self, enc, gst=None, prenet_masks=None, attn_noise=None, seed=0, steps=None, token_lengths=None, teacher_mels=None,
+               seeds=None):
+        """``gsttaco_decode``; with ``teacher_mels`` [B, Tq, Mel_Dim] (see ``Inference_Step``) ``gsttaco_decode_forced``.  ``seeds`` [B]:
+        per-utterance seeds (see ``Inference_Step``) in place of ``seed`` (left at 0), ``prenet_masks`` and ``attn_noise``."""
         self._require_ready()
         d = self.dims
         enc = self._dev(enc, torch.float32)
@@ -538,6 +703,9 @@ class GST_Tacotron:
         B, Tv = enc.shape[0], enc.shape[1]
         teacher, Tq = self._teacher(teacher_mels, B, steps)
         S = (Tq - 1 + d.r - 1) // d.r if teacher is not None else d.steps if steps is None else int(steps)
+        if seeds is not None:
+            self._seeds_exclusive(seed or None, prenet_masks, attn_noise)
+            prenet_masks, attn_noise = self.Fill_Randomness(seeds, S, Tv, batch=B)
         masks = self._dev(prenet_masks, torch.float32)
         noise = self._dev(attn_noise, torch.float32)
         pre = torch.empty((B, S * d.r, d.mel), dtype=torch.float32, device=self.device)

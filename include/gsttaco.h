@@ -23,6 +23,9 @@
  *   gsttaco_decode_forced / gsttaco_inference_step_forced / gsttaco_forced_durations
  *                       <- the same loop's training=True branch (Taco2.py:161,185: step t consumes mels[:, t*r]) for GTA mels and forced
  *                          alignments; the per-token frame counts are an EXTENSION
+ *   gsttaco_fill_randomness / gsttaco_utterance_report
+ *                       <- EXTENSION (DESIGN row A16): randomness that depends on an utterance's own seed alone, and the stop test of
+ *                          Model.py:380,413 with alignment diagnostics per utterance on the device
  *   gsttaco_postnet     <- Modules/Taco2.py:131-149, 230
  *   gsttaco_vocoder     <- Modules/Taco2.py:234-260 Vocoder_Taco1.call, CBHG :285-380
  *   gsttaco_mel_frontend <- Pattern_Generator.py:39-60 Mel_Generate + Audio.py:29-32,49-55,70-96 melspectrogram
@@ -307,6 +310,41 @@ int gsttaco_inference_step_forced(gsttaco_ctx* ctx, const int32_t* tokens, const
  * utterance) on the caller's stream straight from / to the caller's pointers; needs no weights. */
 int gsttaco_forced_durations(gsttaco_ctx* ctx, const float* align, const int32_t* token_lengths, const int32_t* mel_lengths,
                              int B, int S, int Tv, int32_t* durations, void* stream);
+
+/* Per-utterance seeds (EXTENSION, DESIGN row A16).  With one `seed` per call an utterance's dropout and noise depend on its row and on
+ * the batch's Tv; this entry writes the randomness of a whole decode so that they depend on the utterance's own seed alone: row b draws
+ * exactly what a batch of ONE draws at its row 0 under seed = seeds[b] --
+ *   keep decisions gt_drop_keep(seeds[b], step, layer, row = 0, col, ncols, rate) (the counter hash at Prenet.Dropout_Rate 0.5, Philox
+ *   otherwise), noise gt_normal of Philox(seeds[b]; position, step, 0, 0x2000) -- for any B, row order and Tv.
+ *   seeds       : [B] uint64 on the DEVICE
+ *   prenet_mask : [steps][2][B][prenet] float32 0/1 at the caller's (unpadded) prenet sizes, or NULL
+ *   attn_noise  : [steps][B][Tv] float32, or NULL
+ * These are the layouts every prenet_mask / attn_noise argument of this library takes and gsttaco_debug_randomness returns: pass the
+ * buffers on to gsttaco_decode[_forced] / gsttaco_inference_step[_styled|_forced] (with token_lengths: without masking the padding of a
+ * ragged batch reaches the outputs whatever the seeds).  One launch on the caller's stream; needs a created context, no weights.
+ * GSTTACO_E_INVALID: NULL seeds, both outputs NULL, a prenet_mask with unequal prenet layer sizes (the stacked layout needs them equal);
+ * GSTTACO_E_CAPACITY: steps > Max_Step // r, B / Tv beyond the capacity given at create. */
+int gsttaco_fill_randomness(gsttaco_ctx* ctx, const uint64_t* seeds, int B, int Tv, int steps,
+                            float* prenet_mask, float* attn_noise, void* stream);
+
+/* The synthesis report (EXTENSION, DESIGN row A16): what stop [B,S] and align [B,S,Tv] (and mel [B,S*r,mel_dim], or NULL) of a decode say
+ * about each utterance, computed on the device.  For utterance b: n = token_lengths ? clip(token_lengths[b], 1, Tv) : Tv;
+ * s* = the first step with stop[b,s] < 0, else S (Model.py:380; a NaN is not below 0); E = min(S, max(1, s*));
+ * a_s = argmax_{j<n} align[b,s,j] (the lowest index on a tie) and m_s that maximum.  report [B][8] int32:
+ *   0 stop_step   s* (== S: the stop token never fired)
+ *   1 frames      max(1, s*) * r (Model.py:413; the `frames` gsttaco_griffin_lim takes)
+ *   2 end_gap     (n - 1) - max_{s<E} a_s (> 0: the speech ended before the text did)
+ *   3 max_jump    max(0, max_{1<=s<E} (a_s - a_{s-1})) (skipped tokens)
+ *   4 back_steps  number of s in [1, E) with a_s < a_{s-1}
+ *   5 max_stall   longest run of equal consecutive a_s in [0, E), in steps (>= 1)
+ *   6 visited     number of distinct values among a_0 .. a_{E-1}
+ *   7 nonfinite   non-finite values in stop[b,:E], align[b,:E,:n] and, with mel, mel[b,:frames,:]
+ * focus [B] float32 (or NULL): the mean of m_s over s < E, summed in double in a fixed order and rounded once.  With nonfinite != 0,
+ * fields 2..6 and focus are unspecified.  Only the E steps an utterance used are read.  One launch (one workgroup per utterance) on the
+ * caller's stream straight from / to the caller's pointers; needs no weights.  No thresholds: what counts as too long a stall depends
+ * on the voice and on r.  GSTTACO_E_INVALID: NULL stop / align / report; GSTTACO_E_CAPACITY as gsttaco_forced_durations. */
+int gsttaco_utterance_report(gsttaco_ctx* ctx, const float* stop, const float* align, const int32_t* token_lengths, const float* mel,
+                             int B, int S, int Tv, int32_t* report, float* focus, void* stream);
 
 /* hipGraph cache policy.  Every entry point replays one cached graph executable per (entry, B, Tv, Tref1, steps, flags) key.
  * The cache is LRU-bounded to `max_cached` executables (default 16 -- an Inference_Step replays two or three: encoder segment, GST + decode + postnet, vocoder; GSTTACO_GRAPH_CACHE; 0 = no graphs, everything is
