@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = (
     "gsttaco_gst_ex", "gsttaco_style_compose", "gsttaco_inference_step_styled",
     "gsttaco_decode_forced", "gsttaco_inference_step_forced", "gsttaco_forced_durations",
     "gsttaco_fill_randomness", "gsttaco_utterance_report",
+    "gsttaco_losses", "gsttaco_feature_frontend",
 )
 
 # GSTTACO_CONV_V_*: the conv/GEMM dispatcher's kernel instantiations (gsttaco_debug_conv_run reports which one ran)
@@ -139,10 +140,12 @@ def load_library(path=None):
     lib.gsttaco_forced_durations.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]
     lib.gsttaco_fill_randomness.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
     lib.gsttaco_utterance_report.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
+    lib.gsttaco_losses.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
     lib.gsttaco_postnet.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.gsttaco_vocoder.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.gsttaco_inference_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.gsttaco_mel_frontend.argtypes = [vp, vp, vp, i32, i32, ctypes.c_float, vp, vp, i32, vp]
+    lib.gsttaco_feature_frontend.argtypes = [vp, vp, vp, i32, i32, ctypes.c_float, vp, vp, vp, i32, vp]
     lib.gsttaco_mel_basis.argtypes = [vp, f32p]
     lib.gsttaco_griffin_lim.argtypes = [vp, vp, vp, i32, i32, i32, ctypes.c_float, ctypes.c_float, vp, u64, vp, vp, i32, vp]
     lib.gsttaco_set_profiling.argtypes = [vp, i32]
@@ -176,7 +179,7 @@ def load_library(path=None):
                "gsttaco_inference_step", "gsttaco_set_profiling", "gsttaco_get_profile", "gsttaco_mel_frontend",
                "gsttaco_mel_basis", "gsttaco_griffin_lim", "gsttaco_gst_ex", "gsttaco_style_compose", "gsttaco_inference_step_styled",
                "gsttaco_decode_forced", "gsttaco_inference_step_forced", "gsttaco_forced_durations",
-               "gsttaco_fill_randomness", "gsttaco_utterance_report"):
+               "gsttaco_fill_randomness", "gsttaco_utterance_report", "gsttaco_losses", "gsttaco_feature_frontend"):
         getattr(lib, fn).restype = ctypes.c_int
     if path is None:
         _lib = lib

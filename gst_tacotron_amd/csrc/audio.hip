@@ -12,7 +12,8 @@
 //   gt_trim_bounds_kernel   per utterance: max, first / last frame above -top_db -> sample bounds, mel frame count
 //   gt_stft_mel_kernel      one workgroup per output frame: gather (reflect padding) * window -> n_fft-point real FFT
 //                           as an n_fft/2 complex radix-2 FFT in LDS -> magnitudes -> mel bands -> dB -> normalise,
-//                           written straight into the mels_for_gst batch layout (zero frame 0, zero padding)
+//                           written straight into the mels_for_gst batch layout (zero frame 0, zero padding); with `specs` the
+//                           magnitudes also go out as the linear spectrogram (Audio.spectrogram) in the same layout
 // Back end = Audio.inv_spectrogram (Audio.py:23-27, 57-68, 74-75): see the second half of this file.
 //
 // All of this is a few MFLOP per utterance; the kernels are written for coalesced accesses and zero host round trips,
@@ -120,10 +121,12 @@ __global__ __launch_bounds__(256) void gt_stft_mel_kernel(AudioFrontArgs P) {
     const int N = P.n_fft, H = N >> 1, bits = P.log2_h;
     float* mag = reinterpret_cast<float*>(zsm + H);
     const int b = blockIdx.y, f = blockIdx.x, tid = threadIdx.x;
-    float* out = P.mels + ((size_t)b * P.cap_frames + f) * P.n_mels;
+    float* out = P.mels ? P.mels + ((size_t)b * P.cap_frames + f) * P.n_mels : nullptr;
+    float* sout = P.specs ? P.specs + ((size_t)b * P.cap_frames + f) * (H + 1) : nullptr;
     const int nmel = P.mel_len[b];
     if (f == 0 || f - 1 >= nmel) {                                    // prepended zero frame / zero padding
-        for (int m = tid; m < P.n_mels; m += blockDim.x) out[m] = 0.f;
+        if (out) for (int m = tid; m < P.n_mels; m += blockDim.x) out[m] = 0.f;
+        if (sout) for (int k = tid; k <= H; k += blockDim.x) sout[k] = 0.f;
         return;
     }
     const int j = f - 1;
@@ -152,7 +155,7 @@ __global__ __launch_bounds__(256) void gt_stft_mel_kernel(AudioFrontArgs P) {
         mag[k] = sqrtf(xr * xr + xi * xi);
     }
     __syncthreads();
-    for (int m = tid; m < P.n_mels; m += blockDim.x) {
+    if (out) for (int m = tid; m < P.n_mels; m += blockDim.x) {
         const float* wrow = P.mel_basis + (size_t)m * (H + 1);
         float acc = 0.f;
         for (int k = P.band_lo[m]; k < P.band_hi[m]; ++k) acc += wrow[k] * mag[k];
@@ -161,6 +164,15 @@ __global__ __launch_bounds__(256) void gt_stft_mel_kernel(AudioFrontArgs P) {
         if (P.max_abs > 0.f) v = fminf(fmaxf(2.f * P.max_abs * ((db + 100.f) / 100.f) - P.max_abs, -P.max_abs), P.max_abs);   // :95-96
         else v = fminf(fmaxf((db + 100.f) / 100.f, 0.f), 1.f);                              // :92-93
         out[m] = v;
+    }
+    // the linear spectrogram of the same frame, Audio.spectrogram (Audio.py:18-21): the mel's dB and normalisation on the bins
+    // themselves, 20 dB (ref_level_db) lower.  (The mel lines above are kept as they were: gsttaco_mel_frontend stays bitwise.)
+    if (sout) for (int k = tid; k <= H; k += blockDim.x) {
+        const float db = 20.f * log10f(fmaxf(1e-5f, mag[k])) - 20.f;
+        float v;
+        if (P.max_abs > 0.f) v = fminf(fmaxf(2.f * P.max_abs * ((db + 100.f) / 100.f) - P.max_abs, -P.max_abs), P.max_abs);
+        else v = fminf(fmaxf((db + 100.f) / 100.f, 0.f), 1.f);
+        sout[k] = v;
     }
 }
 

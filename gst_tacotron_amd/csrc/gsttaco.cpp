@@ -2605,6 +2605,27 @@ int gsttaco_utterance_report(gsttaco_ctx* c, const float* stop, const float* ali
     return 0;
 }
 
+// The loss sums of a teacher-forced pass (the four terms of Train_Step, Model.py:210-241, per utterance): one launch, one workgroup per
+// utterance, straight from / to the caller's pointers.  Needs no weights (only Step_Reduction, Mel_Dim and Spectrogram_Dim).
+int gsttaco_losses(gsttaco_ctx* c, const float* pre_mel, const float* mel, const float* stop, const float* spectrogram,
+                   const float* teacher, const float* spec_target, const int32_t* mel_lengths, const int32_t* spec_lengths, int B, int S,
+                   int Tq, double* losses, void* stream) {
+    if (!c) return GSTTACO_E_INVALID;
+    if (!pre_mel || !mel || !stop || !teacher || !losses) return fail(c, GSTTACO_E_INVALID, "null argument");
+    if (B < 1 || S < 1 || Tq < 2 || (int64_t)S * c->r < Tq - 1) return fail(c, GSTTACO_E_INVALID, "bad B / S / Tq (Tq >= 2, S * r >= Tq - 1)");
+    if (S > c->steps_max || B > c->cfg.max_batch)
+        return fail(c, GSTTACO_E_CAPACITY, "batch / steps exceed the capacity given at create");
+    if (spectrogram && spec_target && c->cfg.spec_dim < 1) return fail(c, GSTTACO_E_INVALID, "Sound.Spectrogram_Dim not set");
+    int rc = ensure_device(c);
+    if (rc) return rc;
+    LossArgs a{};
+    a.pre_mel = pre_mel; a.mel = mel; a.stop = stop; a.spec = spectrogram; a.teacher = teacher; a.spec_target = spec_target;
+    a.mel_len = mel_lengths; a.spec_len = spec_lengths; a.losses = losses;
+    a.B = B; a.S = S; a.Tq = Tq; a.r = c->r; a.mel_dim = c->cfg.mel_dim; a.spec_dim = c->cfg.spec_dim > 0 ? c->cfg.spec_dim : 1;
+    HIPCHECK(c, gt_launch_losses(a, (hipStream_t)stream));
+    return 0;
+}
+
 int gsttaco_postnet(gsttaco_ctx* c, const float* pre_mel, int B, int Tf, float* mel, void* stream) {
     int rc = check_ready(c);
     if (rc) return rc;
@@ -2635,19 +2656,20 @@ int gsttaco_vocoder(gsttaco_ctx* c, const float* mel, int B, int Tf, float* spec
     return 0;
 }
 
-int gsttaco_mel_frontend(gsttaco_ctx* c, const float* wav, const int32_t* wav_lengths, int B, int ld_wav, float top_db,
-                         float* mels_for_gst, int32_t* mel_lengths, int cap_frames, void* stream) {
+// wav -> mels and / or linear spectrograms of the same trimmed signal, from one STFT (either output may be NULL, not both).
+int gsttaco_feature_frontend(gsttaco_ctx* c, const float* wav, const int32_t* wav_lengths, int B, int ld_wav, float top_db, float* mels,
+                             float* spectrograms, int32_t* lengths, int cap_frames, void* stream) {
     if (!c) return GSTTACO_E_INVALID;
     int rc = ensure_audio(c);
     if (rc) return rc;
     const gsttaco_config& g = c->cfg;
-    if (!wav || !wav_lengths || !mels_for_gst || !mel_lengths) return fail(c, GSTTACO_E_INVALID, "null argument");
+    if (!wav || !wav_lengths || (!mels && !spectrograms) || !lengths) return fail(c, GSTTACO_E_INVALID, "null argument");
     if (B < 1 || ld_wav < 17 || !(top_db > 0.f)) return fail(c, GSTTACO_E_INVALID, "bad B / ld_wav / top_db");
     if (B > g.max_batch || ld_wav > g.max_wav_samples) return fail(c, GSTTACO_E_CAPACITY, "batch / samples exceed capacity");
     if (cap_frames < 2 + ld_wav / g.frame_shift) return fail(c, GSTTACO_E_INVALID, "cap_frames must be >= 2 + ld_wav / Frame_Shift");
     AudioFrontArgs a{};
     a.wav = wav; a.wav_len = wav_lengths; a.mse = c->a_mse; a.bounds = c->a_bounds;
-    a.mels = mels_for_gst; a.mel_len = mel_lengths;
+    a.mels = mels; a.specs = spectrograms; a.mel_len = lengths;
     a.window = c->a_window; a.twiddle = c->a_twiddle; a.mel_basis = c->a_mel_basis; a.band_lo = c->a_band_lo; a.band_hi = c->a_band_hi;
     a.B = B; a.ld_wav = ld_wav; a.ld_mse = c->a_ld_mse; a.cap_frames = cap_frames;
     a.n_fft = c->n_fft; a.log2_h = 0;
@@ -2658,6 +2680,15 @@ int gsttaco_mel_frontend(gsttaco_ctx* c, const float* wav, const int32_t* wav_le
     a.top_db = top_db; a.max_abs = g.max_abs_mel;
     HIPCHECK(c, gt_launch_audio_front(a, (hipStream_t)stream));
     return 0;
+}
+
+int gsttaco_mel_frontend(gsttaco_ctx* c, const float* wav, const int32_t* wav_lengths, int B, int ld_wav, float top_db,
+                         float* mels_for_gst, int32_t* mel_lengths, int cap_frames, void* stream) {
+    if (!c) return GSTTACO_E_INVALID;
+    int rc = ensure_audio(c);
+    if (rc) return rc;
+    if (!mels_for_gst) return fail(c, GSTTACO_E_INVALID, "null argument");
+    return gsttaco_feature_frontend(c, wav, wav_lengths, B, ld_wav, top_db, mels_for_gst, nullptr, mel_lengths, cap_frames, stream);
 }
 
 int gsttaco_griffin_lim(gsttaco_ctx* c, const float* spectrogram, const int32_t* frames, int B, int T, int iters,

@@ -441,7 +441,8 @@ struct AudioFrontArgs {
     const int32_t* wav_len;     // [B]
     double* mse;                // [B, ld_mse] workspace: trim frame mean-squares
     int32_t* bounds;            // [B, 2] workspace: trimmed (start, length) in samples
-    float* mels;                // [B, cap_frames, n_mels] mels_for_gst layout (frame 0 = zeros)
+    float* mels;                // [B, cap_frames, n_mels] mels_for_gst layout (frame 0 = zeros), or NULL
+    float* specs;               // [B, cap_frames, n_fft/2+1] linear spectrograms (Audio.spectrogram) in the same layout, or NULL
     int32_t* mel_len;           // [B] frames excluding the prepended one
     const float* window;        // [n_fft] hann (periodic), zero-padded centred to n_fft
     const float2* twiddle;      // [n_fft/2] exp(-2 pi i k / n_fft)
@@ -492,3 +493,20 @@ hipError_t gt_launch_fill_randomness(const uint64_t* seeds, float* masks, float*
 hipError_t gt_launch_utterance_report(const float* stop, const float* align, const int32_t* tok_len, const float* mel, int32_t* report,
                                       float* focus, int B, int S, int Tv, int r, int mel_dim, hipStream_t stream);
 
+
+// ---------------------------------------------------------------- loss.hip
+// The per-utterance loss sums of a teacher-forced pass (the table in include/gsttaco.h).  The target of prediction frame t is
+// teacher[b, 1 + t]; only t < min(length, Tq - 1) is read.  One workgroup per utterance, double throughout after the fp32 subtraction.
+struct LossArgs {
+    const float* pre_mel;       // [B, S*r, mel_dim]
+    const float* mel;           // [B, S*r, mel_dim]
+    const float* stop;          // [B, S]
+    const float* spec;          // [B, S*r, spec_dim], or NULL
+    const float* teacher;       // [B, Tq, mel_dim] (frame 0 = the go frame)
+    const float* spec_target;   // [B, Tq, spec_dim], or NULL
+    const int32_t* mel_len;     // [B], or NULL (= Tq - 1)
+    const int32_t* spec_len;    // [B], or NULL (= Tq - 1)
+    double* losses;             // [B][6]
+    int B, S, Tq, r, mel_dim, spec_dim;
+};
+hipError_t gt_launch_losses(const LossArgs& a, hipStream_t stream);

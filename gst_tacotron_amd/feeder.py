@@ -109,3 +109,31 @@ class Feeder:
         pattern["teacher_mels"] = mels
         pattern["mel_lengths"] = np.array([m.shape[0] for m in mel_List], dtype=np.int32)
         return pattern
+
+    def Get_Evaluation_Pattern(self, sentence_List, mel_List, spectrogram_List=None):
+        """Extension (``GST_Tacotron.Evaluate``): ``Get_Teacher_Pattern`` plus the linear spectrogram targets [T, Spectrogram_Dim] in the
+        layout the reference's training batch has (Feeder.py:103-143): both padded to ONE length -- the longer of the two, go frame
+        included, rounded up to Step_Reduction (:134-135) -- plus the frame that ``mels[:, 0:-1:r]`` drops.  Adds ``spectrograms``
+        [B, Tq, Spectrogram_Dim] and ``spectrogram_lengths`` [B]; without ``spectrogram_List`` it is ``Get_Teacher_Pattern``."""
+        pattern = self.Get_Teacher_Pattern(sentence_List, mel_List)
+        if spectrogram_List is None:
+            return pattern
+        if len(spectrogram_List) != len(sentence_List):
+            raise ValueError("spectrogram_List must hold one spectrogram per sentence")
+        spec_dim, r = int(self.hp["Sound"]["Spectrogram_Dim"]), int(self.hp["Step_Reduction"])
+        spec_List = [np.asarray(s, dtype=np.float32) for s in spectrogram_List]
+        for s in spec_List:
+            if s.ndim != 2 or s.shape[1] != spec_dim or s.shape[0] < 1:
+                raise ValueError("spectrogram targets must be [T>=1, {}] arrays".format(spec_dim))
+        mels = pattern["teacher_mels"]
+        longest = max(int(pattern["mel_lengths"].max()), max(s.shape[0] for s in spec_List))
+        padded = -(-(longest + 1) // r) * r                         # Feeder.py:134-135 (go frame included)
+        if padded + 1 > mels.shape[1]:                              # (a spectrogram is the longest: the mels grow to its length)
+            mels = np.concatenate([mels, np.zeros((mels.shape[0], padded + 1 - mels.shape[1], mels.shape[2]), np.float32)], 1)
+        specs = np.zeros((len(spec_List), padded + 1, spec_dim), dtype=np.float32)      # :140-143
+        for i, s in enumerate(spec_List):
+            specs[i, 1:s.shape[0] + 1] = s
+        pattern["teacher_mels"] = mels
+        pattern["spectrograms"] = specs
+        pattern["spectrogram_lengths"] = np.array([s.shape[0] for s in spec_List], dtype=np.int32)
+        return pattern

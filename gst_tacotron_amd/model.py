@@ -7,6 +7,7 @@
     .Inference(sentence_List, mel_List_for_GST)
     .Style_Compose(token_weights, query)                 (extension: a style from token weights)
     .Inference_GTA(sentence_List, mel_or_wav_List)       (extension: teacher-forced decoding -- GTA mels, forced durations)
+    .Evaluate(sentence_List, mel_or_wav_List)            (extension: Train_Step's loss terms of a teacher-forced pass)
 
 Same names, argument order/meaning and error behaviour; the Keras functional model
 behind them (Model.py:145-156) is replaced by the HIP kernels behind include/gsttaco.h.
@@ -30,7 +31,10 @@ PyTorch is used for device memory and streams only.  Differences, all additive:
   * per-utterance seeds and a synthesis report: ``seeds=`` ([batch], one per utterance) in place of ``seed`` makes an utterance's
     dropout and noise depend on its own seed alone -- not on its row or the batch --, ``Utterance_Report`` says on the device where each
     utterance stopped and how its attention moved, and ``Inference_Checked`` runs a batch, reads the report and redoes only the
-    rejected rows under new seeds.
+    rejected rows under new seeds;
+  * validation losses: ``Evaluate`` runs one teacher-forced pass and returns the four loss terms of the reference's ``Train_Step``
+    (Model.py:210-241), per utterance and per batch (``Loss_Terms`` on the device, ``gst_tacotron_amd.evaluate`` on the host);
+    ``Feature_Generate`` is ``Mel_Generate`` with the linear spectrogram target from the same STFT.
 """
 import ctypes
 import os
@@ -39,8 +43,9 @@ from datetime import datetime
 import numpy as np
 import torch
 
-from . import capi, checked, weights as weights_mod
+from . import capi, checked, evaluate, weights as weights_mod
 from .checked import REPORT_FIELDS  # noqa: F401  -- the columns of Utterance_Report's first result
+from .evaluate import LOSS_FIELDS  # noqa: F401  -- the columns of Loss_Terms' result
 from .feeder import Feeder
 from .hparams import Dims, load_hp, load_token_dict
 
@@ -336,6 +341,102 @@ class GST_Tacotron:
         self.synchronize()
         return [mel[i, :int(n)] for i, n in enumerate(mel_lengths)], stop, align, dur
 
+    def Loss_Terms(self, pre_mel, mel, stop, teacher_mels, mel_lengths=None, spectrogram=None, spectrogram_targets=None,
+                   spectrogram_lengths=None):
+        """Extension: the loss sums of a teacher-forced pass (``gsttaco_losses``) -> float64 [B, 6] on the device, columns
+        ``LOSS_FIELDS``.  ``pre_mel`` / ``mel`` [B, S * r, Mel_Dim], ``stop`` [B, S] and ``spectrogram`` [B, S * r, Spectrogram_Dim] as
+        ``Inference_Step(teacher_mels=, return_pre_mel=True, with_vocoder=True)`` returns them; ``teacher_mels`` [B, Tq, Mel_Dim] and
+        ``spectrogram_targets`` [B, Tq, Spectrogram_Dim] with the go frame at index 0: the target of frame t is frame 1 + t.  Per
+        utterance: sums over the frames below its length of the channel means of |difference| and difference^2, and the stop token's
+        sigmoid cross entropy summed over all steps (label 1 while s < ceil(mel_length / r)).  The spectrogram fields are 0 unless
+        both spectrogram tensors are given.  Works before Restore (no weights involved)."""
+        d = self.dims
+        pm, ml, st = self._dev(pre_mel, torch.float32), self._dev(mel, torch.float32), self._dev(stop, torch.float32)
+        tg = self._dev(teacher_mels, torch.float32)
+        if st.dim() != 2:
+            raise ValueError("stop must be [batch, steps]")
+        B, S = st.shape
+        if tg.dim() != 3 or tg.shape[0] != B or tg.shape[2] != d.mel or tg.shape[1] < 2:
+            raise ValueError("teacher_mels must be [batch, Tq >= 2, Mel_Dim] (frame 0 = the go frame)")
+        Tq = int(tg.shape[1])
+        if S * d.r < Tq - 1:
+            raise ValueError("the predictions hold fewer than Tq - 1 frames")
+        for name, v in (("pre_mel", pm), ("mel", ml)):
+            if tuple(v.shape) != (B, S * d.r, d.mel):
+                raise ValueError(name + " must be [batch, steps * Step_Reduction, Mel_Dim]")
+        sp, sg = self._dev(spectrogram, torch.float32), self._dev(spectrogram_targets, torch.float32)
+        if sp is not None and tuple(sp.shape) != (B, S * d.r, d.spec):
+            raise ValueError("spectrogram must be [batch, steps * Step_Reduction, Spectrogram_Dim]")
+        if sg is not None and tuple(sg.shape) != (B, Tq, d.spec):
+            raise ValueError("spectrogram_targets must be [batch, Tq, Spectrogram_Dim] with teacher_mels' Tq")
+        mlen, slen = self._dev(mel_lengths, torch.int32), self._dev(spectrogram_lengths, torch.int32)
+        for name, v in (("mel_lengths", mlen), ("spectrogram_lengths", slen)):
+            if v is not None and tuple(v.shape) != (B,):
+                raise ValueError(name + " must be [batch]")
+        if not torch.cuda.is_available():
+            raise capi.GstTacoError(-2, "no HIP device: the gfx950 kernels are the only compute path (no CPU fallback)")
+        sums = torch.empty((B, len(LOSS_FIELDS)), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            self.ctx.check(self.ctx.lib.gsttaco_losses(self.ctx.handle, _ptr(pm), _ptr(ml), _ptr(st), _ptr(sp), _ptr(tg), _ptr(sg),
+                                                       _ptr(mlen), _ptr(slen), B, S, Tq, _ptr(sums), self._stream()))
+        return sums
+
+    def Evaluate_Step(self, tokens, token_lengths, teacher_mels, mel_lengths, spectrograms=None, spectrogram_lengths=None,
+                      style_embeddings=None, mels_for_gst=None, mel_lengths_for_gst=None, **kwargs):
+        """Extension: one teacher-forced ``Inference_Step`` (``return_pre_mel=True``; the vocoder runs iff ``spectrograms`` -- the targets
+        [B, Tq, Spectrogram_Dim] -- are given) and ``Loss_Terms`` of its outputs on the same stream.  Returns (sums float64 [B, 6],
+        (mel, stop, spec, align, pre_mel)).  ``kwargs``: ``seed`` / ``seeds`` / ``prenet_masks`` / ``attn_noise`` and ``masked`` as
+        ``Inference_Step`` takes them.  With GST on and no style given the style input is ``teacher_mels`` itself with ``mel_lengths``
+        -- go frame and trailing padding included --, which is what the reference's training model is fed (Model.py:206:
+        ``[mels, mel_lengths]``), not ``Inference_GTA``'s re-packed copy.  Every layer runs in inference mode: this is the
+        validation loss of the inference graph, not Train_Step's forward (no batch-statistics BN, no encoder dropout)."""
+        for k in kwargs:
+            if k not in ("seed", "seeds", "prenet_masks", "attn_noise", "masked"):
+                raise ValueError("Evaluate_Step sets '{}' itself".format(k))
+        if self.dims.gst and style_embeddings is None and mels_for_gst is None:
+            mels_for_gst, mel_lengths_for_gst = teacher_mels, mel_lengths
+        out = self.Inference_Step(tokens, token_lengths, None, mels_for_gst, mel_lengths_for_gst, return_pre_mel=True,
+                                  with_vocoder=spectrograms is not None, style_embeddings=style_embeddings,
+                                  teacher_mels=teacher_mels, **kwargs)
+        mel, stop, spec, align, pre = out
+        sums = self.Loss_Terms(pre, mel, stop, teacher_mels, mel_lengths, spec, spectrograms, spectrogram_lengths)
+        return sums, out
+
+    def Evaluate(self, sentence_List, mel_or_wav_List, spectrogram_List=None, use_l2=None, seeds=None, **kwargs):
+        """Extension: the loss the reference's ``Train_Step`` computes (Model.py:210-241), as a validation number of this checkpoint on
+        the given sentences and targets.  ``mel_or_wav_List`` holds one target per sentence: wav paths / 1-D sample arrays, which go
+        through ``Feature_Generate`` (top_db 15, what ``Inference_GTA`` uses) and then carry their spectrogram targets with them, or
+        mels [T, Mel_Dim] taken as given, with ``spectrogram_List`` ([T, Spectrogram_Dim] each) optionally beside them.  The
+        spectrogram term is included only when spectrogram targets exist (and the model has a vocoder).  ``use_l2``:
+        ``Train.Use_L2_Loss``; None reads it from the hyper parameters (False when absent).
+        Returns a dict: ``pre_mel``, ``mel``, ``stop``, ``spectrogram``, ``loss`` (``evaluate.combine``: means over the PADDED batch like
+        the reference's, so padding dilutes the frame terms), ``per_utterance`` (numpy float64 [B, 6], ``LOSS_FIELDS``: sums),
+        ``mel_lengths`` and ``steps``.
+        Prenet dropout and the SMA noise are live at inference, so these losses are random variables: give ``seed`` or ``seeds``
+        ([B], per utterance; the call then runs masked) for a repeatable number."""
+        print("Evaluation running...")
+        if seeds is not None:
+            kwargs["seeds"], kwargs["masked"] = seeds, True
+        targets = list(mel_or_wav_List)
+        if len(targets) != len(sentence_List):
+            raise ValueError("mel_or_wav_List must hold one target per sentence")
+        if not all(self.feeder._is_mel(m) for m in targets):
+            if spectrogram_List is not None:
+                raise ValueError("wav targets bring their own spectrograms: spectrogram_List must be None")
+            mels, specs, lens = self.Feature_Generate(targets, 15)
+            mels, specs, lens = mels.cpu().numpy(), specs.cpu().numpy(), lens.cpu().numpy()
+            targets = [mels[i, 1:1 + int(lens[i])] for i in range(len(targets))]
+            if self.dims.vocoder:
+                spectrogram_List = [specs[i, 1:1 + int(lens[i])] for i in range(len(targets))]
+        pattern = self.feeder.Get_Evaluation_Pattern(sentence_List, targets, spectrogram_List)
+        sums, out = self.Evaluate_Step(**pattern, **kwargs)
+        self.synchronize()
+        per = sums.cpu().numpy()
+        S, T = int(out[1].shape[1]), int(pattern["teacher_mels"].shape[1]) - 1
+        result = evaluate.combine(per, T, S, evaluate.use_l2_of(self.hp_Dict) if use_l2 is None else bool(use_l2))
+        result.update(per_utterance=per, mel_lengths=pattern["mel_lengths"], steps=S)
+        return result
+
     def Inference_GST(self, wav_List, tag_List=None, label=None):
         """reference Model.py:427-446: style embeddings [B, Attention.Size] of the wavs; with ``tag_List`` the table
         of Model.py:448-459 is written too."""
@@ -422,6 +523,37 @@ class GST_Tacotron:
         if int(mel_len.min().item()) < 1:
             raise ValueError("a reference wav is shorter than n_fft/2 samples after trimming (librosa.stft raises there)")
         return mels[:, :n + 1].contiguous(), mel_len
+
+    def Feature_Generate(self, wav_List, top_db=60):
+        """Extension: ``Mel_Generate`` plus the linear spectrogram of the same trimmed signal from the same STFT (reference
+        Pattern_Generator.Spectrogram_Generate / Audio.spectrogram, Audio.py:18-21: what Train_Step compares the vocoder's output
+        with) -> (mels [B, 1+max_len, Mel_Dim], spectrograms [B, 1+max_len, Spectrogram_Dim], lengths [B]) as device tensors, both
+        with a zero frame 0 and zero padding.  ``mels`` is bitwise ``Mel_Generate``'s.  Works before Restore."""
+        from .audio import as_signal
+        d = self.dims
+        if not d.audio or not self.ctx.cfg.max_wav_samples:
+            raise ValueError("the audio front end needs the Sound section of Hyper_Parameters and max_wav_seconds > 0")
+        if not torch.cuda.is_available():
+            raise capi.GstTacoError(-2, "no HIP device: the gfx950 kernels are the only compute path (no CPU fallback)")
+        sigs = [as_signal(w, d.sample_rate) for w in wav_List]
+        B, ld = len(sigs), max(s.shape[0] for s in sigs)
+        host = np.zeros((B, ld), dtype=np.float32)
+        for i, s_ in enumerate(sigs):
+            host[i, :s_.shape[0]] = s_
+        wav = torch.from_numpy(host).to(self.device)
+        lens = torch.tensor([s_.shape[0] for s_ in sigs], dtype=torch.int32, device=self.device)
+        cap = 2 + ld // d.frame_shift
+        mels = torch.empty((B, cap, d.mel), dtype=torch.float32, device=self.device)
+        specs = torch.empty((B, cap, d.spec), dtype=torch.float32, device=self.device)
+        out_len = torch.empty((B,), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            self.ctx.check(self.ctx.lib.gsttaco_feature_frontend(
+                self.ctx.handle, _ptr(wav), _ptr(lens), B, ld, ctypes.c_float(float(top_db)), _ptr(mels), _ptr(specs), _ptr(out_len),
+                cap, self._stream()))
+        n = int(out_len.max().item())            # the one host sync: the output length is data dependent (trim)
+        if int(out_len.min().item()) < 1:
+            raise ValueError("a wav is shorter than n_fft/2 samples after trimming (librosa.stft raises there)")
+        return mels[:, :n + 1].contiguous(), specs[:, :n + 1].contiguous(), out_len
 
     def Inference(self, sentence_List, wav_List_for_GST=None, label=None, export=False, style_embeddings=None,
                   style_token_weights=None, seeds=None, **kwargs):

@@ -26,6 +26,9 @@
  *   gsttaco_fill_randomness / gsttaco_utterance_report
  *                       <- EXTENSION (DESIGN row A16): randomness that depends on an utterance's own seed alone, and the stop test of
  *                          Model.py:380,413 with alignment diagnostics per utterance on the device
+ *   gsttaco_losses / gsttaco_feature_frontend
+ *                       <- EXTENSION (DESIGN row A17): the four loss terms of Train_Step (Model.py:210-241) of a teacher-forced pass, per
+ *                          utterance on the device, and the mel plus the linear spectrogram target (Audio.py:18-21) from one STFT
  *   gsttaco_postnet     <- Modules/Taco2.py:131-149, 230
  *   gsttaco_vocoder     <- Modules/Taco2.py:234-260 Vocoder_Taco1.call, CBHG :285-380
  *   gsttaco_mel_frontend <- Pattern_Generator.py:39-60 Mel_Generate + Audio.py:29-32,49-55,70-96 melspectrogram
@@ -235,6 +238,18 @@ int gsttaco_vocoder(gsttaco_ctx* ctx, const float* mel, int B, int T, float* spe
 int gsttaco_mel_frontend(gsttaco_ctx* ctx, const float* wav, const int32_t* wav_lengths, int B, int ld_wav, float top_db,
                          float* mels_for_gst, int32_t* mel_lengths, int cap_frames, void* stream);
 
+/* gsttaco_mel_frontend with a second output from the same STFT (EXTENSION, DESIGN row A17): the linear spectrogram Train_Step compares
+ * the vocoder's output with (Pattern_Generator.Spectrogram_Generate / Audio.spectrogram, Audio.py:18-21) of the same trimmed signal,
+ *   normalise(20 log10(max(1e-5, |STFT|)) - 20),
+ * with the normalisation the mel has: symmetric with Max_Abs_Mel, or [0,1] when it is 0 (Pattern_Generator.py:75-82 passes Max_Abs_Mel).
+ * wav, wav_lengths, top_db, cap_frames: as gsttaco_mel_frontend.
+ * mels         : [B, cap_frames, mel_dim] as gsttaco_mel_frontend writes it (bitwise), or NULL
+ * spectrograms : [B, cap_frames, spec_dim] in the same batch layout -- frame 0 zero, frames 1..lengths[b], zero padding --, or NULL
+ * lengths      : [B] int32, the frame count of both (excluding frame 0)
+ * GSTTACO_E_INVALID when both outputs are NULL, otherwise as gsttaco_mel_frontend. */
+int gsttaco_feature_frontend(gsttaco_ctx* ctx, const float* wav, const int32_t* wav_lengths, int B, int ld_wav, float top_db,
+                             float* mels, float* spectrograms, int32_t* lengths, int cap_frames, void* stream);
+
 /* spectrogram -> waveform: Audio.inv_spectrogram (reference Audio.py:23-27) = symmetric de-normalisation (max_abs_mel,
  * or the [0,1] one when it is 0), + ref_level_db, dB -> amplitude, ^power, `iters` Griffin-Lim iterations
  * (Audio.py:57-68; librosa stft / istft, hann, centred), inverse pre-emphasis 0.97.  Needs cfg.max_wav_samples > 0.
@@ -345,6 +360,30 @@ int gsttaco_fill_randomness(gsttaco_ctx* ctx, const uint64_t* seeds, int B, int 
  * on the voice and on r.  GSTTACO_E_INVALID: NULL stop / align / report; GSTTACO_E_CAPACITY as gsttaco_forced_durations. */
 int gsttaco_utterance_report(gsttaco_ctx* ctx, const float* stop, const float* align, const int32_t* token_lengths, const float* mel,
                              int B, int S, int Tv, int32_t* report, float* focus, void* stream);
+
+/* Validation losses (EXTENSION, DESIGN row A17): the four terms of the reference's Train_Step (Model.py:210-241) of a teacher-forced pass
+ * -- gsttaco_inference_step_forced's pre_mel, mel, stop and spectrogram against the teacher it consumed -- per utterance, as SUMS (the
+ * means over the padded batch are the host's: gst_tacotron_amd/evaluate.py).
+ *   pre_mel, mel : [B, S*r, mel_dim]     stop : [B, S]     spectrogram : [B, S*r, spec_dim] or NULL
+ *   teacher      : [B, Tq, mel_dim]      spec_target : [B, Tq, spec_dim] or NULL      (frame 0 = the go frame, Feeder.py:125-143)
+ *   mel_lengths, spec_lengths : [B] int32 or NULL (= T)
+ * T = Tq - 1; the target of prediction frame t is teacher[b, 1 + t]; L = clip(mel_lengths[b], 0, T), Ls = clip(spec_lengths[b], 0, T);
+ * S*r >= T and prediction frames t >= T are never read.  losses [B][6] DOUBLE -- the one double output of this header:
+ *   0 pre_mel_l1  (sum_{t<L} sum_c |teacher - pre_mel|) / mel_dim
+ *   1 mel_l1      the same with mel
+ *   2 mel_l2      (sum_{t<L} sum_c (teacher - mel)^2) / mel_dim
+ *   3 stop_bce    sum_{s<S} bce(x = stop[b,s], z = [s < ceil(mel_lengths[b] / r)]) over ALL S steps, unmasked as Model.py:227-234 leaves
+ *                 it; bce = max(x,0) - x z + log1p(exp(-|x|)); mel_lengths NULL: z = 1 everywhere
+ *   4 spec_l1     as field 1 with the spectrogram pair over t < Ls and spec_dim; 0 when either spectrogram pointer is NULL
+ *   5 spec_l2     as field 2, likewise
+ * Each element's difference is ONE fp32 subtraction; everything after it is double: |.|, the square, the bce, every sum and the one
+ * division by the channel count.  Sums run in a fixed order (no floating-point atomics): a call is bitwise reproducible.  A non-finite
+ * input propagates to the fields that read it.  One launch (one workgroup per utterance) on the caller's stream straight from / to the
+ * caller's pointers; needs no weights.
+ * GSTTACO_E_INVALID: a NULL required pointer, Tq < 2, S*r < Tq - 1; GSTTACO_E_CAPACITY as gsttaco_forced_durations (S, B). */
+int gsttaco_losses(gsttaco_ctx* ctx, const float* pre_mel, const float* mel, const float* stop, const float* spectrogram,
+                   const float* teacher, const float* spec_target, const int32_t* mel_lengths, const int32_t* spec_lengths,
+                   int B, int S, int Tq, double* losses, void* stream);
 
 /* hipGraph cache policy.  Every entry point replays one cached graph executable per (entry, B, Tv, Tref1, steps, flags) key.
  * The cache is LRU-bounded to `max_cached` executables (default 16 -- an Inference_Step replays two or three: encoder segment, GST + decode + postnet, vocoder; GSTTACO_GRAPH_CACHE; 0 = no graphs, everything is
