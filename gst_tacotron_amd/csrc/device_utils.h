@@ -92,7 +92,8 @@ __device__ __forceinline__ float gt_wave_max(float m) {
 }
 
 // tanh(x) = 1 - 2/(exp(2x)+1) on one v_exp_f32 + one v_rcp_f32 (5 VALU ops).  No clamp is needed: exp(2x) -> inf
-// gives rcp -> 0 -> +1, exp(2x) -> 0 gives -1, never NaN.  abs error <= ~2e-7 (covered by the parity tests).
+// gives rcp -> 0 -> +1, exp(2x) -> 0 gives -1, never NaN.  abs error <= ~2e-7.  tests/test_gpu_saturated.py holds this form, gt_tanh2
+// and gt_sigmoid to the float64 oracle where they saturate (|x| up to ~100, gates beyond |z| = 16, p that rounds to exactly 1.0f).
 __device__ __forceinline__ float gt_tanh(float x) {
     const float e = __builtin_amdgcn_exp2f(x * 2.885390081777927f);      // exp(2x) = 2^(2x*log2(e))
     // (an explicit fma: whether `1 - 2 r` contracts is otherwise the optimiser's choice per call site, and kernels whose results
