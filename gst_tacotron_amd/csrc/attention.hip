@@ -14,6 +14,7 @@
 // Scores: one lane per memory row (no cross-lane reduction over a); BMA prefix sums: one wave, serial
 // chunk per lane + wave scan; context: one lane per output channel.
 #include "device_utils.h"
+#include "chain_common.h"
 #include "kernels.h"
 #include "../../include/gsttaco.h"
 
@@ -29,8 +30,6 @@ size_t gt_attn_lds_bytes(int Tv, int A, int loc_f, int loc_k, int* rows_lds) {
     if (loc_f > 0) fl += (size_t)rows * (loc_f + 1) + (size_t)loc_f * A + (size_t)loc_k * loc_f + loc_f + 2 * (size_t)A;
     return fl * sizeof(float);
 }
-
-__device__ __forceinline__ float wave_incl_scan(float x, int lane) { return gt_wave_incl_scan(x, lane); }
 
 __global__ __launch_bounds__(ATT_THREADS) void gt_attn_step_kernel(AttnStepArgs P) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -146,26 +145,11 @@ __global__ __launch_bounds__(ATT_THREADS) void gt_attn_step_kernel(AttnStepArgs 
     __syncthreads();
 
     if (lsa) {
-        // softmax (or smoothing normalisation, Layers.py:426-444) over the Tv positions: one wave, serial chunk per lane
-        if (tid < 64) {
-            const int per = (Tv + 63) / 64;
-            const int t0 = tid * per, t1 = min(Tv, t0 + per);
-            float mx = -INFINITY;
-            for (int t = t0; t < t1; ++t) mx = fmaxf(mx, sc[t]);
-            mx = gt_wave_max(mx);
-            float sum = 0.f;
-            for (int t = t0; t < t1; ++t) {
-                const float e = P.lsa_smoothing ? 1.f / (1.f + expf(-sc[t])) : expf(sc[t] - mx);
-                al[t] = e;
-                sum += e;
-            }
-            sum = gt_wave_sum(sum);
-            const float inv = 1.f / sum;
-            for (int t = t0; t < t1; ++t) {
-                al[t] *= inv;
-                P.lsa_state[(size_t)b * TvFull + t] = P.lsa_cumulate ? pv[t] + al[t] : al[t];
-            }
-        }
+        // the state the next step's location features read is the running sum of the alignments (or the last one)
+        if (tid < 64)
+            gt_softmax_align_wave(sc, al, Tv, tid, P.lsa_smoothing != 0, [&](const int t, const float a) {
+                P.lsa_state[(size_t)b * TvFull + t] = P.lsa_cumulate ? pv[t] + a : a;
+            });
     } else {
     // ---- noise + sigmoid
     for (int t = tid; t < Tv; t += ATT_THREADS) {
@@ -187,33 +171,11 @@ __global__ __launch_bounds__(ATT_THREADS) void gt_attn_step_kernel(AttnStepArgs 
     if (P.type == GSTTACO_ATT_SMA) {
         for (int t = tid; t < Tv; t += ATT_THREADS) {
             float v = pv[t] * sc[t];
-            if (t > 0) v = __builtin_fmaf(pv[t - 1], 1.f - sc[t - 1], v);       // (explicit: a*b + c*d can contract either way)
+            if (t > 0) v = gt_sma(v, pv[t - 1], sc[t - 1]);
             al[t] = v;
         }
-    } else {
-        // BMA: cp = exp(exclusive_cumsum(log(clip(1-p, tiny, 1)))); align = p*cp*cumsum(prev/clip(cp,1e-10,1))
-        if (tid < 64) {
-            const int per = (Tv + 63) / 64;
-            const int t0 = tid * per, t1 = min(Tv, t0 + per);
-            float run = 0.f;
-            for (int t = t0; t < t1; ++t) run += logf(fminf(fmaxf(1.f - sc[t], 1.17549435e-38f), 1.f));
-            float incl = wave_incl_scan(run, tid);
-            float base = incl - run;
-            for (int t = t0; t < t1; ++t) {
-                const float lg = logf(fminf(fmaxf(1.f - sc[t], 1.17549435e-38f), 1.f));
-                al[t] = expf(base);            // exclusive cumprod
-                base += lg;
-            }
-            // second scan: cumsum(prev / clip(cp, 1e-10, 1))
-            run = 0.f;
-            for (int t = t0; t < t1; ++t) run += pv[t] / fminf(fmaxf(al[t], 1e-10f), 1.f);
-            incl = wave_incl_scan(run, tid);
-            base = incl - run;
-            for (int t = t0; t < t1; ++t) {
-                base += pv[t] / fminf(fmaxf(al[t], 1e-10f), 1.f);
-                al[t] = sc[t] * al[t] * base;
-            }
-        }
+    } else if (tid < 64) {
+        gt_bma_align_wave(sc, pv, al, Tv, tid, [](int, float) {});
     }
     }   // !lsa
     __syncthreads();

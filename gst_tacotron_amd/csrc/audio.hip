@@ -19,6 +19,7 @@
 // All of this is a few MFLOP per utterance; the kernels are written for coalesced accesses and zero host round trips,
 // not for a roofline.
 #include <algorithm>
+#include <float.h>
 
 #include "device_utils.h"
 #include "kernels.h"
@@ -229,7 +230,7 @@ __device__ __forceinline__ float gt_gl_ola(const GriffinLimArgs& P, const float*
         acc += frm[(size_t)tt * N + off];
         wss = (float)((double)wss + P.win_sq[off]);      // float32 accumulator, float64 addend (filters.window_sumsquare)
     }
-    return wss > 1.17549435e-38f ? acc / wss : acc;
+    return wss > FLT_MIN ? acc / wss : acc;        // (librosa: the smallest normal float32)
 }
 
 template <bool INIT>

@@ -138,15 +138,18 @@ __global__ __launch_bounds__(FT) void gt_dec_front_lean_kernel(DecFrontArgs P) {
     }
 }
 
-// Z0: the projection launch of the previous step already produced this step's prenet-0 pre-activations (the projection and
-// the first prenet Dense are both linear: frame.W0 + b0 = [h2|ctx].(Wp_last.W0) + (bp_last.W0 + b0), DecFrontArgs::z0), so the
-// chain starts at prenet 1 and the query weights are requested at kernel start in place of prenet 0's.
-// sum helper of the LSA score epilogue: the value of another lane of the same 16-lane row (DPP control word CTRL), no LDS round trip
+// sum helper of the LSA score epilogue: the value of another lane of the same 16-lane row (DPP control word CTRL), no LDS round trip.
+// Its four uses are the additions of gt_row_sum<16>, spelled with a zero `old` operand.  Kept beside gt_row_sum: through it the scratch
+// size of four LSA instantiations of gt_dec_front_kernel changes (<8,1,Z0,1,EXACT> 68 -> 0, <8,4,Z0,1,EXACT> 36 -> 0,
+// <8,8,!Z0,1,!EXACT> 132 -> 200 bytes per lane and one more spilled VGPR, <8,8,Z0,2,EXACT> 0 -> 36).
 template <int CTRL>
 __device__ __forceinline__ float front_dpp(float x) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xF, 0xF, false));
 }
 
+// Z0: the projection launch of the previous step already produced this step's prenet-0 pre-activations (the projection and
+// the first prenet Dense are both linear: frame.W0 + b0 = [h2|ctx].(Wp_last.W0) + (bp_last.W0 + b0), DecFrontArgs::z0), so the
+// chain starts at prenet 1 and the query weights are requested at kernel start in place of prenet 0's.
 //
 // LSA (dec_front_lsa.hip): the step-wise location-sensitive extension (reference Modules/Attention/Layers.py:345-424) in
 // the same kernel.  Per utterance and step it is two small GEMMs -- location features  lfeat[t][f] = cb[f] + sum_j state[t+j-pad].cw[j][f]
@@ -470,52 +473,25 @@ __global__ __launch_bounds__(FT) void gt_dec_front_kernel(DecFrontArgs P) {
             continue;
         }
         const int t = c * ROWS + row;
-        f32x2 s2 = {0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            const int a0 = 4 * (li + L * j);
-            const float4 m4 = *reinterpret_cast<const float4*>(tile + row * LD + a0);
-            const float4 q4 = *reinterpret_cast<const float4*>(qs + a0);
-            const float4 w4 = *reinterpret_cast<const float4*>(vs + a0);
-            s2 = __builtin_elementwise_fma(f32x2{w4.x, w4.y}, gt_tanh2(f32x2{q4.x, q4.y} + f32x2{m4.x, m4.y}), s2);
-            s2 = __builtin_elementwise_fma(f32x2{w4.z, w4.w}, gt_tanh2(f32x2{q4.z, q4.w} + f32x2{m4.z, m4.w}), s2);
-        }
-        float s = s2.x + s2.y;
-        s = gt_row_sum<L>(s);
+        const float s = gt_score_row<L, NP, LD>(tile, row, qs, vs, li);
         if (li == 0 && t < Tv) sc[t] = s + sbias;
     }
     __syncthreads();
     GT_STAMP(P.dbg, 5);
     // ---- noise + sigmoid + alignment
     if (LSA) {
-        // softmax (or the smoothing normalisation, Layers.py:426-444) over the Tv positions: one wave, a serial run per lane;
         // the state the next step's location features read is the running sum of the alignments (or the last one)
-        if (tid < 64) {
-            const int per = (Tv + 63) / 64;
-            const int t0 = lane * per, t1 = min(Tv, t0 + per);
-            float mx = -INFINITY;
-            for (int t = t0; t < t1; ++t) mx = fmaxf(mx, sc[t]);
-            mx = gt_wave_max(mx);
-            float sum = 0.f;
-            for (int t = t0; t < t1; ++t) {
-                const float e = P.lsa_smoothing ? 1.f / (1.f + expf(-sc[t])) : expf(sc[t] - mx);
-                al[t] = e;
-                sum += e;
-            }
-            sum = gt_wave_sum(sum);
-            const float inv = 1.f / sum;
-            for (int t = t0; t < t1; ++t) {
-                al[t] *= inv;
-                P.lsa_state[(size_t)b * TvFull + t] = P.lsa_cumulate ? pv[t] + al[t] : al[t];
-            }
-        }
+        if (tid < 64)
+            gt_softmax_align_wave(sc, al, Tv, lane, P.lsa_smoothing != 0, [&](const int t, const float a) {
+                P.lsa_state[(size_t)b * TvFull + t] = P.lsa_cumulate ? pv[t] + a : a;
+            });
     } else if (P.type == GSTTACO_ATT_SMA) {
         // each position needs its own and its left neighbour's probability: both sigmoids are evaluated here (same
         // arithmetic as a separate sigmoid pass, one barrier and one LDS round trip fewer)
         for (int t = tid; t < Tv; t += FT) {
             const bool nz = P.sigmoid_noise > 0.f;
             float v = pv[t] * gt_sigmoid(sc[t] + (nz ? snz[t] : 0.f));
-            if (t > 0) v = __builtin_fmaf(pv[t - 1], 1.f - gt_sigmoid(sc[t - 1] + (nz ? snz[t - 1] : 0.f)), v);
+            if (t > 0) v = gt_sma(v, pv[t - 1], gt_sigmoid(sc[t - 1] + (nz ? snz[t - 1] : 0.f)));
             al[t] = v;
         }
     } else {
@@ -526,25 +502,7 @@ __global__ __launch_bounds__(FT) void gt_dec_front_kernel(DecFrontArgs P) {
         }
         __syncthreads();
     }
-    if (!LSA && P.type != GSTTACO_ATT_SMA && tid < 64) {
-        const int per = (Tv + 63) / 64;
-        const int t0 = lane * per, t1 = min(Tv, t0 + per);
-        float run = 0.f;
-        for (int t = t0; t < t1; ++t) run += logf(fminf(fmaxf(1.f - sc[t], 1.17549435e-38f), 1.f));
-        float base = front_wave_incl_scan(run, lane) - run;
-        for (int t = t0; t < t1; ++t) {
-            const float lg = logf(fminf(fmaxf(1.f - sc[t], 1.17549435e-38f), 1.f));
-            al[t] = expf(base);
-            base += lg;
-        }
-        run = 0.f;
-        for (int t = t0; t < t1; ++t) run += pv[t] / fminf(fmaxf(al[t], 1e-10f), 1.f);
-        base = front_wave_incl_scan(run, lane) - run;
-        for (int t = t0; t < t1; ++t) {
-            base += pv[t] / fminf(fmaxf(al[t], 1e-10f), 1.f);
-            al[t] = sc[t] * al[t] * base;
-        }
-    }
+    if (!LSA && P.type != GSTTACO_ATT_SMA && tid < 64) gt_bma_align_wave(sc, pv, al, Tv, lane, [](int, float) {});
     __syncthreads();
     GT_STAMP(P.dbg, 6);
     for (int t = tid; t < TvFull; t += FT) P.align[(size_t)b * P.ldalign + t] = t < Tv ? al[t] : 0.f;
@@ -561,19 +519,12 @@ __global__ __launch_bounds__(FT) void gt_dec_front_kernel(DecFrontArgs P) {
             store_rows(v);
             __syncthreads();
         }
-        const int nr = min(ROWS, Tv - c * ROWS);
-        const float* alc = al + c * ROWS;
-        float p0 = 0.f, p1 = 0.f;
-        int t = cp;
-        for (; t + CPARTS < nr; t += 2 * CPARTS) {
-            p0 = __builtin_fmaf(alc[t], tile[t * LD + ca], p0);
-            p1 = __builtin_fmaf(alc[t + CPARTS], tile[(t + CPARTS) * LD + ca], p1);
-        }
-        if (t < nr) p0 = __builtin_fmaf(alc[t], tile[t * LD + ca], p0);
-        cacc += p0 + p1;
+        cacc += gt_ctx_rows<CPARTS, LD>(al + c * ROWS, tile, ca, cp, min(ROWS, Tv - c * ROWS));
     }
     red[cp * A + ca] = cacc;
     __syncthreads();
+    // (the reduction stays written out here and in front_lean.h: as a shared function, in each of four spellings tried, the
+    // <8, 8, Z0 = false, LEAN = 1, LSA> instantiation of this kernel spills one more VGPR)
     for (int a = tid; a < A; a += FT) {
         float v[CPARTS];
 #pragma unroll

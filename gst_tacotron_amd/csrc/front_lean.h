@@ -213,18 +213,7 @@ __device__ __forceinline__ void gt_front_lean(const DecFrontArgs& P, float* smem
             __syncthreads();
         }
         const int t = c * ROWS + row;
-        f32x2 s2 = {0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            const int a0 = 4 * (li + L * j);
-            const float4 m4 = *reinterpret_cast<const float4*>(tile + row * LD + a0);
-            const float4 q4 = *reinterpret_cast<const float4*>(qs + a0);
-            const float4 w4 = *reinterpret_cast<const float4*>(vs + a0);
-            s2 = __builtin_elementwise_fma(f32x2{w4.x, w4.y}, gt_tanh2(f32x2{q4.x, q4.y} + f32x2{m4.x, m4.y}), s2);
-            s2 = __builtin_elementwise_fma(f32x2{w4.z, w4.w}, gt_tanh2(f32x2{q4.z, q4.w} + f32x2{m4.z, m4.w}), s2);
-        }
-        float s = s2.x + s2.y;
-        s = gt_row_sum<L>(s);
+        const float s = gt_score_row<L, NP, LD>(tile, row, qs, vs, li);
         if (li == 0 && t < Tv) sc[t] = s + sbias;
     }
     __syncthreads();
@@ -234,9 +223,7 @@ __device__ __forceinline__ void gt_front_lean(const DecFrontArgs& P, float* smem
         if (tid < Tv) {
             const int t = tid;
             float v = pv[t] * gt_sigmoid(sc[t] + (noisy ? snz[t] : 0.f));
-            // (explicit fma: `a*b + c*d` may contract around either product, and this kernel, the general one and the persistent decode
-            // kernel must round alike -- their outputs are compared bitwise)
-            if (t > 0) v = __builtin_fmaf(pv[t - 1], 1.f - gt_sigmoid(sc[t - 1] + (noisy ? snz[t - 1] : 0.f)), v);
+            if (t > 0) v = gt_sma(v, pv[t - 1], gt_sigmoid(sc[t - 1] + (noisy ? snz[t - 1] : 0.f)));
             al[t] = v;
         }
     } else {
@@ -247,25 +234,7 @@ __device__ __forceinline__ void gt_front_lean(const DecFrontArgs& P, float* smem
         }
         __syncthreads();
     }
-    if (P.type != GSTTACO_ATT_SMA && tid < 64) {
-        const int per = (Tv + 63) / 64;
-        const int t0 = lane * per, t1 = min(Tv, t0 + per);
-        float run = 0.f;
-        for (int t = t0; t < t1; ++t) run += logf(fminf(fmaxf(1.f - sc[t], 1.17549435e-38f), 1.f));
-        float base = front_wave_incl_scan(run, lane) - run;
-        for (int t = t0; t < t1; ++t) {
-            const float lg = logf(fminf(fmaxf(1.f - sc[t], 1.17549435e-38f), 1.f));
-            al[t] = expf(base);
-            base += lg;
-        }
-        run = 0.f;
-        for (int t = t0; t < t1; ++t) run += pv[t] / fminf(fmaxf(al[t], 1e-10f), 1.f);
-        base = front_wave_incl_scan(run, lane) - run;
-        for (int t = t0; t < t1; ++t) {
-            base += pv[t] / fminf(fmaxf(al[t], 1e-10f), 1.f);
-            al[t] = sc[t] * al[t] * base;
-        }
-    }
+    if (P.type != GSTTACO_ATT_SMA && tid < 64) gt_bma_align_wave(sc, pv, al, Tv, lane, [](int, float) {});
     __syncthreads();
     GT_LSTAMP(6);
     if (tid < TvFull) P.align[(size_t)b * P.ldalign + tid] = tid < Tv ? al[tid] : 0.f;
@@ -282,16 +251,7 @@ __device__ __forceinline__ void gt_front_lean(const DecFrontArgs& P, float* smem
             store_rows(v);
             __syncthreads();
         }
-        const int nr = min(ROWS, Tv - c * ROWS);
-        const float* alc = al + c * ROWS;
-        float p0 = 0.f, p1 = 0.f;
-        int t = cp;
-        for (; t + CPARTS < nr; t += 2 * CPARTS) {
-            p0 = __builtin_fmaf(alc[t], tile[t * LD + ca], p0);
-            p1 = __builtin_fmaf(alc[t + CPARTS], tile[(t + CPARTS) * LD + ca], p1);
-        }
-        if (t < nr) p0 = __builtin_fmaf(alc[t], tile[t * LD + ca], p0);
-        cacc += p0 + p1;
+        cacc += gt_ctx_rows<CPARTS, LD>(al + c * ROWS, tile, ca, cp, min(ROWS, Tv - c * ROWS));
     }
     red[cp * A + ca] = cacc;
     __syncthreads();

@@ -863,35 +863,19 @@ __device__ __forceinline__ void pd_chain_rest(const PersistDecodeArgs& A, const 
     // pass reads them as four 16-byte words instead of sixteen broadcast reads (a third of its LDS instructions); rows >= Tv: zeros.
     // In the slabs behind the context's row-group sums: free between the query's reduction and the cells' first spill.
     float* alp = L.red + 8 * PD_A;
+    const auto to_alp = [&](const int tt, const float a) {
+        if (TV128) alp[(tt & 7) * 16 + (tt >> 3)] = a;
+    };
     if (LSA) {
-        // softmax (or the smoothing normalisation, Layers.py:426-444) over the Tv positions: one wave, a serial run per lane (front_body.h)
-        if (tid < 64) {
-            const int per = (Tv + 63) / 64;
-            const int t0 = lane * per, t1 = min(Tv, t0 + per);
-            float mx = -INFINITY;
-            for (int tt = t0; tt < t1; ++tt) mx = fmaxf(mx, L.sc[tt]);
-            mx = gt_wave_max(mx);
-            float sum = 0.f;
-            for (int tt = t0; tt < t1; ++tt) {
-                const float e = A.lsa_smoothing ? 1.f / (1.f + expf(-L.sc[tt])) : expf(L.sc[tt] - mx);
-                L.al[tt] = e;
-                sum += e;
-            }
-            sum = gt_wave_sum(sum);
-            const float inv = 1.f / sum;
-            for (int tt = t0; tt < t1; ++tt) {
-                L.al[tt] *= inv;
-                if (TV128) alp[(tt & 7) * 16 + (tt >> 3)] = L.al[tt];
-            }
-        }
+        if (tid < 64) gt_softmax_align_wave(L.sc, L.al, Tv, lane, A.lsa_smoothing != 0, to_alp);
         if (TV128 && tid >= Tv && tid < 128) alp[(tid & 7) * 16 + (tid >> 3)] = 0.f;
     } else if (A.att_type == GSTTACO_ATT_SMA) {
         if (tid < Tv) {
             const int tt = tid;
             float v = L.pv[tt] * gt_sigmoid(L.sc[tt] + (R.noisy ? L.nz[tt] : 0.f));
-            if (tt > 0) v = __builtin_fmaf(L.pv[tt - 1], 1.f - gt_sigmoid(L.sc[tt - 1] + (R.noisy ? L.nz[tt - 1] : 0.f)), v);
+            if (tt > 0) v = gt_sma(v, L.pv[tt - 1], gt_sigmoid(L.sc[tt - 1] + (R.noisy ? L.nz[tt - 1] : 0.f)));
             L.al[tt] = v;
-            if (TV128) alp[(tt & 7) * 16 + (tt >> 3)] = v;
+            to_alp(tt, v);
         } else if (TV128 && tid < 128) alp[(tid & 7) * 16 + (tid >> 3)] = 0.f;
     } else {
         if (tid < Tv) {
@@ -900,26 +884,7 @@ __device__ __forceinline__ void pd_chain_rest(const PersistDecodeArgs& A, const 
             L.sc[tid] = gt_sigmoid(s);
         }
         __syncthreads();
-        if (tid < 64) {
-            const int per = (Tv + 63) / 64;
-            const int t0 = lane * per, t1 = min(Tv, t0 + per);
-            float run = 0.f;
-            for (int tt = t0; tt < t1; ++tt) run += logf(fminf(fmaxf(1.f - L.sc[tt], 1.17549435e-38f), 1.f));
-            float base = front_wave_incl_scan(run, lane) - run;
-            for (int tt = t0; tt < t1; ++tt) {
-                const float lg = logf(fminf(fmaxf(1.f - L.sc[tt], 1.17549435e-38f), 1.f));
-                L.al[tt] = expf(base);
-                base += lg;
-            }
-            run = 0.f;
-            for (int tt = t0; tt < t1; ++tt) run += L.pv[tt] / fminf(fmaxf(L.al[tt], 1e-10f), 1.f);
-            base = front_wave_incl_scan(run, lane) - run;
-            for (int tt = t0; tt < t1; ++tt) {
-                base += L.pv[tt] / fminf(fmaxf(L.al[tt], 1e-10f), 1.f);
-                L.al[tt] = L.sc[tt] * L.al[tt] * base;
-                if (TV128) alp[(tt & 7) * 16 + (tt >> 3)] = L.al[tt];
-            }
-        }
+        if (tid < 64) gt_bma_align_wave(L.sc, L.pv, L.al, Tv, lane, to_alp);
         if (TV128 && tid >= Tv && tid < 128) alp[(tid & 7) * 16 + (tid >> 3)] = 0.f;
     }
     __syncthreads();
@@ -951,19 +916,8 @@ __device__ __forceinline__ void pd_chain_rest(const PersistDecodeArgs& A, const 
                 }
                 cacc += p0 + p1;
             } else
-            for (int c = nchunks - 1; c >= 0; --c) {
-                const int nr = min(128, Tv - 128 * c);
-                const float* alc = L.al + 128 * c;
-                const float* tl = L.tile + 128 * c * PD_LDV;
-                float p0 = 0.f, p1 = 0.f;
-                int tt = cp;
-                for (; tt + 8 < nr; tt += 16) {
-                    p0 = __builtin_fmaf(alc[tt], tl[tt * PD_LDV + ca], p0);
-                    p1 = __builtin_fmaf(alc[tt + 8], tl[(tt + 8) * PD_LDV + ca], p1);
-                }
-                if (tt < nr) p0 = __builtin_fmaf(alc[tt], tl[tt * PD_LDV + ca], p0);
-                cacc += p0 + p1;
-            }
+            for (int c = nchunks - 1; c >= 0; --c)
+                cacc += gt_ctx_rows<8, PD_LDV>(L.al + 128 * c, L.tile + 128 * c * PD_LDV, ca, cp, min(128, Tv - 128 * c));
             L.red[cp * PD_A + ca] = cacc;
         }
     }

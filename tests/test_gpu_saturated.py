@@ -18,7 +18,7 @@ PATHS = {
     "persistent": {},                                                                   # persist_decode.hip: the default at <= 128 rows
     "launch": {"GSTTACO_PERSIST_DECODE": "0"},                                          # front_lean.h + fused LSTM + projection per step
     "four_kernel": {"GSTTACO_FUSED_FRONT": "0", "GSTTACO_PERSIST_DECODE": "0"},         # attention.hip
-    "general_front": {"GSTTACO_FUSED_FRONT": "1", "GSTTACO_PERSIST_DECODE": "0"},       # front_body.h: the general fused kernel's own chains
+    "general_front": {"GSTTACO_FUSED_FRONT": "1", "GSTTACO_PERSIST_DECODE": "0"},       # front_body.h: the general fused kernel every step
     # (GSTTACO_LEAN=0 leaves the front end on front_lean.h; it moves the LSTM input halves and the projection to the general skinny GEMM bodies)
     "general": {"GSTTACO_LEAN": "0", "GSTTACO_PERSIST_DECODE": "0"},
 }
@@ -92,10 +92,14 @@ def test_saturated_decode_matches_the_oracle_on_every_path(monkeypatch, name, pa
     if c.token_lengths is not None:
         for b, n in enumerate(c.token_lengths):
             assert not got["persistent"][2][b][:, n:].any()
-    # the persistent launch and the launch path are the same arithmetic in the same order HERE too: a clamp added to one copy of the
-    # BMA / SMA / softmax chain shows up as a difference first
+    # the persistent launch and the launch path are the same arithmetic in the same order HERE too: a clamp that one caller puts around
+    # the shared BMA / SMA / softmax chain shows up as a difference first
     for k, a, b in zip(keys, got["persistent"], got["launch"]):
         assert np.array_equal(a, b), (name, k, float(np.abs(a - b).max()))
+    # the launch path's lean front kernel and the general front kernel call the same chain functions behind heads that sum alike
+    if "general_front" in got:
+        for k, a, b in zip(keys, got["launch"], got["general_front"]):
+            assert np.array_equal(a, b), (name, k, float(np.abs(a - b).max()))
 
 
 def test_saturated_mixed_precision_persistent_is_bitwise_the_launch_path(monkeypatch):
