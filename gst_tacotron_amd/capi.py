@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = (
     "gsttaco_decode_forced", "gsttaco_inference_step_forced", "gsttaco_forced_durations",
     "gsttaco_fill_randomness", "gsttaco_utterance_report",
     "gsttaco_losses", "gsttaco_feature_frontend",
+    "gsttaco_postnet_variants", "gsttaco_debug_wino_h_planes",
 )
 
 # GSTTACO_CONV_V_*: the conv/GEMM dispatcher's kernel instantiations (gsttaco_debug_conv_run reports which one ran)
@@ -48,9 +49,13 @@ CONV_V = {
     "BF16_RM1": 28, "BF16_RM1_XB": 29, "BF16_RM1_OB": 30, "BF16_RM1_XB_OB": 31,
 }
 CONV_V_INVALID = -1
+# GSTTACO_CONV_VH_*: the bounded-input variants (two fp16 planes, three products), numbered on behind CONV_V; a call runs one only with
+# the WINO_SPLIT_H form and a promised bound (ConvCall.x_absmax)
+CONV_VH = {"WINO4_S": 32, "WINO2_S": 33}
 CONV_V_NAMES = {v: k for k, v in CONV_V.items()}
+CONV_V_NAMES.update({v: k + "_H" for k, v in CONV_VH.items()})
 # GSTTACO_CONV_FORM_*: the weight forms gsttaco_debug_conv_prepare builds
-CONV_FORM = {"FP32": 1, "BF16": 2, "WINO2": 4, "WINO4": 8, "WINO_SPLIT": 16, "GEMM_SPLIT": 32}
+CONV_FORM = {"FP32": 1, "BF16": 2, "WINO2": 4, "WINO4": 8, "WINO_SPLIT": 16, "GEMM_SPLIT": 32, "WINO_SPLIT_H": 64}
 
 
 class ConvDesc(ctypes.Structure):
@@ -64,7 +69,9 @@ class ConvCall(ctypes.Structure):
                 ("pool2", ctypes.c_int32), ("x_bf16", ctypes.c_int32), ("out_bf16", ctypes.c_int32), ("wino_x3", ctypes.c_int32),
                 ("wino_min_wgs", ctypes.c_int32),
                 ("conv2d", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("Wo", ctypes.c_int32), ("kw", ctypes.c_int32),
-                ("stride", ctypes.c_int32), ("pad_h", ctypes.c_int32), ("pad_w", ctypes.c_int32), ("xb", ctypes.c_int64)]
+                ("stride", ctypes.c_int32), ("pad_h", ctypes.c_int32), ("pad_w", ctypes.c_int32),
+                ("x_absmax", ctypes.c_float),       # (in what was the padding in front of xb: size and offsets unchanged)
+                ("xb", ctypes.c_int64)]
 
 _I32A = ctypes.c_int32 * MAX_LAYERS
 
@@ -174,6 +181,12 @@ def load_library(path=None):
     lib.gsttaco_debug_conv_prepare.restype = ctypes.c_int
     lib.gsttaco_debug_conv_run.argtypes = [vp, i32, ctypes.POINTER(ConvCall), vp, vp, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int), vp]
     lib.gsttaco_debug_conv_run.restype = ctypes.c_int
+    if hasattr(lib, "gsttaco_postnet_variants"):       # (an older build of the same ABI given through GSTTACO_LIB, for A/B, has neither)
+        lib.gsttaco_postnet_variants.argtypes = [vp, i32, i32, ctypes.POINTER(ctypes.c_int32)]
+        lib.gsttaco_postnet_variants.restype = ctypes.c_int
+        lib.gsttaco_debug_wino_h_planes.argtypes = [ctypes.POINTER(ctypes.c_double), i32, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_uint16),
+                                                    ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
+        lib.gsttaco_debug_wino_h_planes.restype = ctypes.c_int
     for fn in ("gsttaco_create", "gsttaco_num_weights", "gsttaco_weight_info", "gsttaco_load_weight",
                "gsttaco_finalize_weights", "gsttaco_encode", "gsttaco_gst", "gsttaco_decode", "gsttaco_postnet", "gsttaco_vocoder",
                "gsttaco_inference_step", "gsttaco_set_profiling", "gsttaco_get_profile", "gsttaco_mel_frontend",

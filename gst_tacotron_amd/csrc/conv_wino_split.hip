@@ -19,6 +19,11 @@
 // [3][128 columns][32 k] bf16 with the four 16-byte chunks of a column XOR-swizzled by (column / 8) % 4: a ds_read_b128 is served in four
 // groups of 16 lanes -- {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32 -- over 64 banks, and the column quads {0, 3, 5, 6} /
 // {1, 2, 4, 7} of a group then sit at four different chunk positions (unpadded, conflict-free for the reads and the 16-byte stores).
+//
+// A third plane mode for calls whose input is BOUNDED by construction (|x| <= 1: the postnet layers behind a tanh): two fp16 planes per
+// operand and three products (hh, hl, lh) at 22 significand bits -- two thirds of the plane bytes and half the MFMAs of x6 at the fp32
+// chain's accuracy, with the input transform scaled by 2^SV and every weight column by 2^SU[n] so that both operands sit inside fp16's
+// 5-bit exponent range; limited to those layers because without a bound on |x| no fixed scaling does that.  See H3 below.
 #include "wino_common.h"
 #include <type_traits>
 
@@ -52,10 +57,40 @@ __device__ __forceinline__ void ws_split(const float v, __bf16& h, __bf16& m, __
 // X3 (knob GSTTACO_WINO_SPLIT=3, NOT the default): only the planes hi and mid of both operands and the products hh, hm, mh -- what the review
 // priced as "three products = 5.3 x at ~2^-16": half the MFMAs, two thirds of the plane traffic; what is dropped (mm, hl, lh) is ~2^-17 of
 // |a b| per product, 9.3 units of 2^-24 sum|a b| on K = 2 048 dot products against x6's 3.0 and the fp32 chain's 2.7 (tools/split_bf16.hip).
-template <int MO, bool X3>
+//
+// H3 (the default WHERE THE CALL SITE PROMISES |x| <= 1, i.e. behind a tanh: gt_wino5h_takes): two FP16 planes per operand and the products
+// hh, hl, lh into the same single accumulator -- the x3 knob's skeleton (two thirds of the plane bytes, half the MFMAs;
+// v_mfma_f32_32x32x16_f16 has the bf16 form's rate and lane maps), but 11 + 11 = 22 significand bits instead of 8 + 8: what is dropped
+// (ll) is below 2^-22 of |a b|.  fp16 has a 5-bit exponent, so both operands are brought into its range by construction:
+//   V: |x| <= 1 and the input transform's largest row sum (15 / 3) bound |V|; the transform carries the factor 2^SV (ws_h_sv(): the
+//      largest power of two with rowsum . bound . 2^SV <= 2^15 -- 2^11, |V 2^SV| <= 30 720 < 65 504), folded into its coefficients
+//      (a power of two: exact).  hi = fp16(v), lo = fp16(v - hi).
+//   U: static.  Finalize scales column n by 2^SU[n] so that its largest |U| lies in [2^13, 2^14] (gsttaco.cpp wino_split_h_planes).
+//   The epilogue's per-column scale is the layer's scale times 2^-(SV + SU[n]) (ConvGemmArgs::wino_hsc): y * sc + sh as before.
+// With both scalings every low plane that carries weight is a NORMAL fp16 number: the result does not depend on whether the matrix
+// unit flushes fp16 subnormals.  Without a bound on |x| (postnet layer 0: mels; the encoder: ReLU outputs) the form is not offered.
+enum { WS_X6 = 0, WS_X3 = 1, WS_H3 = 2 };      // plane modes
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+
+// SV of the H3 mode, from the promised bound and the larger of the two transforms' row sums (one value: the host folds it into one
+// scale array per transform)
+constexpr int ws_h_sv() {
+    const float reach = (Wino<4>::bt_rowsum() > Wino<2>::bt_rowsum() ? Wino<4>::bt_rowsum() : Wino<2>::bt_rowsum()) * GT_WINO_H_XMAX;
+    int sv = 0;
+    while (reach * (float)(2 << sv) <= 32768.f) ++sv;
+    return sv;
+}
+constexpr int WS_SV = ws_h_sv();
+
+template <int MO, int PM>
 __global__ __launch_bounds__(WT, 2) void gt_conv_wino5s_kernel(ConvGemmArgs A, const __bf16* __restrict__ Us, const int npad) {
     constexpr int AL = Wino<MO>::ALPHA;
+    constexpr bool X3 = PM != WS_X6, H3 = PM == WS_H3;
     constexpr int NPL = X3 ? 2 : 3;             // planes moved and multiplied
+    constexpr int NST = H3 ? 2 : 3;             // planes per xi in memory (the x3 knob reads the first two of x6's three)
+    constexpr float VS = H3 ? (float)(1 << WS_SV) : 1.f;      // H3: the input transform's power-of-two factor
+    static_assert(!H3 || Wino<MO>::bt_rowsum() * GT_WINO_H_XMAX * VS <= 32768.f, "the scaled transform must stay inside fp16");
     extern __shared__ __attribute__((aligned(16))) __bf16 ws_lds[];
     __bf16* As = ws_lds;                            // [2][3][64][WS_LDA]
     __bf16* Bs = ws_lds + 2 * WS_A_STAGE;           // [3][3][128][32]
@@ -95,7 +130,7 @@ __global__ __launch_bounds__(WT, 2) void gt_conv_wino5s_kernel(ConvGemmArgs A, c
     // of 24 KB per step were 300 cycles of the CU's store path).  A DMA instruction writes its 64 lanes' 16 bytes side by side = 16
     // columns of one plane; wave w fills columns 16 w .. 16 w + 15 of each plane; lane l: column l / 4 of the sixteen, position l % 4, for
     // which it FETCHES logical chunk (l % 4) ^ swizzle(column) -- the swizzle costs the DMA nothing and the fragment reads undo it.
-    const auto rs_u = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(Us), 0, (int)((size_t)AL * 3 * npad * A.wino_cin * 2), 0x00020000);
+    const auto rs_u = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(Us), 0, (int)((size_t)AL * NST * npad * A.wino_cin * 2), 0x00020000);
     const int bcol = __builtin_amdgcn_readfirstlane(wave) * 16 + (lane >> 2);
     const uint32_t vb = (uint32_t)((((n0 + bcol) * A.wino_cin) + (((lane & 3) ^ ((bcol >> 3) & 3)) * 8)) * 2);
     const uint32_t lds_b = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)Bs + (uint32_t)(__builtin_amdgcn_readfirstlane(wave) * 16 * WS_BK * 2);
@@ -103,7 +138,7 @@ __global__ __launch_bounds__(WT, 2) void gt_conv_wino5s_kernel(ConvGemmArgs A, c
     auto dma_b = [&](const int st, const int xi, const int c0) {
 #pragma unroll
         for (int p = 0; p < NPL; ++p)
-            ws_lds_dma16(rs_u, lds_b + (uint32_t)((st * WS_B_STAGE + p * WS_BN * WS_BK) * 2), vb, (uint32_t)((((size_t)(xi * 3 + p) * npad) * A.wino_cin + c0) * 2));
+            ws_lds_dma16(rs_u, lds_b + (uint32_t)((st * WS_B_STAGE + p * WS_BN * WS_BK) * 2), vb, (uint32_t)((((size_t)(xi * NST + p) * npad) * A.wino_cin + c0) * 2));
     };
     // the NEXT step's A planes, in four pieces that are dealt between the current step's MFMAs below: transform of channels (0, 1) /
     // (2, 3) of this thread's quad, split of each pair, one 8-byte store per plane
@@ -112,12 +147,18 @@ __global__ __launch_bounds__(WT, 2) void gt_conv_wino5s_kernel(ConvGemmArgs A, c
         f32x2 v = {0.f, 0.f};
 #pragma unroll
         for (int tap = 0; tap < AL; ++tap) {
-            const float cf = Wino<MO>::bt(XI, tap);
+            const float cf = Wino<MO>::bt(XI, tap) * VS;
             if (cf != 0.f) v = __builtin_elementwise_fma((f32x2){cf, cf}, HALF ? (f32x2){d[tap].z, d[tap].w} : (f32x2){d[tap].x, d[tap].y}, v);
         }
         return v;
     };
     auto split2 = [&](const f32x2 v, bf16x2& h, bf16x2& m, bf16x2& l) {
+        if constexpr (H3) {         // two fp16 planes (their bits travel in the bf16-typed fragments); the remainder is exact in fp32
+            const f16x2 hh = {(_Float16)v[0], (_Float16)v[1]};
+            const f16x2 ll = {(_Float16)(v[0] - (float)hh[0]), (_Float16)(v[1] - (float)hh[1])};
+            h = __builtin_bit_cast(bf16x2, hh); m = __builtin_bit_cast(bf16x2, ll); l = m;
+            return;
+        }
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
             __bf16 he, me, le;
@@ -144,7 +185,9 @@ __global__ __launch_bounds__(WT, 2) void gt_conv_wino5s_kernel(ConvGemmArgs A, c
 #ifdef WS_NO_MFMA
 #define WS_MFMA(ACC, x, y) ACC[0] += (float)(x)[0] + (float)(y)[1]
 #else
-#define WS_MFMA(ACC, x, y) ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, ACC, 0, 0, 0)
+#define WS_MFMA(ACC, x, y)                                                                                         \
+        do { if constexpr (H3) ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, x), __builtin_bit_cast(f16x8, y), ACC, 0, 0, 0); \
+             else ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, ACC, 0, 0, 0); } while (0)
 #endif
 #define WS_MFMA6(ACC, x, y) do { if (!X3) WS_MFMA(ACC, x, y); } while (0)      /* (the products x6 has and x3 drops) */
 #define WS_FENCE() __builtin_amdgcn_sched_barrier(0)
@@ -406,25 +449,36 @@ __global__ __launch_bounds__(WT, 2) void gt_gemm_split_kernel(ConvGemmArgs A, co
 
 hipError_t gt_conv_wino5s_init() {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gt_gemm_split_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, GS_LDS_BYTES);
-#define WS_ATTR(MO, X3) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(gt_conv_wino5s_kernel<MO, X3>), hipFuncAttributeMaxDynamicSharedMemorySize, WS_LDS_BYTES);
-    WS_ATTR(4, false) WS_ATTR(2, false) WS_ATTR(4, true) WS_ATTR(2, true)
+#define WS_ATTR(MO, PM) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(gt_conv_wino5s_kernel<MO, PM>), hipFuncAttributeMaxDynamicSharedMemorySize, WS_LDS_BYTES);
+    WS_ATTR(4, WS_X6) WS_ATTR(2, WS_X6) WS_ATTR(4, WS_X3) WS_ATTR(2, WS_X3) WS_ATTR(4, WS_H3) WS_ATTR(2, WS_H3)
 #undef WS_ATTR
     return e;
 }
 
-// mo = 4 / 2: which transform (the caller -- gt_launch_conv_gemm -- has applied the grid-fill rule); planes = a.wino_s4 / a.wino_s
+int gt_wino5h_sv() { return WS_SV; }
+
+// mo = 4 / 2: which transform (the caller -- gt_launch_conv_gemm -- has applied the grid-fill rule); planes = a.wino_s4 / a.wino_s, or
+// a.wino_h4 / a.wino_h where the call's input is bounded (gt_wino5h_takes: what gt_conv_gemm_variant reported)
 hipError_t gt_launch_conv_wino5s(const ConvGemmArgs& a, int mo, hipStream_t stream) {
     const int nb = (a.N + WS_BN - 1) / WS_BN;
     const int P = a.B * ((a.T + mo - 1) / mo);
     const dim3 grid(8 * (((P + WS_BMP - 1) / WS_BMP + 7) / 8) * nb);
-    const __bf16* planes = reinterpret_cast<const __bf16*>(mo == 4 ? a.wino_s4 : a.wino_s);
-    if (a.wino_x3) {        // (the knob's reduced form: two planes, three products)
-        if (mo == 4) hipLaunchKernelGGL((gt_conv_wino5s_kernel<4, true>), grid, dim3(WT), WS_LDS_BYTES, stream, a, planes, a.wino_npad);
-        else hipLaunchKernelGGL((gt_conv_wino5s_kernel<2, true>), grid, dim3(WT), WS_LDS_BYTES, stream, a, planes, a.wino_npad);
+    if (gt_wino5h_takes(a, mo)) {       // two fp16 planes, three products; the epilogue's scale is the one that undoes 2^(SV + SU[n])
+        ConvGemmArgs h = a;
+        h.scale = mo == 4 ? a.wino_hsc4 : a.wino_hsc;
+        const __bf16* hp = reinterpret_cast<const __bf16*>(mo == 4 ? a.wino_h4 : a.wino_h);
+        if (mo == 4) hipLaunchKernelGGL((gt_conv_wino5s_kernel<4, WS_H3>), grid, dim3(WT), WS_LDS_BYTES, stream, h, hp, a.wino_npad);
+        else hipLaunchKernelGGL((gt_conv_wino5s_kernel<2, WS_H3>), grid, dim3(WT), WS_LDS_BYTES, stream, h, hp, a.wino_npad);
         return hipGetLastError();
     }
-    if (mo == 4) hipLaunchKernelGGL((gt_conv_wino5s_kernel<4, false>), grid, dim3(WT), WS_LDS_BYTES, stream, a, planes, a.wino_npad);
-    else hipLaunchKernelGGL((gt_conv_wino5s_kernel<2, false>), grid, dim3(WT), WS_LDS_BYTES, stream, a, planes, a.wino_npad);
+    const __bf16* planes = reinterpret_cast<const __bf16*>(mo == 4 ? a.wino_s4 : a.wino_s);
+    if (a.wino_x3) {        // (the knob's reduced form: two planes, three products)
+        if (mo == 4) hipLaunchKernelGGL((gt_conv_wino5s_kernel<4, WS_X3>), grid, dim3(WT), WS_LDS_BYTES, stream, a, planes, a.wino_npad);
+        else hipLaunchKernelGGL((gt_conv_wino5s_kernel<2, WS_X3>), grid, dim3(WT), WS_LDS_BYTES, stream, a, planes, a.wino_npad);
+        return hipGetLastError();
+    }
+    if (mo == 4) hipLaunchKernelGGL((gt_conv_wino5s_kernel<4, WS_X6>), grid, dim3(WT), WS_LDS_BYTES, stream, a, planes, a.wino_npad);
+    else hipLaunchKernelGGL((gt_conv_wino5s_kernel<2, WS_X6>), grid, dim3(WT), WS_LDS_BYTES, stream, a, planes, a.wino_npad);
     return hipGetLastError();
 }
 

@@ -898,14 +898,15 @@ int gt_conv_gemm_variant(const ConvGemmArgs& a) {
     if (gt_conv_wino5_applies(a)) {
         // worth it when the grid (nearly) fills the chip: the 4096-row encoder convs would leave half of it idle (one round of
         // 128 Winograd workgroups ~275 us against 136 us for the implicit GEMM); 250 workgroups (the 512 -> 80 layer) do pay.
-        // F(4,5) where its (half as large) grid still does, else F(2,5).
+        // F(4,5) where its (half as large) grid still does, else F(2,5).  Behind a promised input bound (a.x_absmax, with the fp16
+        // planes: gt_wino5h_takes) the same choice runs the split kernel's fp16 x3 form.
         const int min_wgs = a.wino_min_wgs > 0 ? a.wino_min_wgs : 240;
         const int nb = (a.N + 127) / 128;
         const int P4 = a.B * ((a.T + 3) / 4), P2 = a.B * ((a.T + 1) / 2);
         if (a.wino_u4 && ((P4 + 63) / 64) * nb >= min_wgs)
-            return a.wino_s4 ? (a.wino_x3 ? GSTTACO_CONV_V_WINO4_S_X3 : GSTTACO_CONV_V_WINO4_S) : GSTTACO_CONV_V_WINO4;
+            return gt_wino5h_takes(a, 4) ? GSTTACO_CONV_VH_WINO4_S : a.wino_s4 ? (a.wino_x3 ? GSTTACO_CONV_V_WINO4_S_X3 : GSTTACO_CONV_V_WINO4_S) : GSTTACO_CONV_V_WINO4;
         if (((P2 + 63) / 64) * nb >= min_wgs)
-            return a.wino_s ? (a.wino_x3 ? GSTTACO_CONV_V_WINO2_S_X3 : GSTTACO_CONV_V_WINO2_S) : GSTTACO_CONV_V_WINO2;
+            return gt_wino5h_takes(a, 2) ? GSTTACO_CONV_VH_WINO2_S : a.wino_s ? (a.wino_x3 ? GSTTACO_CONV_V_WINO2_S_X3 : GSTTACO_CONV_V_WINO2_S) : GSTTACO_CONV_V_WINO2;
     }
     if (a.conv2d) {
         if ((size_t)a.B * a.xb * 4 >= 0x7FFFFFFFull) {
@@ -972,8 +973,8 @@ hipError_t gt_launch_conv_gemm(const ConvGemmArgs& a, hipStream_t stream) {
     GT_V(GSTTACO_CONV_V_BF16_RM1_OB, (gt_conv_gemm_bf16_kernel<1, false, true>), bfg1, 0);
     GT_V(GSTTACO_CONV_V_BF16_RM1_XB_OB, (gt_conv_gemm_bf16_kernel<1, true, true>), bfg1, 0);
     case GSTTACO_CONV_V_GEMM_SPLIT: return gt_launch_gemm_split(a, stream);
-    case GSTTACO_CONV_V_WINO4_S: case GSTTACO_CONV_V_WINO4_S_X3: return gt_launch_conv_wino5s(a, 4, stream);
-    case GSTTACO_CONV_V_WINO2_S: case GSTTACO_CONV_V_WINO2_S_X3: return gt_launch_conv_wino5s(a, 2, stream);
+    case GSTTACO_CONV_V_WINO4_S: case GSTTACO_CONV_V_WINO4_S_X3: case GSTTACO_CONV_VH_WINO4_S: return gt_launch_conv_wino5s(a, 4, stream);
+    case GSTTACO_CONV_V_WINO2_S: case GSTTACO_CONV_V_WINO2_S_X3: case GSTTACO_CONV_VH_WINO2_S: return gt_launch_conv_wino5s(a, 2, stream);
     case GSTTACO_CONV_V_WINO4: hipLaunchKernelGGL(gt_conv_wino5_kernel<4>, wg4, dim3(WT), 0, stream, a, a.wino_u4); break;
     case GSTTACO_CONV_V_WINO2: hipLaunchKernelGGL(gt_conv_wino5_kernel<2>, wg2, dim3(WT), 0, stream, a, a.wino_u); break;
     GT_V(GSTTACO_CONV_V_C2D_1411, (gt_conv_gemm_kernel<1, 4, 1, 1, true>), g32, 0);

@@ -60,7 +60,9 @@ struct ConvLayer {
     int wino_cin = 0;
     void *wino_s = nullptr, *wino_s4 = nullptr;     // WINO_SPLIT: the same U as three bf16 planes [xi][plane][wino_npad][wino_cin] (conv_wino_split.hip)
     void* gemm_s = nullptr;     // GEMM_SPLIT: w as three bf16 planes [plane][wino_npad][taps*Cin] (taps == 1)
-    int wino_npad = 0;          // column padding of the planes (wino_s / wino_s4 / gemm_s)
+    int wino_npad = 0;          // column padding of the planes (wino_s / wino_s4 / gemm_s / wino_h / wino_h4)
+    void *wino_h = nullptr, *wino_h4 = nullptr;     // WINO_SPLIT_H: U[:, n] 2^SU[n] as two fp16 planes [xi][plane][wino_npad][wino_cin] (wino_split_h_planes)
+    float *wino_hsc = nullptr, *wino_hsc4 = nullptr;    // ... and their epilogue scale [Cout]: scale[n] 2^-(SV + SU[n])
 };
 
 // The three launch forms that need their workgroups co-resident and can give up (note_give_up).  The context holds what it still allows
@@ -189,6 +191,8 @@ struct gsttaco_ctx {
     int wino = 4;                // Winograd for the 5-tap Conv1D layers that fill the chip: 4 = F(4,5) where its grid fills the chip and F(2,5)
                                  // otherwise, 2 = F(2,5) only, 0 = implicit GEMM only (GSTTACO_WINO)
     bool wino_x3 = false;        // GSTTACO_WINO_SPLIT=3: the postnet's split kernel with two planes and three products (~2^-16; NOT fp32-accurate)
+    bool wino_split_h = true;    // ... and as two fp16 planes x3 where the input is bounded by construction (the postnet layers behind a
+                                 // tanh); GSTTACO_WINO_SPLIT=6: x6 everywhere
     bool wino_split = true;      // the Winograd layers' transform-domain GEMMs as split-bf16 x6 on the bf16 matrix pipe, fp32 accuracy
                                  // (conv_wino_split.hip; GSTTACO_WINO_SPLIT=0: the fp32-MFMA Winograd kernel)
     int enc_wino = 2;            // the text encoder's five-tap layers behind the token gather on the split-bf16 Winograd kernel (GSTTACO_ENC_WINO)
@@ -641,6 +645,65 @@ int upload_wino_split(gsttaco_ctx* c, void** dst, const std::vector<double>& u, 
     return 0;
 }
 
+// rne(v) as fp16 bits, subnormals kept (|v| < 65 520), and back
+uint16_t f16_bits(double v) {
+    const uint16_t sign = std::signbit(v) ? 0x8000u : 0u;
+    const double a = std::fabs(v);
+    if (a == 0.0) return sign;
+    int e;
+    (void)std::frexp(a, &e);                            // a in [2^(e-1), 2^e)
+    const int E = std::max(e - 1, -14);                 // (below 2^-14: the subnormal quantum 2^-24)
+    const int r = (int)std::nearbyint(std::ldexp(a, 10 - E));      // exact scaling, one rounding to nearest even; 1024 <= r <= 2048 when normal
+    return (uint16_t)(sign | (uint16_t)(a >= std::ldexp(1.0, -14) ? ((E + 15) << 10) + (r - 1024) : r));
+}
+double f16_value(uint16_t b) {
+    const int ex = (b >> 10) & 31, man = b & 1023;
+    const double a = ex ? std::ldexp(1024.0 + man, ex - 25) : std::ldexp((double)man, -24);
+    return (b & 0x8000u) ? -a : a;
+}
+
+// Two-plane fp16 form of the Winograd-domain weights for the bounded-input kernel (conv_wino_split.hip, mode H3).  Plain host code: no
+// device call (gsttaco_debug_wino_h_planes hands it to the CPU tests).  u: the FLOAT64 transform [al][cin][cout].  Per output column n,
+// over every xi and k: SU[n] = floor(log2(2^14 / max|u|)) (0 for an all-zero column) brings the column's largest entry into (2^13, 2^14]
+// -- fp16's 5-bit exponent then holds hi AND the remainder of every entry that matters as normal numbers; hi = fp16(u 2^SU),
+// lo = fp16(u 2^SU - hi) (22 significand bits).  planes: [al][2][npad][wino_cin] fp16 bits, k contiguous, padding zero; su: [cout].
+void wino_split_h_planes(const double* u, int al, int cin, int wino_cin, int cout, int npad, uint16_t* planes, int32_t* su) {
+    std::fill(planes, planes + (size_t)al * 2 * npad * wino_cin, (uint16_t)0);
+    for (int n = 0; n < cout; ++n) {
+        double mx = 0.0;
+        for (int xi = 0; xi < al; ++xi)
+            for (int k = 0; k < cin; ++k) mx = std::max(mx, std::fabs(u[((size_t)xi * cin + k) * cout + n]));
+        int sh = 0;
+        if (mx > 0.0) {
+            int e;
+            const double m = std::frexp(mx, &e);                // mx = m 2^e, m in [0.5, 1)
+            sh = std::min(14 - e + (m == 0.5 ? 1 : 0), 96);       // (a column below 2^-83 keeps a finite epilogue scale)
+        }
+        su[n] = sh;
+        for (int xi = 0; xi < al; ++xi)
+            for (int k = 0; k < cin; ++k) {
+                const double v = std::ldexp(u[((size_t)xi * cin + k) * cout + n], sh);
+                const uint16_t hi = f16_bits(v);
+                planes[(((size_t)xi * 2 + 0) * npad + n) * wino_cin + k] = hi;
+                planes[(((size_t)xi * 2 + 1) * npad + n) * wino_cin + k] = f16_bits(v - f16_value(hi));
+            }
+    }
+}
+
+// ... uploaded, with the epilogue scale that undoes both power-of-two factors: sc[n] 2^-(SV + SU[n]) (sc NULL: the power alone)
+int upload_wino_split_h(gsttaco_ctx* c, void** dst, float** dst_sc, const std::vector<double>& u, int al, int cin, int wino_cin, int cout, int npad,
+                        const float* sc) {
+    std::vector<uint16_t> planes((size_t)al * 2 * npad * wino_cin);
+    std::vector<int32_t> su(cout);
+    wino_split_h_planes(u.data(), al, cin, wino_cin, cout, npad, planes.data(), su.data());
+    std::vector<float> hs(cout);
+    for (int n = 0; n < cout; ++n) hs[n] = std::ldexp(sc ? sc[n] : 1.f, -(gt_wino5h_sv() + su[n]));
+    int rc = dev_alloc(c, dst, planes.size() * 2);
+    if (rc) return rc;
+    HIPCHECK(c, hipMemcpy(*dst, planes.data(), planes.size() * 2, hipMemcpyHostToDevice));
+    return upload(c, dst_sc, hs.data(), hs.size());
+}
+
 // the same for a plain GEMM's weights w [K, N] (row stride ldw): [plane][npad][K], k contiguous (conv_wino_split.hip gt_gemm_split_kernel)
 int upload_gemm_split(gsttaco_ctx* c, void** dst, const float* w, int K, int N, int ldw, int* npad_out) {
     const int npad = (N + 127) / 128 * 128;
@@ -674,16 +737,16 @@ int prepare_conv_forms(gsttaco_ctx* c, ConvLayer* L, const float* w, int taps, i
     if (!rc && (forms & GSTTACO_CONV_FORM_BF16)) rc = upload_bf16_t(c, w, K, cout, ldw, &L->wt_bf16, &L->ldk);
     if (!rc && sc) rc = upload(c, &L->scale, sc, cout);
     if (!rc && sh) rc = upload(c, &L->shift, sh, cout);
-    const bool split = (forms & GSTTACO_CONV_FORM_WINO_SPLIT) != 0;
+    const bool split = (forms & GSTTACO_CONV_FORM_WINO_SPLIT) != 0, split_h = (forms & GSTTACO_CONV_FORM_WINO_SPLIT_H) != 0;
     if (!rc && (forms & (GSTTACO_CONV_FORM_WINO2 | GSTTACO_CONV_FORM_WINO4))) {
         if (taps != 5 || cin % 4 || cout % 4) return fail(c, GSTTACO_E_INVALID, "Winograd forms need taps 5, cin and cout multiples of 4");
         const size_t cn = (size_t)cin * cout;
         L->wino_cin = std::max(128, (cin + 63) / 64 * 64);   // zero rows for the padding channels (an even number >= 4 of 32-channel slices)
         L->wino_npad = (cout + 127) / 128 * 128;
         const size_t cnp = (size_t)L->wino_cin * cout;
-        std::vector<double> ud(split ? 8 * cn : 0);
+        std::vector<double> ud(split || split_h ? 8 * cn : 0);
         // U_xi = sum_k G[xi][k] w[k], formed in float64, [xi][wino_cin][cout]
-        auto transform = [&](const double (*G)[5], int al, float** dst, void** dst_s) {
+        auto transform = [&](const double (*G)[5], int al, float** dst, void** dst_s, void** dst_h, float** dst_hsc) {
             std::vector<float> u(al * cnp, 0.f);
             for (int xi = 0; xi < al; ++xi)
                 for (int ci = 0; ci < cin; ++ci)
@@ -691,10 +754,11 @@ int prepare_conv_forms(gsttaco_ctx* c, ConvLayer* L, const float* w, int taps, i
                         double acc = 0.0;
                         for (int tap = 0; tap < 5; ++tap) acc += G[xi][tap] * (double)w[((size_t)tap * cin + ci) * ldw + n];
                         u[xi * cnp + (size_t)ci * cout + n] = (float)acc;
-                        if (split) ud[xi * cn + (size_t)ci * cout + n] = acc;
+                        if (split || split_h) ud[xi * cn + (size_t)ci * cout + n] = acc;
                     }
             int r = upload(c, dst, u.data(), u.size());
             if (!r && split) r = upload_wino_split(c, dst_s, ud, al, cin, L->wino_cin, cout, L->wino_npad);
+            if (!r && split_h) r = upload_wino_split_h(c, dst_h, dst_hsc, ud, al, cin, L->wino_cin, cout, L->wino_npad, sc);
             return r;
         };
         if (forms & GSTTACO_CONV_FORM_WINO2) {
@@ -705,7 +769,7 @@ int prepare_conv_forms(gsttaco_ctx* c, ConvLayer* L, const float* w, int taps, i
                                            {-8.0 / 3, -4.0 / 3, -2.0 / 3, -1.0 / 3, -1.0 / 6},
                                            {-8.0 / 3, 4.0 / 3, -2.0 / 3, 1.0 / 3, -1.0 / 6},
                                            {0, 0, 0, 0, 1}};
-            rc = transform(G, 6, &L->wino_u, &L->wino_s);
+            rc = transform(G, 6, &L->wino_u, &L->wino_s, &L->wino_h, &L->wino_hsc);
         }
         if (!rc && (forms & GSTTACO_CONV_FORM_WINO4)) {
             // F(4,5), points 0, +-1, +-1/2, +-2, infinity
@@ -717,7 +781,7 @@ int prepare_conv_forms(gsttaco_ctx* c, ConvLayer* L, const float* w, int taps, i
                                             {1.0 / 90, 1.0 / 45, 2.0 / 45, 4.0 / 45, 8.0 / 45},
                                             {1.0 / 90, -1.0 / 45, 2.0 / 45, -4.0 / 45, 8.0 / 45},
                                             {0, 0, 0, 0, 1}};
-            rc = transform(G4, 8, &L->wino_u4, &L->wino_s4);
+            rc = transform(G4, 8, &L->wino_u4, &L->wino_s4, &L->wino_h4, &L->wino_hsc4);
         }
     }
     if (!rc && (forms & GSTTACO_CONV_FORM_GEMM_SPLIT)) {
@@ -736,17 +800,21 @@ ConvGemmArgs conv_args(const ConvLayer& L, int forms) {
     a.Cin = L.cin; a.N = L.cout; a.taps = L.taps;
     if (forms & GSTTACO_CONV_FORM_BF16) { a.wt_bf16 = L.wt_bf16; a.ldk = L.ldk; }
     const bool split = (forms & GSTTACO_CONV_FORM_WINO_SPLIT) != 0;
-    if (forms & GSTTACO_CONV_FORM_WINO2) { a.wino_u = L.wino_u; if (split) a.wino_s = L.wino_s; }
-    if (forms & GSTTACO_CONV_FORM_WINO4) { a.wino_u4 = L.wino_u4; if (split) a.wino_s4 = L.wino_s4; }
+    const bool split_h = (forms & GSTTACO_CONV_FORM_WINO_SPLIT_H) != 0;     // (taken only by a call that also states a.x_absmax)
+    if (forms & GSTTACO_CONV_FORM_WINO2) { a.wino_u = L.wino_u; if (split) a.wino_s = L.wino_s; if (split_h) { a.wino_h = L.wino_h; a.wino_hsc = L.wino_hsc; } }
+    if (forms & GSTTACO_CONV_FORM_WINO4) { a.wino_u4 = L.wino_u4; if (split) a.wino_s4 = L.wino_s4; if (split_h) { a.wino_h4 = L.wino_h4; a.wino_hsc4 = L.wino_hsc4; } }
     if (forms & GSTTACO_CONV_FORM_GEMM_SPLIT) a.gemm_s = L.gemm_s;
     if (a.wino_u || a.wino_u4) a.wino_cin = L.wino_cin;
-    if (a.wino_s || a.wino_s4 || a.gemm_s) a.wino_npad = L.wino_npad;
+    if (a.wino_s || a.wino_s4 || a.gemm_s || a.wino_h || a.wino_h4) a.wino_npad = L.wino_npad;
     return a;
 }
 
+// Postnet layer i reads the output of a tanh (layer i - 1 is one of the first post_tanh layers): |x| <= 1 by construction
+inline bool postnet_input_is_tanh(const gsttaco_config& g, int i) { return i >= 1 && i - 1 < g.post_tanh; }
+
 // What every call may use: FP32, and the bf16 copy mixed precision builds (a call with wt_bf16 takes a bf16 kernel: gt_conv_gemm_variant)
 constexpr int kFormsPlain = GSTTACO_CONV_FORM_FP32 | GSTTACO_CONV_FORM_BF16;
-constexpr int kFormsWino = GSTTACO_CONV_FORM_WINO2 | GSTTACO_CONV_FORM_WINO4 | GSTTACO_CONV_FORM_WINO_SPLIT;
+constexpr int kFormsWino = GSTTACO_CONV_FORM_WINO2 | GSTTACO_CONV_FORM_WINO4 | GSTTACO_CONV_FORM_WINO_SPLIT | GSTTACO_CONV_FORM_WINO_SPLIT_H;
 
 // A Dense (or any taps-1 GEMM) w [K, N], row stride ldw, bias [N] or NULL.  split: the call site may take the plain split-bf16 GEMM
 // (GSTTACO_WINO_SPLIT; mixed precision runs the bf16 kernel instead; its k loop needs K % 32 == 0).
@@ -757,15 +825,17 @@ int upload_dense(gsttaco_ctx* c, ConvLayer* L, const float* w, int K, int N, int
 }
 
 // A Conv1D + BatchNorm layer by manifest name.  wino: the module's call site can pass the Winograd forms of a five-tap layer (mixed
-// precision runs the bf16 five-tap kernel instead and builds none)
-int upload_conv(gsttaco_ctx* c, ConvLayer* L, const std::string& prefix, bool wino) {
+// precision runs the bf16 five-tap kernel instead and builds none); bounded_in: every call of the layer reads the output of a tanh, so
+// the two-plane fp16 form is built too (its call site states the bound: enqueue_postnet)
+int upload_conv(gsttaco_ctx* c, ConvLayer* L, const std::string& prefix, bool wino, bool bounded_in = false) {
     const HostTensor& k = T(c, prefix + ".kernel");
     const int taps = (int)k.shape[0], cin = (int)k.shape[1], cout = (int)k.shape[2];
     std::vector<float> sc, sh;
     fold_bn(c, prefix, sc, sh);
     int forms = GSTTACO_CONV_FORM_FP32 | (c->cfg.mixed_precision ? GSTTACO_CONV_FORM_BF16 : 0);
     if (wino && !c->cfg.mixed_precision && c->wino != 0 && taps == 5 && cin % 4 == 0 && cout % 4 == 0)
-        forms |= GSTTACO_CONV_FORM_WINO2 | (c->wino >= 4 ? GSTTACO_CONV_FORM_WINO4 : 0) | (c->wino_split ? GSTTACO_CONV_FORM_WINO_SPLIT : 0);
+        forms |= GSTTACO_CONV_FORM_WINO2 | (c->wino >= 4 ? GSTTACO_CONV_FORM_WINO4 : 0) | (c->wino_split ? GSTTACO_CONV_FORM_WINO_SPLIT : 0) |
+                 (c->wino_split && c->wino_split_h && bounded_in ? GSTTACO_CONV_FORM_WINO_SPLIT_H : 0);
     return prepare_conv_forms(c, L, k.data.data(), taps, cin, cout, cout, sc.data(), sh.data(), forms);
 }
 
@@ -1542,27 +1612,40 @@ int enqueue_decode(gsttaco_ctx* c, hipStream_t s, const LaunchForms& forms, int 
     return 0;
 }
 
+// Postnet layer i's call without its buffers: everything the kernel choice depends on (enqueue_postnet adds x / out / res;
+// gsttaco_postnet_variants asks gt_conv_gemm_variant about it)
+ConvGemmArgs postnet_call(const gsttaco_ctx* c, int i, int B, int Tf) {
+    const gsttaco_config& g = c->cfg;
+    const ConvLayer& L = c->post_conv[i];
+    ConvGemmArgs a = conv_args(L, kFormsPlain | kFormsWino);       // (everything the layer has)
+    a.wino_x3 = c->wino_x3 ? 1 : 0;
+    a.ldo = L.cout;
+    a.B = B; a.T = Tf;
+    a.pad_before = same_pad_before(Tf, L.taps, 1, nullptr);
+    a.act = i < g.post_tanh ? ACT_TANH : ACT_NONE;     // tanh on the first post_tanh layers only (F9)
+    // THE PROMISE the two-plane fp16 Winograd form needs: this layer reads what layer i - 1's tanh wrote, so |x| <= 1.  Made here and
+    // nowhere else (layer 0 reads the decoder's mels: no bound)
+    a.x_absmax = postnet_input_is_tanh(g, i) ? 1.f : 0.f;
+    // mixed precision: the activations BETWEEN the layers are stored as bf16 -- the next layer rounds them to bf16 on its way into
+    // LDS anyway, so no result changes and half the bytes move; the residual input and the last layer's output stay fp32
+    if (a.wt_bf16) {
+        a.x_bf16 = i > 0 && c->post_conv[i - 1].wt_bf16 ? 1 : 0;
+        // (a bf16 output row is stored as PAIRS of columns: an even channel count only)
+        a.out_bf16 = i != g.n_post - 1 && L.cout % 2 == 0 && c->post_conv[i + 1].wt_bf16 ? 1 : 0;
+    }
+    return a;
+}
+
 int enqueue_postnet(gsttaco_ctx* c, hipStream_t s, int B, int Tf, const float* pre, float* out) {
     const gsttaco_config& g = c->cfg;
     const float* x = pre;
     int cur = 0;
     for (int i = 0; i < g.n_post; ++i) {
-        const ConvLayer& L = c->post_conv[i];
         const bool last = i == g.n_post - 1;
-        ConvGemmArgs a = conv_args(L, kFormsPlain | kFormsWino);       // (everything the layer has)
-        a.x = x; a.wino_x3 = c->wino_x3 ? 1 : 0;
-        a.out = last ? out : c->w_post[cur]; a.ldo = L.cout;
+        ConvGemmArgs a = postnet_call(c, i, B, Tf);
+        a.x = x;
+        a.out = last ? out : c->w_post[cur];
         a.res = last ? pre : nullptr;                       // post = postnet(x) + x (Taco2.py:230)
-        a.B = B; a.T = Tf;
-        a.pad_before = same_pad_before(Tf, L.taps, 1, nullptr);
-        a.act = i < g.post_tanh ? ACT_TANH : ACT_NONE;     // tanh on the first post_tanh layers only (F9)
-        // mixed precision: the activations BETWEEN the layers are stored as bf16 -- the next layer rounds them to bf16 on its way into
-        // LDS anyway, so no result changes and half the bytes move; the residual input and the last layer's output stay fp32
-        if (a.wt_bf16) {
-            a.x_bf16 = i > 0 && c->post_conv[i - 1].wt_bf16 ? 1 : 0;
-            // (a bf16 output row is stored as PAIRS of columns: an even channel count only)
-            a.out_bf16 = !last && L.cout % 2 == 0 && c->post_conv[i + 1].wt_bf16 ? 1 : 0;
-        }
         HIPCHECK(c, gt_launch_conv_gemm(a, s));
         x = a.out; cur ^= 1;
     }
@@ -2058,6 +2141,7 @@ int gsttaco_create(const gsttaco_config* cfg, gsttaco_ctx** out) {
     if (c->wino != 0 && c->wino != 2) c->wino = 4;      // {0, 2, 4}; any other non-zero value (the old boolean's 1 included) means the default
     c->wino_split = env_int("GSTTACO_WINO_SPLIT", 1) != 0;
     c->wino_x3 = env_int("GSTTACO_WINO_SPLIT", 1) == 3;
+    c->wino_split_h = env_int("GSTTACO_WINO_SPLIT", 1) == 1;       // (6: split-bf16 x6 everywhere, for A/B against the two-plane fp16 form)
     c->enc_wino = env_int("GSTTACO_ENC_WINO", 2);
     if (c->enc_wino != 0 && c->enc_wino != 4) c->enc_wino = 2;
     c->pad_dec = env_int("GSTTACO_PAD_DECODER", 1) != 0;
@@ -2270,7 +2354,7 @@ int finalize_decoder_step(gsttaco_ctx* c) {
 int finalize_postnet(gsttaco_ctx* c) {
     int rc = 0;
     c->post_conv.resize(c->cfg.n_post);
-    for (int i = 0; i < c->cfg.n_post && !rc; ++i) rc = upload_conv(c, &c->post_conv[i], "postnet.conv" + std::to_string(i), true);
+    for (int i = 0; i < c->cfg.n_post && !rc; ++i) rc = upload_conv(c, &c->post_conv[i], "postnet.conv" + std::to_string(i), true, postnet_input_is_tanh(c->cfg, i));
     return rc;
 }
 
@@ -2991,7 +3075,7 @@ int gsttaco_debug_conv_prepare(gsttaco_ctx* c, const gsttaco_conv_desc* d, const
     if (!c || !d || !w_host || !id) return GSTTACO_E_INVALID;
     if (!c->finalized) return fail(c, GSTTACO_E_WEIGHTS, "weights not finalized (call gsttaco_finalize_weights)");
     const int ldw = d->ldw ? d->ldw : d->n;
-    if (d->taps < 1 || d->cin < 4 || d->cin % 4 || d->n < 1 || ldw < d->n || ldw % 4 || !(d->forms & GSTTACO_CONV_FORM_FP32) || (d->forms & ~63))
+    if (d->taps < 1 || d->cin < 4 || d->cin % 4 || d->n < 1 || ldw < d->n || ldw % 4 || !(d->forms & GSTTACO_CONV_FORM_FP32) || (d->forms & ~127))
         return fail(c, GSTTACO_E_INVALID, "gsttaco_debug_conv_prepare: bad descriptor");
     gsttaco_ctx::DbgConv e{};
     const int rc = prepare_conv_forms(c, &e.L, w_host, d->taps, d->cin, d->n, ldw, scale_host, shift_host, d->forms);
@@ -3008,7 +3092,7 @@ int gsttaco_debug_conv_run(gsttaco_ctx* c, int id, const gsttaco_conv_call* k, c
     if (id < 0 || id >= (int)c->dbg_conv.size()) return fail(c, GSTTACO_E_INVALID, "gsttaco_debug_conv_run: unknown weight id");
     const ConvLayer& L = c->dbg_conv[id].L;
     const int f = k->forms;
-    if ((f & c->dbg_conv[id].forms) != f || !(f & GSTTACO_CONV_FORM_FP32) || k->B < 1 || k->T < 1 || (k->ldo && k->ldo < L.cout))
+    if ((f & c->dbg_conv[id].forms) != f || !(f & GSTTACO_CONV_FORM_FP32) || k->B < 1 || k->T < 1 || (k->ldo && k->ldo < L.cout) || !(k->x_absmax >= 0.f))
         return fail(c, GSTTACO_E_INVALID, "gsttaco_debug_conv_run: bad call (a form that was not prepared?)");
     // (the weight half through the builder the production call sites use; the call's own half from the caller's fields: no allocation,
     // no synchronisation)
@@ -3016,7 +3100,7 @@ int gsttaco_debug_conv_run(gsttaco_ctx* c, int id, const gsttaco_conv_call* k, c
     a.x = reinterpret_cast<const float*>(x); a.tokens = tokens;
     a.rowbias = rowbias; a.res = res; a.row_len = row_len; a.pool2 = k->pool2;
     a.x_bf16 = k->x_bf16; a.out_bf16 = k->out_bf16;
-    a.wino_x3 = k->wino_x3; a.wino_min_wgs = k->wino_min_wgs;
+    a.wino_x3 = k->wino_x3; a.wino_min_wgs = k->wino_min_wgs; a.x_absmax = k->x_absmax;
     a.out = reinterpret_cast<float*>(out); a.ldo = k->ldo ? k->ldo : L.cout;
     a.B = k->B; a.T = k->T; a.pad_before = k->pad_before; a.act = k->act;
     a.conv2d = k->conv2d; a.H = k->H; a.W = k->W; a.Wo = k->Wo; a.kw = k->kw; a.stride = k->stride; a.pad_h = k->pad_h; a.pad_w = k->pad_w;
@@ -3025,6 +3109,19 @@ int gsttaco_debug_conv_run(gsttaco_ctx* c, int id, const gsttaco_conv_call* k, c
     if (variant) *variant = v;
     if (v == GSTTACO_CONV_V_INVALID) return fail(c, GSTTACO_E_INVALID, "gsttaco_debug_conv_run: no kernel takes this call");
     HIPCHECK(c, gt_launch_conv_gemm(a, reinterpret_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int gsttaco_postnet_variants(const gsttaco_ctx* c, int B, int Tf, int32_t variants[8]) {
+    if (!c || !variants || B < 1 || Tf < 1 || !c->finalized) return GSTTACO_E_INVALID;
+    for (int i = 0; i < c->cfg.n_post && i < 8; ++i) variants[i] = gt_conv_gemm_variant(postnet_call(c, i, B, Tf));
+    return 0;
+}
+
+int gsttaco_debug_wino_h_planes(const double* u, int al, int cin, int wino_cin, int cout, int npad, uint16_t* planes, int32_t* su, int32_t* sv) {
+    if (!u || !planes || !su || al < 1 || cin < 1 || wino_cin < cin || cout < 1 || npad < cout) return GSTTACO_E_INVALID;
+    wino_split_h_planes(u, al, cin, wino_cin, cout, npad, planes, su);
+    if (sv) *sv = gt_wino5h_sv();
     return 0;
 }
 

@@ -218,7 +218,22 @@ struct ConvGemmArgs {
     // x[b][ho*stride + i - pad_h][wo*stride + j - pad_w][c] of an NHWC input with batch stride xb floats; taps = kh*kw.
     int conv2d, H, W, Wo, kw, stride, pad_h, pad_w;
     int64_t xb;
+    // Bounded-input Winograd (conv_wino_split.hip, plane mode fp16 x3): the call site's PROMISE that |x| <= x_absmax everywhere (0 = no
+    // promise: the form is never taken), the same U as TWO fp16 planes of U[:, n] 2^SU[n], [xi][plane][wino_npad][wino_cin], and the
+    // per-column epilogue scale that undoes both scalings: scale[n] 2^-(SV + SU[n]) (the power alone where the layer has no scale).
+    float x_absmax;
+    const void* wino_h;     // F(2,5), or NULL
+    const void* wino_h4;    // F(4,5), or NULL
+    const float* wino_hsc;  // [N] for wino_h
+    const float* wino_hsc4; // [N] for wino_h4
 };
+// The largest bound the fp16 x3 form is built for: its transform-domain scaling 2^SV is derived from it (gt_wino5h_sv).
+constexpr float GT_WINO_H_XMAX = 1.0f;
+// true when `a` may run the fp16 x3 form of transform mo (4 / 2): the planes are there and the site has promised |x| <= GT_WINO_H_XMAX
+inline bool gt_wino5h_takes(const ConvGemmArgs& a, int mo) {
+    return a.x_absmax > 0.f && a.x_absmax <= GT_WINO_H_XMAX && !a.wino_x3 && (mo == 4 ? a.wino_h4 && a.wino_hsc4 : a.wino_h && a.wino_hsc);
+}
+int gt_wino5h_sv();      // SV: the fp16 x3 form's input transform carries the factor 2^SV (conv_wino_split.hip)
 
 hipError_t gt_launch_conv_gemm(const ConvGemmArgs& a, hipStream_t stream);
 int gt_conv_gemm_variant(const ConvGemmArgs& a);     // the GSTTACO_CONV_V_* the launch runs (include/gsttaco.h)

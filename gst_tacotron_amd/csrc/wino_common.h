@@ -30,6 +30,16 @@ struct Wino {
                                    {0.f, 1.f, 1.f, 0.25f, 0.25f, 4.f, 4.f, 0.f},      {0.f, 1.f, -1.f, 0.125f, -0.125f, 8.f, -8.f, 1.f}};
         return t[o % 4][xi % 8];
     }
+    // the input transform's largest absolute row sum: |V_xi| <= bt_rowsum() max|x| (15 for F(4,5), 3 for F(2,5))
+    static constexpr float bt_rowsum() {
+        float worst = 0.f;
+        for (int xi = 0; xi < ALPHA; ++xi) {
+            float s = 0.f;
+            for (int i = 0; i < ALPHA; ++i) s += bt(xi, i) < 0.f ? -bt(xi, i) : bt(xi, i);
+            worst = s > worst ? s : worst;
+        }
+        return worst;
+    }
 };
 
 #define GT_WINO_OOB 0x80000000u

@@ -864,6 +864,13 @@ class GST_Tacotron:
             self.ctx.check(self.ctx.lib.gsttaco_vocoder(self.ctx.handle, _ptr(x), B, T, _ptr(spec), self._stream()))
         return spec
 
+    def postnet_variants(self, B, T):
+        """The conv/GEMM dispatcher variant (capi.CONV_V / capi.CONV_VH ids) each postnet layer runs at (B, T)."""
+        self._require_ready()
+        v = (ctypes.c_int32 * 8)()
+        self.ctx.check(self.ctx.lib.gsttaco_postnet_variants(self.ctx.handle, B, T, v))
+        return [int(v[i]) for i in range(min(len(self.dims.post_filters), 8))]
+
     def postnet(self, pre_mel):
         self._require_ready()
         pre = self._dev(pre_mel, torch.float32)

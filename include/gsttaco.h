@@ -474,13 +474,21 @@ enum {
     GSTTACO_CONV_V_BF16_RM1 = 28, GSTTACO_CONV_V_BF16_RM1_XB = 29, GSTTACO_CONV_V_BF16_RM1_OB = 30, GSTTACO_CONV_V_BF16_RM1_XB_OB = 31,
     GSTTACO_CONV_V_COUNT = 32
 };
+/* The bounded-input variants, numbered on behind the list above (no id moves): WINO4_S / WINO2_S as two fp16 planes and three
+ * products (conv_wino_split.hip).  A call reaches them only with the WINO_SPLIT_H form AND a promised input bound
+ * (gsttaco_conv_call::x_absmax), so they are kept as a group of their own: what a call without a bound can run is the list above. */
+enum {
+    GSTTACO_CONV_VH_WINO4_S = 32, GSTTACO_CONV_VH_WINO2_S = 33,
+    GSTTACO_CONV_VH_END = 34
+};
 /* Weight forms gsttaco_debug_conv_prepare builds (bit set), as finalize builds them for a layer:
  * FP32 = w [taps*cin, ldw] with scale / shift (always built), BF16 = its transposed bf16 copy (the mixed-precision kernels),
  * WINO2 / WINO4 = the float64 Winograd transforms U / U4 rounded to fp32 (taps 5), WINO_SPLIT = the three bf16 planes of each
- * Winograd transform built, GEMM_SPLIT = the three bf16 planes of w (taps 1). */
+ * Winograd transform built, GEMM_SPLIT = the three bf16 planes of w (taps 1), WINO_SPLIT_H = each Winograd transform built as two fp16
+ * planes with per-column power-of-two scaling (only a call that promises |x| <= 1 takes them: x_absmax below). */
 enum {
     GSTTACO_CONV_FORM_FP32 = 1, GSTTACO_CONV_FORM_BF16 = 2, GSTTACO_CONV_FORM_WINO2 = 4, GSTTACO_CONV_FORM_WINO4 = 8,
-    GSTTACO_CONV_FORM_WINO_SPLIT = 16, GSTTACO_CONV_FORM_GEMM_SPLIT = 32
+    GSTTACO_CONV_FORM_WINO_SPLIT = 16, GSTTACO_CONV_FORM_GEMM_SPLIT = 32, GSTTACO_CONV_FORM_WINO_SPLIT_H = 64
 };
 typedef struct gsttaco_conv_desc {
     int32_t taps, cin, n, ldw;  /* ldw: row stride of w in floats (0 = n) */
@@ -492,6 +500,9 @@ typedef struct gsttaco_conv_call {
     int64_t ldo;                /* output row stride (0 = n) */
     int32_t pool2, x_bf16, out_bf16, wino_x3, wino_min_wgs;
     int32_t conv2d, H, W, Wo, kw, stride, pad_h, pad_w;     /* 2-D mode: T = Ho * Wo, taps = kh * kw */
+    float x_absmax;             /* the caller's promise that |x| <= x_absmax everywhere; 0 = none.  (It lies in what was the alignment
+                                 * padding in front of xb: the struct's size and every other offset are what they were, and a zeroed
+                                 * struct of an older caller makes no promise.) */
     int64_t xb;                 /* 2-D mode: batch stride of x in floats */
 } gsttaco_conv_call;
 /* Uploads the forms of one conv/GEMM weight (host w [taps*cin, ldw], scale / shift [n] or NULL) as finalize would; the context
@@ -503,6 +514,15 @@ int gsttaco_debug_conv_prepare(gsttaco_ctx* ctx, const gsttaco_conv_desc* desc, 
  * receives the GSTTACO_CONV_V_* the call ran. */
 int gsttaco_debug_conv_run(gsttaco_ctx* ctx, int id, const gsttaco_conv_call* call, const void* x, const int32_t* tokens,
                            const int32_t* row_len, const float* rowbias, const float* res, void* out, int* variant, void* stream);
+
+/* Test support: the GSTTACO_CONV_V_* / GSTTACO_CONV_VH_* each postnet layer runs at (B, Tf) on this context (variants[i], i < the
+ * number of postnet layers; at most 8 are written).  Built by the function that enqueues them; launches nothing. */
+int gsttaco_postnet_variants(const gsttaco_ctx* ctx, int B, int Tf, int32_t variants[8]);
+/* Test support, host only (no context, no device): the WINO_SPLIT_H plane builder as finalize runs it.  u: a float64 Winograd-domain
+ * weight [al][cin][cout]; planes: [al][2][npad][wino_cin] fp16 bits (hi, lo of u[:, n] 2^su[n]); su: [cout]; *sv (may be NULL): the
+ * power of two the kernel's input transform carries. */
+int gsttaco_debug_wino_h_planes(const double* u, int al, int cin, int wino_cin, int cout, int npad, uint16_t* planes, int32_t* su,
+                                int32_t* sv);
 
 #ifdef __cplusplus
 }
