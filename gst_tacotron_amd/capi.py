@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = (
     "gsttaco_fill_randomness", "gsttaco_utterance_report",
     "gsttaco_losses", "gsttaco_feature_frontend",
     "gsttaco_postnet_variants", "gsttaco_debug_wino_h_planes",
+    "gsttaco_encoder_variants", "gsttaco_vocoder_variants",
 )
 
 # GSTTACO_CONV_V_*: the conv/GEMM dispatcher's kernel instantiations (gsttaco_debug_conv_run reports which one ran)
@@ -49,6 +50,8 @@ CONV_V = {
     "BF16_RM1": 28, "BF16_RM1_XB": 29, "BF16_RM1_OB": 30, "BF16_RM1_XB_OB": 31,
 }
 CONV_V_INVALID = -1
+# GSTTACO_VOC_*: the kinds of GEMM gsttaco_vocoder_variants reports, in the order the vocoder enqueues them
+VOC_KINDS = {"bank": 0, "proj": 1, "proj_dense": 2, "highway_in": 3, "highway": 4, "dense": 5}
 # GSTTACO_CONV_VH_*: the bounded-input variants (two fp16 planes, three products), numbered on behind CONV_V; a call runs one only with
 # the WINO_SPLIT_H form and a promised bound (ConvCall.x_absmax)
 CONV_VH = {"WINO4_S": 32, "WINO2_S": 33}
@@ -187,6 +190,11 @@ def load_library(path=None):
         lib.gsttaco_debug_wino_h_planes.argtypes = [ctypes.POINTER(ctypes.c_double), i32, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_uint16),
                                                     ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
         lib.gsttaco_debug_wino_h_planes.restype = ctypes.c_int
+    if hasattr(lib, "gsttaco_encoder_variants"):       # (likewise)
+        lib.gsttaco_encoder_variants.argtypes = [vp, i32, i32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
+        lib.gsttaco_encoder_variants.restype = ctypes.c_int
+        lib.gsttaco_vocoder_variants.argtypes = [vp, i32, i32, i32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
+        lib.gsttaco_vocoder_variants.restype = ctypes.c_int
     for fn in ("gsttaco_create", "gsttaco_num_weights", "gsttaco_weight_info", "gsttaco_load_weight",
                "gsttaco_finalize_weights", "gsttaco_encode", "gsttaco_gst", "gsttaco_decode", "gsttaco_postnet", "gsttaco_vocoder",
                "gsttaco_inference_step", "gsttaco_set_profiling", "gsttaco_get_profile", "gsttaco_mel_frontend",
@@ -205,8 +213,11 @@ def make_config(hp, vocab=None, device=0, max_batch=32, max_tokens=256, max_ref_
     c.abi_version, c.device = ABI_VERSION, device
     c.mel_dim, c.step_reduction, c.max_step = d.mel, d.r, d.max_step
     c.vocab, c.emb, c.n_enc_conv = d.vocab, d.emb, len(d.enc_filters)
-    if max(len(d.enc_filters), len(d.post_filters), len(d.prenet), len(d.dec_rnn)) > MAX_LAYERS:
-        raise ValueError("too many layers for the C-ABI config (max {})".format(MAX_LAYERS))
+    # (post_filters: Decoder.Conv.Filters plus the postnet's fixed last layer)
+    for field, n in (("Encoder.Conv.Filters", len(d.enc_filters)), ("Decoder.Conv.Filters (+ 1)", len(d.post_filters)),
+                     ("Decoder.Prenet.Size", len(d.prenet)), ("Decoder.RNN.Size", len(d.dec_rnn))):
+        if n > MAX_LAYERS:
+            raise ValueError("too many layers for the C-ABI config: {} has {} (max {})".format(field, n, MAX_LAYERS))
     for i, (f, k) in enumerate(zip(d.enc_filters, d.enc_kernels)):
         c.enc_filters[i], c.enc_kernels[i] = f, k
     c.enc_rnn = d.enc_rnn

@@ -996,13 +996,14 @@ int enqueue_bilstm_steps(gsttaco_ctx* c, hipStream_t s, const PackedLinear* pk, 
 
 // ------------------------------------------------------------------------------------------------ enqueue
 int enqueue_gst(gsttaco_ctx* c, hipStream_t s, int B, int Tref1);
+bool encoder_rows_path(const gsttaco_ctx* c, int B, int Tv);
+ConvGemmArgs encoder_call(const gsttaco_ctx* c, int i, int B, int Tv, bool rows_path);
 
 // gst_Tref1 > 0: the GST branch is forked onto the side stream here and joined in front of the BiLSTM (gsttaco_ctx::gst_fork)
 int enqueue_encoder(gsttaco_ctx* c, hipStream_t s, const LaunchForms& forms, int B, int Tv, bool masked, int gst_Tref1 = 0) {
     const int32_t* tlen = masked ? c->w_tok_len : nullptr;      // masked-mode extension
     const gsttaco_config& g = c->cfg;
     const float* x = c->d_emb;
-    const int32_t* tok = c->w_tokens;
     int cur = 0;
     if (gst_Tref1 > 0) {
         HIPCHECK(c, hipEventRecord(c->ev_fork, s));
@@ -1020,32 +1021,18 @@ int enqueue_encoder(gsttaco_ctx* c, hipStream_t s, const LaunchForms& forms, int
         gsttaco_ctx* c; hipStream_t s; bool armed;
         ~JoinGuard() { if (armed) (void)hipStreamWaitEvent(s, c->ev_join, 0); }
     } join_guard{c, s, gst_Tref1 > 0};
-    // (round 6) the embedding lookup as rows in memory when the first convolution can then take the Winograd kernel on the bf16 pipe
-    // (it resolves the lookup inside its gather only as an implicit GEMM: 140 us against ~90 for lookup + Winograd at 4 096 rows)
-    if (g.n_enc_conv > 0 && c->enc_wino && c->enc_conv[0].wino_s && tok && c->enc_conv[0].cin == g.emb &&
-        (B * ((Tv + 1) / 2) + 63) / 64 * ((c->enc_conv[0].cout + 127) / 128) >= 100) {
-        HIPCHECK(c, gt_launch_embed_rows(c->d_emb, tok, c->w_act[1], B * Tv, g.emb, s));
-        x = c->w_act[1]; tok = nullptr;
+    const bool rows_path = encoder_rows_path(c, B, Tv);
+    if (rows_path) {
+        HIPCHECK(c, gt_launch_embed_rows(c->d_emb, c->w_tokens, c->w_act[1], B * Tv, g.emb, s));
+        x = c->w_act[1];
     }
     for (int i = 0; i < g.n_enc_conv; ++i) {
-        const ConvLayer& L = c->enc_conv[i];
-        // (round 6) the five-tap layers behind the token gather as Winograd on the bf16 pipe (conv_wino_split.hip): B x Tv = 4 096 rows are
-        // 128 workgroups of F(2,5) -- half the chip, where the fp32 Winograd kernel lost to the implicit GEMM (275 against 136 us) --
-        // enc_wino: 0 = implicit GEMM, 2 = F(2,5), 4 = F(4,5) where its grid reaches 60 workgroups
-        const bool wino = c->enc_wino && !tok && L.wino_s;
-        // (F(4,5) where ITS grid fills the chip -- batches of 128 utterances --, else F(2,5) down to 100 workgroups)
-        const bool f4 = c->enc_wino == 4 || ((B * ((Tv + 3) / 4) + 63) / 64) * ((L.cout + 127) / 128) >= 240;
-        // (nothing but FP32 / BF16 while the token gather is still in front)
-        ConvGemmArgs a = conv_args(L, kFormsPlain | (wino ? GSTTACO_CONV_FORM_WINO2 | GSTTACO_CONV_FORM_WINO_SPLIT | (f4 ? GSTTACO_CONV_FORM_WINO4 : 0) : 0));
-        if (wino) a.wino_min_wgs = c->enc_wino == 4 ? 60 : 100;
-        a.x = x; a.tokens = tok;
-        a.out = c->w_act[cur]; a.ldo = L.cout;
-        a.B = B; a.T = Tv;
-        a.pad_before = same_pad_before(Tv, L.taps, 1, nullptr);
-        a.act = ACT_RELU;
+        ConvGemmArgs a = encoder_call(c, i, B, Tv, rows_path);
+        a.x = x;
+        a.out = c->w_act[cur];
         a.row_len = tlen;
         HIPCHECK(c, gt_launch_conv_gemm(a, s));
-        x = c->w_act[cur]; tok = nullptr; cur ^= 1;
+        x = c->w_act[cur]; cur ^= 1;
     }
     const int H = g.enc_rnn;
     // (joining BEHIND the BiLSTM instead measured 10.83-10.86 against 10.85-10.89 ms per Inference_Step: not worth GST kernels lingering
@@ -1636,6 +1623,58 @@ ConvGemmArgs postnet_call(const gsttaco_ctx* c, int i, int B, int Tf) {
     return a;
 }
 
+// (round 6) Whether the embedding lookup is written out as rows in front of encoder layer 0, so that layer 0 too can take the Winograd
+// kernel on the bf16 pipe (it resolves the lookup inside its gather only as an implicit GEMM: 140 us against ~90 for lookup + Winograd
+// at 4 096 rows).  The rows go to w_act[1]; layer 0 writes w_act[0].
+bool encoder_rows_path(const gsttaco_ctx* c, int B, int Tv) {
+    const gsttaco_config& g = c->cfg;
+    return g.n_enc_conv > 0 && c->enc_wino && c->enc_conv[0].wino_s && c->w_tokens && c->enc_conv[0].cin == g.emb &&
+           (B * ((Tv + 1) / 2) + 63) / 64 * ((c->enc_conv[0].cout + 127) / 128) >= 100;
+}
+
+// Encoder layer i's call without its buffers, as postnet_call (enqueue_encoder adds x / out / row_len; gsttaco_encoder_variants asks
+// gt_conv_gemm_variant about it).  rows_path: encoder_rows_path() of the call; without it layer 0 gathers the embedding rows by token.
+ConvGemmArgs encoder_call(const gsttaco_ctx* c, int i, int B, int Tv, bool rows_path) {
+    const ConvLayer& L = c->enc_conv[i];
+    const bool gather = i == 0 && !rows_path;
+    // (round 6) the five-tap layers behind the token gather as Winograd on the bf16 pipe (conv_wino_split.hip): B x Tv = 4 096 rows are
+    // 128 workgroups of F(2,5) -- half the chip, where the fp32 Winograd kernel lost to the implicit GEMM (275 against 136 us) --
+    // enc_wino: 0 = implicit GEMM, 2 = F(2,5), 4 = F(4,5) where its grid reaches 60 workgroups
+    const bool wino = c->enc_wino && !gather && L.wino_s;
+    // (F(4,5) where ITS grid fills the chip -- batches of 128 utterances --, else F(2,5) down to 100 workgroups)
+    const bool f4 = c->enc_wino == 4 || ((B * ((Tv + 3) / 4) + 63) / 64) * ((L.cout + 127) / 128) >= 240;
+    // (nothing but FP32 / BF16 while the token gather is still in front)
+    ConvGemmArgs a = conv_args(L, kFormsPlain | (wino ? GSTTACO_CONV_FORM_WINO2 | GSTTACO_CONV_FORM_WINO_SPLIT | (f4 ? GSTTACO_CONV_FORM_WINO4 : 0) : 0));
+    if (wino) a.wino_min_wgs = c->enc_wino == 4 ? 60 : 100;
+    a.tokens = gather ? c->w_tokens : nullptr;
+    a.ldo = L.cout;
+    a.B = B; a.T = Tv;
+    a.pad_before = same_pad_before(Tv, L.taps, 1, nullptr);
+    a.act = ACT_RELU;
+    return a;
+}
+
+// One GEMM of the vocoder without its buffers, as postnet_call (enqueue_vocoder adds x / out / res; gsttaco_vocoder_variants asks
+// gt_conv_gemm_variant about it).  which: GSTTACO_VOC_*; i: the layer among its kind (0 for the three single Dense layers).
+// Every GEMM of the vocoder: FP32, BF16 under mixed precision, never Winograd.
+ConvGemmArgs vocoder_call(const gsttaco_ctx* c, int which, int i, int B, int Tf) {
+    const gsttaco_config& g = c->cfg;
+    const ConvLayer& L = which == GSTTACO_VOC_BANK ? c->voc_bank[i] : which == GSTTACO_VOC_PROJ ? c->voc_proj[i] :
+                         which == GSTTACO_VOC_PROJ_DENSE ? c->voc_pd : which == GSTTACO_VOC_HIGHWAY_IN ? c->voc_hin :
+                         which == GSTTACO_VOC_HIGHWAY ? c->voc_hw[i] : c->voc_dense;
+    ConvGemmArgs a = conv_args(L, kFormsPlain);
+    a.ldo = which == GSTTACO_VOC_BANK ? g.bank_count * g.bank_filters : L.cout;     // (the bank layers write side by side)
+    a.B = B; a.T = Tf;
+    a.act = ACT_NONE;
+    if (which == GSTTACO_VOC_BANK || which == GSTTACO_VOC_PROJ) {
+        a.pad_before = same_pad_before(Tf, L.taps, 1, nullptr);       // even kernels pad asymmetrically (F10)
+        // conv bank: + BN + ReLU each; projections: Conv1D + BN (+ReLU except the last) (Taco2.py:319-340, 383-407)
+        a.act = which == GSTTACO_VOC_BANK || i < g.n_voc_proj - 1 ? ACT_RELU : ACT_NONE;
+        a.pool2 = which == GSTTACO_VOC_PROJ && i == 0;                // MaxPool1D(2,1,'same') fused into the first projection's gather
+    }
+    return a;
+}
+
 int enqueue_postnet(gsttaco_ctx* c, hipStream_t s, int B, int Tf, const float* pre, float* out) {
     const gsttaco_config& g = c->cfg;
     const float* x = pre;
@@ -1752,59 +1791,48 @@ int ensure_audio(gsttaco_ctx* c) {
 // mel [B,Tf,mel] -> spectrogram [B,Tf,spec]  (reference Taco2.py:258-260, 366-380)
 int enqueue_vocoder(gsttaco_ctx* c, hipStream_t s, const LaunchForms& forms, int B, int Tf, const float* mel_in, float* spec) {
     const gsttaco_config& g = c->cfg;
-    const int NB = g.bank_count * g.bank_filters;
     // conv bank: kernel sizes 1..N on the INPUT, each + BN + ReLU, concatenated on the channel axis (Taco2.py:383-407)
     // (every GEMM of the vocoder: FP32, BF16 under mixed precision, never Winograd)
     for (int i = 0; i < g.bank_count; ++i) {
-        const ConvLayer& L = c->voc_bank[i];
-        ConvGemmArgs a = conv_args(L, kFormsPlain);
+        ConvGemmArgs a = vocoder_call(c, GSTTACO_VOC_BANK, i, B, Tf);
         a.x = mel_in;
-        a.out = c->w_vbank + (size_t)i * g.bank_filters; a.ldo = NB;
-        a.B = B; a.T = Tf;
-        a.pad_before = same_pad_before(Tf, L.taps, 1, nullptr);       // even kernels pad asymmetrically (F10)
-        a.act = ACT_RELU;
+        a.out = c->w_vbank + (size_t)i * g.bank_filters;
         HIPCHECK(c, gt_launch_conv_gemm(a, s));
     }
     // MaxPool1D(2,1,'same') fused into the first projection conv's gather; Conv1D + BN (+ReLU except the last) (Taco2.py:319-340)
     const float* x = c->w_vbank;
     int cur = 0;
     for (int i = 0; i < g.n_voc_proj; ++i) {
-        const ConvLayer& L = c->voc_proj[i];
-        ConvGemmArgs a = conv_args(L, kFormsPlain);
+        ConvGemmArgs a = vocoder_call(c, GSTTACO_VOC_PROJ, i, B, Tf);
         a.x = x;
-        a.out = c->w_vbuf[cur]; a.ldo = L.cout;
-        a.B = B; a.T = Tf;
-        a.pad_before = same_pad_before(Tf, L.taps, 1, nullptr);
-        a.act = i < g.n_voc_proj - 1 ? ACT_RELU : ACT_NONE;
-        a.pool2 = i == 0;
+        a.out = c->w_vbuf[cur];
         const bool last = i == g.n_voc_proj - 1;
         if (last && !c->voc_pd.w) a.res = mel_in;                     // residual directly when no Dense follows (:373)
         HIPCHECK(c, gt_launch_conv_gemm(a, s));
         x = a.out; cur ^= 1;
     }
     // a Dense over the frames: x -> out [B*Tf, L.cout]
-    auto dense = [&](const ConvLayer& L, const float* in, float* out, const float* res) {
-        ConvGemmArgs a = conv_args(L, kFormsPlain);
+    auto dense = [&](int which, int i, const float* in, float* out, const float* res) {
+        ConvGemmArgs a = vocoder_call(c, which, i, B, Tf);
         a.x = in; a.res = res;
-        a.out = out; a.ldo = L.cout;
-        a.B = B; a.T = Tf; a.act = ACT_NONE;
+        a.out = out;
         HIPCHECK(c, gt_launch_conv_gemm(a, s));
         return 0;
     };
     int rc = 0;
     if (c->voc_pd.w) {                                                // Dense back to mel width + residual (:342-345, 373)
-        if ((rc = dense(c->voc_pd, x, c->w_vbuf[cur], mel_in))) return rc;
+        if ((rc = dense(GSTTACO_VOC_PROJ_DENSE, 0, x, c->w_vbuf[cur], mel_in))) return rc;
         x = c->w_vbuf[cur]; cur ^= 1;
     }
     const int S = g.highway_size;
     if (c->voc_hin.w) {                                               // Dense to the highway width (:348-351)
-        if ((rc = dense(c->voc_hin, x, c->w_vbuf[cur], nullptr))) return rc;
+        if ((rc = dense(GSTTACO_VOC_HIGHWAY_IN, 0, x, c->w_vbuf[cur], nullptr))) return rc;
         x = c->w_vbuf[cur]; cur ^= 1;
     }
     float* hbuf[2] = {c->w_vbuf[cur], c->w_vbuf[2]};
     int hcur = 0;
     for (int i = 0; i < g.highway_count; ++i) {                       // Highwaynet (:409-424)
-        if ((rc = dense(c->voc_hw[i], x, c->w_vz, nullptr))) return rc;
+        if ((rc = dense(GSTTACO_VOC_HIGHWAY, i, x, c->w_vz, nullptr))) return rc;
         HIPCHECK(c, gt_launch_highway(c->w_vz, x, hbuf[hcur], (int64_t)B * Tf, S, s));
         x = hbuf[hcur]; hcur ^= 1;
     }
@@ -1814,7 +1842,7 @@ int enqueue_vocoder(gsttaco_ctx* c, hipStream_t s, const LaunchForms& forms, int
     if (lean_bilstm_usable(c, forms, c->voc_lean, B)) rc = enqueue_lean_bilstm(c, s, forms, c->voc_lean, x, B, Tf, c->w_vc, c->w_vrnn, nullptr);
     else rc = enqueue_bilstm_steps(c, s, c->voc_bilstm, x, B, Tf, S, H, c->w_vc, c->w_vrnn, nullptr);
     if (rc) return rc;
-    return dense(c->voc_dense, c->w_vrnn, spec, nullptr);             // Dense to the linear-spectrogram width (Taco2.py:252-260)
+    return dense(GSTTACO_VOC_DENSE, 0, c->w_vrnn, spec, nullptr);           // Dense to the linear-spectrogram width (Taco2.py:252-260)
 }
 
 int check_ready(gsttaco_ctx* c) {
@@ -2076,7 +2104,7 @@ int gsttaco_create(const gsttaco_config* cfg, gsttaco_ctx** out) {
     if (g.att_size < 16 || g.att_size % 16 || g.att_size > 256) return bad("Attention.Size must be a multiple of 16, <= 256");
     if (g.n_post < 1 || g.n_post > GSTTACO_MAX_LAYERS) return bad("bad postnet layer count");
     for (int i = 0; i < g.n_post; ++i)
-        if (g.post_filters[i] % 4 || g.post_filters[i] < 4 || g.post_kernels[i] < 1) return bad("postnet filters must be multiples of 4");
+        if (g.post_filters[i] % 4 || g.post_filters[i] < 4 || g.post_kernels[i] < 1) return bad("postnet Decoder.Conv.Filters must be multiples of 4");
     if (g.post_filters[g.n_post - 1] != g.mel_dim) return bad("last postnet filter count must equal Mel_Dim");
     if (g.gst_use) {
         if (g.n_ref_conv < 1 || g.n_ref_conv > GSTTACO_MAX_LAYERS) return bad("bad reference-encoder conv count");
@@ -3115,6 +3143,32 @@ int gsttaco_debug_conv_run(gsttaco_ctx* c, int id, const gsttaco_conv_call* k, c
 int gsttaco_postnet_variants(const gsttaco_ctx* c, int B, int Tf, int32_t variants[8]) {
     if (!c || !variants || B < 1 || Tf < 1 || !c->finalized) return GSTTACO_E_INVALID;
     for (int i = 0; i < c->cfg.n_post && i < 8; ++i) variants[i] = gt_conv_gemm_variant(postnet_call(c, i, B, Tf));
+    return 0;
+}
+
+int gsttaco_encoder_variants(const gsttaco_ctx* c, int B, int Tv, int32_t variants[8], int32_t* rows_path) {
+    if (!c || !variants || !c->finalized || B < 1 || Tv < 1) return GSTTACO_E_INVALID;
+    const bool rows = encoder_rows_path(c, B, Tv);
+    if (rows_path) *rows_path = rows ? 1 : 0;
+    for (int i = 0; i < c->cfg.n_enc_conv && i < 8; ++i) variants[i] = gt_conv_gemm_variant(encoder_call(c, i, B, Tv, rows));
+    return 0;
+}
+
+int gsttaco_vocoder_variants(const gsttaco_ctx* c, int which, int B, int Tf, int32_t variants[32], int32_t* count) {
+    if (!c || !variants || !count || !c->finalized || !c->cfg.voc_use || B < 1 || Tf < 1) return GSTTACO_E_INVALID;
+    const gsttaco_config& g = c->cfg;
+    int n = 0;
+    switch (which) {
+    case GSTTACO_VOC_BANK: n = g.bank_count; break;
+    case GSTTACO_VOC_PROJ: n = g.n_voc_proj; break;
+    case GSTTACO_VOC_PROJ_DENSE: n = c->voc_pd.w ? 1 : 0; break;
+    case GSTTACO_VOC_HIGHWAY_IN: n = c->voc_hin.w ? 1 : 0; break;
+    case GSTTACO_VOC_HIGHWAY: n = g.highway_count; break;
+    case GSTTACO_VOC_DENSE: n = 1; break;
+    default: return GSTTACO_E_INVALID;
+    }
+    *count = n;
+    for (int i = 0; i < n && i < 32; ++i) variants[i] = gt_conv_gemm_variant(vocoder_call(c, which, i, B, Tf));
     return 0;
 }
 

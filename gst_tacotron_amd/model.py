@@ -871,6 +871,25 @@ class GST_Tacotron:
         self.ctx.check(self.ctx.lib.gsttaco_postnet_variants(self.ctx.handle, B, T, v))
         return [int(v[i]) for i in range(min(len(self.dims.post_filters), 8))]
 
+    def encoder_variants(self, B, Tv):
+        """(the dispatcher variant each encoder conv layer runs at (B, Tv), whether the embedding lookup is launched as rows in front
+        of layer 0) -- ``gsttaco_encoder_variants``."""
+        self._require_ready()
+        v, rows = (ctypes.c_int32 * 8)(), ctypes.c_int32(0)
+        self.ctx.check(self.ctx.lib.gsttaco_encoder_variants(self.ctx.handle, B, Tv, v, ctypes.byref(rows)))
+        return [int(v[i]) for i in range(min(len(self.dims.enc_filters), 8))], bool(rows.value)
+
+    def vocoder_variants(self, B, T):
+        """{kind: [dispatcher variant of each of the vocoder's GEMMs of that kind at (B, T)]} over ``capi.VOC_KINDS``, in the order
+        they are enqueued; a Dense the model does not have gives [] (``gsttaco_vocoder_variants``)."""
+        self._require_ready()
+        out = {}
+        for kind, code in capi.VOC_KINDS.items():
+            v, n = (ctypes.c_int32 * 32)(), ctypes.c_int32(0)
+            self.ctx.check(self.ctx.lib.gsttaco_vocoder_variants(self.ctx.handle, code, B, T, v, ctypes.byref(n)))
+            out[kind] = [int(v[i]) for i in range(min(int(n.value), 32))]
+        return out
+
     def postnet(self, pre_mel):
         self._require_ready()
         pre = self._dev(pre_mel, torch.float32)

@@ -518,6 +518,20 @@ int gsttaco_debug_conv_run(gsttaco_ctx* ctx, int id, const gsttaco_conv_call* ca
 /* Test support: the GSTTACO_CONV_V_* / GSTTACO_CONV_VH_* each postnet layer runs at (B, Tf) on this context (variants[i], i < the
  * number of postnet layers; at most 8 are written).  Built by the function that enqueues them; launches nothing. */
 int gsttaco_postnet_variants(const gsttaco_ctx* ctx, int B, int Tf, int32_t variants[8]);
+/* The same for the encoder's conv layers at (B, Tv).  *rows_path (may be NULL): 1 when the embedding lookup is launched as rows in
+ * front of layer 0 (layer 0 then reads rows, not tokens), else 0.  The report is for the call's arguments WITHOUT its buffers and
+ * without the masked mode's row lengths: it holds for a masked call only while no form the encoder passes looks at row_len (today
+ * none does: FP32, BF16 and the Winograd forms; the plain split GEMM form would). */
+int gsttaco_encoder_variants(const gsttaco_ctx* ctx, int B, int Tv, int32_t variants[8], int32_t* rows_path);
+/* The same for the vocoder's GEMMs of one kind at (B, Tf), in the order they are enqueued.  *count receives how many layers of the
+ * kind the model has (0 for a Dense it does not have); at most 32 variants are written. */
+#define GSTTACO_VOC_BANK 0            /* the conv bank, kernel sizes 1 .. Stack_Count */
+#define GSTTACO_VOC_PROJ 1            /* the Conv1D projections */
+#define GSTTACO_VOC_PROJ_DENSE 2      /* the Dense back to Mel_Dim, where the last projection is not that wide */
+#define GSTTACO_VOC_HIGHWAY_IN 3      /* the Dense to Highwaynet.Size, where that is not Mel_Dim */
+#define GSTTACO_VOC_HIGHWAY 4         /* the highway layers (relu | sigmoid in one GEMM) */
+#define GSTTACO_VOC_DENSE 5           /* the Dense to Spectrogram_Dim behind the BiLSTM */
+int gsttaco_vocoder_variants(const gsttaco_ctx* ctx, int which, int B, int Tf, int32_t variants[32], int32_t* count);
 /* Test support, host only (no context, no device): the WINO_SPLIT_H plane builder as finalize runs it.  u: a float64 Winograd-domain
  * weight [al][cin][cout]; planes: [al][2][npad][wino_cin] fp16 bits (hi, lo of u[:, n] 2^su[n]); su: [cout]; *sv (may be NULL): the
  * power of two the kernel's input transform carries. */
