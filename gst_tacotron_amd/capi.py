@@ -36,7 +36,11 @@ EXPORTED_SYMBOLS = (
     "gsttaco_losses", "gsttaco_feature_frontend",
     "gsttaco_postnet_variants", "gsttaco_debug_wino_h_planes",
     "gsttaco_encoder_variants", "gsttaco_vocoder_variants",
+    "gsttaco_decode_plan_fields",
 )
+# GSTTACO_PLAN_*: the fields gsttaco_decode_plan_fields fills, in order
+PLAN_FIELDS = ("persist", "persist_bf16", "fused", "lean_front", "lean_rec", "z0", "fuse12", "lean_x0", "lean_x1", "co_tiles", "lean_proj",
+               "mirror", "dec_padded", "pj_tiles")
 
 # GSTTACO_CONV_V_*: the conv/GEMM dispatcher's kernel instantiations (gsttaco_debug_conv_run reports which one ran)
 CONV_V = {
@@ -195,6 +199,9 @@ def load_library(path=None):
         lib.gsttaco_encoder_variants.restype = ctypes.c_int
         lib.gsttaco_vocoder_variants.argtypes = [vp, i32, i32, i32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
         lib.gsttaco_vocoder_variants.restype = ctypes.c_int
+    if hasattr(lib, "gsttaco_decode_plan_fields"):     # (likewise)
+        lib.gsttaco_decode_plan_fields.argtypes = [vp, i32, i32, i32, ctypes.POINTER(ctypes.c_int32)]
+        lib.gsttaco_decode_plan_fields.restype = ctypes.c_int
     for fn in ("gsttaco_create", "gsttaco_num_weights", "gsttaco_weight_info", "gsttaco_load_weight",
                "gsttaco_finalize_weights", "gsttaco_encode", "gsttaco_gst", "gsttaco_decode", "gsttaco_postnet", "gsttaco_vocoder",
                "gsttaco_inference_step", "gsttaco_set_profiling", "gsttaco_get_profile", "gsttaco_mel_frontend",

@@ -3202,6 +3202,26 @@ int gsttaco_decode_plan(const gsttaco_ctx* c, int Tv, int32_t plan[3]) {
     return 0;
 }
 
+int gsttaco_decode_plan_fields(const gsttaco_ctx* c, int B, int Tv, int forced, int32_t fields[GSTTACO_PLAN_COUNT]) {
+    if (!c || !fields || !c->finalized || B < 1 || Tv < 1) return GSTTACO_E_INVALID;
+    const DecodePlan p = plan_decode(c, c->allow, B, Tv, false, forced != 0);
+    fields[GSTTACO_PLAN_PERSIST] = p.persist ? 1 : 0;
+    fields[GSTTACO_PLAN_PERSIST_BF16] = p.persist_bf16 ? 1 : 0;
+    fields[GSTTACO_PLAN_FUSED] = p.fused ? 1 : 0;
+    fields[GSTTACO_PLAN_LEAN_FRONT] = p.lean_front ? 1 : 0;
+    fields[GSTTACO_PLAN_LEAN_REC] = p.lean_rec;
+    fields[GSTTACO_PLAN_Z0] = p.z0 ? 1 : 0;
+    fields[GSTTACO_PLAN_FUSE12] = p.fuse12;
+    fields[GSTTACO_PLAN_LEAN_X0] = p.lean_x[0] ? 1 : 0;
+    fields[GSTTACO_PLAN_LEAN_X1] = p.lean_x[1] ? 1 : 0;
+    fields[GSTTACO_PLAN_CO_TILES] = p.co_tiles;
+    fields[GSTTACO_PLAN_LEAN_PROJ] = p.lean_proj ? 1 : 0;
+    fields[GSTTACO_PLAN_MIRROR] = p.mirror ? 1 : 0;
+    fields[GSTTACO_PLAN_DEC_PADDED] = c->dec_padded ? 1 : 0;
+    fields[GSTTACO_PLAN_PJ_TILES] = c->proj_z.ntiles;
+    return 0;
+}
+
 int64_t gsttaco_lstm_launch_bytes(const gsttaco_ctx* c, int which, int B) {
     if (!c || which < 0 || which > 3) return GSTTACO_E_INVALID;
     // Algorithmic bytes of one launch at batch B and T_v = max_tokens: every weight once, every activation row once

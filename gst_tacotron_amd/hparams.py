@@ -64,6 +64,8 @@ class Dims:
         self.mel = int(hp["Sound"]["Mel_Dim"])
         self.r = int(hp["Step_Reduction"])
         self.max_step = int(hp["Max_Step"])
+        if self.r < 1:          # (gsttaco_create refuses it too; here it would be a division by zero)
+            raise ValueError("Step_Reduction must be at least 1, got {}".format(self.r))
         self.steps = self.max_step // self.r          # Taco2.py:213
         self.vocab = int(vocab) if vocab is not None else len(load_token_dict(hp))
         self.emb = int(enc["Embedding"]["Size"])

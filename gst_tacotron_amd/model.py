@@ -755,6 +755,14 @@ class GST_Tacotron:
         self.ctx.check(self.ctx.lib.gsttaco_decode_plan(self.ctx.handle, int(Tv), plan))
         return bool(plan[0]), bool(plan[1]), bool(plan[2])
 
+    def decode_plan_fields(self, B, Tv, forced=False):
+        """{field: int} -- the whole launch plan of one decode of ``B`` utterances of ``Tv`` tokens (``forced``: teacher-forced), as
+        the function that enqueues it decides it: ``capi.PLAN_FIELDS`` (``gsttaco_decode_plan_fields``; test support)."""
+        self._require_ready()
+        out = (ctypes.c_int32 * len(capi.PLAN_FIELDS))()
+        self.ctx.check(self.ctx.lib.gsttaco_decode_plan_fields(self.ctx.handle, int(B), int(Tv), int(bool(forced)), out))
+        return dict(zip(capi.PLAN_FIELDS, (int(v) for v in out)))
+
     def set_graph_policy(self, max_cached=8, capture_after=1):
         """hipGraph cache policy (``gsttaco_set_graph_policy``): at most ``max_cached`` graph executables are kept (LRU);
         a shape is captured at its ``capture_after``-th use and enqueued eagerly before.  Use ``capture_after=2`` when

@@ -451,6 +451,23 @@ int gsttaco_debug_randomness(gsttaco_ctx* ctx, float* host_masks, float* host_no
  * weight matrix: under Use_Mixed_Precision that matrix is what gets rounded to bf16, which the parity oracle must know);
  * plan[2]: 1 = lean compile-time-K kernels for the LSTM / projection launches, 0 = general skinny GEMM. */
 int gsttaco_decode_plan(const gsttaco_ctx* ctx, int Tv, int32_t plan[3]);
+/* Test support: the WHOLE launch plan of one decode of B utterances of Tv tokens on this (finalized) context, as the function that
+ * enqueues it decides it (forced != 0: a teacher-forced decode), while this is the process's only live context and no keep masks are
+ * injected (those change only whether the keep-mask tensor is read, which is not reported).  fields[GSTTACO_PLAN_*]:
+ * PERSIST / PERSIST_BF16 the whole loop as one persistent launch / its bf16 kernel; FUSED the fused front launch (0: the four-kernel
+ * front end and whole LSTM GEMMs, and every field below is 0); LEAN_FRONT its lean utterance path; LEAN_REC its workers' recurrent body
+ * (0 general, 1 lean fp32, 2 lean bf16); Z0 prenet-0 pre-activations from the previous step's projection launch; FUSE12 both LSTM cells
+ * in one launch (0 no, 1 up to 32 rows, 2 the multi-chunk form); LEAN_X0 / LEAN_X1 LSTM layer 1 / 2's input half on the lean kernel;
+ * CO_TILES layer-2 recurrent tiles beside the projection; LEAN_PROJ that launch on the lean kernel; MIRROR bf16 mirrors of the blocked
+ * activations; DEC_PADDED the decoder runs zero-padded to the reference's sizes; PJ_TILES 16-column tiles of the projection pack
+ * [frames, stop | prenet-0 pre-activations].  Launches nothing. */
+enum {
+    GSTTACO_PLAN_PERSIST = 0, GSTTACO_PLAN_PERSIST_BF16 = 1, GSTTACO_PLAN_FUSED = 2, GSTTACO_PLAN_LEAN_FRONT = 3, GSTTACO_PLAN_LEAN_REC = 4,
+    GSTTACO_PLAN_Z0 = 5, GSTTACO_PLAN_FUSE12 = 6, GSTTACO_PLAN_LEAN_X0 = 7, GSTTACO_PLAN_LEAN_X1 = 8, GSTTACO_PLAN_CO_TILES = 9,
+    GSTTACO_PLAN_LEAN_PROJ = 10, GSTTACO_PLAN_MIRROR = 11, GSTTACO_PLAN_DEC_PADDED = 12, GSTTACO_PLAN_PJ_TILES = 13,
+    GSTTACO_PLAN_COUNT = 14
+};
+int gsttaco_decode_plan_fields(const gsttaco_ctx* ctx, int B, int Tv, int forced, int32_t fields[GSTTACO_PLAN_COUNT]);
 /* Algorithmic bytes one launch of decode-LSTM layer `layer` moves at batch B (weights + activations). */
 int64_t gsttaco_lstm_launch_bytes(const gsttaco_ctx* ctx, int layer, int B);
 
