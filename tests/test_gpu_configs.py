@@ -167,6 +167,7 @@ def test_graph_cache_is_lru_bounded_and_capture_after_matches_eager():
     """Host robustness: the hipGraph cache keeps at most `max_cached` executables (least recently used evicted), and with
     capture_after = 2 a shape runs eagerly at its first use and from a captured graph afterwards -- all bitwise the same."""
     import torch
+    from oracle import oracle_np
     from test_gpu_parity import _full_case
     hp, w, tokens, tl, mels, ml, masks, noise = _full_case(3, 40, 64, 6, seed=61)
     m = _model(hp, w, 3, 40, 65)
@@ -179,6 +180,10 @@ def test_graph_cache_is_lru_bounded_and_capture_after_matches_eager():
         torch.cuda.synchronize()
         return out[0].cpu().numpy()
 
+    def oracle(Tv, steps):
+        return oracle_np.inference_step(hp, w, tokens[:, :Tv], mels, ml, masks[:steps], np.ascontiguousarray(noise[:steps, :, :Tv]), steps=steps,
+                                        dt=np.float64)[0]
+
     a0 = run(40, 6)
     assert m.graph_cache_size() == 2
     b0 = run(32, 6)
@@ -187,6 +192,12 @@ def test_graph_cache_is_lru_bounded_and_capture_after_matches_eager():
     a1 = run(40, 6)                                        # re-captured
     assert m.graph_cache_size() == 4 and np.array_equal(a0, a1)
     assert np.array_equal(b0, run(32, 6)) and np.array_equal(c0, run(24, 5))
+    # the shrinking shapes on this one context against the oracle too, not only against an earlier run of themselves: a stale read that
+    # every run of a shape repeats would pass the bitwise comparisons above
+    for what, got, (Tv, steps) in (("40 tokens", a0, (40, 6)), ("32 tokens behind 40", b0, (32, 6)), ("24 tokens, 5 steps behind 32, 6", c0, (24, 5))):
+        e = float(np.abs(got - oracle(Tv, steps)).max())
+        print("graph cache, %s: mel max abs err against the float64 oracle %.3g" % (what, e))
+        assert e <= TOL, (what, e)
     m.set_graph_policy(max_cached=0, capture_after=1)      # no graphs at all: eager launches
     assert m.graph_cache_size() == 0
     assert np.array_equal(a0, run(40, 6)) and m.graph_cache_size() == 0
