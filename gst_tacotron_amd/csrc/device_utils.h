@@ -121,6 +121,17 @@ __device__ __forceinline__ float gt_sigmoid(float x) {
     return __builtin_amdgcn_rcpf(1.0f + e);
 }
 
+// LSTM cell update from the four gate pre-activations (i, f, c~, o; Appendix A.6, reference Taco2.py:79-85): c <- f c + i c~, returns
+// h = o tanh(c).  THE cell of every recurrent launch form -- general, lean, fused, multi-chunk and persistent, decoder and encoder --
+// which is what makes their states bitwise interchangeable.  Where the gates come from (DPP row shifts, an LDS tile) and where h
+// goes stay with the caller.
+__device__ __forceinline__ float gt_lstm_cell(const float zi, const float zf, const float zg, const float zo, float& c) {
+    const float gi = gt_sigmoid(zi), gf = gt_sigmoid(zf), gg = gt_tanh(zg), go = gt_sigmoid(zo);
+    // (an explicit fma, as in gt_tanh: whether `f c + i c~` contracts must not be the optimiser's choice per call site)
+    c = __builtin_fmaf(gf, c, gi * gg);
+    return go * gt_tanh(c);
+}
+
 // Philox4x32-10 counter RNG: throughput-mode randomness (prenet dropout, SMA noise) is generated
 // on the device; parity runs inject the tensors instead.
 struct Philox4 { uint32_t x, y, z, w; };
@@ -209,6 +220,14 @@ __device__ __forceinline__ float4 gt_bload4_sc1(__amdgpu_buffer_rsrc_t rs, uint3
     float4 r;
     __builtin_memcpy(&r, &t, 16);
     return r;
+}
+
+// One word another workgroup of the same launch may have just written (arrival counters, flags, the error word): an sc1 load, waited
+// for on the spot.  Inline assembly, invisible to the compiler's wait counting, hence the vmcnt(0): it also waits for whatever else the wave has in flight.
+__device__ __forceinline__ uint32_t gt_ld_sc1(const uint32_t* p) {
+    uint32_t v;
+    asm volatile("global_load_dword %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p) : "memory");
+    return v;
 }
 
 // fp32 -> bf16 bits, round to nearest even: what the bf16 GEMM bodies do to an activation on its way into the MFMA

@@ -1435,7 +1435,7 @@ int enqueue_lstm_cells(DecodeCall& d, int t, bool on) {
             float** hb = layer == 0 ? c->w_h1 : c->w_h2;
             LstmXArgs& la = layer == 0 ? fa.l1 : fa.l2;
             la = LstmXArgs{L.wp, layer == 0 ? xa_t : c->w_h1[p], c->w_part[layer], layer == 0 ? c->w_c1 : c->w_c2, hb[p],
-                           nullptr, d.stamps(t, 16 * (1 + layer)), B, MT, layer == 0 ? H1 : H2, 0, L.nkb};
+                           d.stamps(t, 16 * (1 + layer)), B, MT, layer == 0 ? H1 : H2, L.nkb};
             if (P.mirror) {
                 la.xh = layer == 0 ? c->w_xa_h : c->w_h1_h[p];
                 la.hh = layer == 0 ? c->w_h1_h[p] : c->w_h2_h[p];
@@ -1481,7 +1481,7 @@ int enqueue_lstm_cells(DecodeCall& d, int t, bool on) {
         const int tag = layer == 0 ? TAG_DEC_LSTM1 : TAG_DEC_LSTM2;
         const int rc = d.prof.run(on, layer, [&] {
             if (P.lean_x[layer]) {
-                LstmXArgs la{k.wp, k.seg[0].ptr, k.partial_in, k.c, k.h, nullptr, k.dbg, B, MT, H, 0, k.nkb};
+                LstmXArgs la{k.wp, k.seg[0].ptr, k.partial_in, k.c, k.h, k.dbg, B, MT, H, k.nkb};
                 if (P.mirror) {
                     la.xh = layer == 0 ? c->w_xa_h : c->w_h1_h[p];
                     la.hh = layer == 0 ? c->w_h1_h[p] : c->w_h2_h[p];

@@ -90,9 +90,8 @@ struct LstmXArgs {
     const float* partial_in;    // [tiles][MT*16][16]
     float* c;                   // [M, H] cell state, in place
     float* h;                   // blocked output state
-    const int32_t* row_len;     // masked-mode extension (A12) or NULL
     unsigned long long* dbg;
-    int M, MT, H, t_index;
+    int M, MT, H;
     int nkb;                    // K / 16 (the bf16 variant's 32-k blocks need not fill NW x KPW)
     const uint16_t* xh = nullptr;   // bf16 mirror of x or NULL (read by the bf16 multi-chunk body instead of x)
     uint16_t* hh = nullptr;         // bf16 mirror of h or NULL (written beside h)

@@ -90,7 +90,7 @@ __device__ __forceinline__ void pdh_reduce(float* lds, const float (&base)[2], f
     }
     __syncthreads();
 }
-// gates (pd_gates_store's arithmetic) of both elements; h leaves as the bf16 mirror only: 4 units = one 8-byte write-through store
+// gates of both elements, as pd_gates_store; h leaves as the bf16 mirror only: 4 units = one 8-byte write-through store
 __device__ __forceinline__ void pdh_gates_store(const float (&z)[2], float (&c)[2], uint16_t* hh, int tile, int M, int MT) {
     const int col = threadIdx.x & 15;
 #pragma unroll
@@ -98,11 +98,7 @@ __device__ __forceinline__ void pdh_gates_store(const float (&z)[2], float (&c)[
         const int row = (threadIdx.x >> 4) + 32 * e;
         const float zf = gt_row_down<4>(z[e]), zg = gt_row_down<8>(z[e]), zo = gt_row_down<12>(z[e]);
         float hv = 0.f;
-        if (col < 4 && row < M) {
-            const float gi = gt_sigmoid(z[e]), gf = gt_sigmoid(zf), gg = gt_tanh(zg), go = gt_sigmoid(zo);
-            c[e] = __builtin_fmaf(gf, c[e], gi * gg);
-            hv = go * gt_tanh(c[e]);
-        }
+        if (col < 4 && row < M) hv = gt_lstm_cell(z[e], zf, zg, zo, c[e]);
         const float h1v = gt_row_down<1>(hv), h2v = gt_row_down<2>(hv), h3v = gt_row_down<3>(hv);
         if (col == 0 && row < M) {
             uint2 pk;
@@ -178,7 +174,7 @@ __device__ __forceinline__ void pdh_wait_flags_helped(const PersistDecodeArgs& A
             const bool ok = (!h0 || v0 >= want) && (lane > 1 || v1 >= want_h);
             if (__builtin_amdgcn_readfirstlane(__popcll(__ballot(ok))) == 64) break;
             if (++spins > PD_SPIN_MAX) { if (lane == 0) pd_give_up(A, sh, true); break; }
-            if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(pd_ld_sc1(A.err)) != 0u) { if (lane == 0) pd_give_up(A, sh, false); break; }
+            if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(gt_ld_sc1(A.err)) != 0u) { if (lane == 0) pd_give_up(A, sh, false); break; }
         }
     }
     __syncthreads();

@@ -66,11 +66,6 @@ constexpr uint32_t PD_SPIN_MAX = 1u << 20;
 constexpr int PD_F_P = 0, PD_F_C = PD_BMAX * 32, PD_CNT3 = 2 * PD_BMAX * 32, PD_CNT4 = PD_CNT3 + PD_GMAX * PD_NSH * 32,
               PD_F_H = PD_CNT4 + PD_GMAX * PD_NSH * 32, PD_CTL_WORDS = PD_F_H + 128 * 32;     // (helper flags: 2 x 32 tiles, bf16 kernel 2 x 64)
 
-__device__ __forceinline__ uint32_t pd_ld_sc1(const uint32_t* p) {
-    uint32_t v;
-    asm volatile("global_load_dword %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p) : "memory");
-    return v;
-}
 __device__ __forceinline__ uint2 pd_ld2_sc1(const uint2* p) {
     uint2 v;
     asm volatile("global_load_dwordx2 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p) : "memory");
@@ -126,10 +121,10 @@ __device__ __forceinline__ void pd_wait_flags(const PersistDecodeArgs& A, const 
         const int lane = threadIdx.x;
         uint32_t spins = 0;
         for (;;) {
-            const uint32_t v = lane < n ? pd_ld_sc1(f + lane * STRIDE) : want;
+            const uint32_t v = lane < n ? gt_ld_sc1(f + lane * STRIDE) : want;
             if (__builtin_amdgcn_readfirstlane(__popcll(__ballot(v >= want))) == 64) break;
             if (++spins > PD_SPIN_MAX) { if (lane == 0) pd_give_up(A, sh, true); break; }
-            if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(pd_ld_sc1(A.err)) != 0u) { if (lane == 0) pd_give_up(A, sh, false); break; }
+            if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(gt_ld_sc1(A.err)) != 0u) { if (lane == 0) pd_give_up(A, sh, false); break; }
             PD_SLEEP();
         }
     }
@@ -160,7 +155,7 @@ __device__ __forceinline__ void pd_wait_count(const PersistDecodeArgs& A, const 
             for (int k = 0; k < PD_NSH / 64; ++k) { asm volatile("" : "+v"(u[k])); ok = ok && u[k] >= want; }
             if (__builtin_amdgcn_readfirstlane(__popcll(__ballot(ok))) == 64) break;
             if (++spins > PD_SPIN_MAX) { if (lane == 0) pd_give_up(A, sh, true); break; }
-            if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(pd_ld_sc1(A.err)) != 0u) { if (lane == 0) pd_give_up(A, sh, false); break; }
+            if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(gt_ld_sc1(A.err)) != 0u) { if (lane == 0) pd_give_up(A, sh, false); break; }
             PD_SLEEP();
         }
     }
@@ -316,11 +311,7 @@ __device__ __forceinline__ void pd_gates_store(float z, float& c, float* hdst, i
     const float zf = gt_row_down<4>(z), zg = gt_row_down<8>(z), zo = gt_row_down<12>(z);
     float hv = 0.f;
     if (lrow >= rows) return;               // (16-row groups: the slab's upper half is unused; whole 16-lane segments leave together)
-    if (col < 4 && row < M) {
-        const float gi = gt_sigmoid(z), gf = gt_sigmoid(zf), gg = gt_tanh(zg), go = gt_sigmoid(zo);
-        c = __builtin_fmaf(gf, c, gi * gg);
-        hv = go * gt_tanh(c);
-    }
+    if (col < 4 && row < M) hv = gt_lstm_cell(z, zf, zg, zo, c);
     const float h1v = gt_row_down<1>(hv), h2v = gt_row_down<2>(hv), h3v = gt_row_down<3>(hv);
     if (col == 0 && row < M) pd_st4_sc1(hdst + gt_blk_off(row, tile * 4, MT), make_float4(hv, h1v, h2v, h3v));
 }
@@ -677,7 +668,7 @@ __device__ __forceinline__ void pd_chain_rest(const PersistDecodeArgs& A, const 
         uint32_t spins = 0;
         while (__builtin_amdgcn_readfirstlane(__popcll(__ballot(g.y == (uint32_t)t))) != 64) {
             if (++spins > PD_SPIN_MAX) { if (lane == 0) pd_give_up(A, sh, true); break; }
-            if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(pd_ld_sc1(A.err)) != 0u) { if (lane == 0) pd_give_up(A, sh, false); break; }
+            if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(gt_ld_sc1(A.err)) != 0u) { if (lane == 0) pd_give_up(A, sh, false); break; }
             g = pd_ld2_sc1(A.z0g + (size_t)b * PD_P + tid);
         }
         L.y0[tid] = fmaxf(__builtin_bit_cast(float, g.x), 0.f) * k0;
@@ -746,10 +737,10 @@ __device__ __forceinline__ void pd_chain_rest(const PersistDecodeArgs& A, const 
         const int l2 = tid & 63;
         uint32_t spins = 0;
         for (;;) {
-            const uint32_t v = l2 < 1 ? pd_ld_sc1(A.ctl + PD_F_H + b * 32) : (uint32_t)t;
+            const uint32_t v = l2 < 1 ? gt_ld_sc1(A.ctl + PD_F_H + b * 32) : (uint32_t)t;
             if (__builtin_amdgcn_readfirstlane(__popcll(__ballot(v >= (uint32_t)t))) == 64) break;
             if (++spins > PD_SPIN_MAX) { if (l2 == 0) pd_give_up(A, sh, true); break; }
-            if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(pd_ld_sc1(A.err)) != 0u) { if (l2 == 0) pd_give_up(A, sh, false); break; }
+            if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(gt_ld_sc1(A.err)) != 0u) { if (l2 == 0) pd_give_up(A, sh, false); break; }
         }
     }
     PD_STAMP(0, 16);

@@ -38,7 +38,7 @@ __device__ __forceinline__ void pd_wait_flags_all(const PersistDecodeArgs& A, co
             const bool ok = (!h0 || v0 >= want) && (!h1 || v1 >= want);
             if (__builtin_amdgcn_readfirstlane(__popcll(__ballot(ok))) == 64) break;
             if (++spins > PD_SPIN_MAX) { if (lane == 0) pd_give_up(A, sh, true); break; }
-            if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(pd_ld_sc1(A.err)) != 0u) { if (lane == 0) pd_give_up(A, sh, false); break; }
+            if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(gt_ld_sc1(A.err)) != 0u) { if (lane == 0) pd_give_up(A, sh, false); break; }
         }
     }
     __syncthreads();
@@ -63,7 +63,7 @@ __device__ __forceinline__ void pd_wait_count_all(const PersistDecodeArgs& A, co
             for (int g = 0; g < GM; ++g) { asm volatile("" : "+v"(u[g])); ok = ok && u[g] >= want; }
             if (__builtin_amdgcn_readfirstlane(__popcll(__ballot(ok))) == 64) break;
             if (++spins > PD_SPIN_MAX) { if (lane == 0) pd_give_up(A, sh, true); break; }
-            if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(pd_ld_sc1(A.err)) != 0u) { if (lane == 0) pd_give_up(A, sh, false); break; }
+            if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(gt_ld_sc1(A.err)) != 0u) { if (lane == 0) pd_give_up(A, sh, false); break; }
         }
     }
     __syncthreads();

@@ -206,13 +206,9 @@ __device__ __forceinline__ void gt_skinny_body(const SkinnyArgs& A, const int ti
                 if (A.out_blocked) A.h[gt_blk_off(grow, unit, MT)] = 0.f;
                 else A.h[(size_t)grow * A.ldh + unit] = 0.f;
             } else if (grow < M && unit < A.N) {
-                const float gi = gt_sigmoid(zs[row][u]);
-                const float gf = gt_sigmoid(zs[row][4 + u]);
-                const float gg = gt_tanh(zs[row][8 + u]);
-                const float go = gt_sigmoid(zs[row][12 + u]);
-                const float c2 = __builtin_fmaf(gf, c_prev, gi * gg);     // (explicit: the same contraction in every body)
+                float c2 = c_prev;
+                const float hv = gt_lstm_cell(zs[row][u], zs[row][4 + u], zs[row][8 + u], zs[row][12 + u], c2);
                 A.c[(size_t)grow * A.N + unit] = c2;
-                const float hv = go * gt_tanh(c2);
                 if (A.out_blocked) A.h[gt_blk_off(grow, unit, MT)] = hv;
                 else A.h[(size_t)grow * A.ldh + unit] = hv;
             }

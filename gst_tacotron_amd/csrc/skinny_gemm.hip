@@ -90,65 +90,88 @@ hipError_t gt_launch_skinny(int epi, const SkinnyArgs& a0, const SkinnyArgs* a1,
 // Lean decode-step kernels (see lean_body.h for why they exist)
 // ======================================================================================================================
 
-// z[32 rows x 16 gate columns] of tile `blockIdx.x` = x . W_x + partial_in; tile-local column g*4+u is gate g (i,f,c~,o)
-// of hidden unit tile*4+u (Appendix A.6; reference Taco2.py:79-85 via StackedRNNCells).  The 16 columns of a row sit in
-// 16 adjacent lanes, so the lanes with column < 4 collect their unit's four gates with three lane shifts -- no second LDS
-// round trip or barrier.
-template <int NW, int KPW, int TAG, bool BF16>
-__global__ __launch_bounds__(NW * 64) void gt_lstm_x_kernel(LstmXArgs A) {
-    __shared__ __attribute__((aligned(16))) float lds[LeanLds<NW, 1>::kFloats];
+// Gate epilogue of a thread-per-element tile.  z[row][col] = pin + the NW waves' partial sums (gt_lean_spill's slabs, in ascending
+// order); tile-local column g*4+u is gate g (i,f,c~,o) of hidden unit tile*4+u (Appendix A.6; reference Taco2.py:79-85 via
+// StackedRNNCells).  The 16 columns of a row sit in 16 adjacent lanes, so the lanes with column < 4 collect their unit's four gates with
+// three lane shifts -- no second LDS round trip or barrier.  EVERY lane executes the shifts, in front of any branch: a DPP move reads
+// the lanes a branch would have switched off.  The owner lanes then apply the encoder's masked rule (row_len: a step at or beyond
+// the utterance's length writes h = 0 and leaves c alone; NULL: every step exists), update c in place and hand h to
+// `store(grow, unit, h)`: where h goes, and how -- plain, write-through, with a bf16 mirror, with the encoder's output -- is the caller's.
+// (c by reference: a field of the launch's argument block, read where it is used.  Read once up front it makes the cell-state address
+// one value from the prologue's load to the store here: two registers held across the multiply.)
+template <int NW, class Store>
+__device__ __forceinline__ void gt_gate_epilogue(const float (*part)[32][17], const int row, const int col, const int grow, const int unit,
+                                                 const float pin, const float c_prev, float* const& c, const int M, const int H,
+                                                 const int32_t* row_len, const int t_index, Store store) {
+    float z = pin;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) z += part[w][row][col];
+    const float zf = gt_row_down<4>(z), zg = gt_row_down<8>(z), zo = gt_row_down<12>(z);
+    if (col < 4 && grow < M && unit < H) {
+        float hv = 0.f;
+        if (!(row_len && t_index >= row_len[grow])) {
+            float c2 = c_prev;
+            hv = gt_lstm_cell(z, zf, zg, zo, c2);
+            c[(size_t)grow * H + unit] = c2;
+        }
+        store(grow, unit, hv);
+    }
+}
+
+// One lean single-chunk LSTM step: z[32 rows x 16 gate columns] of `tile` = x . W + pin, then the gate epilogue.  `pin_of(grow, col)`
+// is the other half of the pre-activation (the decoder's recurrent-half partial sums, the encoder's hoisted input half); `dbg` may
+// be a literal null (the stamps fold away).  (c, M, H and the mask by reference, for gt_gate_epilogue's reason: the prologue and the
+// epilogue each read the argument block's fields themselves, as the kernels this body came from did.)
+template <int NW, int KPW, bool BF16, class Pin, class Store>
+__device__ __forceinline__ void gt_lean_lstm_step(const float* wp, const float* x, const int nkb, float* const& c, const int& M, const int MT,
+                                                  const int& H, const int tile, const int mchunk, const int32_t* const& row_len, const int& t_index,
+                                                  unsigned long long* dbg, float* lds, Pin pin_of, Store store) {
     constexpr int NE = 512 / (NW * 64);
-    const int tile = blockIdx.x, mchunk = blockIdx.y;
-    const int m0 = mchunk * 32, MT = A.MT;
-    GT_STAMP(A.dbg, 4);
+    const int m0 = mchunk * 32;
     float pin[NE], c_prev[NE];
 #pragma unroll
     for (int i = 0; i < NE; ++i) {
         const int e = threadIdx.x + i * NW * 64;
         const int row = e >> 4, col = e & 15;
         const int grow = m0 + row, unit = tile * 4 + col;
-        pin[i] = (grow < MT * 16) ? A.partial_in[((size_t)tile * MT * 16 + grow) * 16 + col] : 0.f;
-        c_prev[i] = (col < 4 && grow < A.M && unit < A.H) ? A.c[(size_t)grow * A.H + unit] : 0.f;
+        pin[i] = pin_of(grow, col);
+        c_prev[i] = (col < 4 && grow < M && unit < H) ? c[(size_t)grow * H + unit] : 0.f;
     }
-    GT_STAMP(A.dbg, 0);
+    GT_STAMP(dbg, 0);
     f32x4 acc0[1] = {f32x4{0.f, 0.f, 0.f, 0.f}}, acc1[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
     if constexpr (BF16) {
-        gt_lean_core_bf16<NW, KPW, 1, false>(A.wp, tile, 1, LeanX{A.x, A.x, A.nkb}, MT, mchunk, (A.nkb + 1) >> 1, acc0, acc1);
+        gt_lean_core_bf16<NW, KPW, 1, false>(wp, tile, 1, LeanX{x, x, nkb}, MT, mchunk, (nkb + 1) >> 1, acc0, acc1);
     } else {
-        gt_lean_core<NW, KPW, 1, false>(A.wp, tile, 1, LeanX{A.x, A.x, NW * KPW}, MT, mchunk, acc0, acc1);
+        gt_lean_core<NW, KPW, 1, false>(wp, tile, 1, LeanX{x, x, NW * KPW}, MT, mchunk, acc0, acc1);
     }
-    GT_STAMP(A.dbg, 1);
+    GT_STAMP(dbg, 1);
     gt_lean_spill<NW, 1>(lds, acc0, acc1);
     __syncthreads();
-    GT_STAMP(A.dbg, 2);
+    GT_STAMP(dbg, 2);
     const float (*part)[32][17] = reinterpret_cast<const float (*)[32][17]>(lds);     // [NW][32][17]
 #pragma unroll
     for (int i = 0; i < NE; ++i) {
         const int e = threadIdx.x + i * NW * 64;
         const int row = e >> 4, col = e & 15;
-        float z = pin[i];
-#pragma unroll
-        for (int w = 0; w < NW; ++w) z += part[w][row][col];
-        const float zf = gt_row_down<4>(z), zg = gt_row_down<8>(z), zo = gt_row_down<12>(z);
-        const int grow = m0 + row, unit = tile * 4 + col;
-        if (col < 4 && grow < A.M && unit < A.H) {
-            if (A.row_len && A.t_index >= A.row_len[grow]) {
-                A.h[gt_blk_off(grow, unit, MT)] = 0.f;          // masked mode: this step does not exist for this utterance
-            } else {
-                const float gi = gt_sigmoid(z), gf = gt_sigmoid(zf), gg = gt_tanh(zg), go = gt_sigmoid(zo);
-                const float c2 = __builtin_fmaf(gf, c_prev[i], gi * gg);
-                A.c[(size_t)grow * A.H + unit] = c2;
-                A.h[gt_blk_off(grow, unit, MT)] = go * gt_tanh(c2);
-            }
-        }
+        gt_gate_epilogue<NW>(part, row, col, m0 + row, tile * 4 + col, pin[i], c_prev[i], c, M, H, row_len, t_index, store);
     }
-    GT_STAMP(A.dbg, 3);
+    GT_STAMP(dbg, 3);
 }
 
-__device__ __forceinline__ uint32_t gt_ldu_sc1(const uint32_t* p) {
-    uint32_t v;
-    asm volatile("global_load_dword %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p) : "memory");
-    return v;
+// the recurrent half (+ bias) of a decode cell's pre-activation, left in tile order by the workers (gt_lean_partial)
+__device__ __forceinline__ float gt_lstm_pin(const LstmXArgs& A, const int tile, const int grow, const int col) {
+    return (grow < A.MT * 16) ? A.partial_in[((size_t)tile * A.MT * 16 + grow) * 16 + col] : 0.f;
+}
+
+// Input half of a decode LSTM cell (the decoder's masked mode acts on the attention, not on the cells: no row_len)
+template <int NW, int KPW, int TAG, bool BF16>
+__global__ __launch_bounds__(NW * 64) void gt_lstm_x_kernel(LstmXArgs A) {
+    __shared__ __attribute__((aligned(16))) float lds[LeanLds<NW, 1>::kFloats];
+    const int tile = blockIdx.x, MT = A.MT;
+    GT_STAMP(A.dbg, 4);
+    gt_lean_lstm_step<NW, KPW, BF16>(A.wp, A.x, A.nkb, A.c, A.M, MT, A.H, tile, blockIdx.y, nullptr, 0, A.dbg, lds,
+                                     [&](const int grow, const int col) { return gt_lstm_pin(A, tile, grow, col); },
+                                     [&](const int grow, const int unit, const float hv) { A.h[gt_blk_off(grow, unit, MT)] = hv; });
 }
 
 // ======================================================================================================================
@@ -160,7 +183,8 @@ __device__ __forceinline__ uint32_t gt_ldu_sc1(const uint32_t* p) {
 // partial sums and cell state are REQUESTED BEFORE the workgroup starts waiting for layer 1 (they depend on nothing this
 // launch computes), so the wait for the other 255 tiles' h1 hides their latency; h1 itself is stored write-through and read
 // with sc1 loads (gt_xload), the arrival counter is sharded over 8 cache lines and polled with sc1 loads.
-// Arithmetic = gt_lstm_x_kernel<8,3> followed by gt_lstm_x_kernel<8,8>, same orders: bitwise equal states.
+// It is gt_lstm_x_kernel<8,3> followed by gt_lstm_x_kernel<8,8> -- the same multiply, k-block and summation orders, and their
+// gt_gate_epilogue: bitwise equal states.
 //
 // The hand-off needs all of the launch's workgroups resident together: the host checks the grid against occupancy x CUs at
 // finalize (gt_lstm12_blocks_per_cu) and only takes this path while the process has ONE live context and no other context's
@@ -174,6 +198,41 @@ __device__ __forceinline__ void gt_st1_sc1(float* p, float v) {
     asm volatile("global_store_dword %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
 
+// The two give-up rules of a bounded in-kernel wait, for one failed poll: past the bound, raise the host-mapped error word; and now
+// and then look at that word, so that every waiting wave of the launch drains within microseconds of the first give-up.  Either way
+// the workgroup's abort flag is set, and true returned: the caller leaves its poll loop, the workgroup leaves behind its next barrier.
+__device__ __forceinline__ bool gt_wait_give_up(uint32_t& spins, uint32_t* err, int& s_abort, const int lane) {
+    ++spins;
+    if (spins > (1u << 18)) { if (lane == 0) { atomicOr(err, 1u); s_abort = 1; } return true; }
+    if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(gt_ld_sc1(err)) != 0u) { if (lane == 0) s_abort = 1; return true; }
+    return false;
+}
+// The fused launches' hand-off.  Arrive: this workgroup's part of h1 is out once its stores are acknowledged (nothing else is in
+// flight yet); one atomic on the workgroup's shard of the counter.
+__device__ __forceinline__ void gt_l12_arrive(const Lstm12Args& P) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_fetch_add(&P.arrive[(blockIdx.x & (GT_L12_NSH - 1)) * 32], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// Wait (wave 0 polls the shards, everybody else sits at the barrier) until all of the launch's workgroups have arrived; true: gave up,
+// the workgroup returns.  What the caller requested in front of the call stays in front of it and arrives during the wait.
+__device__ __forceinline__ bool gt_l12_wait(const Lstm12Args& P, int& s_abort) {
+    const int lane = threadIdx.x & 63;
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    if (threadIdx.x < 64) {
+        uint32_t spins = 0;
+        for (;;) {
+            uint32_t v = lane < GT_L12_NSH ? gt_ld_sc1(P.arrive + lane * 32) : 0u;
+            v = gt_row_sum_u32<GT_L12_NSH>(v);
+            if (__builtin_amdgcn_readfirstlane(v) >= P.expect) break;
+            if (gt_wait_give_up(spins, P.err, s_abort, lane)) break;
+        }
+    }
+    __syncthreads();
+    return s_abort != 0;
+}
+
 __global__ __launch_bounds__(512) void gt_lstm12_kernel(Lstm12Args P) {
     constexpr int NW = 8;
     __shared__ __attribute__((aligned(16))) float lds[LeanLds<NW, 1>::kFloats];
@@ -185,11 +244,13 @@ __global__ __launch_bounds__(512) void gt_lstm12_kernel(Lstm12Args P) {
     const float (*part)[32][17] = reinterpret_cast<const float (*)[32][17]>(lds);
     GT_STAMP(P.l1.dbg, 4);
     if (threadIdx.x == 0) s_abort = 0;
-    // ---------------------------------------------------------------- layer 1 (gt_lstm_x_kernel<8, 3>)
+    // ---------------------------------------------------------------- layer 1: gt_lean_lstm_step<8, 3, false>'s steps, written out
+    // (called, it costs this kernel four registers); h1 is stored write-through: it is read by every other workgroup below
     {
         const LstmXArgs& A = P.l1;
-        const int MT = A.MT, unit = tile * 4 + col;
-        const float pin = (row < MT * 16) ? A.partial_in[((size_t)tile * MT * 16 + row) * 16 + col] : 0.f;
+        const int MT = A.MT;
+        const int unit = tile * 4 + col;
+        const float pin = gt_lstm_pin(A, tile, row, col);
         const float c_prev = (col < 4 && row < A.M && unit < A.H) ? A.c[(size_t)row * A.H + unit] : 0.f;
         GT_STAMP(A.dbg, 0);
         f32x4 acc0[1] = {f32x4{0.f, 0.f, 0.f, 0.f}}, acc1[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
@@ -198,27 +259,17 @@ __global__ __launch_bounds__(512) void gt_lstm12_kernel(Lstm12Args P) {
         gt_lean_spill<NW, 1>(lds, acc0, acc1);
         __syncthreads();
         GT_STAMP(A.dbg, 2);
-        float z = pin;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) z += part[w][row][col];
-        const float zf = gt_row_down<4>(z), zg = gt_row_down<8>(z), zo = gt_row_down<12>(z);
-        if (col < 4 && row < A.M && unit < A.H) {
-            const float gi = gt_sigmoid(z), gf = gt_sigmoid(zf), gg = gt_tanh(zg), go = gt_sigmoid(zo);
-            const float c2 = __builtin_fmaf(gf, c_prev, gi * gg);
-            A.c[(size_t)row * A.H + unit] = c2;
-            gt_st1_sc1(A.h + gt_blk_off(row, unit, MT), go * gt_tanh(c2));     // write-through: read by every other workgroup below
-        }
+        gt_gate_epilogue<NW>(part, row, col, row, unit, pin, c_prev, A.c, A.M, A.H, nullptr, 0,
+                             [&](const int grow, const int u, const float hv) { gt_st1_sc1(A.h + gt_blk_off(grow, u, MT), hv); });
         GT_STAMP(A.dbg, 3);
     }
-    // ---------------------------------------------------------------- layer 2 (gt_lstm_x_kernel<8, 8>)
+    // ---------------------------------------------------------------- layer 2: gt_lstm_x_kernel<8, 8>'s arithmetic in its own request
+    // order -- weights, partial sums and cell state in front of the wait (they depend on nothing this launch computes and arrive during
+    // it), h1 behind it -- which is why it does not call gt_lean_lstm_step
     const LstmXArgs& A = P.l2;
     const int MT = A.MT, unit = tile * 4 + col;
-    // arrive first: this workgroup's part of h1 is out once its stores are acknowledged (nothing else is in flight yet)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_fetch_add(&P.arrive[(blockIdx.x & (GT_L12_NSH - 1)) * 32], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // ... then everything of layer 2 that does not depend on layer 1 is requested and arrives during the wait
-    const float pin = (row < MT * 16) ? A.partial_in[((size_t)tile * MT * 16 + row) * 16 + col] : 0.f;
+    gt_l12_arrive(P);
+    const float pin = gt_lstm_pin(A, tile, row, col);
     const float c_prev = (col < 4 && row < A.M && unit < A.H) ? A.c[(size_t)row * A.H + unit] : 0.f;
     constexpr int KPW = 8, NKB = NW * KPW;
     float4 b[KPW];
@@ -227,21 +278,7 @@ __global__ __launch_bounds__(512) void gt_lstm12_kernel(Lstm12Args P) {
 #pragma unroll
         for (int i = 0; i < KPW; ++i) b[i] = wl[(size_t)i * NW * 64];
     }
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    if (threadIdx.x < 64) {
-        uint32_t spins = 0;
-        for (;;) {
-            uint32_t v = lane < GT_L12_NSH ? gt_ldu_sc1(P.arrive + lane * 32) : 0u;
-            v = gt_row_sum_u32<GT_L12_NSH>(v);
-            if (__builtin_amdgcn_readfirstlane(v) >= P.expect) break;
-            ++spins;
-            if (spins > (1u << 18)) { if (lane == 0) { atomicOr(P.err, 1u); s_abort = 1; } break; }
-            if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(gt_ldu_sc1(P.err)) != 0u) { if (lane == 0) s_abort = 1; break; }
-        }
-    }
-    __syncthreads();
-    if (s_abort) return;
+    if (gt_l12_wait(P, s_abort)) return;
     GT_STAMP(A.dbg, 4);
     const LeanX X{A.x, A.x, NKB};
     const LeanXR XR = gt_x_rsrc(X);
@@ -274,16 +311,8 @@ __global__ __launch_bounds__(512) void gt_lstm12_kernel(Lstm12Args P) {
     }
     __syncthreads();
     GT_STAMP(A.dbg, 2);
-    float z = pin;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) z += part[w][row][col];
-    const float zf = gt_row_down<4>(z), zg = gt_row_down<8>(z), zo = gt_row_down<12>(z);
-    if (col < 4 && row < A.M && unit < A.H) {
-        const float gi = gt_sigmoid(z), gf = gt_sigmoid(zf), gg = gt_tanh(zg), go = gt_sigmoid(zo);
-        const float c2 = __builtin_fmaf(gf, c_prev, gi * gg);
-        A.c[(size_t)row * A.H + unit] = c2;
-        A.h[gt_blk_off(row, unit, MT)] = go * gt_tanh(c2);
-    }
+    gt_gate_epilogue<NW>(part, row, col, row, unit, pin, c_prev, A.c, A.M, A.H, nullptr, 0,
+                         [&](const int grow, const int u, const float hv) { A.h[gt_blk_off(grow, u, MT)] = hv; });
     GT_STAMP(A.dbg, 3);
 }
 
@@ -317,6 +346,7 @@ __device__ __forceinline__ void gt_lstm_x_mc_body(const LstmXArgs& A, const int 
             c_prev[j] = A.c[(size_t)min(grow, A.M - 1) * A.H + min(unit, A.H - 1)];
         }
     };
+    // gt_gate_epilogue's steps per tile of the pair, written out: called, it costs gt_lstm12_mc_kernel<2, 4, true> a register
     auto epi = [&](const int mc) {
         const int grow = mc * 32 + row;
 #pragma unroll
@@ -327,13 +357,9 @@ __device__ __forceinline__ void gt_lstm_x_mc_body(const LstmXArgs& A, const int 
             const float zf = gt_row_down<4>(z), zg = gt_row_down<8>(z), zo = gt_row_down<12>(z);
             const int unit = (tile0 + j) * 4 + col;
             if (j < ntile && col < 4 && grow < A.M && unit < A.H) {
-                float hv = 0.f;                                     // masked mode: a step that does not exist for this utterance writes 0
-                if (!(A.row_len && A.t_index >= A.row_len[grow])) {
-                    const float gi = gt_sigmoid(z), gf = gt_sigmoid(zf), gg = gt_tanh(zg), go = gt_sigmoid(zo);
-                    const float c2 = __builtin_fmaf(gf, c_prev[j], gi * gg);
-                    A.c[(size_t)grow * A.H + unit] = c2;
-                    hv = go * gt_tanh(c2);
-                }
+                float c2 = c_prev[j];
+                const float hv = gt_lstm_cell(z, zf, zg, zo, c2);
+                A.c[(size_t)grow * A.H + unit] = c2;
                 if (WT) gt_st1_sc1(A.h + gt_blk_off(grow, unit, MT), hv);
                 else A.h[gt_blk_off(grow, unit, MT)] = hv;
                 if (A.hh) {                                          // bf16 mirror for the next GEMMs' bf16 bodies
@@ -377,7 +403,6 @@ __global__ __launch_bounds__(512) void gt_lstm12_mc_kernel(Lstm12Args P) {
     constexpr int NW = 8;
     __shared__ __attribute__((aligned(16))) float lds[LeanLds<NW, 2>::kFloats];
     __shared__ int s_abort;
-    const int lane = threadIdx.x & 63;
     int tile0, ntile, c0, c1;
     const bool job = gt_lstm_mc_job(P.l1, tile0, ntile, c0, c1);
     if (threadIdx.x == 0) s_abort = 0;
@@ -386,27 +411,11 @@ __global__ __launch_bounds__(512) void gt_lstm12_mc_kernel(Lstm12Args P) {
         LeanW<KPW1, 2, BF16> W1;
         gt_lstm_x_mc_body<NW, KPW1, BF16, true, false>(P.l1, tile0, ntile, c0, c1, lds, W1);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_fetch_add(&P.arrive[(blockIdx.x & (GT_L12_NSH - 1)) * 32], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    gt_l12_arrive(P);
     if (!job) return;
     LeanW<KPW2, 2, BF16> W2;
     gt_lean_mc_load_w<NW, KPW2, 2, BF16, false>(P.l2.wp, tile0, ntile, (P.l2.nkb + 1) >> 1, W2);
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    if (threadIdx.x < 64) {
-        uint32_t spins = 0;
-        for (;;) {
-            uint32_t v = lane < GT_L12_NSH ? gt_ldu_sc1(P.arrive + lane * 32) : 0u;
-            v = gt_row_sum_u32<GT_L12_NSH>(v);
-            if (__builtin_amdgcn_readfirstlane(v) >= P.expect) break;
-            ++spins;
-            if (spins > (1u << 18)) { if (lane == 0) { atomicOr(P.err, 1u); s_abort = 1; } break; }
-            if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(gt_ldu_sc1(P.err)) != 0u) { if (lane == 0) s_abort = 1; break; }
-        }
-    }
-    __syncthreads();
-    if (s_abort) return;
+    if (gt_l12_wait(P, s_abort)) return;
     GT_STAMP(P.l2.dbg, 4);
     gt_lstm_x_mc_body<NW, KPW2, BF16, false, true>(P.l2, tile0, ntile, c0, c1, lds, W2);
 }
@@ -486,6 +495,16 @@ __device__ __forceinline__ void gt_pair_map(const int i, const int n, const int 
     mt = r / half;
 }
 
+// element (grow, gcol) of the projection's output into its column region: mel frames | stop logits | the next step's prenet-0
+// pre-activations (ProjArgs)
+__device__ __forceinline__ void gt_proj_store(const ProjArgs& P, const int grow, const int gcol, const float v) {
+    if (grow < P.M && gcol < P.N) {
+        if (P.out3 && gcol >= P.col3) P.out3[(size_t)grow * P.ldo3 + (gcol - P.col3)] = v;
+        else if (gcol < P.n_split) P.out[(size_t)grow * P.ldo + gcol] = v;
+        else if (!P.out3 || gcol < P.n_valid2) P.out2[(size_t)grow * P.ldo2 + (gcol - P.n_split)] = v;
+    }
+}
+
 // Projection (K = 1152 = 8 waves x 9 k-blocks) + co-scheduled layer-2 recurrent tiles (K = 1024 = 8 x 8).
 template <bool BF16>
 __global__ __launch_bounds__(512) void gt_proj_lean_kernel(ProjArgs P, LeanPartialArgs co, int n_main, int co_begin) {
@@ -521,12 +540,7 @@ __global__ __launch_bounds__(512) void gt_proj_lean_kernel(ProjArgs P, LeanParti
         float v = bias;
 #pragma unroll
         for (int w = 0; w < NW; ++w) v += part[w][row][col];
-        const int grow = mt * 16 + row;
-        if (grow < P.M && gcol < P.N) {
-            if (P.out3 && gcol >= P.col3) P.out3[(size_t)grow * P.ldo3 + (gcol - P.col3)] = v;
-            else if (gcol < P.n_split) P.out[(size_t)grow * P.ldo + gcol] = v;
-            else if (!P.out3 || gcol < P.n_valid2) P.out2[(size_t)grow * P.ldo2 + (gcol - P.n_split)] = v;
-        }
+        gt_proj_store(P, mt * 16 + row, gcol, v);
     }
     GT_STAMP(P.dbg, 3);
 }
@@ -566,12 +580,7 @@ __global__ __launch_bounds__(512) void gt_proj_mc_kernel(ProjArgs P, LeanPartial
     float v = bias;
 #pragma unroll
     for (int w = 0; w < NW; ++w) v += part[w][row][col];
-    const int grow = mc * 32 + row;
-    if (grow < P.M && gcol < P.N) {
-        if (P.out3 && gcol >= P.col3) P.out3[(size_t)grow * P.ldo3 + (gcol - P.col3)] = v;
-        else if (gcol < P.n_split) P.out[(size_t)grow * P.ldo + gcol] = v;
-        else if (!P.out3 || gcol < P.n_valid2) P.out2[(size_t)grow * P.ldo2 + (gcol - P.n_split)] = v;
-    }
+    gt_proj_store(P, mc * 32 + row, gcol, v);
 }
 
 bool gt_proj_lean_supported(int nkb_main, int nkb_co) { return nkb_main == 72 && (nkb_co == 64 || nkb_co == 0); }
@@ -599,47 +608,15 @@ hipError_t gt_launch_proj_lean(const ProjArgs& m, int ntiles, const float* co_wp
 template <int NW, int KPW>
 __global__ __launch_bounds__(NW * 64) void gt_bilstm_lean_kernel(BiLstmArgs A) {
     __shared__ __attribute__((aligned(16))) float lds[LeanLds<NW, 1>::kFloats];
-    constexpr int NE = 512 / (NW * 64);
     const BiLstmDir& D = A.d[blockIdx.z];
-    const int tile = blockIdx.x, mchunk = blockIdx.y;
-    const int m0 = mchunk * 32, MT = A.MT;
-    float pin[NE], c_prev[NE];
-#pragma unroll
-    for (int i = 0; i < NE; ++i) {
-        const int e = threadIdx.x + i * NW * 64;
-        const int row = e >> 4, col = e & 15;
-        const int grow = m0 + row, unit = tile * 4 + col;
-        pin[i] = (grow < A.M) ? D.zx[(size_t)grow * A.ldz + tile * 16 + col] : 0.f;
-        c_prev[i] = (col < 4 && grow < A.M && unit < A.H) ? D.c[(size_t)grow * A.H + unit] : 0.f;
-    }
-    f32x4 acc0[1] = {f32x4{0.f, 0.f, 0.f, 0.f}}, acc1[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
-    gt_lean_core<NW, KPW, 1, false>(D.wp, tile, 1, LeanX{D.hprev, D.hprev, NW * KPW}, MT, mchunk, acc0, acc1);
-    gt_lean_spill<NW, 1>(lds, acc0, acc1);
-    __syncthreads();
-    const float (*part)[32][17] = reinterpret_cast<const float (*)[32][17]>(lds);
-#pragma unroll
-    for (int i = 0; i < NE; ++i) {
-        const int e = threadIdx.x + i * NW * 64;
-        const int row = e >> 4, col = e & 15;
-        float z = pin[i];
-#pragma unroll
-        for (int w = 0; w < NW; ++w) z += part[w][row][col];
-        const float zf = gt_row_down<4>(z), zg = gt_row_down<8>(z), zo = gt_row_down<12>(z);
-        const int grow = m0 + row, unit = tile * 4 + col;
-        if (col < 4 && grow < A.M && unit < A.H) {
-            float hv = 0.f;
-            if (!(A.row_len && D.t_index >= A.row_len[grow])) {
-                const float gi = gt_sigmoid(z), gf = gt_sigmoid(zf), gg = gt_tanh(zg), go = gt_sigmoid(zo);
-                const float c2 = __builtin_fmaf(gf, c_prev[i], gi * gg);
-                D.c[(size_t)grow * A.H + unit] = c2;
-                hv = go * gt_tanh(c2);
-            }
-            D.hnext[gt_blk_off(grow, unit, MT)] = hv;
-            D.out[(size_t)grow * A.ldo + unit] = hv;
-        }
-    }
+    const int tile = blockIdx.x, MT = A.MT;
+    gt_lean_lstm_step<NW, KPW, false>(D.wp, D.hprev, NW * KPW, D.c, A.M, MT, A.H, tile, blockIdx.y, A.row_len, D.t_index, nullptr, lds,
+                                      [&](const int grow, const int col) { return (grow < A.M) ? D.zx[(size_t)grow * A.ldz + tile * 16 + col] : 0.f; },
+                                      [&](const int grow, const int unit, const float hv) {
+                                          D.hnext[gt_blk_off(grow, unit, MT)] = hv;
+                                          D.out[(size_t)grow * A.ldo + unit] = hv;
+                                      });
 }
-
 
 // ======================================================================================================================
 // Persistent Bidirectional LSTM: ALL time steps of both directions in ONE launch (reference Taco2.py:39-43, 394-398).
@@ -766,9 +743,7 @@ __global__ __launch_bounds__(512) void gt_bilstm_persist_kernel(BiLstmPersistArg
                 // every word carries the wanted tag: all of them set (tag 1) / none of them set (tag 0)
                 const bool ok = tag_r ? (all & (1u << 30)) != 0u : (any & (1u << 30)) == 0u;
                 if (__builtin_amdgcn_readfirstlane(__popcll(__ballot(ok))) == 64) break;
-                ++spins;
-                if (spins > (1u << 18)) { if (lane == 0) { atomicOr(A.err, 1u); s_abort = 1; } break; }
-                if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(gt_ldu_sc1(A.err)) != 0u) { if (lane == 0) s_abort = 1; break; }
+                if (gt_wait_give_up(spins, A.err, s_abort, lane)) break;
             }
             const uint32_t keep = ~(1u << 30);
 #pragma unroll
@@ -822,11 +797,7 @@ __global__ __launch_bounds__(512) void gt_bilstm_persist_kernel(BiLstmPersistArg
         for (int w = 0; w < NW; ++w) z += pt[w][j_own][row][col];
         const float zf = gt_row_down<4>(z), zg = gt_row_down<8>(z), zo = gt_row_down<12>(z);
         float hv = 0.f;
-        if (owner && real && tt < n_valid) {
-            const float gi = gt_sigmoid(z), gf = gt_sigmoid(zf), gg = gt_tanh(zg), go = gt_sigmoid(zo);
-            c_state = __builtin_fmaf(gf, c_state, gi * gg);
-            hv = go * gt_tanh(c_state);
-        }
+        if (owner && real && tt < n_valid) hv = gt_lstm_cell(z, zf, zg, zo, c_state);
         // the state first (somebody waits for it), tagged; then the encoding
         if (owner && t + 1 < A.T)
             reinterpret_cast<uint32_t*>(hbuf)[(size_t)slot_w * 16 * H + gt_blk_off(row, unit, 1)] = __builtin_bit_cast(uint32_t, hv) | tag_w;

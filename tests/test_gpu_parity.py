@@ -236,11 +236,15 @@ def test_lean_and_general_decode_kernels_are_the_same_arithmetic(monkeypatch, mi
     # utterance workgroups taking recurrent-half jobs after their chain, and two slabs of the persistent encoder BiLSTM)
     hp, w, tokens, tl, mels, ml, masks, noise = _full_case(B, 40, 90, 12, seed=9)
     hp = dict(hp); hp["Use_Mixed_Precision"] = bool(mixed)        # bf16 operands: the lean bf16 bodies, same claim
+    # masked mode (a step at or beyond an utterance's length writes h = 0 and keeps c): ragged lengths, row 0 surely short
+    tl_masked = np.random.default_rng(9).integers(1, 40 + 1, B).astype(np.int32)
+    tl_masked[0] = min(tl_masked[0], 39)
     w64 = None
     outs = []
     for lean in ("1", "0"):
         monkeypatch.setenv("GSTTACO_LEAN", lean)
         m = _model(hp, w, B, 40, 91)
+        enc_masked = m.encode(tokens, tl_masked).cpu().numpy()
         enc = m.encode(tokens)
         gst = m.Inference_GST_Step(mels, ml)
         torch.cuda.synchronize()
@@ -248,11 +252,12 @@ def test_lean_and_general_decode_kernels_are_the_same_arithmetic(monkeypatch, mi
             w64 = (enc.cpu().numpy().copy(), gst.cpu().numpy().copy())     # decode both variants from the SAME memory
         pre, stop, align = m.decode(w64[0], w64[1], masks, noise, steps=12)
         torch.cuda.synchronize()
-        outs.append((enc.cpu().numpy(), pre.cpu().numpy(), stop.cpu().numpy(), align.cpu().numpy()))
+        outs.append((enc.cpu().numpy(), enc_masked, pre.cpu().numpy(), stop.cpu().numpy(), align.cpu().numpy()))
     monkeypatch.delenv("GSTTACO_LEAN")
     # encoder: hoisted vs fused input half (another summation order; under bf16 operands a rounding can flip: mixed tolerance)
     assert np.abs(outs[0][0] - outs[1][0]).max() <= (MIXED_TOL if mixed else TOL)
-    for a, b in zip(outs[0][1:], outs[1][1:]):
+    assert np.abs(outs[0][1] - outs[1][1]).max() <= (MIXED_TOL if mixed else TOL)      # ... and the masked rule spelled both ways
+    for a, b in zip(outs[0][2:], outs[1][2:]):
         assert np.array_equal(a, b)                                          # decode loop: bitwise
 
 
