@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = (
     "gsttaco_postnet_variants", "gsttaco_debug_wino_h_planes",
     "gsttaco_encoder_variants", "gsttaco_vocoder_variants",
     "gsttaco_decode_plan_fields",
+    "gsttaco_mel_dtw",
 )
 # GSTTACO_PLAN_*: the fields gsttaco_decode_plan_fields fills, in order
 PLAN_FIELDS = ("persist", "persist_bf16", "fused", "lean_front", "lean_rec", "z0", "fuse12", "lean_x0", "lean_x1", "co_tiles", "lean_proj",
@@ -155,6 +156,8 @@ def load_library(path=None):
     lib.gsttaco_fill_randomness.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
     lib.gsttaco_utterance_report.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.gsttaco_losses.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
+    lib.gsttaco_mel_dtw.argtypes = [vp, vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, i32, i32, i32, i32, vp, vp, vp, vp]
+    lib.gsttaco_mel_dtw.restype = ctypes.c_int
     lib.gsttaco_postnet.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.gsttaco_vocoder.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.gsttaco_inference_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]

@@ -211,6 +211,11 @@ struct gsttaco_ctx {
     // Teacher forcing (gsttaco_decode_forced / gsttaco_inference_step_forced): the consumed frames [S][B][mel] and every step's prenet-0
     // pre-activations [S][B][P0], allocated by the first forced call (ensure_forced); z0_dense = the plain pw0 / pb0 as a conv/GEMM layer
     float *w_teach = nullptr, *w_zf = nullptr;
+    // MCD-DTW (gsttaco_mel_dtw): both sides' features, allocated by the first call; the back-pointers by the first call that asks for
+    // the path; one DCT-II basis per n_ceps seen (ensure_dtw)
+    double *w_dtw_fx = nullptr, *w_dtw_fy = nullptr;
+    uint8_t* w_dtw_bp = nullptr;
+    std::map<int, double*> dtw_basis;
     ConvLayer z0_dense;
     ConvLayer val_enc;          // the [enc] rows of the Value kernel (+ its bias when no GST row bias carries it)
     float *att_v = nullptr, *att_sb = nullptr;
@@ -2735,6 +2740,67 @@ int gsttaco_losses(gsttaco_ctx* c, const float* pre_mel, const float* mel, const
     a.mel_len = mel_lengths; a.spec_len = spec_lengths; a.losses = losses;
     a.B = B; a.S = S; a.Tq = Tq; a.r = c->r; a.mel_dim = c->cfg.mel_dim; a.spec_dim = c->cfg.spec_dim > 0 ? c->cfg.spec_dim : 1;
     HIPCHECK(c, gt_launch_losses(a, (hipStream_t)stream));
+    return 0;
+}
+
+// The workspace of gsttaco_mel_dtw, sized by the capacity given at create and allocated on first use like the forced decode's
+// (ensure_forced); *basis = the device copy of rows 1..n_ceps of the orthonormal DCT-II over the channels (NULL for n_ceps 0).
+static int ensure_dtw(gsttaco_ctx* c, int n_ceps, bool with_path, const double** basis) {
+    const gsttaco_config& g = c->cfg;
+    const size_t T = (size_t)g.max_step, M = (size_t)g.mel_dim;
+    int rc = 0;
+    if (!c->w_dtw_fx) {
+        HIPCHECK(c, gt_dtw_init());
+        if ((rc = dev_alloc(c, (void**)&c->w_dtw_fx, (size_t)g.max_batch * T * M * sizeof(double)))) return rc;
+    }
+    if (!c->w_dtw_fy && (rc = dev_alloc(c, (void**)&c->w_dtw_fy, (size_t)g.max_batch * T * M * sizeof(double)))) return rc;
+    if (with_path && !c->w_dtw_bp && (rc = dev_alloc(c, (void**)&c->w_dtw_bp, (size_t)g.max_batch * T * T))) return rc;
+    *basis = nullptr;
+    if (n_ceps == 0) return 0;
+    auto it = c->dtw_basis.find(n_ceps);
+    if (it == c->dtw_basis.end()) {
+        std::vector<double> h((size_t)n_ceps * M);
+        const double norm = std::sqrt(2.0 / (double)M);
+        for (int k = 1; k <= n_ceps; ++k)
+            for (size_t m = 0; m < M; ++m) h[(size_t)(k - 1) * M + m] = norm * std::cos(M_PI * k * (2.0 * m + 1.0) / (2.0 * M));
+        double* d = nullptr;
+        if ((rc = dev_alloc(c, (void**)&d, h.size() * sizeof(double)))) return rc;
+        HIPCHECK(c, hipMemcpy(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+        it = c->dtw_basis.emplace(n_ceps, d).first;
+    }
+    *basis = it->second;
+    return 0;
+}
+
+// Mel-cepstral distortion along a DTW path: two launches on the caller's stream straight from / to the caller's pointers.  Needs no
+// weights (only Mel_Dim, Max_Step and Max_Abs_Mel).
+int gsttaco_mel_dtw(gsttaco_ctx* c, const float* x, const int32_t* x_len, int64_t x_stride, const float* y, const int32_t* y_len,
+                    int64_t y_stride, int B, int Tx, int Ty, int n_ceps, double* cost, int32_t* path_len, int32_t* path, void* stream) {
+    if (!c) return GSTTACO_E_INVALID;
+    const gsttaco_config& g = c->cfg;
+    if (!x || !y || !cost || !path_len) return fail(c, GSTTACO_E_INVALID, "null argument");
+    if (B < 1 || Tx < 1 || Ty < 1) return fail(c, GSTTACO_E_INVALID, "bad B / Tx / Ty");
+    if (n_ceps < 0 || n_ceps >= g.mel_dim) return fail(c, GSTTACO_E_INVALID, "n_ceps must be in [0, Mel_Dim)");
+    if (x_stride < 0 || y_stride < 0) return fail(c, GSTTACO_E_INVALID, "negative batch stride");
+    if (B > g.max_batch || Tx > g.max_step || Ty > g.max_step)
+        return fail(c, GSTTACO_E_CAPACITY, "batch / frames exceed the capacity given at create (max_batch, Max_Step)");
+    if (gt_dtw_lds_bytes(Ty) > GT_DTW_MAX_LDS)
+        return fail(c, GSTTACO_E_CAPACITY, "Ty exceeds the 4551 columns whose rolling diagonals fit a workgroup's LDS");
+    int rc = ensure_device(c);
+    if (rc) return rc;
+    DtwArgs a{};
+    if ((rc = ensure_dtw(c, n_ceps, path != nullptr, &a.basis))) return rc;
+    a.x = x; a.y = y; a.x_len = x_len; a.y_len = y_len;
+    a.x_stride = x_stride ? x_stride : (int64_t)Tx * g.mel_dim;
+    a.y_stride = y_stride ? y_stride : (int64_t)Ty * g.mel_dim;
+    const double db_per_unit = g.max_abs_mel > 0.f ? 100.0 / (2.0 * (double)g.max_abs_mel) : 100.0;
+    a.scale = db_per_unit / std::sqrt(2.0);
+    a.clip_lo = g.max_abs_mel > 0.f ? -g.max_abs_mel : 0.f;
+    a.clip_hi = g.max_abs_mel > 0.f ? g.max_abs_mel : 1.f;
+    a.fx = c->w_dtw_fx; a.fy = c->w_dtw_fy; a.backptr = c->w_dtw_bp;
+    a.cost = cost; a.path_len = path_len; a.path = path;
+    a.B = B; a.Tx = Tx; a.Ty = Ty; a.mel_dim = g.mel_dim; a.n_ceps = n_ceps;
+    HIPCHECK(c, gt_launch_mel_dtw(a, (hipStream_t)stream));
     return 0;
 }
 

@@ -524,3 +524,28 @@ struct LossArgs {
     int B, S, Tq, r, mel_dim, spec_dim;
 };
 hipError_t gt_launch_losses(const LossArgs& a, hipStream_t stream);
+
+
+// ---------------------------------------------------------------- dtw.hip
+// Mel-cepstral distortion along a DTW path (the contract: gsttaco_mel_dtw in include/gsttaco.h).  Two launches on the stream: the features
+// of every used frame of both sides into fx / fy, then one workgroup per utterance for the sweep and the walk back.
+struct DtwArgs {
+    const float* x;             // [B, Tx, mel_dim] at batch stride x_stride floats (synthesised)
+    const float* y;             // [B, Ty, mel_dim] at batch stride y_stride floats (reference)
+    const int32_t* x_len;       // [B], or NULL (= Tx); clipped to [0, Tx]
+    const int32_t* y_len;       // [B], or NULL (= Ty); clipped to [0, Ty]
+    int64_t x_stride, y_stride;
+    const double* basis;        // [n_ceps][mel_dim] rows 1..n_ceps of the orthonormal DCT-II, or NULL with n_ceps == 0
+    double scale;               // dB per unit of the normalised mel, over sqrt(2)
+    float clip_lo, clip_hi;     // the normalisation's range
+    double *fx, *fy;            // workspace: [B, F, Tx] and [B, F, Ty] features, F = n_ceps ? n_ceps : mel_dim
+    uint8_t* backptr;           // workspace: [B, Tx, Ty] predecessor of each cell (0 diagonal, 1 up, 2 left); needed only with path
+    double* cost;               // [B]
+    int32_t* path_len;          // [B]
+    int32_t* path;              // [B, Tx + Ty - 1, 2], or NULL
+    int B, Tx, Ty, mel_dim, n_ceps;
+};
+#define GT_DTW_MAX_LDS (160 * 1024)         // the sweep's rolling diagonals: gt_dtw_lds_bytes(Ty) of LDS, Ty <= 4551
+size_t gt_dtw_lds_bytes(int Ty);
+hipError_t gt_dtw_init();                   // once per process and device, before a launch that needs more than 64 KiB of LDS
+hipError_t gt_launch_mel_dtw(const DtwArgs& a, hipStream_t stream);

@@ -54,3 +54,63 @@ def per_utterance_means(sums, lengths, spectrogram_lengths=None, steps=None):
     if steps is not None:
         out[:, 3] = sums[:, 3] / float(steps)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------- the free-run metric (Evaluate_Free)
+# Host side of ``GST_Tacotron.Evaluate_Free``: the constants of ``gsttaco_mel_dtw`` (include/gsttaco.h), stated once for the library's
+# documentation and the test oracle, and how its per-utterance outputs become the reported numbers.
+FREE_FIELDS = ("mcd", "cost", "path_len", "frames", "ref_frames", "duration_ratio", "stop_fired")
+
+
+def dct_basis(n_ceps, mel_dim):
+    """float64 [n_ceps, mel_dim]: rows k = 1 .. n_ceps of the orthonormal DCT-II over ``mel_dim`` channels,
+    sqrt(2 / M) cos(pi k (2 m + 1) / (2 M)) -- c0 is dropped, so the rows are orthonormal (``basis @ basis.T`` = I) for n_ceps < mel_dim."""
+    n_ceps, M = int(n_ceps), int(mel_dim)
+    if not 1 <= n_ceps < M:
+        raise ValueError("n_ceps must be in [1, mel_dim)")
+    k = np.arange(1, n_ceps + 1, dtype=np.float64)[:, None]
+    m = np.arange(M, dtype=np.float64)[None, :]
+    return np.sqrt(2.0 / M) * np.cos(np.pi * k * (2.0 * m + 1.0) / (2.0 * M))
+
+
+def mel_range(hp):
+    """(low, high) of the normalised mel, what the reference's de-normalisation clips to (Audio.py:98-102): +-Sound.Max_Abs_Mel, or
+    (0, 1) when that is 0 or absent.  The value is the float32 the context holds; without a complete Sound section
+    ``capi.make_config`` leaves it 0, and so does this."""
+    from .hparams import Dims
+    d = Dims(hp)
+    a = float(np.float32(d.max_abs_mel)) if d.audio else 0.0
+    return (-a, a) if a > 0 else (0.0, 1.0)
+
+
+def mcd_scale(hp):
+    """What ``gsttaco_mel_dtw`` multiplies every feature by: g / sqrt(2) with g = dB per unit of the normalised mel = 100 / (2 Max_Abs_Mel)
+    (100 for the [0, 1] normalisation).  With it the Euclidean distance of two frames' features is (10 / ln 10) sqrt(2 sum dc^2) on
+    natural-log amplitude cepstra: the usual MCD in dB (derivation: include/gsttaco.h)."""
+    lo, hi = mel_range(hp)
+    return 100.0 / (hi - lo) / np.sqrt(2.0)
+
+
+def combine_free(cost, path_len, frames, ref_frames, stop_step, steps):
+    """float64 [B, len(FREE_FIELDS)] from ``gsttaco_mel_dtw``'s cost / path_len, the synthesis report's frames / stop_step
+    (``REPORT_FIELDS``), the reference lengths and the step count S of the decode: mcd = cost / path_len (a ``path_len`` of 0 gives 0,
+    not NaN), duration_ratio = frames / ref_frames (0 for ref_frames 0), stop_fired = 1 where stop_step < S."""
+    cost = np.asarray(cost, np.float64).reshape(-1)
+    cols = [np.asarray(v, np.float64).reshape(-1) for v in (path_len, frames, ref_frames, stop_step)]
+    if any(c.shape != cost.shape for c in cols) or cost.shape[0] < 1:
+        raise ValueError("cost, path_len, frames, ref_frames and stop_step must be [batch]")
+    n, fr, ref, stop = cols
+    out = np.zeros((cost.shape[0], len(FREE_FIELDS)), np.float64)
+    out[:, 0] = np.where(n > 0, cost / np.maximum(n, 1.0), 0.0)
+    out[:, 1], out[:, 2], out[:, 3], out[:, 4] = cost, n, fr, ref
+    out[:, 5] = np.where(ref > 0, fr / np.maximum(ref, 1.0), 0.0)
+    out[:, 6] = (stop < float(steps)).astype(np.float64)
+    return out
+
+
+def summarize_free(per_utterance):
+    """{mcd: the mean over utterances of cost / path_len, mcd_frames: sum cost / sum path_len (0 for an empty sum)} of
+    ``combine_free``'s result."""
+    per = np.asarray(per_utterance, np.float64)
+    n = per[:, 2].sum()
+    return {"mcd": float(per[:, 0].mean()), "mcd_frames": float(per[:, 1].sum() / n) if n > 0 else 0.0}

@@ -8,6 +8,7 @@
     .Style_Compose(token_weights, query)                 (extension: a style from token weights)
     .Inference_GTA(sentence_List, mel_or_wav_List)       (extension: teacher-forced decoding -- GTA mels, forced durations)
     .Evaluate(sentence_List, mel_or_wav_List)            (extension: Train_Step's loss terms of a teacher-forced pass)
+    .Evaluate_Free(sentence_List, mel_or_wav_List)       (extension: MCD along a DTW path of a free run against its target)
 
 Same names, argument order/meaning and error behaviour; the Keras functional model
 behind them (Model.py:145-156) is replaced by the HIP kernels behind include/gsttaco.h.
@@ -34,7 +35,9 @@ PyTorch is used for device memory and streams only.  Differences, all additive:
     rejected rows under new seeds;
   * validation losses: ``Evaluate`` runs one teacher-forced pass and returns the four loss terms of the reference's ``Train_Step``
     (Model.py:210-241), per utterance and per batch (``Loss_Terms`` on the device, ``gst_tacotron_amd.evaluate`` on the host);
-    ``Feature_Generate`` is ``Mel_Generate`` with the linear spectrogram target from the same STFT.
+    ``Feature_Generate`` is ``Mel_Generate`` with the linear spectrogram target from the same STFT;
+  * a free-run metric: ``Mel_DTW`` aligns two mel sequences of different lengths on the device (mel-cepstral distortion along a
+    dynamic-time-warping path) and ``Evaluate_Free`` reports it for a free-running ``Inference_Step`` against its target.
 """
 import ctypes
 import os
@@ -45,7 +48,7 @@ import torch
 
 from . import capi, checked, evaluate, weights as weights_mod
 from .checked import REPORT_FIELDS  # noqa: F401  -- the columns of Utterance_Report's first result
-from .evaluate import LOSS_FIELDS  # noqa: F401  -- the columns of Loss_Terms' result
+from .evaluate import FREE_FIELDS, LOSS_FIELDS  # noqa: F401  -- the columns of Evaluate_Free's per_utterance and of Loss_Terms' result
 from .feeder import Feeder
 from .hparams import Dims, load_hp, load_token_dict
 
@@ -435,6 +438,93 @@ class GST_Tacotron:
         S, T = int(out[1].shape[1]), int(pattern["teacher_mels"].shape[1]) - 1
         result = evaluate.combine(per, T, S, evaluate.use_l2_of(self.hp_Dict) if use_l2 is None else bool(use_l2))
         result.update(per_utterance=per, mel_lengths=pattern["mel_lengths"], steps=S)
+        return result
+
+    def _frames_view(self, t, name):
+        """A float32 device tensor [B, T, Mel_Dim] whose frames are dense (a slice along the frame axis stays a view: its batch stride is
+        passed on), the batch stride in floats and T."""
+        t = t if isinstance(t, torch.Tensor) and t.device == self.device and t.dtype == torch.float32 else self._dev(t, torch.float32)
+        if t.dim() != 3 or t.shape[2] != self.dims.mel or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError(name + " must be [batch, frames >= 1, Mel_Dim]")
+        if t.stride(2) != 1 or t.stride(1) != t.shape[2] or (t.shape[0] > 1 and t.stride(0) < t.shape[1] * t.shape[2]):
+            t = t.contiguous()
+        return t, int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1] * t.shape[2]), int(t.shape[1])
+
+    def Mel_DTW(self, mels, mel_lengths, ref_mels, ref_lengths, n_ceps=13, return_path=False):
+        """Extension: mel-cepstral distortion along a dynamic-time-warping path (``gsttaco_mel_dtw``) between ``mels`` [B, Tx, Mel_Dim]
+        (synthesised) and ``ref_mels`` [B, Ty, Mel_Dim] (reference), torch or numpy, with ``mel_lengths`` / ``ref_lengths`` [B] or None
+        (all frames; ``mel_lengths`` may be the ``frames`` column of ``Utterance_Report`` as a device tensor).  A view sliced along the
+        frame axis -- ``mels_for_gst[:, 1:]`` -- is taken without a copy.  Returns (cost float64 [B], path_len int32 [B]) on the
+        device, and with ``return_path=True`` also path int32 [B, Tx + Ty - 1, 2]: the cells (i, j) from (0, 0) to the last frames,
+        -1 beyond ``path_len``.  ``cost / path_len`` is the utterance's MCD in dB of the log-mel cepstra 1 .. ``n_ceps`` (0: the mel
+        channels themselves); comparable between checkpoints of one configuration, not with SPTK mel-cepstrum figures.  Works before
+        Restore (no weights involved)."""
+        x, xs, Tx = self._frames_view(mels, "mels")
+        y, ys, Ty = self._frames_view(ref_mels, "ref_mels")
+        B = int(x.shape[0])
+        if y.shape[0] != B:
+            raise ValueError("mels and ref_mels must have one batch size")
+        xl, yl = self._dev(mel_lengths, torch.int32), self._dev(ref_lengths, torch.int32)
+        for name, v in (("mel_lengths", xl), ("ref_lengths", yl)):
+            if v is not None and tuple(v.shape) != (B,):
+                raise ValueError(name + " must be [batch]")
+        if not torch.cuda.is_available():
+            raise capi.GstTacoError(-2, "no HIP device: the gfx950 kernels are the only compute path (no CPU fallback)")
+        cost = torch.empty((B,), dtype=torch.float64, device=self.device)
+        plen = torch.empty((B,), dtype=torch.int32, device=self.device)
+        path = torch.empty((B, Tx + Ty - 1, 2), dtype=torch.int32, device=self.device) if return_path else None
+        with torch.cuda.device(self.device):
+            self.ctx.check(self.ctx.lib.gsttaco_mel_dtw(self.ctx.handle, _ptr(x), _ptr(xl), xs, _ptr(y), _ptr(yl), ys, B, Tx, Ty, int(n_ceps),
+                                                        _ptr(cost), _ptr(plen), _ptr(path), self._stream()))
+        return (cost, plen, path) if return_path else (cost, plen)
+
+    def Evaluate_Free(self, sentence_List, mel_or_wav_List, wav_List_for_GST=None, style_embeddings=None, seeds=None, n_ceps=13,
+                      **kwargs):
+        """Extension: the free-run metric of this checkpoint on the given sentences and targets -- what ``Evaluate`` cannot give, because
+        the free-running decoder's output has another length than its target: one ``Inference_Step`` (not teacher-forced),
+        ``Utterance_Report`` for the frames each utterance used, and ``Mel_DTW`` of those frames against the target's.
+        ``mel_or_wav_List`` holds one target per sentence as ``Evaluate`` takes them: wav paths / 1-D sample arrays (``Mel_Generate`` at
+        top_db 15) or mels [T, Mel_Dim] taken as given.  The style comes from ``style_embeddings`` or ``wav_List_for_GST`` when given,
+        else from the target itself.  ``seeds`` [B]: per-utterance seeds; the call then runs masked (dropout is live at inference:
+        without a seed the number is a random variable).  ``kwargs`` go to ``Inference_Step`` (``seed``, ``steps``, ``masked``, ...).
+        Nothing is read back before the final result.  Returns a dict: ``mcd`` (the mean over utterances of cost / path_len, dB),
+        ``mcd_frames`` (sum cost / sum path_len), ``per_utterance`` (numpy float64 [B, 7], ``evaluate.FREE_FIELDS``), ``report`` (numpy
+        int32 [B, 8], ``REPORT_FIELDS``), ``mel_lengths`` / ``ref_lengths`` (numpy int32 [B]), and the device tensors ``mels``
+        [B, S * r, Mel_Dim] and ``ref_mels`` [B, T, Mel_Dim] the distance was taken between."""
+        print("Free-run evaluation running...")
+        for k in ("teacher_mels", "return_pre_mel", "with_vocoder", "mels_for_gst", "mel_lengths_for_gst"):
+            if k in kwargs:
+                raise ValueError("Evaluate_Free sets '{}' itself".format(k))
+        if seeds is not None:
+            kwargs["seeds"], kwargs["masked"] = seeds, True
+        targets = list(mel_or_wav_List)
+        if len(targets) != len(sentence_List):
+            raise ValueError("mel_or_wav_List must hold one target per sentence")
+        if all(self.feeder._is_mel(m) for m in targets):
+            ref = self.feeder.Get_Inference_GST_Pattern(targets)
+            ref_all, ref_len = self._dev(ref["mels_for_gst"], torch.float32), self._dev(ref["mel_lengths_for_gst"], torch.int32)
+        else:
+            ref_all, ref_len = self.Mel_Generate(targets, 15)
+        pattern = self.feeder.Get_Inference_Pattern(sentence_List, style_given=True)
+        if self.hp_Dict["GST"]["Use"]:
+            if style_embeddings is not None:
+                if wav_List_for_GST is not None:
+                    raise ValueError("wav_List_for_GST and style_embeddings are mutually exclusive")
+                pattern["style_embeddings"] = style_embeddings
+            elif wav_List_for_GST is not None:
+                pattern.update(self.feeder.Get_Inference_GST_Pattern(list(wav_List_for_GST)))
+            else:
+                pattern["mels_for_gst"], pattern["mel_lengths_for_gst"] = ref_all, ref_len
+        mel, stop, _, align = self.Inference_Step(**pattern, **kwargs)
+        report, _ = self.Utterance_Report(stop, align, pattern["token_lengths"] if kwargs.get("masked") else None, mel)
+        frames = report[:, REPORT_FIELDS.index("frames")].contiguous()
+        ref_mels = ref_all[:, 1:]                                   # (behind the prepended zero frame: a view, no copy)
+        cost, plen = self.Mel_DTW(mel, frames, ref_mels, ref_len, n_ceps=n_ceps)
+        self.synchronize()
+        rep, ref_lengths = report.cpu().numpy(), ref_len.cpu().numpy()
+        per = evaluate.combine_free(cost.cpu().numpy(), plen.cpu().numpy(), rep[:, 1], ref_lengths, rep[:, 0], int(stop.shape[1]))
+        result = evaluate.summarize_free(per)
+        result.update(per_utterance=per, report=rep, mel_lengths=rep[:, 1].copy(), ref_lengths=ref_lengths, mels=mel, ref_mels=ref_mels)
         return result
 
     def Inference_GST(self, wav_List, tag_List=None, label=None):

@@ -29,6 +29,8 @@
  *   gsttaco_losses / gsttaco_feature_frontend
  *                       <- EXTENSION (DESIGN row A17): the four loss terms of Train_Step (Model.py:210-241) of a teacher-forced pass, per
  *                          utterance on the device, and the mel plus the linear spectrogram target (Audio.py:18-21) from one STFT
+ *   gsttaco_mel_dtw     <- EXTENSION (DESIGN row A18): the free-run metric, mel-cepstral distortion along a dynamic-time-warping path
+ *                          between synthesised and reference mels of different lengths, per utterance on the device
  *   gsttaco_postnet     <- Modules/Taco2.py:131-149, 230
  *   gsttaco_vocoder     <- Modules/Taco2.py:234-260 Vocoder_Taco1.call, CBHG :285-380
  *   gsttaco_mel_frontend <- Pattern_Generator.py:39-60 Mel_Generate + Audio.py:29-32,49-55,70-96 melspectrogram
@@ -384,6 +386,43 @@ int gsttaco_utterance_report(gsttaco_ctx* ctx, const float* stop, const float* a
 int gsttaco_losses(gsttaco_ctx* ctx, const float* pre_mel, const float* mel, const float* stop, const float* spectrogram,
                    const float* teacher, const float* spec_target, const int32_t* mel_lengths, const int32_t* spec_lengths,
                    int B, int S, int Tq, double* losses, void* stream);
+
+/* Free-run metric (EXTENSION, DESIGN row A18): mel-cepstral distortion along a dynamic-time-warping path (MCD-DTW) between x (synthesised)
+ * and y (reference), whose lengths differ, per utterance on the device.
+ *   x : [B, Tx, mel_dim]    y : [B, Ty, mel_dim]    float32; x_stride / y_stride = batch stride in floats (0 = T * mel_dim), so
+ *       mels_for_gst + mel_dim with y_stride = Tref1 * mel_dim skips the prepended zero frame without a copy
+ *   x_len, y_len : [B] int32 or NULL (= Tx / Ty); Lx = clip(x_len[b], 0, Tx), Ly = clip(y_len[b], 0, Ty).  Frames at or beyond the length
+ *       are never read.
+ * Features.  Every value v is clipped to the normalisation's range as the reference's de-normalisation clips it (Audio.py:98-102):
+ * [-A, A] with A = Sound.Max_Abs_Mel (held as float32), [0, 1] when A == 0 (or the context has no Sound section); then converted to
+ * double.  n_ceps == 0: the feature vector is the mel_dim channels; 1 <= n_ceps < mel_dim: coefficients k = 1 .. n_ceps (c0 dropped)
+ * of the orthonormal DCT-II over the M = mel_dim channels, sum_m v_m sqrt(2/M) cos(pi k (2m+1) / (2M)), summed in double in ascending
+ * m; the basis is built in double on the host once per n_ceps.  Either kind is multiplied by g / sqrt(2), g = dB per unit of the
+ * normalised mel = 100 / (2A) (100 when A == 0).  Derivation: the normalised mel is affine in the mel's dB value with slope 2A / 100
+ * (Audio.py:92-96, min_level_db = -100), so a difference of 1 is g dB; dB = 20 log10(amplitude), so a difference ddB is
+ * dc = ddB ln10 / 20 in natural-log amplitude; the usual MCD in dB of a frame pair is (10 / ln10) sqrt(2 sum_k dc_k^2)
+ * = (10 / ln10) sqrt(2) (ln10 / 20) sqrt(sum_k ddB_k^2) = (g / sqrt(2)) sqrt(sum_k dv_k^2), and an orthonormal transform keeps that
+ * sum.  So the Euclidean distance of two scaled feature vectors IS that frame pair's MCD in dB -- of these log-mel cepstra: comparable
+ * between checkpoints of one configuration, NOT with SPTK mel-cepstrum figures from papers.
+ * Recurrence, double throughout.  C(i,j) = sqrt(sum_k (f_ik - g_jk)^2); D(0,0) = C(0,0); D(i,j) = C(i,j) + min(D(i-1,j-1), D(i-1,j),
+ * D(i,j-1)) over the predecessors that exist; unit weights, no band.  Ties: the diagonal, replaced by up (i-1,j) only if that is
+ * strictly smaller, then by left (i,j-1) only if that is strictly smaller than the best so far.  The path is the chain of chosen
+ * predecessors from (Lx-1, Ly-1).
+ *   cost     : [B] DOUBLE  D(Lx-1, Ly-1)            path_len : [B] int32  cells on that path (max(Lx,Ly) .. Lx+Ly-1)
+ *   path     : [B, Tx+Ty-1, 2] int32 or NULL: the cells (i, j) from (0,0) to (Lx-1, Ly-1); rows at or beyond path_len[b] are -1
+ * A row with Lx == 0 or Ly == 0: cost 0, path_len 0, path all -1.  A non-finite value (NaN or +-Inf: an infinity is NOT clipped into
+ * range) in a used frame makes that row's cost non-finite and its path_len / path unspecified (but within bounds); the other rows are
+ * unaffected and the call finishes: every loop is bounded by the lengths.  No floating-point atomics: two calls are bitwise equal;
+ * identical x and y rows give cost exactly 0 (one code path computes both sides' features).
+ * Two launches (features of all used frames; one workgroup per utterance sweeping the anti-diagonals, then walking back) on the
+ * caller's stream straight from / to the caller's pointers; needs a created context, no weights.  Workspace, allocated by the first
+ * call and kept: max_batch * Max_Step * max(n_ceps, mel_dim) * 8 bytes for each side's features; by the first call that passes `path`:
+ * max_batch * Max_Step^2 back-pointers of one byte.  The sweep keeps three anti-diagonals in LDS (36 bytes per column of Ty).
+ * GSTTACO_E_INVALID: NULL x / y / cost / path_len, B < 1, Tx < 1, Ty < 1, n_ceps outside [0, mel_dim), a negative stride;
+ * GSTTACO_E_CAPACITY: B > max_batch, Tx or Ty > Max_Step (frames), Ty > 4551 (the LDS of one workgroup). */
+int gsttaco_mel_dtw(gsttaco_ctx* ctx, const float* x, const int32_t* x_len, int64_t x_stride,
+                    const float* y, const int32_t* y_len, int64_t y_stride,
+                    int B, int Tx, int Ty, int n_ceps, double* cost, int32_t* path_len, int32_t* path, void* stream);
 
 /* hipGraph cache policy.  Every entry point replays one cached graph executable per (entry, B, Tv, Tref1, steps, flags) key.
  * The cache is LRU-bounded to `max_cached` executables (default 16 -- an Inference_Step replays two or three: encoder segment, GST + decode + postnet, vocoder; GSTTACO_GRAPH_CACHE; 0 = no graphs, everything is
