@@ -1,7 +1,7 @@
 // The bf16 kernel of the persistent decode launch (Use_Mixed_Precision, <= 64 rows as ONE group, helper workgroups for the chain tiles'
 // recurrent halves): included by persist_decode.hip inside its anonymous namespace, behind the group kernels (it shares their waits and
 // the per-utterance chain).  DESIGN.md 3.1d, EXPERIMENTS.md round 5 item 2.
-// INVARIANT (give-up safety, PD_PHASE_ABORT in persist_decode.hip): after a bounded wait has given up, the workgroup runs the REST of the
+// INVARIANT (give-up safety, PdShared in persist_decode.hip): after a bounded wait has given up, the workgroup runs the REST of the
 // step on whatever the wait left and leaves at the top of its next step.  That is only safe because NO ADDRESS AND NO LOOP BOUND behind a
 // wait depends on data that came through a hand-off: every index below is a function of blockIdx / threadIdx / the step counter / launch
 // arguments (token lengths are read from the caller's tensor before the first wait).  Keep it so when editing this file.
@@ -108,9 +108,9 @@ __device__ __forceinline__ void pdh_gates_store(const float (&z)[2], float (&c)[
         }
     }
 }
-// sums of a recurrent-half tile: 16-wave order (fragments 0, 2 -> a; 1, 3 -> b; 16 slabs, or two passes over 8) or 8-wave order
+// sums of a recurrent-half tile: 16-wave order (fragments 0, 2 -> a; 1, 3 -> b; 16 slabs) or 8-wave order
 template <bool ORDER16>
-__device__ __forceinline__ void pdh_rec(const u32x4 (&x)[PDH_MT][4], const u32x4 (&w)[4], float bias, float* lds, bool two, float (&p)[2]) {
+__device__ __forceinline__ void pdh_rec(const u32x4 (&x)[PDH_MT][4], const u32x4 (&w)[4], float bias, float* lds, float (&p)[2]) {
     const int wave = threadIdx.x >> 6;
     const float b2[2] = {bias, bias};
     if (ORDER16) {
@@ -119,17 +119,9 @@ __device__ __forceinline__ void pdh_rec(const u32x4 (&x)[PDH_MT][4], const u32x4
         for (int mt = 0; mt < PDH_MT; ++mt) { a[mt] = f32x4{0, 0, 0, 0}; b[mt] = f32x4{0, 0, 0, 0}; }
         pdh_mma<4, 0, 2>(x, w, 32, a);
         pdh_mma<4, 1, 2>(x, w, 32, b);
-        if (two) {
-            float z1[2];
-            pdh_spill(lds, wave, a);
-            pdh_reduce<8>(lds, b2, z1);
-            pdh_spill(lds, wave, b);
-            pdh_reduce<8>(lds, z1, p);
-        } else {
-            pdh_spill(lds, wave, a);
-            pdh_spill(lds, wave + 8, b);
-            pdh_reduce<16>(lds, b2, p);
-        }
+        pdh_spill(lds, wave, a);
+        pdh_spill(lds, wave + 8, b);
+        pdh_reduce<16>(lds, b2, p);
     } else {
         f32x4 a[PDH_MT];
 #pragma unroll
@@ -173,8 +165,7 @@ __device__ __forceinline__ void pdh_wait_flags_helped(const PersistDecodeArgs& A
             asm volatile("global_load_dword %0, %2, off sc1\n\tglobal_load_dword %1, %3, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(v0), "=&v"(v1) : "v"(p0), "v"(p1) : "memory");
             const bool ok = (!h0 || v0 >= want) && (lane > 1 || v1 >= want_h);
             if (__builtin_amdgcn_readfirstlane(__popcll(__ballot(ok))) == 64) break;
-            if (++spins > PD_SPIN_MAX) { if (lane == 0) pd_give_up(A, sh, true); break; }
-            if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(gt_ld_sc1(A.err)) != 0u) { if (lane == 0) pd_give_up(A, sh, false); break; }
+            PD_POLL_BOUND(lane);
         }
     }
     __syncthreads();
@@ -190,7 +181,6 @@ __device__ __forceinline__ void pdh_cell1(const PersistDecodeArgs& A, const u32x
     PD_HOLD(xahp); PD_HOLD(h1hd);           // (persist_decode.hip PD_HOLD: no kernel-argument reload behind the wait)
     if (HELPED) pdh_wait_flags_helped(A, A.ctl + zt + PD_F_C, (uint32_t)t + 1u, A.ctl + zt + PD_F_H + tile * 32, A.ctl + zt + PD_F_H + (PDH_BMAX + tile) * 32, (uint32_t)t, sh);
     else pd_wait_flags_all(A, A.ctl + zt + PD_F_C, (uint32_t)t + 1u, sh);
-    PD_PHASE_ABORT(sh);
     PD_STAMP(role, 2);
     // (the helpers' sums: requested without a branch -- out of range at step 0 -- and assigned BEHIND the MFMAs: a use inside a branch
     // right here is a wait for them, and for every fragment request that follows in program order, before the first MFMA)
@@ -230,7 +220,6 @@ __device__ __forceinline__ void pdh_cell2(const PersistDecodeArgs& A, const u32x
     uint16_t* h2hd = A.h2h[par];
     PD_HOLD(h1hp); PD_HOLD(h2hd);
     pd_wait_count(A, A.ctl + zt + PD_CNT3, PD_WANT(A, t), sh);
-    PD_PHASE_ABORT(sh);
     PD_STAMP(role, 4);
     pdh_xload<4>(h1hp, MT, PD_KBH / 2, 0, x);
     PD_PIN();
@@ -246,17 +235,14 @@ __device__ __forceinline__ void pdh_cell2(const PersistDecodeArgs& A, const u32x
     PD_STAMP(role, 5);
 }
 // layer-1 recurrent half of tile `tl` for the next step from the fragments cell 2 left in `x` (own tile: into `p`; a chain tile's: published)
-__device__ __forceinline__ void pdh_rec1(const PersistDecodeArgs& A, const u32x4 (&x)[PDH_MT][4], const u32x4 (&wh1)[4], int tl, float* lds, bool two, float (&p)[2]) {
-    pdh_rec<true>(x, wh1, A.b1h[tl * 16 + (threadIdx.x & 15)], lds, two, p);
+__device__ __forceinline__ void pdh_rec1(const PersistDecodeArgs& A, const u32x4 (&x)[PDH_MT][4], const u32x4 (&wh1)[4], int tl, float* lds, float (&p)[2]) {
+    pdh_rec<true>(x, wh1, A.b1h[tl * 16 + (threadIdx.x & 15)], lds, p);
 }
 // layer-2 recurrent half for the next step: this workgroup's tile and, HELP, chain tile `help` (published)
 template <bool WAIT, bool HELP>
 __device__ __forceinline__ void pdh_rec2(const PersistDecodeArgs& A, u32x4 (&wh2)[4], int t, int tile, float* lds, PdHS& S, PdShared* sh, int role, int zt, int help) {
     if (HELP) pdh_load_tile<4>(A.w2h, tile, PD_KBH / 2, wh2, zt);  // (a helper streams its own W2h: arrives during the wait)
-    if (WAIT) {
-        pd_wait_count(A, A.ctl + zt + PD_CNT4, PD_WANT(A, t), sh);
-        PD_PHASE_ABORT(sh);
-    }
+    if (WAIT) pd_wait_count(A, A.ctl + zt + PD_CNT4, PD_WANT(A, t), sh);
     PD_STAMP(role, 7);
     const int col = threadIdx.x & 15;
     // (the summation order is a property of the tile.  Each arm loads its own fragments: shared between the arms of a branch, the
@@ -265,12 +251,12 @@ __device__ __forceinline__ void pdh_rec2(const PersistDecodeArgs& A, u32x4 (&wh2
         u32x4 x[PDH_MT][4];
         pdh_xload<4>(A.h2h[t & 1], A.MT, PD_KBH / 2, 0, x);
         PD_PIN();
-        pdh_rec<false>(x, wh2, A.b2h[tile * 16 + col], lds, false, S.p2);
+        pdh_rec<false>(x, wh2, A.b2h[tile * 16 + col], lds, S.p2);
     } else {
         u32x4 x[PDH_MT][4];
         pdh_xload<4>(A.h2h[t & 1], A.MT, PD_KBH / 2, 0, x);
         PD_PIN();
-        pdh_rec<true>(x, wh2, A.b2h[tile * 16 + col], lds, false, S.p2);
+        pdh_rec<true>(x, wh2, A.b2h[tile * 16 + col], lds, S.p2);
     }
     PD_STAMP(role, 8);
     if (HELP) {         // (behind the own half: the chain workgroup needs it at its next cell 2, a whole chain away)
@@ -280,12 +266,12 @@ __device__ __forceinline__ void pdh_rec2(const PersistDecodeArgs& A, u32x4 (&wh2
             u32x4 x[PDH_MT][4];
             pdh_xload<4>(A.h2h[t & 1], A.MT, PD_KBH / 2, 0, x);
             PD_PIN();
-            pdh_rec<false>(x, wh2, A.b2h[help * 16 + col], lds, false, v);
+            pdh_rec<false>(x, wh2, A.b2h[help * 16 + col], lds, v);
         } else {
             u32x4 x[PDH_MT][4];
             pdh_xload<4>(A.h2h[t & 1], A.MT, PD_KBH / 2, 0, x);
             PD_PIN();
-            pdh_rec<true>(x, wh2, A.b2h[help * 16 + col], lds, false, v);
+            pdh_rec<true>(x, wh2, A.b2h[help * 16 + col], lds, v);
         }
         pdh_publish(v, A.hpart + (size_t)(PDH_BMAX + help) * PDH_HP + zt, A.ctl + zt + PD_F_H + (PDH_BMAX + help) * 32, (uint32_t)t + 1u);
     }
@@ -322,21 +308,7 @@ __device__ __forceinline__ void pdh_proj(const PersistDecodeArgs& A, const u32x4
     const f32x4 zero = {0, 0, 0, 0};
     pd_spill(lds, threadIdx.x >> 6, a0, zero);
     const float v = pd_reduce<8>(lds, A.bp[ptile * 16 + (threadIdx.x & 15)]);
-    const int row = threadIdx.x >> 4, col = threadIdx.x & 15;
-    const int grow = pmt * 16 + row, gcol = ptile * 16 + col;
-    if (row < 16 && grow < A.B) {
-        if (gcol >= A.z_col0) {
-            if (gcol < A.z_col0 + PD_P) {
-                uint2 g;
-                g.x = __builtin_bit_cast(uint32_t, v); g.y = (uint32_t)t + 1u;
-                pd_st2_sc1(z0g + (size_t)grow * PD_P + (gcol - A.z_col0), g);
-            }
-        } else if (gcol < A.n_split) {
-            A.pre[(size_t)grow * A.ld_pre + (size_t)t * A.n_split + gcol] = v;
-        } else if (gcol < A.n_out) {
-            A.stop[(size_t)grow * A.steps + t] = v;
-        }
-    }
+    pd_proj_store(A, z0g, t, ptile, pmt, v);
 }
 
 // CHAIN: utterance blockIdx.x's chain, then cell 1 and cell 2 of its tile with W1x / W2x streamed (its recurrent halves come from a
@@ -354,21 +326,7 @@ __device__ __forceinline__ void pdh_run_tile(const PersistDecodeArgs& A, float* 
     PdChainRegs R{};
     if (CHAIN) {
         L = pd_carve(smem, A.tvp, 8, PDH_SLAB);
-        R.Tv = A.tok_len ? max(1, min(A.Tv, (int)A.tok_len[b])) : A.Tv;
-        R.drop = A.drop_rate > 0.f;
-        R.hashed = R.drop && A.keep_hash != 0;
-        R.noisy = A.sigmoid_noise > 0.f;
-        R.seed = R.hashed ? *A.seed_ptr : 0ull;
-        R.bias1 = tid < PD_P ? A.b1[tid] : 0.f;
-        R.biasq = tid < PD_A ? A.bq[tid] : 0.f;
-        R.sbias = A.score_bias[0];
-        const float4* src = reinterpret_cast<const float4*>(A.pm + (size_t)b * A.Tv * PD_A);
-        for (int e = tid; e < A.tvp * PD_A / 4; e += PD_NT) {
-            const int row = e / (PD_A / 4), c4 = e % (PD_A / 4);
-            *reinterpret_cast<float4*>(L.tile + row * PD_LDV + 4 * c4) = row < R.Tv ? src[(size_t)row * (PD_A / 4) + c4] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        if (tid < PD_A) L.vs[tid] = A.av[tid];
-        if (tid < A.tvp) L.pv[tid] = tid == 0 ? 1.f : 0.f;
+        pd_chain_setup(A, L, R, b);
     } else {
         // (a helper keeps the input halves resident and streams the recurrent tiles -- its own, then the chain tile's, through the same
         // registers: four resident tiles and a streamed fifth did not fit beside the 64-row fragments)
@@ -377,7 +335,7 @@ __device__ __forceinline__ void pdh_run_tile(const PersistDecodeArgs& A, float* 
     }
     __syncthreads();
     for (int t = 0; t < A.steps; ++t) {
-        if (sh->abort) return;          // (the one abort check of the step: PD_PHASE_ABORT)
+        if (sh->abort) return;          // (the one abort check of the step: PdShared, persist_decode.hip)
         PD_STAMP(role, 0);
         PD_ZT(zt);
         if (CHAIN) {
@@ -385,30 +343,26 @@ __device__ __forceinline__ void pdh_run_tile(const PersistDecodeArgs& A, float* 
             int bs = b;
             asm volatile("" : "+s"(bs));
             pd_chain<false, true>(A, L, R, t, bs, sh, unused4, zt);
-            PD_PHASE_ABORT(sh);
             PD_STAMP(role, 1);
             PD_PIN();
             pdh_load_tile<2>(A.w1x, tile, PD_KBP / 2 + PD_KBC / 2, W.x1, zt);
             pdh_load_tile<4>(A.w2x, tile, PD_KBH / 2, W.x2, zt);    // (arrives during cell 1)
         }
         pdh_cell1<CHAIN>(A, W.x1, t, tile, lds, S, sh, role, zt);
-        PD_PHASE_ABORT(sh);
         if (HELP && t + 1 < A.steps) pdh_load_tile<4>(A.w1h, tile, PD_KBH / 2, W.h1, zt);  // (streamed: arrives during the wait for h1)
         u32x4 x[PDH_MT][4];
         pdh_cell2(A, W.x2, x, t, tile, lds, S, sh, role, zt);
-        PD_PHASE_ABORT(sh);
         if (CHAIN) continue;                          // (a chain workgroup goes straight on to the next chain)
         if (t + 1 == A.steps) break;
-        pdh_rec1(A, x, W.h1, tile, lds, false, S.p1);
+        pdh_rec1(A, x, W.h1, tile, lds, S.p1);
         PD_STAMP(role, 6);
         if (HELP) {         // (the chain workgroup needs it at its NEXT cell 1, a whole chain away: own half first)
             pdh_load_tile<4>(A.w1h, help, PD_KBH / 2, W.h1, zt);
             float v[2];
-            pdh_rec1(A, x, W.h1, help, lds, false, v);
+            pdh_rec1(A, x, W.h1, help, lds, v);
             pdh_publish(v, A.hpart + (size_t)help * PDH_HP + zt, A.ctl + zt + PD_F_H + help * 32, (uint32_t)t + 1u);
         }
         pdh_rec2<true, HELP>(A, W.h2, t, tile, lds, S, sh, role, zt, help);
-        PD_PHASE_ABORT(sh);
     }
 }
 
@@ -426,22 +380,19 @@ __device__ __forceinline__ void pdh_run_proj(const PersistDecodeArgs& A, float* 
 #pragma unroll
     for (int e = 0; e < 2; ++e) { S.c1[e] = 0.f; S.c2[e] = 0.f; S.p1[e] = A.b1h[tile * 16 + col]; S.p2[e] = A.b2h[tile * 16 + col]; }
     for (int t = 0; t < A.steps; ++t) {
-        if (sh->abort) return;          // (the one abort check of the step: PD_PHASE_ABORT)
+        if (sh->abort) return;          // (the one abort check of the step: PdShared, persist_decode.hip)
         PD_STAMP(1, 0);
         PD_ZT(zt);
         pdh_cell1<false>(A, W.x1, t, tile, lds, S, sh, 1, zt);
-        PD_PHASE_ABORT(sh);
         {
             u32x4 x[PDH_MT][4];
             pdh_cell2(A, W.x2, x, t, tile, lds, S, sh, 1, zt);
-            PD_PHASE_ABORT(sh);
         }
         const uint16_t* h2hp = A.h2h[t & 1];
         const uint16_t* xahp = A.xah[t & 1];
         uint2* z0g = A.z0g;
         PD_HOLD(h2hp); PD_HOLD(xahp); PD_HOLD(z0g);
         pd_wait_count(A, A.ctl + zt + PD_CNT4, PD_WANT(A, t), sh);
-        PD_PHASE_ABORT(sh);
         pdh_proj(A, wpj, t, ptile, pmt, lds, h2hp, xahp, z0g);
         PD_STAMP(1, 6);
         if (t + 1 == A.steps) break;
@@ -449,7 +400,7 @@ __device__ __forceinline__ void pdh_run_proj(const PersistDecodeArgs& A, float* 
             u32x4 x[PDH_MT][4];
             pdh_xload<4>(A.h1h[t & 1], A.MT, PD_KBH / 2, 0, x);
             PD_PIN();
-            pdh_rec1(A, x, W.h1, tile, lds, false, S.p1);
+            pdh_rec1(A, x, W.h1, tile, lds, S.p1);
         }
         pdh_rec2<false, false>(A, W.h2, t, tile, lds, S, sh, 1, zt, -1);
     }

@@ -89,7 +89,6 @@ struct PdShared { int abort; };
 // one LDS read of the flag per step instead of one behind every wait -- each was a read, a wait for it and a branch, ~60 ns, four or
 // five of them on the step's critical path.  Until then the remaining phases of the step run on whatever the failed wait left
 // (no address and no loop bound depends on data), and each of their waits gives up on the error word after 64 polls.
-#define PD_PHASE_ABORT(sh) do { } while (0)
 // a pointer argument into scalar registers NOW: placed in front of a wait, for what is dereferenced right behind it -- kernel
 // arguments the compiler does not keep in registers are otherwise re-read (s_load + wait, ~0.1-0.2 us) between the hand-off and the
 // first fragment request
@@ -114,6 +113,14 @@ __device__ __forceinline__ void pd_give_up(const PersistDecodeArgs& A, PdShared*
     if (raise) atomicOr(A.err, 1u);         // (this launch's OWN give-up word: the fused LSTM launches poll theirs on any bit)
     sh->abort = 1;
 }
+// THE bound of every poll loop of the three kernels, behind a poll that did not find its words: the only place that knows the spin
+// bound, the look at the launch's error word every 64 polls and the give-up.  It LEAVES the enclosing loop (`spins`: the loop's counter).
+// A macro, not a function around the loop: with the loop in one shared body (the polls as lambdas), and likewise with these lines as a
+// function returning "over", the allocation of kernels that sit at the edge of the register file moves (EXPERIMENTS.md, "shared poll").
+#define PD_POLL_BOUND(lane)                                                                                                                      \
+    if (++spins > PD_SPIN_MAX) { if ((lane) == 0) pd_give_up(A, sh, true); break; }                                                              \
+    if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(gt_ld_sc1(A.err)) != 0u) { if ((lane) == 0) pd_give_up(A, sh, false); break; }     \
+    PD_SLEEP()
 // flags [n] (a line each) all >= want
 template <int STRIDE = 32>
 __device__ __forceinline__ void pd_wait_flags(const PersistDecodeArgs& A, const uint32_t* f, int n, uint32_t want, PdShared* sh) {
@@ -123,9 +130,7 @@ __device__ __forceinline__ void pd_wait_flags(const PersistDecodeArgs& A, const 
         for (;;) {
             const uint32_t v = lane < n ? gt_ld_sc1(f + lane * STRIDE) : want;
             if (__builtin_amdgcn_readfirstlane(__popcll(__ballot(v >= want))) == 64) break;
-            if (++spins > PD_SPIN_MAX) { if (lane == 0) pd_give_up(A, sh, true); break; }
-            if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(gt_ld_sc1(A.err)) != 0u) { if (lane == 0) pd_give_up(A, sh, false); break; }
-            PD_SLEEP();
+            PD_POLL_BOUND(lane);
         }
     }
     __syncthreads();
@@ -154,9 +159,7 @@ __device__ __forceinline__ void pd_wait_count(const PersistDecodeArgs& A, const 
 #pragma unroll
             for (int k = 0; k < PD_NSH / 64; ++k) { asm volatile("" : "+v"(u[k])); ok = ok && u[k] >= want; }
             if (__builtin_amdgcn_readfirstlane(__popcll(__ballot(ok))) == 64) break;
-            if (++spins > PD_SPIN_MAX) { if (lane == 0) pd_give_up(A, sh, true); break; }
-            if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(gt_ld_sc1(A.err)) != 0u) { if (lane == 0) pd_give_up(A, sh, false); break; }
-            PD_SLEEP();
+            PD_POLL_BOUND(lane);
         }
     }
     __syncthreads();
@@ -170,6 +173,7 @@ __device__ __forceinline__ void pd_arrive(uint32_t* c) {
 
 // ---- GEMM pieces (lean_body.h's arithmetic): wave w owns k-blocks w, w + 8, ... of a blocked A operand [kb][MT][64][4]
 // fragments i0 <= i < i1 of the wave's k-blocks kb = wave + 8 i, both M-tiles (MT == 1: the second is the first again, never stored)
+// (= pd_g_xload at g = 0.  Its own text: as a call of that one the one-group kernel's allocation moves -- 125 spilled SGPRs for 129)
 template <int I0, int I1, int NB>
 __device__ __forceinline__ void pd_xload(const float* base, int MT, float4 (&x0)[NB], float4 (&x1)[NB]) {
     const int lane = threadIdx.x & 63;
@@ -183,18 +187,18 @@ __device__ __forceinline__ void pd_xload(const float* base, int MT, float4 (&x0)
         x1[i] = gt_bload4_sc1(rs, (uint32_t)lane * 16u, so + m1);
     }
 }
-// the same for group g of MTG M-tiles (M-tiles MTG g, MTG g + 1; MTG == 1: only x0)
-template <int MTG, int I0, int I1, int NB>
+// the same for group g of two M-tiles (M-tiles 2 g, 2 g + 1)
+template <int I0, int I1, int NB>
 __device__ __forceinline__ void pd_g_xload(const float* base, int MT, int g, float4 (&x0)[NB], float4 (&x1)[NB]) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const auto rs = gt_rsrc(base, 0x7FFFF000u);
-    const uint32_t m0 = (uint32_t)(MTG * g) * 1024u, m1 = (uint32_t)min(MTG * g + 1, MT - 1) * 1024u;
+    const uint32_t m0 = (uint32_t)(2 * g) * 1024u, m1 = (uint32_t)min(2 * g + 1, MT - 1) * 1024u;
 #pragma unroll
     for (int i = I0; i < I1; ++i) {
         const uint32_t so = (uint32_t)((wave + i * PD_NW) * MT) * 1024u;
         x0[i] = gt_bload4_sc1(rs, (uint32_t)lane * 16u, so + m0);
-        if (MTG == 2) x1[i] = gt_bload4_sc1(rs, (uint32_t)lane * 16u, so + m1);
+        x1[i] = gt_bload4_sc1(rs, (uint32_t)lane * 16u, so + m1);
     }
 }
 // b[OFF + i * STRIDE], i < KPW (compile-time indices only: the weight fragments must stay registers)
@@ -209,21 +213,6 @@ __device__ __forceinline__ void pd_mma(const float4 (&x0)[NB], const float4 (&x1
         a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(x0[k].w, b[k].w, a0, 0, 0, 0); a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(x1[k].w, b[k].w, a1, 0, 0, 0);
     }
 }
-template <int MTG, int KPW, int OFF, int STRIDE, int NB>
-__device__ __forceinline__ void pd_g_mma(const float4 (&x0)[NB], const float4 (&x1)[NB], const float4 (&b)[NB], f32x4& a0, f32x4& a1) {
-    if constexpr (MTG == 2) {
-        pd_mma<KPW, OFF, STRIDE, NB>(x0, x1, b, a0, a1);
-    } else {
-#pragma unroll
-        for (int i = 0; i < KPW; ++i) {
-            const int k = OFF + i * STRIDE;
-            a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(x0[k].x, b[k].x, a0, 0, 0, 0);
-            a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(x0[k].y, b[k].y, a0, 0, 0, 0);
-            a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(x0[k].z, b[k].z, a0, 0, 0, 0);
-            a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(x0[k].w, b[k].w, a0, 0, 0, 0);
-        }
-    }
-}
 __device__ __forceinline__ void pd_spill(float* lds, int slab, const f32x4& a0, const f32x4& a1) {
     float (*part)[32][17] = reinterpret_cast<float (*)[32][17]>(lds);
     const int lane = threadIdx.x & 63;
@@ -234,21 +223,10 @@ __device__ __forceinline__ void pd_spill(float* lds, int slab, const f32x4& a0, 
 // element (row = tid >> 4, col = tid & 15) = base + sum over the first `nslab` slabs (ascending)
 // TRAIL = false: without the closing barrier -- for the caller whose next spill into the slabs lies behind another workgroup barrier
 // anyway (an arrival, a wait): the epilogue's stores then leave one barrier earlier
+// `cnt` != NULL: one lane signals that arrival counter behind the first barrier: the DEFERRED arrival of an earlier store -- every wave
+// has drained its stores before it got here (pd_drain in front of the spill)
 template <int NSLAB, bool TRAIL = true>
-__device__ __forceinline__ float pd_reduce(float* lds, float base) {
-    __syncthreads();
-    const float (*part)[32][17] = reinterpret_cast<const float (*)[32][17]>(lds);
-    const int row = threadIdx.x >> 4, col = threadIdx.x & 15;
-    float z = base;
-#pragma unroll
-    for (int w = 0; w < NSLAB; ++w) z += part[w][row][col];
-    if (TRAIL) __syncthreads();            // the slabs are re-used by the next reduction
-    return z;
-}
-// the same, and one lane signals an arrival counter behind the first barrier (`cnt` != NULL): the DEFERRED arrival of an earlier
-// store -- every wave has drained its stores before it got here (pd_drain in front of the spill)
-template <int NSLAB>
-__device__ __forceinline__ float pd_reduce_arrive(float* lds, float base, uint32_t* cnt) {
+__device__ __forceinline__ float pd_reduce(float* lds, float base, uint32_t* cnt = nullptr) {
     __syncthreads();
     if (cnt && threadIdx.x == 0) __hip_atomic_fetch_add(cnt + (blockIdx.x & (PD_NSH - 1)) * 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const float (*part)[32][17] = reinterpret_cast<const float (*)[32][17]>(lds);
@@ -256,7 +234,7 @@ __device__ __forceinline__ float pd_reduce_arrive(float* lds, float base, uint32
     float z = base;
 #pragma unroll
     for (int w = 0; w < NSLAB; ++w) z += part[w][row][col];
-    __syncthreads();
+    if (TRAIL) __syncthreads();            // the slabs are re-used by the next reduction
     return z;
 }
 // h . W_h (+ bias) of one tile from the fragments x0 / x1 of the whole state (8 k-blocks per wave).  ORDER16: the summation order
@@ -279,38 +257,15 @@ __device__ __forceinline__ float pd_rec_tile(const float4 (&x0)[8], const float4
         return pd_reduce<8>(lds, bias);
     }
 }
-// The same for a group of MTG M-tiles.  TWOPASS: the 16-slab sum through EIGHT slabs -- virtual waves 0..7, then 8..15 onto the running
-// sum: the same sequence of additions (chain workgroups, whose LDS holds the utterance's processed memory).
-template <bool ORDER16, int MTG, bool TWOPASS>
-__device__ __forceinline__ float pd_g_rec_tile(const float4 (&x0)[8], const float4 (&x1)[8], const float4 (&wh)[8], float bias, float* lds) {
-    const int wave = threadIdx.x >> 6;
-    if (ORDER16) {
-        f32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0}, b0 = {0, 0, 0, 0}, b1 = {0, 0, 0, 0};
-        pd_g_mma<MTG, 4, 0, 2, 8>(x0, x1, wh, a0, a1);
-        pd_g_mma<MTG, 4, 1, 2, 8>(x0, x1, wh, b0, b1);
-        if (TWOPASS) {
-            pd_spill(lds, wave, a0, a1);
-            const float z = pd_reduce<8>(lds, bias);
-            pd_spill(lds, wave, b0, b1);
-            return pd_reduce<8>(lds, z);
-        }
-        pd_spill(lds, wave, a0, a1);
-        pd_spill(lds, wave + 8, b0, b1);
-        return pd_reduce<16>(lds, bias);
-    } else {
-        f32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
-        pd_g_mma<MTG, 8, 0, 1, 8>(x0, x1, wh, a0, a1);
-        pd_spill(lds, wave, a0, a1);
-        return pd_reduce<8>(lds, bias);
-    }
-}
 // gates of tile-local column g*4+u (i, f, c~, o of unit tile*4+u; Appendix A.6, reference Taco2.py:79-85): lanes col < 4 own a unit;
 // h of the tile's 4 units leaves as ONE 16-byte write-through store per row (rows >= M are never stored)
-__device__ __forceinline__ void pd_gates_store(float z, float& c, float* hdst, int tile, int M, int MT, int row0 = 0, int rows = 32) {
-    const int lrow = threadIdx.x >> 4, row = row0 + lrow, col = threadIdx.x & 15;       // (a group: rows row0 .. row0 + rows - 1)
+__device__ __forceinline__ void pd_gates_store(float z, float& c, float* hdst, int tile, int M, int MT, int row0 = 0) {
+    const int lrow = threadIdx.x >> 4, row = row0 + lrow, col = threadIdx.x & 15;       // (a group: rows row0 .. row0 + 31)
     const float zf = gt_row_down<4>(z), zg = gt_row_down<8>(z), zo = gt_row_down<12>(z);
     float hv = 0.f;
-    if (lrow >= rows) return;               // (16-row groups: the slab's upper half is unused; whole 16-lane segments leave together)
+    // (never taken: 512 threads are 32 rows.  It stays because the allocation hangs on it: without this line the one-group kernel spills
+    // 133 SGPRs for 129 and gt_persist_decode_g_kernel<4> 10 VGPRs for 8)
+    if (lrow >= 32) return;
     if (col < 4 && row < M) hv = gt_lstm_cell(z, zf, zg, zo, c);
     const float h1v = gt_row_down<1>(hv), h2v = gt_row_down<2>(hv), h3v = gt_row_down<3>(hv);
     if (col == 0 && row < M) pd_st4_sc1(hdst + gt_blk_off(row, tile * 4, MT), make_float4(hv, h1v, h2v, h3v));
@@ -338,39 +293,42 @@ struct PdW { float4 x1[3], h1[8], x2[8], h2[8]; };
 // ====================================================================================================================== phases
 // LSTM cell 1: z = [p | ctx] . W1x + part1 (= h1_{t-1} . W1h + b1).  split: the prenet part is multiplied as soon as the chains
 // have published it, the context part when it arrives (same accumulator, same k-block order as gt_lstm_x_kernel<8, 3>).
-__device__ __forceinline__ void pd_cell1(const PersistDecodeArgs& A, PdW& W, int t, int tile, float* lds, float& c1v, float p1v, PdShared* sh, bool split,
-                                        bool stream_x1 = false, int role = 2, bool stream_x2 = false) {
+struct PdCell1 {
+    int role;                   // the stamps' role: 0 chain, 1 projection, 2 plain
+    bool split;
+    bool stream_x1 = false;     // the chain role: W1x is streamed -- arrives while the other chains finish
+    bool stream_x2 = false;     // the chain role: W2x is requested here, behind this cell's fragments (PD_X2_EARLY)
+};
+__device__ __forceinline__ void pd_cell1(const PersistDecodeArgs& A, PdW& W, int t, int tile, float* lds, float& c1v, float p1v, PdShared* sh, const PdCell1 o) {
+    const int role = o.role;
     const int par = t & 1, MT = A.MT;
-    if (stream_x1) pd_load_tile<3>(A.w1x, tile, W.x1);          // (the chain role: arrives while the other chains finish)
+    if (o.stream_x1) pd_load_tile<3>(A.w1x, tile, W.x1);
     const float* xa = A.xa[par];
     float* h1d = A.h1[par];
     PD_HOLD(xa); PD_HOLD(h1d);
     f32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
     float4 x0[3], x1[3];
-    if (split) {
+    if (o.split) {
         pd_wait_flags<PD_FS>(A, A.ctl + PD_F_P, A.B, (uint32_t)t + 1u, sh);
-        PD_PHASE_ABORT(sh);
         PD_STAMP(role, 1);
         pd_xload<0, 2, 3>(xa, MT, x0, x1);
         PD_PIN();
         pd_mma<2, 0, 1, 3>(x0, x1, W.x1, a0, a1);
         PD_STAMP(role, 2);
         pd_wait_flags<PD_FS>(A, A.ctl + PD_F_C, A.B, (uint32_t)t + 1u, sh);
-        PD_PHASE_ABORT(sh);
         PD_STAMP(role, 3);
         pd_xload<2, 3, 3>(xa, MT, x0, x1);
         PD_PIN();
         pd_mma<1, 2, 1, 3>(x0, x1, W.x1, a0, a1);
     } else {
         pd_wait_flags<PD_FS>(A, A.ctl + PD_F_C, A.B, (uint32_t)t + 1u, sh);      // (a chain's context flag is set after its prenet flag)
-        PD_PHASE_ABORT(sh);
         PD_STAMP(role, 3);
         pd_xload<0, 3, 3>(xa, MT, x0, x1);
         // (the chain role: cell 2's input half, behind this cell's fragments -- requested at cell 2's entry, the poll of the h1 arrivals
         // queued behind its 64 KB, loads returning in order, and this role, which everybody waits for, saw the hand-off ~1 us late)
         // (the tile index through an opaque register: its load addresses are otherwise hoisted out of the step loop, live across the
         // chain, and the allocator -- at 250 of 256 registers there -- spills three dozen other loop invariants)
-        if (stream_x2) { int tz = tile; asm volatile("" : "+s"(tz)); pd_load_tile<8>(A.w2x, tz, W.x2); }
+        if (o.stream_x2) { int tz = tile; asm volatile("" : "+s"(tz)); pd_load_tile<8>(A.w2x, tz, W.x2); }
         PD_PIN();
         pd_mma<3, 0, 1, 3>(x0, x1, W.x1, a0, a1);
     }
@@ -381,33 +339,41 @@ __device__ __forceinline__ void pd_cell1(const PersistDecodeArgs& A, PdW& W, int
     pd_arrive(A.ctl + PD_CNT3);
 }
 
-// LSTM cell 2: z = h1_t . W2x + part2; then, from the same fragments, recurrent halves of cell 1 for the NEXT step: a chain
-// workgroup's (help_tile >= 0, published for it) and this workgroup's own (with_rec1)
-// helped_p2 >= 0 (chain role, t > 0): this tile's layer-2 recurrent half comes from its helper -- the helper's flag rides in the poll
-// of the h1 arrivals, the sums (slot helped_p2 of hpart) are requested with the h1 fragments
-__device__ __forceinline__ void pd_cell2(const PersistDecodeArgs& A, PdW& W, int t, int tile, float* lds, float& c2v, float& p2v, float& p1_next, bool with_rec1,
-                                        PdShared* sh, int help_tile, bool stream_h1, bool stream_x2, int role = 2, int helped_p2 = -1, bool helped_role = false) {
+// LSTM cell 2: z = h1_t . W2x + part2; then, from the same fragments, recurrent halves of cell 1 for the NEXT step
+struct PdCell2 {
+    int role;
+    bool with_rec1 = false;     // this workgroup's own layer-1 recurrent half, into p1_next
+    int help_tile = -1;         // >= 0: a chain workgroup's layer-1 recurrent half, published for it
+    bool stream_h1 = false;     // layer-2 helpers keep W2h resident and stream their own W1h
+    bool stream_x2 = false;     // the chain role without PD_X2_EARLY: W2x is requested behind the h1 wait
+    // the chain role: this tile's layer-2 recurrent half comes from its helper (t > 0: slot helped_p2 of hpart, else -1) -- the helper's
+    // flag rides in the poll of the h1 arrivals, the sums are requested with the h1 fragments
+    bool helped_role = false;
+    int helped_p2 = -1;
+};
+__device__ __forceinline__ void pd_cell2(const PersistDecodeArgs& A, PdW& W, int t, int tile, float* lds, float& c2v, float& p2v, float& p1_next, PdShared* sh,
+                                        const PdCell2 o) {
+    const int role = o.role, help_tile = o.help_tile, helped_p2 = o.helped_p2;
     const int par = t & 1, MT = A.MT;
     // (the chain role streams W2x: these registers belong to the chain's operands until cell 1.  Requested BEHIND the wait, with the
     // h1 fragments: in front of it the poll queued behind its 64 KB -- loads return in order -- and this role, which everybody waits
     // for, saw the hand-off ~1 us after the others)
     float4 wu[8];
     if (help_tile >= 0) pd_load_tile<8>(A.w1h, help_tile, wu);  // (a chain workgroup's W1h tile, streamed: arrives during the wait)
-    if (stream_h1) pd_load_tile<8>(A.w1h, tile, W.h1);          // (layer-2 helpers keep W2h resident and stream their own W1h)
+    if (o.stream_h1) pd_load_tile<8>(A.w1h, tile, W.h1);
     const float* h1p = A.h1[par];
     float* h2d = A.h2[par];
     PD_HOLD(h1p); PD_HOLD(h2d);
     pd_wait_count(A, A.ctl + PD_CNT3, PD_WANT(A, t), sh, helped_p2 >= 0 ? A.ctl + PD_F_H + helped_p2 * 32 : nullptr, (uint32_t)t);
-    PD_PHASE_ABORT(sh);
     PD_STAMP(role, 5);
     float4 x0[8], x1[8];
-    if (stream_x2) pd_load_tile<8>(A.w2x, tile, W.x2);
+    if (o.stream_x2) pd_load_tile<8>(A.w2x, tile, W.x2);
     pd_xload<0, 8, 8>(h1p, MT, x0, x1);
     // (the helper's sums: requested with the fragments -- out of range when there are none: no branch around the request -- and looked
     // at BEHIND the MFMAs: a use right here, or inside a branch, is a wait for every fragment before the first MFMA instead of a
     // counted wait per fragment)
     float4 d2 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (helped_role) {
+    if (o.helped_role) {
         const auto rh = gt_rsrc(A.hpart, 2u * 32u * 512u * 4u);
         d2 = gt_bload4_sc1(rh, helped_p2 >= 0 ? (uint32_t)((helped_p2 * 512 + ((int)threadIdx.x & ~3)) * 4) : GT_OOB, 0u);
     }
@@ -416,7 +382,7 @@ __device__ __forceinline__ void pd_cell2(const PersistDecodeArgs& A, PdW& W, int
     f32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
     pd_mma<8, 0, 1, 8>(x0, x1, W.x2, a0, a1);
     PD_STAMP(role, 6);
-    if (helped_role && helped_p2 >= 0) {
+    if (o.helped_role && helped_p2 >= 0) {
         const int e = threadIdx.x & 3;
         p2v = e == 0 ? d2.x : e == 1 ? d2.y : e == 2 ? d2.z : d2.w;
     }
@@ -432,7 +398,7 @@ __device__ __forceinline__ void pd_cell2(const PersistDecodeArgs& A, PdW& W, int
         const float v = pd_rec_tile<true>(x0, x1, wu, A.b1h[help_tile * 16 + col], lds);
         pd_publish_part(v, A.hpart + (size_t)help_tile * 512, A.ctl + PD_F_H + help_tile * 32, (uint32_t)t + 1u);
     }
-    if (with_rec1) p1_next = pd_rec_tile<true>(x0, x1, W.h1, A.b1h[tile * 16 + col], lds);
+    if (o.with_rec1) p1_next = pd_rec_tile<true>(x0, x1, W.h1, A.b1h[tile * 16 + col], lds);
 }
 
 // layer-2 recurrent half of this workgroup's tile from h2 in memory (+ a chain workgroup's, for helpers); tiles below co_tiles sum
@@ -458,6 +424,25 @@ __device__ __forceinline__ float pd_rec1_mem(const PersistDecodeArgs& A, const f
     return pd_rec_tile<true>(x0, x1, wh, A.b1h[tile * 16 + (threadIdx.x & 15)], lds);
 }
 
+// the split store of projection element (row = tid >> 4 < 16, col = tid & 15) of tile `ptile`, M-tile `pmt`: the prenet-0 columns as
+// {value, t + 1} granules for the chains (S1), columns below n_split into `pre`, below n_out into `stop`
+__device__ __forceinline__ void pd_proj_store(const PersistDecodeArgs& A, uint2* z0g, int t, int ptile, int pmt, float v) {
+    const int row = threadIdx.x >> 4, col = threadIdx.x & 15;
+    const int grow = pmt * 16 + row, gcol = ptile * 16 + col;
+    if (row < 16 && grow < A.B) {
+        if (gcol >= A.z_col0) {
+            if (gcol < A.z_col0 + PD_P) {
+                uint2 g;
+                g.x = __builtin_bit_cast(uint32_t, v); g.y = (uint32_t)t + 1u;
+                pd_st2_sc1(z0g + (size_t)grow * PD_P + (gcol - A.z_col0), g);
+            }
+        } else if (gcol < A.n_split) {
+            A.pre[(size_t)grow * A.ld_pre + (size_t)t * A.n_split + gcol] = v;
+        } else if (gcol < A.n_out) {
+            A.stop[(size_t)grow * A.steps + t] = v;
+        }
+    }
+}
 // Projection tile `ptile`, M-tile `pmt` (Taco2.py:112-118: r mel frames | stop logit) + the next step's prenet-0 pre-activations
 // (both layers are linear: gsttaco.cpp proj_z), gt_proj_lean_kernel's arithmetic
 template <bool GK = false>     // GK: called by a group kernel (its stamp slots)
@@ -467,10 +452,7 @@ __device__ __forceinline__ void pd_proj(const PersistDecodeArgs& A, const float4
     const float* xap = A.xa[par];
     uint2* z0g = A.z0g;
     PD_HOLD(h2p); PD_HOLD(xap); PD_HOLD(z0g);
-    if (!GK) {          // (a group kernel has waited for every group's arrivals at once)
-        pd_wait_count(A, A.ctl + PD_CNT4, PD_WANT(A, t), sh);
-        PD_PHASE_ABORT(sh);
-    }
+    if (!GK) pd_wait_count(A, A.ctl + PD_CNT4, PD_WANT(A, t), sh);         // (a group kernel has waited for every group's arrivals at once)
     if (!GK) PD_STAMP(1, 9);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -496,21 +478,7 @@ __device__ __forceinline__ void pd_proj(const PersistDecodeArgs& A, const float4
     pd_spill(lds, threadIdx.x >> 6, a0, a1);
     // (one-group kernel: the projection role's next spill -- the next step's cell 1 -- lies behind that phase's flag wait and its barrier)
     const float v = GK ? pd_reduce<8>(lds, A.bp[ptile * 16 + (threadIdx.x & 15)]) : pd_reduce<8, false>(lds, A.bp[ptile * 16 + (threadIdx.x & 15)]);
-    const int row = threadIdx.x >> 4, col = threadIdx.x & 15;
-    const int grow = pmt * 16 + row, gcol = ptile * 16 + col;
-    if (row < 16 && grow < A.B) {
-        if (gcol >= A.z_col0) {
-            if (gcol < A.z_col0 + PD_P) {
-                uint2 g;
-                g.x = __builtin_bit_cast(uint32_t, v); g.y = (uint32_t)t + 1u;
-                pd_st2_sc1(z0g + (size_t)grow * PD_P + (gcol - A.z_col0), g);
-            }
-        } else if (gcol < A.n_split) {
-            A.pre[(size_t)grow * A.ld_pre + (size_t)t * A.n_split + gcol] = v;
-        } else if (gcol < A.n_out) {
-            A.stop[(size_t)grow * A.steps + t] = v;
-        }
-    }
+    pd_proj_store(A, z0g, t, ptile, pmt, v);
     if (!GK) PD_STAMP(1, 11);
     else PD_STAMP(1, 6 + 7 * g);
 }
@@ -548,6 +516,27 @@ __device__ __forceinline__ PdChainLds pd_carve(float* smem, int tvp, int nslab =
 struct PdChainRegs { float bias1, biasq, sbias; int Tv; uint64_t seed; bool hashed, drop, noisy; };
 // the LSA chain's LDS behind the 128-row tile: location features of the tile's rows + the weight image
 __host__ __device__ inline int pd_lsa_floats(int loc_f, int loc_k) { const LsaPack lp = gt_lsa_pack(PD_A, loc_f, loc_k); return 128 * lp.LFS + lp.total; }
+// a chain workgroup's set-up for utterance b, once per launch: the chain's registers from the launch arguments and its LDS (the caller's
+// barrier closes it).  The group kernels' and the bf16 kernel's; pd_run_chain has its own beside the LSA lines
+__device__ __forceinline__ void pd_chain_setup(const PersistDecodeArgs& A, const PdChainLds& L, PdChainRegs& R, int b) {
+    const int tid = threadIdx.x;
+    R.Tv = A.tok_len ? max(1, min(A.Tv, (int)A.tok_len[b])) : A.Tv;         // masked mode (A12): only the first tok_len[b] positions exist
+    R.drop = A.drop_rate > 0.f;
+    R.hashed = R.drop && A.keep_hash != 0;
+    R.noisy = A.sigmoid_noise > 0.f;
+    R.seed = R.hashed ? *A.seed_ptr : 0ull;
+    R.bias1 = tid < PD_P ? A.b1[tid] : 0.f;
+    R.biasq = tid < PD_A ? A.bq[tid] : 0.f;
+    R.sbias = A.score_bias[0];
+    // processed memory of utterance b -> LDS, once (rows >= T_v: zeros, as the launch path's bounded descriptor reads them)
+    const float4* src = reinterpret_cast<const float4*>(A.pm + (size_t)b * A.Tv * PD_A);
+    for (int e = tid; e < A.tvp * PD_A / 4; e += PD_NT) {
+        const int row = e / (PD_A / 4), c4 = e % (PD_A / 4);
+        *reinterpret_cast<float4*>(L.tile + row * PD_LDV + 4 * c4) = row < R.Tv ? src[(size_t)row * (PD_A / 4) + c4] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    if (tid < PD_A) L.vs[tid] = A.av[tid];
+    if (tid < A.tvp) L.pv[tid] = tid == 0 ? 1.f : 0.f;      // one-hot(0) initial alignment (Steps.py:201-206)
+}
 
 // ---- ALL of prenet-1's weights for step t, requested before the projection's hand-off is even looked at (the bf16 kernel: a phase
 // earlier still, in front of the recurrent half of the step before).  Launch-path wave kp (of 16) owns rows 16 kp .. 16 kp + 15,
@@ -615,7 +604,7 @@ __device__ __forceinline__ void pd_lsa_features(const PersistDecodeArgs& A, cons
     }
 }
 
-// (give-up invariant, PD_PHASE_ABORT: the LSA chain's loop bounds -- filter / tap counts, Tv -- are launch arguments or the caller's token
+// (give-up invariant, PdShared: the LSA chain's loop bounds -- filter / tap counts, Tv -- are launch arguments or the caller's token
 // lengths, its LDS indices functions of the thread index: nothing behind a wait is data-dependent)
 // LSA (with TV128, tvp = 128; the one-group kernel): the step-wise location-sensitive extension in the chain -- dec_front_lsa.hip's two
 // MFMA products on 8 waves instead of 16, each score row's two channel halves summed as the 16-wave kernel's two waves sum them
@@ -667,14 +656,12 @@ __device__ __forceinline__ void pd_chain_rest(const PersistDecodeArgs& A, const 
         uint2 g = pd_ld2_sc1(A.z0g + (size_t)b * PD_P + tid);
         uint32_t spins = 0;
         while (__builtin_amdgcn_readfirstlane(__popcll(__ballot(g.y == (uint32_t)t))) != 64) {
-            if (++spins > PD_SPIN_MAX) { if (lane == 0) pd_give_up(A, sh, true); break; }
-            if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(gt_ld_sc1(A.err)) != 0u) { if (lane == 0) pd_give_up(A, sh, false); break; }
+            PD_POLL_BOUND(lane);
             g = pd_ld2_sc1(A.z0g + (size_t)b * PD_P + tid);
         }
         L.y0[tid] = fmaxf(__builtin_bit_cast(float, g.x), 0.f) * k0;
     }
     __syncthreads();
-    PD_PHASE_ABORT(sh);
     PD_STAMP(0, 14);
     // ---- prenet layer 1 (Taco2.py:262-283): two launch-path threads' 16-row sums each.  The query weights (Steps.py:122) are
     // requested into the first half's registers: row i's request right behind the multiply-add that consumed register i, so the 16
@@ -739,8 +726,7 @@ __device__ __forceinline__ void pd_chain_rest(const PersistDecodeArgs& A, const 
         for (;;) {
             const uint32_t v = l2 < 1 ? gt_ld_sc1(A.ctl + PD_F_H + b * 32) : (uint32_t)t;
             if (__builtin_amdgcn_readfirstlane(__popcll(__ballot(v >= (uint32_t)t))) == 64) break;
-            if (++spins > PD_SPIN_MAX) { if (l2 == 0) pd_give_up(A, sh, true); break; }
-            if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(gt_ld_sc1(A.err)) != 0u) { if (l2 == 0) pd_give_up(A, sh, false); break; }
+            PD_POLL_BOUND(l2);
         }
     }
     PD_STAMP(0, 16);
@@ -769,7 +755,6 @@ __device__ __forceinline__ void pd_chain_rest(const PersistDecodeArgs& A, const 
         pd_drain();
         if (tid == 0) pd_st1_sc1(A.ctl + PD_F_P + b * PD_FS, (uint32_t)t + 1u);
     }
-    PD_PHASE_ABORT(sh);
     if (HELPED) {       // (behind the barrier the flag poll joined: the helper's sums, consumed by cell 1.  Requested without a branch
                         // -- out of range at step 0 -- and handed out raw: a use in here is a full memory wait inside the chain)
         const auto rh = gt_rsrc(A.hpart, 2u * 32u * 512u * 4u);
@@ -966,8 +951,8 @@ __device__ __forceinline__ void pd_run_chain(const PersistDecodeArgs& A, float* 
     PdW W;
     float c1v = 0.f, c2v = 0.f, p1v = A.b1h[tile * 16 + col], p2v = A.b2h[tile * 16 + col];
     PdChainRegs R{};
-    if (live) {
-        R.Tv = A.tok_len ? max(1, min(A.Tv, (int)A.tok_len[b])) : A.Tv;         // masked mode (A12): only the first tok_len[b] positions exist
+    if (live) {         // (pd_chain_setup with the LSA lines.  Its own text: as a call of that one this kernel's allocation moves, 125 spilled SGPRs for 129)
+        R.Tv = A.tok_len ? max(1, min(A.Tv, (int)A.tok_len[b])) : A.Tv;
         R.drop = A.drop_rate > 0.f;
         R.hashed = R.drop && A.keep_hash != 0;
         R.noisy = A.sigmoid_noise > 0.f;
@@ -975,14 +960,13 @@ __device__ __forceinline__ void pd_run_chain(const PersistDecodeArgs& A, float* 
         R.bias1 = tid < PD_P ? A.b1[tid] : 0.f;
         R.biasq = tid < PD_A ? A.bq[tid] : 0.f;
         R.sbias = lsa ? 0.f : A.score_bias[0];
-        // processed memory of utterance b -> LDS, once (rows >= T_v: zeros, as the launch path's bounded descriptor reads them)
         const float4* src = reinterpret_cast<const float4*>(A.pm + (size_t)b * A.Tv * PD_A);
         for (int e = tid; e < A.tvp * PD_A / 4; e += PD_NT) {
             const int row = e / (PD_A / 4), c4 = e % (PD_A / 4);
             *reinterpret_cast<float4*>(L.tile + row * PD_LDV + 4 * c4) = row < R.Tv ? src[(size_t)row * (PD_A / 4) + c4] : make_float4(0.f, 0.f, 0.f, 0.f);
         }
         if (tid < PD_A) L.vs[tid] = lsa ? 0.f : A.av[tid];      // LSA has no attention_v (Layers.py:407)
-        if (tid < A.tvp) L.pv[tid] = (tid == 0 && !lsa) ? 1.f : 0.f;     // one-hot(0) initial alignment (Steps.py:201-206); LSA: the zero state (Layers.py:356)
+        if (tid < A.tvp) L.pv[tid] = (tid == 0 && !lsa) ? 1.f : 0.f;     // LSA: the zero state (Layers.py:356)
         if (lsa) {
             const int n4 = gt_lsa_pack(PD_A, A.loc_f, A.loc_k).total >> 2;
             for (int i = tid; i < n4; i += PD_NT) reinterpret_cast<float4*>(L.lpack)[i] = reinterpret_cast<const float4*>(A.loc_pack)[i];
@@ -990,7 +974,7 @@ __device__ __forceinline__ void pd_run_chain(const PersistDecodeArgs& A, float* 
     }
     __syncthreads();
     for (int t = 0; t < A.steps; ++t) {
-        if (sh->abort) return;          // (the one abort check of the step: PD_PHASE_ABORT)
+        if (sh->abort) return;          // (the one abort check of the step: PdShared, persist_decode.hip)
         PD_STAMP(0, 0);
         // (diagnostic: when this workgroup's steps 0, 1, 2, 8, 64, half, 3/4 and last begin -- slots 24..31 of the chain role)
         if (A.dbg && threadIdx.x == 0 && blockIdx.x == 0) {
@@ -1004,22 +988,18 @@ __device__ __forceinline__ void pd_run_chain(const PersistDecodeArgs& A, float* 
             if (lsa) pd_chain<true, false, true, true>(A, L, R, t, b, sh, hraw, zt);
             else if (A.tvp == 128) pd_chain<true, false, true>(A, L, R, t, b, sh, hraw, zt);
             else pd_chain<true>(A, L, R, t, b, sh, hraw, zt);
-            PD_PHASE_ABORT(sh);
             if (t > 0) { const int e = tid & 3; p1v = e == 0 ? hraw.x : e == 1 ? hraw.y : e == 2 ? hraw.z : hraw.w; }
         } else if (t > 0) {                                     // no chain to hide it behind: fetch the layer-1 half directly
             pd_wait_flags(A, A.ctl + PD_F_H + tile * 32, 1, (uint32_t)t, sh);
-            PD_PHASE_ABORT(sh);
             const auto rh = gt_rsrc(A.hpart, 2u * 32u * 512u * 4u);
             const float4 d1 = gt_bload4_sc1(rh, (uint32_t)((tile * 512 + (tid & ~3)) * 4), 0u);
             const int e = tid & 3;
             p1v = e == 0 ? d1.x : e == 1 ? d1.y : e == 2 ? d1.z : d1.w;
         }
-        pd_cell1(A, W, t, tile, lds, c1v, p1v, sh, false, true, 0, PD_X2_EARLY != 0);
-        PD_PHASE_ABORT(sh);
+        pd_cell1(A, W, t, tile, lds, c1v, p1v, sh, {.role = 0, .split = false, .stream_x1 = true, .stream_x2 = PD_X2_EARLY != 0});
         float unused = 0.f;
         // (the layer-2 half from its helper: flag and sums ride with the h1 arrivals' poll and fragments)
-        pd_cell2(A, W, t, tile, lds, c2v, p2v, unused, false, sh, -1, false, PD_X2_EARLY == 0, 0, t > 0 ? 32 + tile : -1, true);
-        PD_PHASE_ABORT(sh);
+        pd_cell2(A, W, t, tile, lds, c2v, p2v, unused, sh, {.role = 0, .stream_x2 = PD_X2_EARLY == 0, .helped_role = true, .helped_p2 = t > 0 ? 32 + tile : -1});
     }
 }
 
@@ -1034,16 +1014,13 @@ __device__ __forceinline__ void pd_run_proj(const PersistDecodeArgs& A, float* l
     pd_load_tile<9>(A.wp, ptile, wpj);
     float c1v = 0.f, c2v = 0.f, p1v = A.b1h[tile * 16 + col], p2v = A.b2h[tile * 16 + col];
     for (int t = 0; t < A.steps; ++t) {
-        if (sh->abort) return;          // (the one abort check of the step: PD_PHASE_ABORT)
+        if (sh->abort) return;          // (the one abort check of the step: PdShared, persist_decode.hip)
         const int par = t & 1;
         PD_STAMP(1, 0);
-        pd_cell1(A, W, t, tile, lds, c1v, p1v, sh, true, false, 1);
-        PD_PHASE_ABORT(sh);
+        pd_cell1(A, W, t, tile, lds, c1v, p1v, sh, {.role = 1, .split = true});
         float unused = 0.f;
-        pd_cell2(A, W, t, tile, lds, c2v, p2v, unused, false, sh, -1, false, false, 1);
-        PD_PHASE_ABORT(sh);
+        pd_cell2(A, W, t, tile, lds, c2v, p2v, unused, sh, {.role = 1});
         pd_proj(A, wpj, t, ptile, pmt, lds, sh);
-        PD_PHASE_ABORT(sh);
         if (t + 1 == A.steps) break;
         pd_load_tile<8>(A.w1h, tile, W.h1);
         PD_PIN();
@@ -1065,18 +1042,15 @@ __device__ __forceinline__ void pd_run_plain(const PersistDecodeArgs& A, float* 
     if (HELP != 1) pd_load_tile<8>(A.w2h, tile, W.h2);
     float c1v = 0.f, c2v = 0.f, p1v = A.b1h[tile * 16 + col], p2v = A.b2h[tile * 16 + col];
     for (int t = 0; t < A.steps; ++t) {
-        if (sh->abort) return;          // (the one abort check of the step: PD_PHASE_ABORT)
+        if (sh->abort) return;          // (the one abort check of the step: PdShared, persist_decode.hip)
         const int par = t & 1;
         PD_STAMP(2, 0);
-        pd_cell1(A, W, t, tile, lds, c1v, p1v, sh, true);
-        PD_PHASE_ABORT(sh);
-        pd_cell2(A, W, t, tile, lds, c2v, p2v, p1v, true, sh, HELP == 1 ? help_tile : -1, HELP == 2, false);
+        pd_cell1(A, W, t, tile, lds, c1v, p1v, sh, {.role = 2, .split = true});
+        pd_cell2(A, W, t, tile, lds, c2v, p2v, p1v, sh, {.role = 2, .with_rec1 = true, .help_tile = HELP == 1 ? help_tile : -1, .stream_h1 = HELP == 2});
         PD_STAMP(2, 12);
-        PD_PHASE_ABORT(sh);
         if (t + 1 == A.steps) break;
         if (HELP == 1) pd_load_tile<8>(A.w2h, tile, W.h2);      // (streamed: arrives during the wait)
         pd_wait_count(A, A.ctl + PD_CNT4, PD_WANT(A, t), sh);
-        PD_PHASE_ABORT(sh);
         PD_STAMP(2, 13);
         p2v = pd_rec2(A, t, A.h2[par], W.h2, tile, HELP == 2 ? help_tile : -1, lds);        // for step t + 1
         PD_STAMP(2, 14);
@@ -1181,25 +1155,26 @@ int gt_persist_decode_blocks_per_cu() {
 
 hipError_t gt_launch_persist_decode(const PersistDecodeArgs& a_in, const float* b0, hipStream_t stream) {
     PersistDecodeArgs a = a_in;
+    PdKernel k = gt_persist_decode_h_kernel;
+    size_t lds_floats;
     if (a.bf16) {           // mixed precision: one group of up to 64 rows
         a.G = 1;
         a.tvp = (a.Tv + 63) / 64 * 64;
         a.n_chain = a.B;
         a.twopass = 0;          // (the workgroups that sum recurrent halves have 16 slabs: no chain state beside them)
-        const int n = PD_CTL_WORDS > a.B * PD_P ? PD_CTL_WORDS : a.B * PD_P;
-        hipLaunchKernelGGL(gt_persist_decode_init_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, a.z0g, b0, a.ctl, a.B);
-        hipLaunchKernelGGL(gt_persist_decode_h_kernel, dim3(PD_NWG), dim3(PD_NT), (size_t)pdh_lds_floats(a.tvp) * 4, stream, a);
-        return hipGetLastError();
+        lds_floats = pdh_lds_floats(a.tvp);
+    } else {
+        const bool lsa = a.att_type == GSTTACO_ATT_LSA;
+        k = pd_kernel_for(a.B, &a.G);
+        a.tvp = lsa ? 128 : (a.Tv + 63) / 64 * 64;       // (LSA: the 128-token chain only; gt_persist_decode_lsa_fits)
+        const bool gk = k != gt_persist_decode_kernel;
+        if (lsa && (gk || !gt_persist_decode_lsa_fits(a.B, a.Tv, a.loc_f, a.loc_k))) return hipErrorInvalidValue;
+        a.n_chain = gk ? a.B : PD_UTT;
+        a.twopass = pd_chain_slabs(a.tvp, gk) == 8 ? 1 : 0;
+        lds_floats = pd_lds_floats(a.tvp, gk) + (lsa ? pd_lsa_floats(a.loc_f, a.loc_k) : 0);
     }
-    const bool lsa = a.att_type == GSTTACO_ATT_LSA;
-    const PdKernel k = pd_kernel_for(a.B, &a.G);
-    a.tvp = lsa ? 128 : (a.Tv + 63) / 64 * 64;       // (LSA: the 128-token chain only; gt_persist_decode_lsa_fits)
-    const bool gk = k != gt_persist_decode_kernel;
-    if (lsa && (gk || !gt_persist_decode_lsa_fits(a.B, a.Tv, a.loc_f, a.loc_k))) return hipErrorInvalidValue;
-    a.n_chain = gk ? a.B : PD_UTT;
-    a.twopass = pd_chain_slabs(a.tvp, gk) == 8 ? 1 : 0;
     const int n = PD_CTL_WORDS > a.B * PD_P ? PD_CTL_WORDS : a.B * PD_P;
     hipLaunchKernelGGL(gt_persist_decode_init_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, a.z0g, b0, a.ctl, a.B);
-    hipLaunchKernelGGL(k, dim3(PD_NWG), dim3(PD_NT), (size_t)(pd_lds_floats(a.tvp, gk) + (lsa ? pd_lsa_floats(a.loc_f, a.loc_k) : 0)) * 4, stream, a);
+    hipLaunchKernelGGL(k, dim3(PD_NWG), dim3(PD_NT), lds_floats * 4, stream, a);
     return hipGetLastError();
 }

@@ -1,7 +1,7 @@
 // Group kernels of the persistent decode launch (fp32, 33..128 rows): included by
 // persist_decode.hip inside its anonymous namespace, behind the one-group kernel whose primitives (waits, fragment loads, MFMA pieces,
 // reductions, the per-utterance chain) they share.  DESIGN.md 3.1c, EXPERIMENTS.md round 5 item 1.
-// INVARIANT (give-up safety, PD_PHASE_ABORT in persist_decode.hip): after a bounded wait has given up, the workgroup runs the REST of the
+// INVARIANT (give-up safety, PdShared in persist_decode.hip): after a bounded wait has given up, the workgroup runs the REST of the
 // step on whatever the wait left and leaves at the top of its next step.  That is only safe because NO ADDRESS AND NO LOOP BOUND behind a
 // wait depends on data that came through a hand-off: every index below is a function of blockIdx / threadIdx / the step counter / launch
 // arguments (token lengths are read from the caller's tensor before the first wait).  Keep it so when editing this file.
@@ -37,8 +37,7 @@ __device__ __forceinline__ void pd_wait_flags_all(const PersistDecodeArgs& A, co
             asm volatile("global_load_dword %0, %2, off sc1\n\tglobal_load_dword %1, %3, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(v0), "=&v"(v1) : "v"(p0), "v"(p1) : "memory");
             const bool ok = (!h0 || v0 >= want) && (!h1 || v1 >= want);
             if (__builtin_amdgcn_readfirstlane(__popcll(__ballot(ok))) == 64) break;
-            if (++spins > PD_SPIN_MAX) { if (lane == 0) pd_give_up(A, sh, true); break; }
-            if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(gt_ld_sc1(A.err)) != 0u) { if (lane == 0) pd_give_up(A, sh, false); break; }
+            PD_POLL_BOUND(lane);
         }
     }
     __syncthreads();
@@ -62,8 +61,7 @@ __device__ __forceinline__ void pd_wait_count_all(const PersistDecodeArgs& A, co
 #pragma unroll
             for (int g = 0; g < GM; ++g) { asm volatile("" : "+v"(u[g])); ok = ok && u[g] >= want; }
             if (__builtin_amdgcn_readfirstlane(__popcll(__ballot(ok))) == 64) break;
-            if (++spins > PD_SPIN_MAX) { if (lane == 0) pd_give_up(A, sh, true); break; }
-            if ((spins & 63u) == 0u && __builtin_amdgcn_readfirstlane(gt_ld_sc1(A.err)) != 0u) { if (lane == 0) pd_give_up(A, sh, false); break; }
+            PD_POLL_BOUND(lane);
         }
     }
     __syncthreads();
@@ -98,7 +96,7 @@ __device__ __forceinline__ void pd_g_mma8(float4 (&x0)[8], float4 (&x1)[8], cons
 }
 // sums of a recurrent-half tile from its accumulators (pd_rec_tile's orders).  TWOPASS: the 16-slab sum through EIGHT slabs -- virtual
 // waves 0..7, then 8..15 onto the running sum: the same sequence of additions (chain workgroups: their LDS holds the processed memory).
-// `cnt`: a deferred arrival (pd_reduce_arrive) or NULL
+// `cnt`: a deferred arrival (pd_reduce) or NULL
 template <bool ORDER16, bool TWOPASS>
 __device__ __forceinline__ float pd_g_rec_sum(float* lds, float bias, const f32x4& a0, const f32x4& a1, const f32x4& b0, const f32x4& b1, uint32_t* cnt = nullptr,
                                               bool two = true) {
@@ -106,29 +104,27 @@ __device__ __forceinline__ float pd_g_rec_sum(float* lds, float bias, const f32x
     if (ORDER16) {
         if (TWOPASS && two) {
             pd_spill(lds, wave, a0, a1);
-            const float z = pd_reduce_arrive<8>(lds, bias, cnt);
+            const float z = pd_reduce<8>(lds, bias, cnt);
             pd_spill(lds, wave, b0, b1);
             return pd_reduce<8>(lds, z);
         }
         pd_spill(lds, wave, a0, a1);
         pd_spill(lds, wave + 8, b0, b1);
-        return pd_reduce_arrive<16>(lds, bias, cnt);
+        return pd_reduce<16>(lds, bias, cnt);
     }
     pd_spill(lds, wave, a0, a1);
-    return pd_reduce_arrive<8>(lds, bias, cnt);
+    return pd_reduce<8>(lds, bias, cnt);
 }
 
 // ---- the phases, for all groups.  State access: `c(g)` / `p(g)` return references (registers, or LDS in the projection role).
 // LSTM cell 1 of every group: z = [p | ctx] . W1x + p1[g]; the next group's fragments in a second buffer
 template <int GM, class C1, class P1>
 __device__ __forceinline__ void pd_g_cell1_all(const PersistDecodeArgs& A, const float4 (&wx1)[3], int t, int tile, float* lds, C1 c1, P1 p1, PdShared* sh, int role, int zt) {
-    constexpr int RG = 32;
     const int par = t & 1, MT = A.MT;
     pd_wait_flags_all(A, A.ctl + zt + PD_F_C, (uint32_t)t + 1u, sh);       // (a chain's context flag follows its prenet flag)
-    PD_PHASE_ABORT(sh);
     PD_STAMP(role, 2);
     float4 xa0[3], xa1[3], xb0[3], xb1[3];
-    pd_g_xload<2, 0, 3, 3>(A.xa[par], MT, 0, xa0, xa1);
+    pd_g_xload<0, 3, 3>(A.xa[par], MT, 0, xa0, xa1);
 #pragma unroll
     for (int g = 0; g < GM; ++g) {
         if (g < A.G) {
@@ -136,20 +132,20 @@ __device__ __forceinline__ void pd_g_cell1_all(const PersistDecodeArgs& A, const
             float4 (&x1)[3] = (g & 1) ? xb1 : xa1;
             PD_PIN();
             f32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
-            pd_g_mma<2, 3, 0, 1, 3>(x0, x1, wx1, a0, a1);
+            pd_mma<3, 0, 1, 3>(x0, x1, wx1, a0, a1);
             // (group g - 1's h1 stores were left in flight: their acknowledgement arrived under this group's MFMAs; drained here, its
             // arrival is signalled behind the reduction's first barrier -- the last group's at once, everybody waits for it.  The next
             // group's fragments are requested BEHIND the drain -- in front of it the drain waited for them -- and land under the epilogue)
             if (g > 0) pd_drain();
             PD_PIN();
             if (g + 1 < GM && g + 1 < A.G) {
-                if (g & 1) pd_g_xload<2, 0, 3, 3>(A.xa[par], MT, g + 1, xa0, xa1);
-                else pd_g_xload<2, 0, 3, 3>(A.xa[par], MT, g + 1, xb0, xb1);
+                if (g & 1) pd_g_xload<0, 3, 3>(A.xa[par], MT, g + 1, xa0, xa1);
+                else pd_g_xload<0, 3, 3>(A.xa[par], MT, g + 1, xb0, xb1);
             }
             PD_PIN();
             pd_spill(lds, threadIdx.x >> 6, a0, a1);
-            const float z = pd_reduce_arrive<8>(lds, p1(g), g > 0 ? A.ctl + zt + PD_CNT3 + (g - 1) * (PD_NSH * 32) : nullptr);
-            pd_gates_store(z, c1(g), A.h1[par], tile + zt, A.B, MT, RG * g, RG);
+            const float z = pd_reduce<8>(lds, p1(g), g > 0 ? A.ctl + zt + PD_CNT3 + (g - 1) * (PD_NSH * 32) : nullptr);
+            pd_gates_store(z, c1(g), A.h1[par], tile + zt, A.B, MT, 32 * g);
             if (g == A.G - 1) pd_arrive(A.ctl + zt + PD_CNT3 + g * (PD_NSH * 32));
             PD_STAMP(role, 3 + 7 * g);
         }
@@ -163,13 +159,11 @@ __device__ __forceinline__ void pd_g_cell1_all(const PersistDecodeArgs& A, const
 template <int GM, bool REC1, bool TWOPASS, bool STREAM_H2, class C2, class P2, class P1>
 __device__ __forceinline__ void pd_g_cell2_all(const PersistDecodeArgs& A, const float4 (&wx2)[8], const float4 (&wh1)[8], float4 (&wh2)[8], int t, int tile, float* lds,
                                                C2 c2, P2 p2, P1 p1, PdShared* sh, int role, int zt) {
-    constexpr int RG = 32;
     const int par = t & 1, MT = A.MT;
     pd_wait_count_all<GM>(A, A.ctl + zt + PD_CNT3, PD_WANT(A, t), sh);
-    PD_PHASE_ABORT(sh);
     PD_STAMP(role, 4);
     float4 x0[8], x1[8];
-    pd_g_xload<2, 0, 8, 8>(A.h1[par], MT, 0, x0, x1);
+    pd_g_xload<0, 8, 8>(A.h1[par], MT, 0, x0, x1);
     PD_PIN();
     const float bias1 = A.b1h[tile * 16 + (threadIdx.x & 15)];
 #pragma unroll
@@ -184,8 +178,8 @@ __device__ __forceinline__ void pd_g_cell2_all(const PersistDecodeArgs& A, const
             const bool deferred = REC1 && g > 0;
             if (deferred) pd_drain();
             pd_spill(lds, threadIdx.x >> 6, a0, a1);
-            const float z = pd_reduce_arrive<8>(lds, p2(g), deferred ? A.ctl + zt + PD_CNT4 + (g - 1) * (PD_NSH * 32) : nullptr);
-            pd_gates_store(z, c2(g), A.h2[par], tile + zt, A.B, MT, RG * g, RG);
+            const float z = pd_reduce<8>(lds, p2(g), deferred ? A.ctl + zt + PD_CNT4 + (g - 1) * (PD_NSH * 32) : nullptr);
+            pd_gates_store(z, c2(g), A.h2[par], tile + zt, A.B, MT, 32 * g);
             if (!REC1 || g == A.G - 1) pd_arrive(A.ctl + zt + PD_CNT4 + g * (PD_NSH * 32));
             PD_STAMP(role, 5 + 7 * g);
             if (STREAM_H2 && g == A.G - 1 && t + 1 < A.steps) pd_load_tile<8>(A.w2h, tile, wh2);
@@ -204,10 +198,7 @@ __device__ __forceinline__ void pd_g_cell2_all(const PersistDecodeArgs& A, const
 template <int GM, int LAYER, bool TWOPASS, bool WAIT, class P>
 __device__ __forceinline__ void pd_g_rec_all(const PersistDecodeArgs& A, const float4 (&wh)[8], int t, int tile, float* lds, P p, PdShared* sh, int role, int zt) {
     const int MT = A.MT;
-    if (WAIT) {
-        pd_wait_count_all<GM>(A, A.ctl + zt + PD_CNT4, PD_WANT(A, t), sh);
-        PD_PHASE_ABORT(sh);
-    }
+    if (WAIT) pd_wait_count_all<GM>(A, A.ctl + zt + PD_CNT4, PD_WANT(A, t), sh);
     PD_STAMP(role, 7);
     const float* hb = LAYER == 1 ? A.h1[t & 1] : A.h2[t & 1];
     const float bias = (LAYER == 1 ? A.b1h : A.b2h)[tile * 16 + (threadIdx.x & 15)];
@@ -216,7 +207,7 @@ __device__ __forceinline__ void pd_g_rec_all(const PersistDecodeArgs& A, const f
     // fragment a register of its own and spilled)
     if (LAYER == 1 || tile >= A.co_tiles) {
         float4 x0[8], x1[8];
-        pd_g_xload<2, 0, 8, 8>(hb, MT, 0, x0, x1);
+        pd_g_xload<0, 8, 8>(hb, MT, 0, x0, x1);
         PD_PIN();
 #pragma unroll
         for (int g = 0; g < GM; ++g) {
@@ -229,7 +220,7 @@ __device__ __forceinline__ void pd_g_rec_all(const PersistDecodeArgs& A, const f
         }
     } else {
         float4 x0[8], x1[8];
-        pd_g_xload<2, 0, 8, 8>(hb, MT, 0, x0, x1);
+        pd_g_xload<0, 8, 8>(hb, MT, 0, x0, x1);
         PD_PIN();
 #pragma unroll
         for (int g = 0; g < GM; ++g) {
@@ -262,21 +253,7 @@ __device__ __forceinline__ void pd_g_run_tile(const PersistDecodeArgs& A, float*
     PdChainRegs R{};
     if (CHAIN) {
         L = pd_carve(smem, A.tvp, A.twopass ? 8 : 16);
-        R.Tv = A.tok_len ? max(1, min(A.Tv, (int)A.tok_len[b])) : A.Tv;
-        R.drop = A.drop_rate > 0.f;
-        R.hashed = R.drop && A.keep_hash != 0;
-        R.noisy = A.sigmoid_noise > 0.f;
-        R.seed = R.hashed ? *A.seed_ptr : 0ull;
-        R.bias1 = tid < PD_P ? A.b1[tid] : 0.f;
-        R.biasq = tid < PD_A ? A.bq[tid] : 0.f;
-        R.sbias = A.score_bias[0];
-        const float4* src = reinterpret_cast<const float4*>(A.pm + (size_t)b * A.Tv * PD_A);
-        for (int e = tid; e < A.tvp * PD_A / 4; e += PD_NT) {
-            const int row = e / (PD_A / 4), c4 = e % (PD_A / 4);
-            *reinterpret_cast<float4*>(L.tile + row * PD_LDV + 4 * c4) = row < R.Tv ? src[(size_t)row * (PD_A / 4) + c4] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        if (tid < PD_A) L.vs[tid] = A.av[tid];
-        if (tid < A.tvp) L.pv[tid] = tid == 0 ? 1.f : 0.f;
+        pd_chain_setup(A, L, R, b);
     } else {
         pd_load_tile<3>(A.w1x, tile, W.x1); pd_load_tile<8>(A.w2x, tile, W.x2);
         pd_load_tile<8>(A.w1h, tile, W.h1); pd_load_tile<8>(A.w2h, tile, W.h2);
@@ -286,7 +263,7 @@ __device__ __forceinline__ void pd_g_run_tile(const PersistDecodeArgs& A, float*
     // recurrent halves -- waits in memory meanwhile (its own rows of `stash`, written and re-read by the same thread: L2 hits,
     // requested back before the first flag wait).
     for (int t = 0; t < A.steps; ++t) {
-        if (sh->abort) return;          // (the one abort check of the step: PD_PHASE_ABORT)
+        if (sh->abort) return;          // (the one abort check of the step: PdShared, persist_decode.hip)
         PD_STAMP(role, 0);
         PD_ZT(zt);
         float* st = A.stash + (size_t)blockIdx.x * (4 * GM * PD_NT) + tid + zt;
@@ -301,7 +278,6 @@ __device__ __forceinline__ void pd_g_run_tile(const PersistDecodeArgs& A, float*
             int bs = b;
             asm volatile("" : "+s"(bs));
             pd_chain<false>(A, L, R, t, bs, sh, unused4, zt);
-            PD_PHASE_ABORT(sh);
             PD_STAMP(role, 1);
             PD_PIN();
             pd_load_tile<3>(A.w1x, tile, W.x1);
@@ -313,12 +289,9 @@ __device__ __forceinline__ void pd_g_run_tile(const PersistDecodeArgs& A, float*
             pd_load_tile<8>(A.w2x, tile, W.x2); pd_load_tile<8>(A.w1h, tile, W.h1);        // (for the NEXT phase: they arrive during cell 1)
         }
         pd_g_cell1_all<GM>(A, W.x1, t, tile, lds, c1, p1, sh, role, zt);
-        PD_PHASE_ABORT(sh);
         pd_g_cell2_all<GM, true, CHAIN, CHAIN>(A, W.x2, W.h1, W.h2, t, tile, lds, c2, p2, p1, sh, role, zt);
-        PD_PHASE_ABORT(sh);
         if (t + 1 == A.steps) break;
         pd_g_rec_all<GM, 2, CHAIN, true>(A, W.h2, t, tile, lds, p2, sh, role, zt);
-        PD_PHASE_ABORT(sh);
     }
 }
 
@@ -342,20 +315,17 @@ __device__ __forceinline__ void pd_g_run_proj(const PersistDecodeArgs& A, float*
     auto p1 = [&](int g) -> float& { return sl[(4 * g + 2) * PD_NT]; };
     auto p2 = [&](int g) -> float& { return sl[(4 * g + 3) * PD_NT]; };
     for (int t = 0; t < A.steps; ++t) {
-        if (sh->abort) return;          // (the one abort check of the step: PD_PHASE_ABORT)
+        if (sh->abort) return;          // (the one abort check of the step: PdShared, persist_decode.hip)
         PD_STAMP(1, 0);
         PD_ZT(zt);
         pd_load_tile<3>(A.w1x, tile, W.x1);
         pd_g_cell1_all<GM>(A, W.x1, t, tile, lds, c1, p1, sh, 1, zt);
-        PD_PHASE_ABORT(sh);
         pd_g_cell2_all<GM, true, false, false>(A, W.x2, W.h1, W.h2, t, tile, lds, c2, p2, p1, sh, 1, zt);
-        PD_PHASE_ABORT(sh);
         // every group's projection behind ONE wait for the h2 arrivals (the chains that need them start ~10 us later: their
         // workgroups still have this step's recurrent halves to multiply); the projection tile (72 KB) arrives during that wait
         float4 wpj[9];
         pd_load_tile<9>(A.wp, ptile, wpj);
         pd_wait_count_all<GM>(A, A.ctl + zt + PD_CNT4, PD_WANT(A, t), sh);
-        PD_PHASE_ABORT(sh);
 #pragma unroll
         for (int g = 0; g < GM; ++g)
             // (an M-tile past the batch's last -- 33..48 rows: group 1's second -- does not exist: its fragment would be read one block

@@ -66,5 +66,6 @@ for src in srcs:
                 os.makedirs(os.path.join(asm_dir, src), exist_ok=True)
                 with open(os.path.join(asm_dir, src, name[:150] + "." + hashlib.sha256(name.encode()).hexdigest()[:8] + ".s"), "w") as f:
                     f.write("\n".join(lines) + "\n")
-        print("%-100s VGPR %3s AGPR %3s SGPR %3s spill %3s scratch %4s occ %2s LDS %6s%s" % (dn[:100], v.get("VGPRs"), v.get("AGPRs"), v.get("TotalSGPRs"),
-              v.get("VGPRs Spill"), v.get("ScratchSize [bytes/lane]"), v.get("Occupancy [waves/SIMD]"), v.get("LDS Size [bytes/block]"), tail))
+        print("%-100s VGPR %3s AGPR %3s SGPR %3s spill %3s sspill %3s scratch %4s occ %2s LDS %6s%s" % (dn[:100], v.get("VGPRs"), v.get("AGPRs"),
+              v.get("TotalSGPRs"), v.get("VGPRs Spill"), v.get("SGPRs Spill"), v.get("ScratchSize [bytes/lane]"), v.get("Occupancy [waves/SIMD]"),
+              v.get("LDS Size [bytes/block]"), tail))
