@@ -66,9 +66,17 @@ def resample_kaiser_best(x, sr_orig, sr_new, chunk=8192):
     return y[:n_fix] if y.shape[0] >= n_fix else np.pad(y, (0, n_fix - y.shape[0]))
 
 
-def load_wav(path, sample_rate):
-    """float32 mono samples at ``sample_rate``: what ``librosa.core.load(path, sr)`` returns for a PCM wav (8/16/32-bit via the
-    standard library): int / 2^(bits-1), channel mean, and for a file at another rate the 'kaiser_best' resampling above."""
+def resample_lengths(n, sr_orig, sr_new):
+    """(n_out, n_fix) of ``n`` samples: the int(n * ratio) samples the resampling computes and the ceil(n * ratio) that
+    ``fix_length`` leaves (at most one trailing zero more) -- the expressions of ``resample_kaiser_best`` and of
+    ``gsttaco_resample``."""
+    ratio = float(sr_new) / float(sr_orig)
+    return int(n * ratio), int(np.ceil(n * ratio))
+
+
+def read_wav(path):
+    """(float32 mono samples, the file's rate): the decoding half of ``librosa.core.load`` for a PCM wav (8/16/32-bit via the
+    standard library): int / 2^(bits-1), channel mean."""
     with wave.open(path, "rb") as f:
         nch, width, sr, n = f.getnchannels(), f.getsampwidth(), f.getframerate(), f.getnframes()
         raw = f.readframes(n)
@@ -82,16 +90,35 @@ def load_wav(path, sample_rate):
         raise ValueError("{}: unsupported PCM sample width {}".format(path, width))
     if nch > 1:
         y = y.reshape(-1, nch).mean(axis=1).astype(np.float32)
+    return y, sr
+
+
+def load_wav(path, sample_rate):
+    """float32 mono samples at ``sample_rate``: what ``librosa.core.load(path, sr)`` returns for a PCM wav: ``read_wav`` and, for a
+    file at another rate, the 'kaiser_best' resampling above."""
+    y, sr = read_wav(path)
     if sr != sample_rate:
         y = resample_kaiser_best(y, sr, sample_rate)
     return y
 
 
-def as_signal(item, sample_rate):
-    """A path -> samples; a 1-D array is taken as samples already at ``sample_rate``."""
+def as_signal_at_rate(item, sample_rate):
+    """(samples, rate) with nothing resampled: a path -> the file's samples and rate; a ``(samples, rate)`` pair -> itself; a bare
+    1-D array is taken as samples already at ``sample_rate``."""
     if isinstance(item, (str, bytes)) or hasattr(item, "__fspath__"):
-        return load_wav(item, sample_rate)
+        return read_wav(item)
+    rate = sample_rate
+    if isinstance(item, tuple) and len(item) == 2 and np.ndim(item[1]) == 0 and np.ndim(item[0]) == 1:
+        item, rate = item[0], int(item[1])
+        if rate < 1:
+            raise ValueError("a (samples, rate) reference signal needs a positive rate")
     a = np.asarray(item, dtype=np.float32)
     if a.ndim != 1:
-        raise ValueError("a reference signal must be a wav path or a 1-D sample array")
-    return a
+        raise ValueError("a reference signal must be a wav path, a 1-D sample array or a (samples, rate) pair")
+    return a, rate
+
+
+def as_signal(item, sample_rate):
+    """Samples at ``sample_rate``, resampled on the host where needed: ``as_signal_at_rate`` + ``resample_kaiser_best``."""
+    a, rate = as_signal_at_rate(item, sample_rate)
+    return a if rate == sample_rate else resample_kaiser_best(a, rate, sample_rate)

@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = (
     "gsttaco_encoder_variants", "gsttaco_vocoder_variants",
     "gsttaco_decode_plan_fields",
     "gsttaco_mel_dtw",
+    "gsttaco_resample",
 )
 # GSTTACO_PLAN_*: the fields gsttaco_decode_plan_fields fills, in order
 PLAN_FIELDS = ("persist", "persist_bf16", "fused", "lean_front", "lean_rec", "z0", "fuse12", "lean_x0", "lean_x1", "co_tiles", "lean_proj",
@@ -158,6 +159,9 @@ def load_library(path=None):
     lib.gsttaco_losses.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
     lib.gsttaco_mel_dtw.argtypes = [vp, vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, i32, i32, i32, i32, vp, vp, vp, vp]
     lib.gsttaco_mel_dtw.restype = ctypes.c_int
+    i32p = ctypes.POINTER(ctypes.c_int32)       # (host arrays)
+    lib.gsttaco_resample.argtypes = [vp, vp, i32p, i32p, i32, i32, i32, vp, i32, i32p, vp]
+    lib.gsttaco_resample.restype = ctypes.c_int
     lib.gsttaco_postnet.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.gsttaco_vocoder.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.gsttaco_inference_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]

@@ -216,6 +216,22 @@ struct gsttaco_ctx {
     double *w_dtw_fx = nullptr, *w_dtw_fy = nullptr;
     uint8_t* w_dtw_bp = nullptr;
     std::map<int, double*> dtw_basis;
+    // Resampling (gsttaco_resample): the tables of up to GT_RS_MAX_PAIRS rate pairs, least recently used evicted (ensure_resample_pair).
+    // A slot's device memory and pinned host image are allocated at its first use and reused by the pairs that follow in it; `uploaded`
+    // is recorded behind a slot's upload, and waited for before its host image is rewritten.
+    struct ResampleSlot {
+        int sr_in = 0, sr_out = 0;          // 0: the slot has never held a pair
+        uint64_t last_use = 0;
+        double* d_time = nullptr;           // [max_wav_samples]
+        double2* d_table = nullptr;         // [GT_RS_NWIN] {win, delta}
+        double* h_image = nullptr;          // pinned: the register, then the table
+        hipEvent_t uploaded = nullptr;
+        double scale = 0.0;
+        int step = 0;
+    };
+    ResampleSlot rs_slot[GT_RS_MAX_PAIRS];
+    std::vector<double> rs_window;          // the un-gained kaiser_best table, built by the first call
+    uint64_t rs_clock = 0;
     ConvLayer z0_dense;
     ConvLayer val_enc;          // the [enc] rows of the Value kernel (+ its bias when no GST row bias carries it)
     float *att_v = nullptr, *att_sb = nullptr;
@@ -2196,6 +2212,10 @@ void gsttaco_destroy(gsttaco_ctx* c) {
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     for (void* p : c->allocs) (void)hipFree(p);
+    for (auto& rs : c->rs_slot) {
+        if (rs.h_image) (void)hipHostFree(rs.h_image);
+        if (rs.uploaded) (void)hipEventDestroy(rs.uploaded);
+    }
     if (c->h_err) (void)hipHostFree(c->h_err);
     if (c->counted) g_live_contexts.fetch_sub(1);
     {
@@ -2801,6 +2821,140 @@ int gsttaco_mel_dtw(gsttaco_ctx* c, const float* x, const int32_t* x_len, int64_
     a.cost = cost; a.path_len = path_len; a.path = path;
     a.B = B; a.Tx = Tx; a.Ty = Ty; a.mel_dim = g.mel_dim; a.n_ceps = n_ceps;
     HIPCHECK(c, gt_launch_mel_dtw(a, (hipStream_t)stream));
+    return 0;
+}
+
+// resampy's published 'kaiser_best' design (resampy/filters.py sinc_window): the right half of a Kaiser-windowed sinc, 64 zero crossings,
+// 512 entries per crossing.  scipy.signal.windows.kaiser(2n + 1, beta)[n + j] = I0(beta sqrt(1 - (j / n)^2)) / I0(beta), I0 by its
+// power series (all terms positive: no cancellation); numpy.sinc(x) = sin(pi x) / (pi x); linspace(0, 64, n + 1)[j] = j / 512 exactly.
+static double bessel_i0(double x) {
+    const double q = 0.25 * x * x;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < 500; ++k) {
+        term *= q / ((double)k * (double)k);
+        sum += term;
+        if (term < 1e-18 * sum) break;
+    }
+    return sum;
+}
+
+static void kaiser_best_window(std::vector<double>& win) {
+    const double beta = 14.769656459379492, rolloff = 0.9475937167399596;
+    const int n = GT_RS_NWIN - 1;
+    win.resize(GT_RS_NWIN);
+    const double i0_beta = bessel_i0(beta);
+    for (int j = 0; j <= n; ++j) {
+        const double r = (double)j / (double)n;
+        const double taper = bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - r * r))) / i0_beta;
+        const double px = M_PI * (rolloff * ((double)j / 512.0));
+        const double sinc = j == 0 ? 1.0 : std::sin(px) / px;
+        win[j] = taper * (rolloff * sinc);
+    }
+}
+
+// The slot holding the tables of (sr_in, sr_out), built and uploaded on `s` when the cache does not hold the pair.  `clock` is this
+// call's stamp: a slot stamped with it serves another row of the same call and is not evicted.
+static int ensure_resample_pair(gsttaco_ctx* c, int sr_in, int sr_out, uint64_t clock, hipStream_t s, int* slot_out) {
+    const int T = c->cfg.max_wav_samples;
+    int victim = -1;
+    for (int i = 0; i < GT_RS_MAX_PAIRS; ++i) {
+        gsttaco_ctx::ResampleSlot& rs = c->rs_slot[i];
+        if (rs.sr_in == sr_in && rs.sr_out == sr_out) {
+            rs.last_use = clock;
+            *slot_out = i;
+            return 0;
+        }
+        if (rs.last_use != clock && (victim < 0 || rs.last_use < c->rs_slot[victim].last_use)) victim = i;
+    }
+    if (victim < 0) return fail(c, GSTTACO_E_INVALID, "internal: no resampling table slot left for this call");
+    gsttaco_ctx::ResampleSlot& rs = c->rs_slot[victim];
+    int rc = 0;
+    if (!rs.d_time) {
+        if ((rc = dev_alloc(c, (void**)&rs.d_time, (size_t)T * sizeof(double)))) return rc;
+        if ((rc = dev_alloc(c, (void**)&rs.d_table, (size_t)GT_RS_NWIN * sizeof(double2)))) return rc;
+        HIPCHECK(c, hipHostMalloc((void**)&rs.h_image, ((size_t)T + 2 * (size_t)GT_RS_NWIN) * sizeof(double), hipHostMallocDefault));
+        HIPCHECK(c, hipEventCreateWithFlags(&rs.uploaded, hipEventDisableTiming));
+    } else {
+        HIPCHECK(c, hipEventSynchronize(rs.uploaded));          // the evicted pair's upload has read the host image
+    }
+    rs.sr_in = rs.sr_out = 0;                                   // (nothing valid in the slot until the uploads below are enqueued)
+    if (c->rs_window.empty()) kaiser_best_window(c->rs_window);
+    const double ratio = (double)sr_out / (double)sr_in, inc = 1.0 / ratio, gain = ratio < 1.0 ? ratio : 1.0;
+    double* h_time = rs.h_image;
+    double* h_table = rs.h_image + T;
+    double reg = 0.0;
+    for (int t = 0; t < T; ++t) {                               // accumulated, as resampy does: not t * inc
+        h_time[t] = reg;
+        reg += inc;
+    }
+    for (int j = 0; j < GT_RS_NWIN; ++j) h_table[2 * j] = ratio < 1.0 ? c->rs_window[j] * ratio : c->rs_window[j];
+    for (int j = 0; j < GT_RS_NWIN; ++j) h_table[2 * j + 1] = j + 1 < GT_RS_NWIN ? h_table[2 * (j + 1)] - h_table[2 * j] : 0.0;
+    HIPCHECK(c, hipMemcpyAsync(rs.d_time, h_time, (size_t)T * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHECK(c, hipMemcpyAsync(rs.d_table, h_table, (size_t)GT_RS_NWIN * sizeof(double2), hipMemcpyHostToDevice, s));
+    HIPCHECK(c, hipEventRecord(rs.uploaded, s));
+    rs.scale = gain;
+    rs.step = (int)(gain * 512.0);
+    rs.sr_in = sr_in; rs.sr_out = sr_out; rs.last_use = clock;
+    *slot_out = victim;
+    return 0;
+}
+
+// wav at any rate -> wav at sr_out: one launch per GT_RS_MAX_ROWS rows on the caller's stream, straight from / to the caller's pointers.
+// Everything is validated, and out_lengths filled, before the first table is built or anything is enqueued.
+int gsttaco_resample(gsttaco_ctx* c, const float* x, const int32_t* in_lengths, const int32_t* sr_in, int B, int ld_in, int sr_out,
+                     float* y, int ld_out, int32_t* out_lengths, void* stream) {
+    if (!c) return GSTTACO_E_INVALID;
+    int rc = ensure_audio(c);
+    if (rc) return rc;
+    const gsttaco_config& g = c->cfg;
+    if (!x || !in_lengths || !sr_in || !y || !out_lengths) return fail(c, GSTTACO_E_INVALID, "null argument");
+    if (B < 1 || ld_in < 1 || ld_out < 1 || sr_out < 1) return fail(c, GSTTACO_E_INVALID, "bad B / ld_in / ld_out / sr_out");
+    if (B > g.max_batch || ld_out > g.max_wav_samples) return fail(c, GSTTACO_E_CAPACITY, "batch / output samples exceed capacity");
+    std::vector<int32_t> n_out(B), n_fix(B);
+    std::vector<std::pair<int, int>> pairs;                     // the call's distinct rate pairs that need a table
+    std::vector<int> pair_of(B, -1);
+    for (int b = 0; b < B; ++b) {
+        const int n = in_lengths[b], sr = sr_in[b];
+        if (n < 0 || n > ld_in) return fail(c, GSTTACO_E_INVALID, "an input length is outside [0, ld_in]");
+        if (sr < 1) return fail(c, GSTTACO_E_INVALID, "a sample rate is not positive");
+        if ((int64_t)sr > (int64_t)GT_RS_MAX_FACTOR * sr_out || (int64_t)sr_out > (int64_t)GT_RS_MAX_FACTOR * sr)
+            return fail(c, GSTTACO_E_INVALID, "a resampling factor is beyond 16 (sr_in <= 16 sr_out and sr_out <= 16 sr_in)");
+        const double ratio = (double)sr_out / (double)sr;       // the expressions of audio.py resample_lengths
+        const double fix = std::ceil((double)n * ratio);
+        if (fix > (double)ld_out) return fail(c, GSTTACO_E_INVALID, "a row's resampled length ceil(in_length * sr_out / sr_in) exceeds ld_out");
+        n_fix[b] = (int32_t)fix;
+        n_out[b] = sr == sr_out ? n : (int32_t)((double)n * ratio);
+        if (sr == sr_out) continue;
+        const std::pair<int, int> key(sr, sr_out);
+        size_t k = 0;
+        while (k < pairs.size() && pairs[k] != key) ++k;
+        if (k == pairs.size()) {
+            if (pairs.size() == GT_RS_MAX_PAIRS)
+                return fail(c, GSTTACO_E_INVALID, "more than eight distinct rate pairs in one call (the table cache holds eight)");
+            pairs.push_back(key);
+        }
+        pair_of[b] = (int)k;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const uint64_t clock = ++c->rs_clock;
+    int slot_of[GT_RS_MAX_PAIRS];
+    ResampleArgs a{};
+    for (size_t k = 0; k < pairs.size(); ++k) {
+        if ((rc = ensure_resample_pair(c, pairs[k].first, pairs[k].second, clock, s, &slot_of[k]))) return rc;
+        const gsttaco_ctx::ResampleSlot& rs = c->rs_slot[slot_of[k]];
+        a.pair[slot_of[k]] = ResamplePair{rs.d_time, rs.d_table, rs.scale, rs.step, g.max_wav_samples};
+    }
+    a.x = x; a.y = y; a.ld_in = ld_in; a.ld_out = ld_out;
+    for (int b0 = 0; b0 < B; b0 += GT_RS_MAX_ROWS) {
+        a.row0 = b0; a.rows = std::min(B - b0, GT_RS_MAX_ROWS);
+        for (int b = 0; b < a.rows; ++b) {
+            a.n_in[b] = in_lengths[b0 + b];
+            a.n_out[b] = n_out[b0 + b];
+            a.slot[b] = pair_of[b0 + b] < 0 ? (uint8_t)GT_RS_PASS : (uint8_t)slot_of[pair_of[b0 + b]];
+        }
+        HIPCHECK(c, gt_launch_resample(a, s));
+    }
+    for (int b = 0; b < B; ++b) out_lengths[b] = n_fix[b];
     return 0;
 }
 

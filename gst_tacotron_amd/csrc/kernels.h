@@ -549,3 +549,32 @@ struct DtwArgs {
 size_t gt_dtw_lds_bytes(int Ty);
 hipError_t gt_dtw_init();                   // once per process and device, before a launch that needs more than 64 KiB of LDS
 hipError_t gt_launch_mel_dtw(const DtwArgs& a, hipStream_t stream);
+
+
+// ---------------------------------------------------------------- resample.hip
+// resampy 'kaiser_best' resampling of a batch of rows (the contract: gsttaco_resample in include/gsttaco.h).  One launch per
+// GT_RS_MAX_ROWS rows; the per-row parameters and the rate pairs' tables travel by value in the kernel arguments.
+#define GT_RS_THREADS 256
+#define GT_RS_NWIN 32769                    // 64 zero crossings x 512 table entries + 1
+#define GT_RS_MAX_FACTOR 16                 // sr_in <= 16 sr_out and sr_out <= 16 sr_in
+#define GT_RS_MAX_PAIRS 8
+#define GT_RS_MAX_ROWS 256
+#define GT_RS_PASS 255                      // ResampleArgs::slot of a row already at the target rate
+struct ResamplePair {
+    const double* time;         // [time_len] the accumulated time register: time[0] = 0, time[t] = time[t-1] + 1 / ratio
+    const double2* table;       // [GT_RS_NWIN] {win, delta}: the table times min(1, ratio) and its forward differences (the last 0)
+    double scale;               // min(1, ratio)
+    int step;                   // int(scale * 512)
+    int time_len;
+};
+struct ResampleArgs {
+    const float* x;             // [.., ld_in]
+    float* y;                   // [.., ld_out]
+    int row0, rows;             // rows row0 .. row0 + rows - 1 of x and y; entry b of the arrays below is row row0 + b
+    int ld_in, ld_out;
+    ResamplePair pair[GT_RS_MAX_PAIRS];
+    int32_t n_in[GT_RS_MAX_ROWS];       // valid input samples (<= ld_in)
+    int32_t n_out[GT_RS_MAX_ROWS];      // int(n_in * ratio) computed samples (<= ld_out); [n_out, ld_out) is zero-filled
+    uint8_t slot[GT_RS_MAX_ROWS];       // index into pair, or GT_RS_PASS
+};
+hipError_t gt_launch_resample(const ResampleArgs& a, hipStream_t stream);

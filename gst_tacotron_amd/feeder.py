@@ -20,7 +20,8 @@ class Feeder:
 
     @staticmethod
     def _is_mel(item):
-        return not isinstance(item, (str, bytes)) and not hasattr(item, "__fspath__") and np.ndim(item) == 2
+        # (a tuple is a (samples, rate) pair: audio at another rate, for the front end like a path)
+        return not isinstance(item, (str, bytes, tuple)) and not hasattr(item, "__fspath__") and np.ndim(item) == 2
 
     def _from_wavs(self, wav_List, top_db):
         if self.mel_frontend is None:

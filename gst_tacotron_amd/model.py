@@ -37,7 +37,10 @@ PyTorch is used for device memory and streams only.  Differences, all additive:
     (Model.py:210-241), per utterance and per batch (``Loss_Terms`` on the device, ``gst_tacotron_amd.evaluate`` on the host);
     ``Feature_Generate`` is ``Mel_Generate`` with the linear spectrogram target from the same STFT;
   * a free-run metric: ``Mel_DTW`` aligns two mel sequences of different lengths on the device (mel-cepstral distortion along a
-    dynamic-time-warping path) and ``Evaluate_Free`` reports it for a free-running ``Inference_Step`` against its target.
+    dynamic-time-warping path) and ``Evaluate_Free`` reports it for a free-running ``Inference_Step`` against its target;
+  * resampling on the device: reference audio that is not at Sound.Sample_Rate -- a wav path at any rate or a ``(samples, rate)``
+    pair -- is brought there by ``Resample`` (gsttaco_resample: librosa.core.load's 'kaiser_best') inside ``Mel_Generate`` /
+    ``Feature_Generate`` and so behind every method that takes wavs; ``GST_Tacotron(resample="host")`` keeps the NumPy path.
 """
 import ctypes
 import os
@@ -59,9 +62,12 @@ def _ptr(t):
 
 class GST_Tacotron:
     def __init__(self, is_Training=False, hyper_parameters=None, device=None,
-                 max_batch=32, max_tokens=256, max_ref_frames=1025, max_wav_seconds=20.0):
+                 max_batch=32, max_tokens=256, max_ref_frames=1025, max_wav_seconds=20.0, resample="device"):
         if is_Training:
             raise NotImplementedError("only the inference hot path is implemented (training is out of scope)")
+        if resample not in ("device", "host"):
+            raise ValueError("resample must be 'device' (gsttaco_resample) or 'host' (audio.resample_kaiser_best)")
+        self.resample = resample            # where reference audio at another rate is brought to Sound.Sample_Rate (_stage_wavs)
         self.hp_Dict = load_hp(hyper_parameters)
         self.token_Index_Dict = load_token_dict(self.hp_Dict)
         self.dims = Dims(self.hp_Dict, vocab=len(self.token_Index_Dict))
@@ -584,24 +590,79 @@ class GST_Tacotron:
             self.ctx.check(self.ctx.lib.gsttaco_style_compose(self.ctx.handle, _ptr(tw), _ptr(q), B, _ptr(gst), self._stream()))
         return gst
 
-    def Mel_Generate(self, wav_List, top_db=60):
-        """Batched reference Pattern_Generator.Mel_Generate(path, top_db, range_Ignore=True) (Pattern_Generator.py:39-60)
-        on the GPU, already in the mels_for_gst layout of Feeder.py:204-225: returns (mels_for_gst [B, 1+max_len, Mel_Dim]
-        with a zero frame 0 and zero padding, mel_lengths_for_gst [B]) as device tensors.  ``wav_List`` holds wav paths
-        or 1-D float sample arrays at Sound.Sample_Rate.  Works before Restore (no weights involved)."""
-        from .audio import as_signal
-        d = self.dims
-        if not d.audio or not self.ctx.cfg.max_wav_samples:
+    def _require_audio(self):
+        if not self.dims.audio or not self.ctx.cfg.max_wav_samples:
             raise ValueError("the audio front end needs the Sound section of Hyper_Parameters and max_wav_seconds > 0")
         if not torch.cuda.is_available():
             raise capi.GstTacoError(-2, "no HIP device: the gfx950 kernels are the only compute path (no CPU fallback)")
-        sigs = [as_signal(w, d.sample_rate) for w in wav_List]
-        B, ld = len(sigs), max(s.shape[0] for s in sigs)
-        host = np.zeros((B, ld), dtype=np.float32)
+
+    @staticmethod
+    def _pad_rows(sigs):
+        host = np.zeros((len(sigs), max(max(s.shape[0] for s in sigs), 1)), dtype=np.float32)
         for i, s_ in enumerate(sigs):
             host[i, :s_.shape[0]] = s_
-        wav = torch.from_numpy(host).to(self.device)
-        lens = torch.tensor([s_.shape[0] for s_ in sigs], dtype=torch.int32, device=self.device)
+        return host
+
+    def Resample(self, signals, rates, target_rate=None):
+        """Extension: ``librosa.core.load``'s 'kaiser_best' resampling (``audio.resample_kaiser_best``) of a batch of 1-D sample
+        arrays at ``rates`` (one rate, or one per signal) to ``target_rate`` (default Sound.Sample_Rate) on the device
+        (gsttaco_resample) -> (device float32 [B, ld] zero-padded, numpy int32 lengths [B] = ceil(n * ratio)): the padded batch the
+        front end takes.  A row already at the target rate is copied through.  Works before Restore."""
+        self._require_audio()
+        target = int(self.dims.sample_rate if target_rate is None else target_rate)
+        sigs = [np.asarray(s_, dtype=np.float32) for s_ in signals]
+        if not sigs or any(s_.ndim != 1 for s_ in sigs):
+            raise ValueError("signals must be a non-empty list of 1-D sample arrays")
+        rates = np.broadcast_to(np.asarray(rates, dtype=np.int32), (len(sigs),)).copy()
+        return self._resample_rows(sigs, rates, target)
+
+    def _resample_rows(self, sigs, rates, target):
+        from .audio import resample_lengths
+        B = len(sigs)
+        in_len = np.array([s_.shape[0] for s_ in sigs], dtype=np.int32)
+        rates = np.ascontiguousarray(rates, dtype=np.int32)
+        if (rates < 1).any():
+            raise ValueError("a sample rate is not positive")
+        ld_out = max(max(resample_lengths(int(n), int(r), target)[1] for n, r in zip(in_len, rates)), 1)
+        x = torch.from_numpy(self._pad_rows(sigs)).to(self.device)
+        y = torch.empty((B, ld_out), dtype=torch.float32, device=self.device)
+        out_len = np.zeros((B,), dtype=np.int32)
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        with torch.cuda.device(self.device):
+            self.ctx.check(self.ctx.lib.gsttaco_resample(
+                self.ctx.handle, _ptr(x), in_len.ctypes.data_as(i32p), rates.ctypes.data_as(i32p), B, x.shape[1], target, _ptr(y), ld_out,
+                out_len.ctypes.data_as(i32p), self._stream()))
+        return y, out_len
+
+    def _stage_wavs(self, wav_List):
+        """What both generators feed the front end: (device float32 [B, ld] zero-padded signals at Sound.Sample_Rate, device int32
+        lengths [B], B, ld).  An item is a wav path (at any rate), a 1-D sample array already at Sound.Sample_Rate, or a
+        ``(samples, rate)`` pair.  Audio at another rate is resampled on the device (``Resample``) and stays there, or with
+        ``resample="host"`` by ``audio.resample_kaiser_best`` before the upload; when every item is at the rate already, neither runs."""
+        from .audio import as_signal_at_rate, resample_kaiser_best
+        self._require_audio()
+        target = self.dims.sample_rate
+        pairs = [as_signal_at_rate(w, target) for w in wav_List]
+        sigs, rates = [p[0] for p in pairs], np.array([p[1] for p in pairs], dtype=np.int32)
+        if self.resample == "host":
+            sigs = [s_ if r == target else resample_kaiser_best(s_, int(r), target) for s_, r in zip(sigs, rates)]
+            rates[:] = target
+        if (rates == target).all():
+            wav = torch.from_numpy(self._pad_rows(sigs)).to(self.device)
+            lens = torch.tensor([s_.shape[0] for s_ in sigs], dtype=torch.int32, device=self.device)
+        else:
+            wav, out_len = self._resample_rows(sigs, rates, target)
+            lens = torch.from_numpy(out_len).to(self.device)
+        return wav, lens, wav.shape[0], wav.shape[1]
+
+    def Mel_Generate(self, wav_List, top_db=60):
+        """Batched reference Pattern_Generator.Mel_Generate(path, top_db, range_Ignore=True) (Pattern_Generator.py:39-60)
+        on the GPU, already in the mels_for_gst layout of Feeder.py:204-225: returns (mels_for_gst [B, 1+max_len, Mel_Dim]
+        with a zero frame 0 and zero padding, mel_lengths_for_gst [B]) as device tensors.  ``wav_List`` holds wav paths (at any
+        rate), 1-D float sample arrays at Sound.Sample_Rate, or ``(samples, rate)`` pairs; audio at another rate is resampled on
+        the device (``Resample``) unless the model was built with ``resample="host"``.  Works before Restore (no weights involved)."""
+        d = self.dims
+        wav, lens, B, ld = self._stage_wavs(wav_List)
         cap = 2 + ld // d.frame_shift
         mels = torch.empty((B, cap, d.mel), dtype=torch.float32, device=self.device)
         mel_len = torch.empty((B,), dtype=torch.int32, device=self.device)
@@ -619,19 +680,8 @@ class GST_Tacotron:
         Pattern_Generator.Spectrogram_Generate / Audio.spectrogram, Audio.py:18-21: what Train_Step compares the vocoder's output
         with) -> (mels [B, 1+max_len, Mel_Dim], spectrograms [B, 1+max_len, Spectrogram_Dim], lengths [B]) as device tensors, both
         with a zero frame 0 and zero padding.  ``mels`` is bitwise ``Mel_Generate``'s.  Works before Restore."""
-        from .audio import as_signal
         d = self.dims
-        if not d.audio or not self.ctx.cfg.max_wav_samples:
-            raise ValueError("the audio front end needs the Sound section of Hyper_Parameters and max_wav_seconds > 0")
-        if not torch.cuda.is_available():
-            raise capi.GstTacoError(-2, "no HIP device: the gfx950 kernels are the only compute path (no CPU fallback)")
-        sigs = [as_signal(w, d.sample_rate) for w in wav_List]
-        B, ld = len(sigs), max(s.shape[0] for s in sigs)
-        host = np.zeros((B, ld), dtype=np.float32)
-        for i, s_ in enumerate(sigs):
-            host[i, :s_.shape[0]] = s_
-        wav = torch.from_numpy(host).to(self.device)
-        lens = torch.tensor([s_.shape[0] for s_ in sigs], dtype=torch.int32, device=self.device)
+        wav, lens, B, ld = self._stage_wavs(wav_List)
         cap = 2 + ld // d.frame_shift
         mels = torch.empty((B, cap, d.mel), dtype=torch.float32, device=self.device)
         specs = torch.empty((B, cap, d.spec), dtype=torch.float32, device=self.device)

@@ -31,6 +31,8 @@
  *                          utterance on the device, and the mel plus the linear spectrogram target (Audio.py:18-21) from one STFT
  *   gsttaco_mel_dtw     <- EXTENSION (DESIGN row A18): the free-run metric, mel-cepstral distortion along a dynamic-time-warping path
  *                          between synthesised and reference mels of different lengths, per utterance on the device
+ *   gsttaco_resample    <- EXTENSION (DESIGN row A19): librosa.core.load's 'kaiser_best' resampling of reference audio at another rate
+ *                          (Pattern_Generator.py:40-43), batched on the device ahead of gsttaco_mel_frontend
  *   gsttaco_postnet     <- Modules/Taco2.py:131-149, 230
  *   gsttaco_vocoder     <- Modules/Taco2.py:234-260 Vocoder_Taco1.call, CBHG :285-380
  *   gsttaco_mel_frontend <- Pattern_Generator.py:39-60 Mel_Generate + Audio.py:29-32,49-55,70-96 melspectrogram
@@ -232,8 +234,9 @@ int gsttaco_vocoder(gsttaco_ctx* ctx, const float* mel, int B, int T, float* spe
  * (Pattern_Generator.py:39-60; top_db is 60 for one reference wav and 15 for several, Feeder.py:204-209, and 60 in
  * Get_Inference_GST_Pattern, Feeder.py:232), stacked as Feeder does: frame 0 of every utterance is zero, frames
  * 1..mel_lengths[b] hold the mel, the rest is zero padding.
- * wav          : [B, ld_wav] float32 samples in [-1,1) at Sound.Sample_Rate (librosa.load's output; resampling is the
- *                caller's job), wav_lengths [B] valid samples (17 <= length <= max_wav_samples)
+ * wav          : [B, ld_wav] float32 samples in [-1,1) at Sound.Sample_Rate (librosa.load's output; gsttaco_resample below brings
+ *                audio at another rate there on the device, in this layout), wav_lengths [B] valid samples
+ *                (17 <= length <= max_wav_samples)
  * mels_for_gst : [B, cap_frames, mel_dim] with cap_frames >= 2 + ld_wav / frame_shift
  * mel_lengths  : [B] int32, frames EXCLUDING the prepended one; 0 when the trimmed signal is shorter than n_fft/2+1
  *                samples (librosa.stft raises there) */
@@ -251,6 +254,35 @@ int gsttaco_mel_frontend(gsttaco_ctx* ctx, const float* wav, const int32_t* wav_
  * GSTTACO_E_INVALID when both outputs are NULL, otherwise as gsttaco_mel_frontend. */
 int gsttaco_feature_frontend(gsttaco_ctx* ctx, const float* wav, const int32_t* wav_lengths, int B, int ld_wav, float top_db,
                              float* mels, float* spectrograms, int32_t* lengths, int cap_frames, void* stream);
+
+/* EXTENSION (DESIGN row A19): the resampling of librosa.core.load(path, sr) on the device -- resampy.resample(x, sr_in, sr_out,
+ * filter='kaiser_best') followed by fix_length to ceil(n * ratio) samples (Pattern_Generator.py:40-43 on a file that is not at
+ * Sound.Sample_Rate) -- for a batch of rows at possibly different rates.  Needs cfg.max_wav_samples > 0, no weights.
+ *   x           : [B, ld_in] float32, DEVICE; row b holds in_lengths[b] samples at sr_in[b]
+ *   in_lengths, sr_in : [B] int32, HOST.  The launch geometry and the tables depend on them, and a caller has them on the host anyway
+ *                 (it read them from the files' headers); they are read before the call returns.
+ *   y           : [B, ld_out] float32, DEVICE.  Row b: samples [0, int(n * ratio)) are computed, [int(n * ratio), ld_out) are 0.0 --
+ *                 so y with out_lengths is the padded batch gsttaco_mel_frontend takes.  Nothing else is written.
+ *   out_lengths : [B] int32, HOST, filled on return (it depends on no device work): ceil(in_lengths[b] * ratio_b) in double with
+ *                 ratio_b = (double)sr_out / (double)sr_in[b], at most one more than the computed samples (fix_length's zero)
+ * Algorithm (resampy core.py / interpn.py, gst_tacotron_amd/audio.py resample_kaiser_best): band-limited sinc interpolation with the
+ * published kaiser_best table -- 64 zero crossings, 512 entries per crossing, beta 14.769656459379492, roll-off 0.9475937167399596,
+ * 32 769 float64 entries, built by the library (Kaiser window by the power series of I0), times ratio when ratio < 1 -- linearly
+ * interpolated between entries; scale = min(1, ratio), table step int(scale * 512), both wings' tap counts clipped at the signal's ends.
+ * The time register of output t is the float64 sum of t additions of 1 / ratio, as resampy accumulates it -- NOT t / ratio: the
+ * truncated step makes the interpolation discontinuous where the register crosses an integer, and the accumulated value often lies one
+ * rounding below.  One array per rate pair serves every row.  Each output is summed in double in one fixed order (left wing tap 0
+ * upward, then right wing tap 0 upward) and rounded to float32 once, so a row is bitwise the same in whatever batch it runs; a row
+ * with sr_in[b] == sr_out is copied through bitwise.
+ * Tables: per context, keyed by (sr_in, sr_out), built on the host and uploaded on `stream` by the first call that needs the pair (the
+ * register to max_wav_samples entries + 512 KiB); the cache holds eight pairs and evicts the least recently used.  One launch per 256
+ * rows on `stream`; the per-row parameters travel in the kernel arguments, so calls may follow each other on a stream without
+ * synchronisation.
+ * GSTTACO_E_INVALID, before anything is enqueued or written: a NULL pointer; B, ld_in, ld_out or a rate < 1; an in_lengths[b] outside
+ * [0, ld_in]; sr_in[b] > 16 sr_out or sr_out > 16 sr_in[b]; an out_lengths[b] above ld_out; more than eight distinct pairs
+ * (sr_in[b] != sr_out) in one call.  GSTTACO_E_CAPACITY: B > max_batch, ld_out > max_wav_samples. */
+int gsttaco_resample(gsttaco_ctx* ctx, const float* x, const int32_t* in_lengths, const int32_t* sr_in, int B, int ld_in, int sr_out,
+                     float* y, int ld_out, int32_t* out_lengths, void* stream);
 
 /* spectrogram -> waveform: Audio.inv_spectrogram (reference Audio.py:23-27) = symmetric de-normalisation (max_abs_mel,
  * or the [0,1] one when it is 0), + ref_level_db, dB -> amplitude, ^power, `iters` Griffin-Lim iterations
