@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = (
     "gsttaco_decode_plan_fields",
     "gsttaco_mel_dtw",
     "gsttaco_resample",
+    "gsttaco_pitch", "gsttaco_pitch_errors",
 )
 # GSTTACO_PLAN_*: the fields gsttaco_decode_plan_fields fills, in order
 PLAN_FIELDS = ("persist", "persist_bf16", "fused", "lean_front", "lean_rec", "z0", "fuse12", "lean_x0", "lean_x1", "co_tiles", "lean_proj",
@@ -162,6 +163,11 @@ def load_library(path=None):
     i32p = ctypes.POINTER(ctypes.c_int32)       # (host arrays)
     lib.gsttaco_resample.argtypes = [vp, vp, i32p, i32p, i32, i32, i32, vp, i32, i32p, vp]
     lib.gsttaco_resample.restype = ctypes.c_int
+    f32 = ctypes.c_float
+    lib.gsttaco_pitch.argtypes = [vp, vp, vp, i32, i32, f32, f32, f32, f32, i32, vp, vp, vp, i32, vp]
+    lib.gsttaco_pitch.restype = ctypes.c_int
+    lib.gsttaco_pitch_errors.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, f32, vp, vp, vp]
+    lib.gsttaco_pitch_errors.restype = ctypes.c_int
     lib.gsttaco_postnet.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.gsttaco_vocoder.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.gsttaco_inference_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]

@@ -177,10 +177,17 @@ __global__ __launch_bounds__(256) void gt_stft_mel_kernel(AudioFrontArgs P) {
     }
 }
 
-hipError_t gt_launch_audio_front(const AudioFrontArgs& a, hipStream_t s) {
+// The trim decision alone: bounds [B, 2] and mel_len [B].  gsttaco_pitch cuts its rows with it, so both entries decide by one code.
+hipError_t gt_launch_trim_bounds(const AudioFrontArgs& a, hipStream_t s) {
     const int max_rms = a.ld_wav / a.trim_hop + 1;
     hipLaunchKernelGGL(gt_preemph_rms_kernel, dim3((max_rms + 255) / 256, a.B), dim3(256), 0, s, a);
     hipLaunchKernelGGL(gt_trim_bounds_kernel, dim3(a.B), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t gt_launch_audio_front(const AudioFrontArgs& a, hipStream_t s) {
+    const hipError_t e = gt_launch_trim_bounds(a, s);
+    if (e != hipSuccess) return e;
     const int H = a.n_fft / 2;
     const size_t lds = (size_t)H * sizeof(float2) + (size_t)(H + 1) * sizeof(float);
     hipLaunchKernelGGL(gt_stft_mel_kernel, dim3(a.cap_frames, a.B), dim3(256), lds, s, a);

@@ -3023,6 +3023,67 @@ int gsttaco_mel_frontend(gsttaco_ctx* c, const float* wav, const int32_t* wav_le
     return gsttaco_feature_frontend(c, wav, wav_lengths, B, ld_wav, top_db, mels_for_gst, nullptr, mel_lengths, cap_frames, stream);
 }
 
+// wav -> F0 and aperiodicity per frame of the front end's grid (YIN).  With top_db >= 0 the front end's two trim launches run first and
+// the tracker reads the bounds they leave; everything is validated before anything is enqueued.
+int gsttaco_pitch(gsttaco_ctx* c, const float* wav, const int32_t* wav_lengths, int B, int ld_wav, float top_db, float fmin, float fmax,
+                  float threshold, int window, float* f0, float* aperiodicity, int32_t* frames, int cap_frames, void* stream) {
+    if (!c) return GSTTACO_E_INVALID;
+    int rc = ensure_audio(c);
+    if (rc) return rc;
+    const gsttaco_config& g = c->cfg;
+    if (!wav || !wav_lengths || !f0 || !frames) return fail(c, GSTTACO_E_INVALID, "null argument");
+    if (B < 1 || ld_wav < 1 || cap_frames < 1 || top_db != top_db) return fail(c, GSTTACO_E_INVALID, "bad B / ld_wav / cap_frames / top_db");
+    if (!(fmin > 0.f) || !(fmax > fmin)) return fail(c, GSTTACO_E_INVALID, "the F0 range needs 0 < fmin < fmax");
+    if (!(threshold > 0.f) || !(threshold <= 1.f)) return fail(c, GSTTACO_E_INVALID, "threshold must be in (0, 1]");
+    if (window < 0) return fail(c, GSTTACO_E_INVALID, "window must be >= 0 (0 = 25 ms)");
+    const double sr = (double)g.sample_rate;
+    const double lag_lo = std::floor(sr / (double)fmax), lag_hi = std::ceil(sr / (double)fmin);
+    if (lag_lo < 2.0) return fail(c, GSTTACO_E_INVALID, "fmax is above Sample_Rate / 2 (tau_min = floor(Sample_Rate / fmax) must be >= 2)");
+    if (lag_lo >= lag_hi) return fail(c, GSTTACO_E_INVALID, "the lag range is empty (tau_min >= tau_max)");
+    const int64_t W = window ? (int64_t)window : (int64_t)std::llround(0.025 * sr);
+    if (W < 1 || (double)W + lag_hi > (double)GT_PITCH_MAX_SPAN)
+        return fail(c, GSTTACO_E_INVALID, "window + tau_max exceeds the 3072 samples one workgroup's LDS holds");
+    if (B > g.max_batch || ld_wav > g.max_wav_samples) return fail(c, GSTTACO_E_CAPACITY, "batch / samples exceed capacity");
+    hipStream_t s = (hipStream_t)stream;
+    PitchArgs p{};
+    if (top_db >= 0.f) {                                // the trim decision of gsttaco_feature_frontend: its kernels, its arguments
+        AudioFrontArgs a{};
+        a.wav = wav; a.wav_len = wav_lengths; a.mse = c->a_mse; a.bounds = c->a_bounds;
+        a.mel_len = frames;                             // (unclipped here; the tracker writes the count again, clipped to cap_frames)
+        a.B = B; a.ld_wav = ld_wav; a.ld_mse = c->a_ld_mse; a.cap_frames = INT_MAX;
+        a.n_fft = c->n_fft; a.hop = g.frame_shift;
+        a.trim_frame = 32; a.trim_hop = 16; a.preemph = 0.97f; a.top_db = top_db;
+        HIPCHECK(c, gt_launch_trim_bounds(a, s));
+        p.bounds = c->a_bounds;
+    }
+    p.wav = wav; p.wav_len = wav_lengths; p.f0 = f0; p.aperiodicity = aperiodicity; p.frames = frames;
+    p.sr = sr; p.threshold = (double)threshold;
+    p.B = B; p.ld_wav = ld_wav; p.cap_frames = cap_frames; p.n_fft = c->n_fft; p.hop = g.frame_shift;
+    p.W = (int)W; p.tau_min = (int)lag_lo; p.tau_max = (int)lag_hi;
+    HIPCHECK(c, gt_launch_pitch(p, s));
+    return 0;
+}
+
+// The pitch errors of two F0 tracks along a path: one launch on the caller's stream.  Needs a created context only.
+int gsttaco_pitch_errors(gsttaco_ctx* c, const float* f0_x, const int32_t* x_len, int Tx, const float* f0_y, const int32_t* y_len, int Ty,
+                         const int32_t* path, const int32_t* path_len, int path_cap, int B, float gross, int32_t* counts, double* sums,
+                         void* stream) {
+    if (!c) return GSTTACO_E_INVALID;
+    if (!f0_x || !f0_y || !counts || !sums) return fail(c, GSTTACO_E_INVALID, "null argument");
+    if (path && !path_len) return fail(c, GSTTACO_E_INVALID, "a path needs its path_len");
+    if (B < 1 || Tx < 1 || Ty < 1 || (path && path_cap < 1)) return fail(c, GSTTACO_E_INVALID, "bad B / Tx / Ty / path_cap");
+    if (!(gross >= 0.f)) return fail(c, GSTTACO_E_INVALID, "gross must be >= 0");
+    if (B > c->cfg.max_batch) return fail(c, GSTTACO_E_CAPACITY, "batch exceeds the capacity given at create");
+    int rc = ensure_device(c);
+    if (rc) return rc;
+    PitchErrorArgs a{};
+    a.f0_x = f0_x; a.f0_y = f0_y; a.x_len = x_len; a.y_len = y_len; a.path = path; a.path_len = path_len;
+    a.counts = counts; a.sums = sums; a.gross = (double)gross;
+    a.B = B; a.Tx = Tx; a.Ty = Ty; a.path_cap = path_cap;
+    HIPCHECK(c, gt_launch_pitch_errors(a, (hipStream_t)stream));
+    return 0;
+}
+
 int gsttaco_griffin_lim(gsttaco_ctx* c, const float* spectrogram, const int32_t* frames, int B, int T, int iters,
                         float power, float ref_level_db, const float* init_phase, uint64_t seed,
                         float* wav, int32_t* wav_lengths, int ld_wav, void* stream) {

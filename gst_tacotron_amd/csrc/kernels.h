@@ -578,3 +578,36 @@ struct ResampleArgs {
     uint8_t slot[GT_RS_MAX_ROWS];       // index into pair, or GT_RS_PASS
 };
 hipError_t gt_launch_resample(const ResampleArgs& a, hipStream_t stream);
+
+
+// ---------------------------------------------------------------- pitch.hip
+// F0 by YIN on the mel front end's frame grid, and the pitch errors of two F0 tracks along a path (the contracts: gsttaco_pitch and
+// gsttaco_pitch_errors in include/gsttaco.h).  The trim of gsttaco_pitch is the front end's: gt_launch_trim_bounds (audio.hip) runs
+// ahead of gt_launch_pitch and leaves the bounds it reads.
+#define GT_PITCH_MAX_SPAN 3072              // W + tau_max: 4 bytes per sample and 16 per lag (tau_max + 1 <= span) stay within 64 KiB of LDS
+struct PitchArgs {
+    const float* wav;           // [B, ld_wav]
+    const int32_t* wav_len;     // [B]
+    const int32_t* bounds;      // [B, 2] (start, length) as gt_trim_bounds_kernel left them, or NULL = (0, wav_len[b]): no trim
+    float* f0;                  // [B, cap_frames] Hz, 0 = unvoiced
+    float* aperiodicity;        // [B, cap_frames], or NULL
+    int32_t* frames;            // [B]
+    double sr, threshold;
+    int B, ld_wav, cap_frames, n_fft, hop, W, tau_min, tau_max;
+};
+hipError_t gt_launch_trim_bounds(const AudioFrontArgs& a, hipStream_t stream);      // audio.hip: the front end's first two launches
+hipError_t gt_launch_pitch(const PitchArgs& a, hipStream_t stream);
+
+struct PitchErrorArgs {
+    const float* f0_x;          // [B, Tx] synthesised
+    const float* f0_y;          // [B, Ty] reference
+    const int32_t* x_len;       // [B], or NULL (= Tx); clipped to [0, Tx]
+    const int32_t* y_len;       // [B], or NULL (= Ty); clipped to [0, Ty]
+    const int32_t* path;        // [B, path_cap, 2] cells (i, j), or NULL = (i, i) for i < min(Lx, Ly)
+    const int32_t* path_len;    // [B] (with path); clipped to [0, path_cap]
+    int32_t* counts;            // [B][6]
+    double* sums;               // [B][2]
+    double gross;
+    int B, Tx, Ty, path_cap;
+};
+hipError_t gt_launch_pitch_errors(const PitchErrorArgs& a, hipStream_t stream);

@@ -114,3 +114,45 @@ def summarize_free(per_utterance):
     per = np.asarray(per_utterance, np.float64)
     n = per[:, 2].sum()
     return {"mcd": float(per[:, 0].mean()), "mcd_frames": float(per[:, 1].sum() / n) if n > 0 else 0.0}
+
+
+# ---------------------------------------------------------------------------------------------------- the prosody metrics (Evaluate_Free(pitch=True))
+# Host side of ``GST_Tacotron.Pitch_Errors``: how the per-utterance counts and sums of ``gsttaco_pitch_errors`` (include/gsttaco.h) become
+# the triple the prosody-transfer literature reports beside MCD-DTW.
+PITCH_COUNTS = ("pairs", "both_voiced", "gross", "voicing", "x_voiced", "y_voiced")
+PITCH_FIELDS = ("gpe", "vde", "ffe", "f0_mae_cents", "f0_rmse_cents", "pairs", "both_voiced", "voiced_ratio")
+
+
+def _ratio(num, den):
+    """num / den element by element; a zero denominator gives 0, not NaN."""
+    num, den = np.asarray(num, np.float64), np.asarray(den, np.float64)
+    return np.where(den > 0, num / np.where(den > 0, den, 1.0), 0.0)
+
+
+def combine_pitch(counts, sums):
+    """float64 [B, len(PITCH_FIELDS)] from ``counts`` [B, 6] (``PITCH_COUNTS``) and ``sums`` [B, 2] (sum |c|, sum c^2 of the cents over
+    the both-voiced, non-gross cells): gpe = gross / both_voiced (gross pitch error), vde = voicing / pairs (voicing decision error),
+    ffe = (gross + voicing) / pairs (F0 frame error), f0_mae_cents = sum |c| / (both_voiced - gross), f0_rmse_cents =
+    sqrt(sum c^2 / (both_voiced - gross)), voiced_ratio = x_voiced / y_voiced.  A zero denominator gives 0, not NaN."""
+    counts, sums = np.asarray(counts, np.float64), np.asarray(sums, np.float64)
+    if counts.ndim != 2 or counts.shape[1] != len(PITCH_COUNTS) or counts.shape[0] < 1 or sums.shape != (counts.shape[0], 2):
+        raise ValueError("counts must be [batch, {}] and sums [batch, 2]".format(len(PITCH_COUNTS)))
+    pairs, both, gross, voicing, xv, yv = (counts[:, k] for k in range(6))
+    fine = both - gross
+    out = np.zeros((counts.shape[0], len(PITCH_FIELDS)), np.float64)
+    out[:, 0], out[:, 1], out[:, 2] = _ratio(gross, both), _ratio(voicing, pairs), _ratio(gross + voicing, pairs)
+    out[:, 3], out[:, 4] = _ratio(sums[:, 0], fine), np.sqrt(_ratio(sums[:, 1], fine))
+    out[:, 5], out[:, 6], out[:, 7] = pairs, both, _ratio(xv, yv)
+    return out
+
+
+def summarize_pitch(counts, sums):
+    """{gpe, vde, ffe: the means over utterances of ``combine_pitch``'s columns; gpe_frames, vde_frames, ffe_frames: the same ratios of the
+    counts summed over the batch (0 for an empty sum)} -- as ``summarize_free`` gives both the mean and the pooled figure."""
+    per = combine_pitch(counts, sums)
+    tot = np.asarray(counts, np.float64).sum(axis=0)
+    out = {k: float(per[:, i].mean()) for i, k in enumerate(("gpe", "vde", "ffe"))}
+    out["gpe_frames"] = float(_ratio(tot[2], tot[1]))
+    out["vde_frames"] = float(_ratio(tot[3], tot[0]))
+    out["ffe_frames"] = float(_ratio(tot[2] + tot[3], tot[0]))
+    return out

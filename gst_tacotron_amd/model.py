@@ -41,6 +41,9 @@ PyTorch is used for device memory and streams only.  Differences, all additive:
   * resampling on the device: reference audio that is not at Sound.Sample_Rate -- a wav path at any rate or a ``(samples, rate)``
     pair -- is brought there by ``Resample`` (gsttaco_resample: librosa.core.load's 'kaiser_best') inside ``Mel_Generate`` /
     ``Feature_Generate`` and so behind every method that takes wavs; ``GST_Tacotron(resample="host")`` keeps the NumPy path.
+  * prosody metrics: ``Pitch`` / ``Pitch_Signals`` track F0 by YIN on the mel front end's frame grid (gsttaco_pitch), ``Pitch_Errors``
+    counts gross pitch, voicing decision and F0 frame errors of two tracks along a DTW path (gsttaco_pitch_errors), and
+    ``Evaluate_Free(..., pitch=True)`` reports them beside the MCD -- on the Griffin-Lim waveform of the vocoder's spectrogram.
 """
 import ctypes
 import os
@@ -485,7 +488,7 @@ class GST_Tacotron:
         return (cost, plen, path) if return_path else (cost, plen)
 
     def Evaluate_Free(self, sentence_List, mel_or_wav_List, wav_List_for_GST=None, style_embeddings=None, seeds=None, n_ceps=13,
-                      **kwargs):
+                      pitch=False, **kwargs):
         """Extension: the free-run metric of this checkpoint on the given sentences and targets -- what ``Evaluate`` cannot give, because
         the free-running decoder's output has another length than its target: one ``Inference_Step`` (not teacher-forced),
         ``Utterance_Report`` for the frames each utterance used, and ``Mel_DTW`` of those frames against the target's.
@@ -496,7 +499,17 @@ class GST_Tacotron:
         Nothing is read back before the final result.  Returns a dict: ``mcd`` (the mean over utterances of cost / path_len, dB),
         ``mcd_frames`` (sum cost / sum path_len), ``per_utterance`` (numpy float64 [B, 7], ``evaluate.FREE_FIELDS``), ``report`` (numpy
         int32 [B, 8], ``REPORT_FIELDS``), ``mel_lengths`` / ``ref_lengths`` (numpy int32 [B]), and the device tensors ``mels``
-        [B, S * r, Mel_Dim] and ``ref_mels`` [B, T, Mel_Dim] the distance was taken between."""
+        [B, S * r, Mel_Dim] and ``ref_mels`` [B, T, Mel_Dim] the distance was taken between.
+        ``pitch=True`` (or a dict of the tracker's ``fmin`` / ``fmax`` / ``threshold`` / ``window``, applied to both sides, in place
+        of ``Pitch``'s defaults) adds the prosody metrics (the targets must then be wavs): the targets are staged once and both their mel and
+        their F0 (``Pitch_Signals`` at the same top_db 15) come from that batch; the step also runs the vocoder, ``Inv_Spectrogram``
+        turns the report's ``frames`` of its spectrogram into a waveform (Griffin-Lim under the seed ``seeds[0]`` / ``seed`` / the
+        model's counter plus 0x9E3779B97F4A7C15, mod 2^64), ``Pitch_Signals`` tracks it untrimmed, and ``Pitch_Errors`` compares the two
+        tracks along the DTW path.  The synthesised side's F0 is therefore that of the Griffin-Lim waveform of the vocoder's
+        spectrogram: comparable between checkpoints and styles of one configuration, not with figures taken off another vocoder.  The
+        result gains ``gpe``, ``vde``, ``ffe`` (means over utterances) and ``gpe_frames`` / ``vde_frames`` / ``ffe_frames`` (of the
+        pooled counts; ``evaluate.summarize_pitch``), ``pitch_per_utterance`` (numpy float64 [B, 8], ``evaluate.PITCH_FIELDS``) and the
+        device tensors ``f0`` [B, S * r] and ``ref_f0`` [B, >= T].  Without the flag nothing of this runs."""
         print("Free-run evaluation running...")
         for k in ("teacher_mels", "return_pre_mel", "with_vocoder", "mels_for_gst", "mel_lengths_for_gst"):
             if k in kwargs:
@@ -506,7 +519,21 @@ class GST_Tacotron:
         targets = list(mel_or_wav_List)
         if len(targets) != len(sentence_List):
             raise ValueError("mel_or_wav_List must hold one target per sentence")
-        if all(self.feeder._is_mel(m) for m in targets):
+        track = dict(pitch) if isinstance(pitch, dict) else {}
+        pitch = bool(pitch) or isinstance(pitch, dict)
+        if pitch:
+            if any(k not in ("fmin", "fmax", "threshold", "window") for k in track):
+                raise ValueError("pitch takes True or a dict of fmin / fmax / threshold / window")
+            if any(self.feeder._is_mel(m) for m in targets):
+                raise ValueError("pitch=True needs wav targets: a mel does not carry its F0")
+            if not self.dims.vocoder:
+                raise ValueError("pitch=True needs the vocoder: Hyper_Parameters has no Vocoder_Taco1 section")
+            base = seeds[0] if seeds is not None else kwargs["seed"] if kwargs.get("seed") is not None else self.seed + 1
+            gl_seed = (int(base) + 0x9E3779B97F4A7C15) & checked.MASK64
+            staged = self._stage_wavs(targets)
+            ref_all, ref_len = self._mel_of_staged(*staged, 15)
+            ref_f0, _, ref_f0_len = self.Pitch_Signals(staged[0], staged[1], 15, **track)
+        elif all(self.feeder._is_mel(m) for m in targets):
             ref = self.feeder.Get_Inference_GST_Pattern(targets)
             ref_all, ref_len = self._dev(ref["mels_for_gst"], torch.float32), self._dev(ref["mel_lengths_for_gst"], torch.int32)
         else:
@@ -521,16 +548,26 @@ class GST_Tacotron:
                 pattern.update(self.feeder.Get_Inference_GST_Pattern(list(wav_List_for_GST)))
             else:
                 pattern["mels_for_gst"], pattern["mel_lengths_for_gst"] = ref_all, ref_len
-        mel, stop, _, align = self.Inference_Step(**pattern, **kwargs)
+        mel, stop, spec, align = self.Inference_Step(**pattern, with_vocoder=pitch, **kwargs)
         report, _ = self.Utterance_Report(stop, align, pattern["token_lengths"] if kwargs.get("masked") else None, mel)
         frames = report[:, REPORT_FIELDS.index("frames")].contiguous()
         ref_mels = ref_all[:, 1:]                                   # (behind the prepended zero frame: a view, no copy)
-        cost, plen = self.Mel_DTW(mel, frames, ref_mels, ref_len, n_ceps=n_ceps)
+        if pitch:
+            syn_wav, syn_len = self.Inv_Spectrogram(spec, frames=frames, seed=gl_seed)
+            f0, _, f0_len = self.Pitch_Signals(syn_wav, syn_len, **track)
+            cost, plen, path = self.Mel_DTW(mel, frames, ref_mels, ref_len, n_ceps=n_ceps, return_path=True)
+            counts, sums = self.Pitch_Errors(f0, f0_len, ref_f0, ref_f0_len, path, plen)
+        else:
+            cost, plen = self.Mel_DTW(mel, frames, ref_mels, ref_len, n_ceps=n_ceps)
         self.synchronize()
         rep, ref_lengths = report.cpu().numpy(), ref_len.cpu().numpy()
         per = evaluate.combine_free(cost.cpu().numpy(), plen.cpu().numpy(), rep[:, 1], ref_lengths, rep[:, 0], int(stop.shape[1]))
         result = evaluate.summarize_free(per)
         result.update(per_utterance=per, report=rep, mel_lengths=rep[:, 1].copy(), ref_lengths=ref_lengths, mels=mel, ref_mels=ref_mels)
+        if pitch:
+            counts, sums = counts.cpu().numpy(), sums.cpu().numpy()
+            result.update(evaluate.summarize_pitch(counts, sums))
+            result.update(pitch_per_utterance=evaluate.combine_pitch(counts, sums), f0=f0, ref_f0=ref_f0)
         return result
 
     def Inference_GST(self, wav_List, tag_List=None, label=None):
@@ -661,8 +698,11 @@ class GST_Tacotron:
         with a zero frame 0 and zero padding, mel_lengths_for_gst [B]) as device tensors.  ``wav_List`` holds wav paths (at any
         rate), 1-D float sample arrays at Sound.Sample_Rate, or ``(samples, rate)`` pairs; audio at another rate is resampled on
         the device (``Resample``) unless the model was built with ``resample="host"``.  Works before Restore (no weights involved)."""
+        return self._mel_of_staged(*self._stage_wavs(wav_List), top_db)
+
+    def _mel_of_staged(self, wav, lens, B, ld, top_db):
+        """``Mel_Generate`` of a batch ``_stage_wavs`` has staged (``Evaluate_Free(pitch=True)`` reads the target F0 off the same batch)."""
         d = self.dims
-        wav, lens, B, ld = self._stage_wavs(wav_List)
         cap = 2 + ld // d.frame_shift
         mels = torch.empty((B, cap, d.mel), dtype=torch.float32, device=self.device)
         mel_len = torch.empty((B,), dtype=torch.int32, device=self.device)
@@ -674,6 +714,69 @@ class GST_Tacotron:
         if int(mel_len.min().item()) < 1:
             raise ValueError("a reference wav is shorter than n_fft/2 samples after trimming (librosa.stft raises there)")
         return mels[:, :n + 1].contiguous(), mel_len
+
+    def Pitch(self, wav_List, top_db=None, fmin=50.0, fmax=500.0, threshold=0.1, window=0):
+        """Extension: F0 by YIN (``gsttaco_pitch``) of what ``Mel_Generate`` takes -- wav paths at any rate, 1-D sample arrays at
+        Sound.Sample_Rate or ``(samples, rate)`` pairs, staged like there, so other-rate audio is resampled on the device -- on the mel
+        front end's frame grid.  ``top_db``: None = no trim; a number = the rows are first cut as ``Mel_Generate(wav_List, top_db)``
+        cuts them, and frame t is then frame t of that mel.  Returns (f0 float32 [B, n] in Hz with 0 = unvoiced, aperiodicity float32
+        [B, n], frames int32 [B]) as device tensors, cut to the longest row's n frames (one host sync, like ``Mel_Generate``).
+        ``fmin`` / ``fmax`` bound the search (lags floor(sr / fmax) .. ceil(sr / fmin)), ``threshold`` is YIN's on the cumulative mean
+        normalised difference, ``window`` the integration window in samples (0: 25 ms).  Works before Restore."""
+        wav, lens, _, _ = self._stage_wavs(wav_List)
+        f0, ap, frames = self.Pitch_Signals(wav, lens, top_db, fmin, fmax, threshold, window)
+        n = max(int(frames.max().item()), 1)
+        return f0[:, :n].contiguous(), ap[:, :n].contiguous(), frames
+
+    def Pitch_Signals(self, wav, wav_lengths, top_db=None, fmin=50.0, fmax=500.0, threshold=0.1, window=0):
+        """Extension: ``Pitch`` of a batch that is on the device already -- ``wav`` float32 [B, ld] at Sound.Sample_Rate with
+        ``wav_lengths`` [B], such as ``Inv_Spectrogram`` returns (whose row of k frames gives k F0 frames).  Nothing is read back:
+        returns (f0 [B, 1 + ld // Frame_Shift], aperiodicity likewise, frames int32 [B]) uncut; entries beyond a row's frames are 0."""
+        self._require_audio()
+        d = self.dims
+        wav, lens = self._dev(wav, torch.float32), self._dev(wav_lengths, torch.int32)
+        if wav.dim() != 2 or wav.shape[0] < 1 or wav.shape[1] < 1 or tuple(lens.shape) != (wav.shape[0],):
+            raise ValueError("wav must be [batch, samples] with wav_lengths [batch]")
+        B, ld = int(wav.shape[0]), int(wav.shape[1])
+        cap = 1 + ld // d.frame_shift
+        f0 = torch.empty((B, cap), dtype=torch.float32, device=self.device)
+        ap = torch.empty((B, cap), dtype=torch.float32, device=self.device)
+        frames = torch.empty((B,), dtype=torch.int32, device=self.device)
+        cf = ctypes.c_float
+        with torch.cuda.device(self.device):
+            self.ctx.check(self.ctx.lib.gsttaco_pitch(
+                self.ctx.handle, _ptr(wav), _ptr(lens), B, ld, cf(-1.0 if top_db is None else float(top_db)), cf(float(fmin)),
+                cf(float(fmax)), cf(float(threshold)), int(window), _ptr(f0), _ptr(ap), _ptr(frames), cap, self._stream()))
+        return f0, ap, frames
+
+    def Pitch_Errors(self, f0, lengths, ref_f0, ref_lengths, path=None, path_len=None, gross=0.2):
+        """Extension: the counts behind gross pitch error, voicing decision error and F0 frame error (``gsttaco_pitch_errors``) of
+        ``f0`` [B, Tx] (synthesised) against ``ref_f0`` [B, Ty] (reference), ``lengths`` / ``ref_lengths`` [B] or None (all frames),
+        along ``path`` [B, rows, 2] with ``path_len`` [B] as ``Mel_DTW(..., return_path=True)`` returns them -- or, with no path, frame
+        i against frame i up to the shorter length (the teacher-forced case).  A frame is voiced where its f0 > 0; a both-voiced pair
+        is gross where |f0 - ref_f0| > ``gross`` * ref_f0.  Returns (counts int32 [B, 6], ``evaluate.PITCH_COUNTS``; sums float64
+        [B, 2]: sum |c| and sum c^2 of c = 1200 log2(f0 / ref_f0) over the both-voiced non-gross pairs) on the device;
+        ``evaluate.combine_pitch`` makes the ratios of them.  Works before Restore."""
+        x, y = self._dev(f0, torch.float32), self._dev(ref_f0, torch.float32)
+        if x.dim() != 2 or y.dim() != 2 or x.shape[0] != y.shape[0] or x.shape[0] < 1 or x.shape[1] < 1 or y.shape[1] < 1:
+            raise ValueError("f0 and ref_f0 must be [batch, frames >= 1] with one batch size")
+        B = int(x.shape[0])
+        xl, yl = self._dev(lengths, torch.int32), self._dev(ref_lengths, torch.int32)
+        p, pl = self._dev(path, torch.int32), self._dev(path_len, torch.int32)
+        for name, v in (("lengths", xl), ("ref_lengths", yl), ("path_len", pl)):
+            if v is not None and tuple(v.shape) != (B,):
+                raise ValueError(name + " must be [batch]")
+        if (p is None) != (pl is None) or (p is not None and (p.dim() != 3 or p.shape[0] != B or p.shape[1] < 1 or p.shape[2] != 2)):
+            raise ValueError("path must be [batch, rows, 2] and come with path_len [batch]")
+        if not torch.cuda.is_available():
+            raise capi.GstTacoError(-2, "no HIP device: the gfx950 kernels are the only compute path (no CPU fallback)")
+        counts = torch.empty((B, len(evaluate.PITCH_COUNTS)), dtype=torch.int32, device=self.device)
+        sums = torch.empty((B, 2), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            self.ctx.check(self.ctx.lib.gsttaco_pitch_errors(
+                self.ctx.handle, _ptr(x), _ptr(xl), int(x.shape[1]), _ptr(y), _ptr(yl), int(y.shape[1]), _ptr(p), _ptr(pl),
+                int(p.shape[1]) if p is not None else 0, B, ctypes.c_float(float(gross)), _ptr(counts), _ptr(sums), self._stream()))
+        return counts, sums
 
     def Feature_Generate(self, wav_List, top_db=60):
         """Extension: ``Mel_Generate`` plus the linear spectrogram of the same trimmed signal from the same STFT (reference

@@ -456,6 +456,57 @@ int gsttaco_mel_dtw(gsttaco_ctx* ctx, const float* x, const int32_t* x_len, int6
                     const float* y, const int32_t* y_len, int64_t y_stride,
                     int B, int Tx, int Ty, int n_ceps, double* cost, int32_t* path_len, int32_t* path, void* stream);
 
+/* F0 and aperiodicity per frame of a batch of waveforms by YIN (EXTENSION, DESIGN row A20; de Cheveigne & Kawahara, JASA 111(4), 2002,
+ * steps 2-5, restated from the paper) on the frame grid of the mel front end: frame t of the F0 track is frame t of the mel of the same
+ * wav.  Needs cfg.max_wav_samples > 0, no weights.
+ *   wav, wav_lengths, ld_wav : as gsttaco_mel_frontend (DEVICE; samples at Sound.Sample_Rate = sr)
+ *   top_db >= 0  : the row is first cut to the trim bounds gsttaco_mel_frontend computes for that top_db (its two trim launches run, no
+ *                  second copy of the decision exists);  top_db < 0 : no trim, y = the row's wav_lengths[b] samples (clipped to
+ *                  [0, ld_wav]) -- the case of a Griffin-Lim output.
+ *   The tracker reads the raw samples y[0 .. n) of the cut signal: no pre-emphasis and no 0.99 factor (YIN is scale-invariant).
+ *   frames       : [B] int32  n > n_fft/2 ? 1 + n / Frame_Shift : 0, clipped to cap_frames (cap_frames >= 1 + ld_wav / Frame_Shift never
+ *                  clips).  With top_db >= 0 this is gsttaco_mel_frontend's mel_lengths[b]; for a gsttaco_griffin_lim wav of k frames, k.
+ *   f0           : [B, cap_frames] float32 Hz, 0.0 = unvoiced; entries at or beyond frames[b] are written as 0
+ *   aperiodicity : [B, cap_frames] float32 or NULL: d' at the chosen lag; for an unvoiced frame the minimum of d' over [tau_min, tau_max];
+ *                  0 at or beyond frames[b]
+ * Lags: tau_min = floor(sr / fmax), tau_max = ceil(sr / fmin) (in double, of the float arguments); W = window, 0 = round(0.025 sr).
+ * Frame t, in double throughout: x_j = y[t * Frame_Shift - (W + tau_max) / 2 + j] (integer division), j in [0, W + tau_max); a sample
+ * outside [0, n) reads as 0.0 (reflection is defined only for a pad below n, and this span is wider than n_fft / 2).
+ *   1. d(tau) = sum_{j < W} (x_j - x_{j+tau})^2, tau = 0 .. tau_max: one accumulator per lag, ascending j
+ *   2. d'(0) = 1, d'(tau) = d(tau) * tau / sum_{k=1..tau} d(k), the running total summed in ascending k; d' = 1 where that total is 0
+ *   3. the first tau in [tau_min, tau_max) with d'(tau) < threshold, then tau + 1 while tau + 1 < tau_max and d'(tau+1) < d'(tau);
+ *      no such tau: the frame is unvoiced
+ *   4. a, b, c = d(tau-1), d(tau), d(tau+1) of the RAW d: offset = (a - c) / (2 (a - 2b + c)) where a - 2b + c > 0, else 0;
+ *      f0 = sr / (tau + offset)
+ *   5. rounded to float32 once.  (The paper's step 6, the best local estimate, is not built.)
+ * One launch (behind the front end's two trim launches when top_db >= 0) on the caller's stream straight from / to the caller's
+ * pointers: one workgroup per frame, a lane per lag.  No floating-point atomics: two calls are bitwise equal and a row is bitwise the
+ * same in whatever batch it runs.  A non-finite sample makes the frames that read it unspecified; every loop stays bounded.
+ * GSTTACO_E_INVALID, before anything is enqueued or written: NULL wav / wav_lengths / f0 / frames; B, ld_wav or cap_frames < 1; a NaN
+ * top_db; fmin <= 0, fmax <= fmin, tau_min < 2, tau_min >= tau_max; threshold outside (0, 1]; window < 0; W + tau_max > 3072 (the
+ * samples, 4 bytes each, and two doubles per lag within 64 KiB of one workgroup's LDS).
+ * GSTTACO_E_CAPACITY: B > max_batch, ld_wav > max_wav_samples. */
+int gsttaco_pitch(gsttaco_ctx* ctx, const float* wav, const int32_t* wav_lengths, int B, int ld_wav,
+                  float top_db, float fmin, float fmax, float threshold, int window,
+                  float* f0, float* aperiodicity, int32_t* frames, int cap_frames, void* stream);
+
+/* Pitch errors of a synthesised F0 track x against a reference track y along a path (EXTENSION, DESIGN row A20): the counts behind
+ * gross pitch error, voicing decision error and F0 frame error.  Voiced means f0 > 0.
+ *   f0_x : [B, Tx], x_len [B] or NULL (= Tx; clipped to [0, Tx]) = Lx;   f0_y : [B, Ty], y_len likewise = Ly
+ *   path : [B, path_cap, 2] int32 cells (i, j) and path_len [B] exactly as gsttaco_mel_dtw writes them (path_cap = Tx + Ty - 1 there;
+ *          path_len is clipped to [0, path_cap]); NULL: the cells (i, i), i < min(Lx, Ly) -- the teacher-forced case.
+ *          A cell outside [0, Lx) x [0, Ly) (the -1 rows) is skipped, never read.
+ *   counts : [B][6] int32  0 pairs (cells used), 1 both_voiced, 2 gross (both voiced and |fx - fy| > gross * fy, in double, strict),
+ *            3 voicing (exactly one side voiced), 4 x_voiced, 5 y_voiced
+ *   sums   : [B][2] DOUBLE over the both-voiced, non-gross cells, c = 1200 log2(fx / fy):  0 sum |c|,  1 sum c^2
+ * One launch, one workgroup per utterance, fixed-order reductions: bitwise reproducible.  Needs a created context only.
+ * GSTTACO_E_INVALID: NULL f0_x / f0_y / counts / sums, a path without path_len, B / Tx / Ty < 1, path_cap < 1 with a path, gross < 0
+ * or NaN;  GSTTACO_E_CAPACITY: B > max_batch. */
+int gsttaco_pitch_errors(gsttaco_ctx* ctx, const float* f0_x, const int32_t* x_len, int Tx,
+                         const float* f0_y, const int32_t* y_len, int Ty,
+                         const int32_t* path, const int32_t* path_len, int path_cap,
+                         int B, float gross, int32_t* counts, double* sums, void* stream);
+
 /* hipGraph cache policy.  Every entry point replays one cached graph executable per (entry, B, Tv, Tref1, steps, flags) key.
  * The cache is LRU-bounded to `max_cached` executables (default 16 -- an Inference_Step replays two or three: encoder segment, GST + decode + postnet, vocoder; GSTTACO_GRAPH_CACHE; 0 = no graphs, everything is
  * enqueued eagerly on the caller's stream); the least recently used one is destroyed when a new shape is captured.
