@@ -213,7 +213,7 @@ __global__ __launch_bounds__(ATT_THREADS) void gt_attn_step_kernel(AttnStepArgs 
 
 hipError_t gt_attn_init() {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(gt_attn_step_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)GT_ATTN_LDS_MAX);
 }
 
 __global__ void gt_set_seed_kernel(uint64_t* dst, uint64_t seed) { *dst = seed; }

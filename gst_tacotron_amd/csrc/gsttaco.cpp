@@ -466,11 +466,18 @@ const HostTensor& T(const gsttaco_ctx* c, const std::string& name) {
 // 5e-5 bar against the float64 oracle (tests/test_gpu_configs.py), not bitwise the unpadded launch path.  Cost: the small model runs at
 // the reference model's speed, not faster.  Row / column maps: TF layouts -- Dense kernels [in, out]; LSTM kernels [in, 4 units]
 // gate-major (i | f | c~ | o); LSTM 1's input is [prenet | context], the projection's [h2 | context].
+// the rule: every size at most the reference's and not all equal to it (gsttaco_create asks too: the Attention.Size the model RUNS at)
+bool decoder_pads(const gsttaco_config& g) {
+    const int P0 = 256, P1 = 256, A = 128, H1 = 1024, H2 = 1024;
+    const int p0 = g.prenet[0], p1 = g.prenet[1], a = g.att_size, h1 = g.dec_rnn[0], h2 = g.dec_rnn[1];     // the caller's
+    return !(p0 > P0 || p1 > P1 || a > A || h1 > H1 || h2 > H2 || (p0 == P0 && p1 == P1 && a == A && h1 == H1 && h2 == H2));
+}
+
 void pad_decoder(gsttaco_ctx* c) {
     const int P0 = 256, P1 = 256, A = 128, H1 = 1024, H2 = 1024;
     if (c->dec_padded) return;      // (a second finalize after a failed one: the padded tensors and sizes are in place)
-    const int p0 = c->cfg.prenet[0], p1 = c->cfg.prenet[1], a = c->cfg.att_size, h1 = c->cfg.dec_rnn[0], h2 = c->cfg.dec_rnn[1];     // the caller's
-    if (!c->pad_dec || p0 > P0 || p1 > P1 || a > A || h1 > H1 || h2 > H2 || (p0 == P0 && p1 == P1 && a == A && h1 == H1 && h2 == H2)) return;
+    const int p1 = c->cfg.prenet[1], h1 = c->cfg.dec_rnn[0], h2 = c->cfg.dec_rnn[1];     // the caller's
+    if (!c->pad_dec || !decoder_pads(c->cfg)) return;
     // dst[rmap(r)][cmap(cc)] = src[r][cc]
     auto embed = [&](const std::string& name, int rows_out, int cols_out, auto rmap, auto cmap) {
         const HostTensor& src = c->tensors[c->index.at(name)];
@@ -2153,6 +2160,25 @@ int gsttaco_create(const gsttaco_config* cfg, gsttaco_ctx** out) {
         if (g.voc_rnn < 16 || g.voc_rnn % 16) return bad("Vocoder_Taco1: RNN.Size must be a multiple of 16");
     }
     if (g.max_batch < 1 || g.max_tokens < 1 || (g.gst_use && g.max_ref_frames < 2)) return bad("bad capacity");
+    auto env_int = [](const char* name, int dflt) { const char* e = getenv(name); return e && *e ? atoi(e) : dflt; };
+    {   // The four-kernel attention step (attention.hip) is what every shape runs that the fused front end and the persistent chain
+        // decline: its LDS at the context's capacity -- the memory tile, 3 x max_tokens floats of scores and alignments and, LSA, the
+        // location filters -- must fit what gt_attn_init opts into.  Arithmetic on the host: nothing is launched to find out.
+        const bool lsa = g.att_type == GSTTACO_ATT_LSA;
+        const int att_run = (env_int("GSTTACO_PAD_DECODER", 1) != 0 && decoder_pads(g)) ? 128 : g.att_size;
+        const size_t need = gt_attn_lds_bytes(g.max_tokens, att_run, lsa ? g.loc_filters : 0, lsa ? g.loc_kernel : 0, nullptr);
+        if (need > GT_ATTN_LDS_MAX) {
+            char m[256];
+            if (lsa)
+                snprintf(m, sizeof m, "LSA: Attention.Conv.Filters %d x Kernel_Size %d at Attention.Size %d and max_tokens %d needs %zu bytes of "
+                         "LDS in the attention step, more than the %zu a workgroup has", g.loc_filters, g.loc_kernel, att_run, g.max_tokens,
+                         need, GT_ATTN_LDS_MAX);
+            else
+                snprintf(m, sizeof m, "max_tokens %d at Attention.Size %d needs %zu bytes of LDS in the attention step, more than the %zu a "
+                         "workgroup has", g.max_tokens, att_run, need, GT_ATTN_LDS_MAX);
+            return bad(m);
+        }
+    }
     if (g.max_wav_samples > 0) {
         const int n_fft = 2 * (g.spec_dim - 1);
         if (g.spec_dim < 33 || n_fft > 8192 || (n_fft & (n_fft - 1))) return bad("Sound.Spectrogram_Dim must be 2^k + 1 with 64 <= n_fft <= 8192");
@@ -2171,7 +2197,6 @@ int gsttaco_create(const gsttaco_config* cfg, gsttaco_ctx** out) {
     c->conv_c = g.enc_filters[g.n_enc_conv - 1];
     c->P0 = g.prenet[0]; c->P1 = g.prenet[1]; c->H1 = g.dec_rnn[0]; c->H2 = g.dec_rnn[1]; c->att = g.att_size;
     // The environment is read ONCE, here (INTEGRATION.md section 6 documents these; GSTTACO_LIB is the Python binding's).
-    auto env_int = [](const char* name, int dflt) { const char* e = getenv(name); return e && *e ? atoi(e) : dflt; };
     c->use_graph = env_int("GSTTACO_GRAPH", 1) != 0;
     c->graph_cache_max = std::max(0, env_int("GSTTACO_GRAPH_CACHE", c->graph_cache_max));
     c->graph_capture_after = std::max(1, env_int("GSTTACO_GRAPH_CAPTURE_AFTER", c->graph_capture_after));

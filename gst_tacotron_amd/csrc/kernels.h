@@ -281,6 +281,8 @@ hipError_t gt_launch_copy_segments(const GtCopySegs& S, hipStream_t stream);
 hipError_t gt_launch_embed_rows(const float* table, const int32_t* tokens, float* out, int rows, int C, hipStream_t stream);
 hipError_t gt_launch_zero(float* p, size_t n_floats, hipStream_t stream);   // n rounded up to a multiple of 4 floats
 size_t gt_attn_lds_bytes(int Tv, int A, int loc_f, int loc_k, int* rows_lds);
+// the dynamic LDS gt_attn_init opts the attention step into: a workgroup's whole 160 KiB (gsttaco_create refuses what needs more)
+constexpr size_t GT_ATTN_LDS_MAX = 160 * 1024;
 
 // ---------------------------------------------------------------- dec_front.hip
 struct DecFrontArgs {
