@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = (
     "gsttaco_mel_dtw",
     "gsttaco_resample",
     "gsttaco_pitch", "gsttaco_pitch_errors",
+    "gsttaco_style_affinities", "gsttaco_style_map",
 )
 # GSTTACO_PLAN_*: the fields gsttaco_decode_plan_fields fills, in order
 PLAN_FIELDS = ("persist", "persist_bf16", "fused", "lean_front", "lean_rec", "z0", "fuse12", "lean_x0", "lean_x1", "co_tiles", "lean_proj",
@@ -168,6 +169,10 @@ def load_library(path=None):
     lib.gsttaco_pitch.restype = ctypes.c_int
     lib.gsttaco_pitch_errors.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, f32, vp, vp, vp]
     lib.gsttaco_pitch_errors.restype = ctypes.c_int
+    lib.gsttaco_style_affinities.argtypes = [vp, vp, i32, i32, ctypes.c_int64, f32, vp, vp, vp, vp]
+    lib.gsttaco_style_affinities.restype = ctypes.c_int
+    lib.gsttaco_style_map.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, f32, i32, i32, f32, f32, f32, vp, vp]
+    lib.gsttaco_style_map.restype = ctypes.c_int
     lib.gsttaco_postnet.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.gsttaco_vocoder.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.gsttaco_inference_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]

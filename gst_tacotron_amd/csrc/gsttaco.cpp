@@ -216,6 +216,8 @@ struct gsttaco_ctx {
     double *w_dtw_fx = nullptr, *w_dtw_fy = nullptr;
     uint8_t* w_dtw_bp = nullptr;
     std::map<int, double*> dtw_basis;
+    // The style map (gsttaco_style_map): the per-row partial sums [5 * GT_TSNE_MAX_N + 1], allocated by the first call
+    double* w_tsne = nullptr;
     // Resampling (gsttaco_resample): the tables of up to GT_RS_MAX_PAIRS rate pairs, least recently used evicted (ensure_resample_pair).
     // A slot's device memory and pinned host image are allocated at its first use and reused by the pairs that follow in it; `uploaded`
     // is recorded behind a slot's upload, and waited for before its host image is rewritten.
@@ -3106,6 +3108,49 @@ int gsttaco_pitch_errors(gsttaco_ctx* c, const float* f0_x, const int32_t* x_len
     a.counts = counts; a.sums = sums; a.gross = (double)gross;
     a.B = B; a.Tx = Tx; a.Ty = Ty; a.path_cap = path_cap;
     HIPCHECK(c, gt_launch_pitch_errors(a, (hipStream_t)stream));
+    return 0;
+}
+
+// Style embeddings -> the symmetric affinities of exact t-SNE: three launches on the caller's stream, everything in the caller's p.
+// Needs a created context only.
+int gsttaco_style_affinities(gsttaco_ctx* c, const float* x, int N, int D, int64_t ldx, float perplexity, double* p, double* beta,
+                             int32_t* search_iters, void* stream) {
+    if (!c) return GSTTACO_E_INVALID;
+    if (!x || !p || !beta) return fail(c, GSTTACO_E_INVALID, "null argument");
+    if (N < 3 || D < 1 || ldx < (int64_t)D) return fail(c, GSTTACO_E_INVALID, "bad N / D / ldx (N >= 3, D >= 1, ldx >= D)");
+    if (!std::isfinite(perplexity) || !((double)perplexity > 1.0) || !((double)perplexity < (double)N - 1.0))
+        return fail(c, GSTTACO_E_INVALID, "perplexity must lie in (1, N - 1): log(N - 1) is the entropy no beta exceeds");
+    if (N > GT_TSNE_MAX_N) return fail(c, GSTTACO_E_CAPACITY, "N exceeds the 8192 points whose distances one workgroup's registers hold");
+    int rc = ensure_device(c);
+    if (rc) return rc;
+    TsneAffinityArgs a{};
+    a.x = x; a.p = p; a.beta = beta; a.search_iters = search_iters; a.ldx = ldx; a.perplexity = perplexity; a.N = N; a.D = D;
+    HIPCHECK(c, gt_launch_style_affinities(a, (hipStream_t)stream));
+    return 0;
+}
+
+// The descent of exact t-SNE from a given state: two launches per step on the caller's stream, four more for the KL divergence.
+// Needs a created context only.
+int gsttaco_style_map(gsttaco_ctx* c, const double* p, int N, double* y, double* velocity, double* gains, int first_iter, int iters,
+                      float exaggeration, int stop_lying_iter, int mom_switch_iter, float momentum, float final_momentum, float eta,
+                      double* kl, void* stream) {
+    if (!c) return GSTTACO_E_INVALID;
+    if (!p || !y || !velocity || !gains) return fail(c, GSTTACO_E_INVALID, "null argument");
+    if (N < 3 || iters < 0 || first_iter < 0) return fail(c, GSTTACO_E_INVALID, "bad N / iters / first_iter (N >= 3, iters >= 0, first_iter >= 0)");
+    if (!std::isfinite(eta) || !(eta > 0.f) || !std::isfinite(exaggeration) || !(exaggeration > 0.f))
+        return fail(c, GSTTACO_E_INVALID, "eta and exaggeration must be finite and positive");
+    if (!(momentum >= 0.f) || !(momentum < 1.f) || !(final_momentum >= 0.f) || !(final_momentum < 1.f))
+        return fail(c, GSTTACO_E_INVALID, "momentum and final_momentum must lie in [0, 1)");
+    if (N > GT_TSNE_MAX_N) return fail(c, GSTTACO_E_CAPACITY, "N exceeds the 8192 points of the style map");
+    int rc = ensure_device(c);
+    if (rc) return rc;
+    if (iters == 0 && !kl) return 0;
+    if (!c->w_tsne && (rc = dev_alloc(c, (void**)&c->w_tsne, ((size_t)5 * GT_TSNE_MAX_N + 1) * sizeof(double)))) return rc;
+    TsneMapArgs a{};
+    a.p = p; a.y = y; a.velocity = velocity; a.gains = gains; a.partials = c->w_tsne; a.kl = kl;
+    a.exaggeration = (double)exaggeration; a.momentum = (double)momentum; a.final_momentum = (double)final_momentum; a.eta = (double)eta;
+    a.N = N; a.first_iter = first_iter; a.iters = iters; a.stop_lying_iter = stop_lying_iter; a.mom_switch_iter = mom_switch_iter;
+    HIPCHECK(c, gt_launch_style_map(a, (hipStream_t)stream));
     return 0;
 }
 

@@ -613,3 +613,30 @@ struct PitchErrorArgs {
     int B, Tx, Ty, path_cap;
 };
 hipError_t gt_launch_pitch_errors(const PitchErrorArgs& a, hipStream_t stream);
+
+
+// ---------------------------------------------------------------- tsne.hip
+// The style map: exact t-SNE of style embeddings (the contracts: gsttaco_style_affinities and gsttaco_style_map in include/gsttaco.h).
+#define GT_TSNE_MAX_N 8192                  // the search keeps a row of distances in the registers of one workgroup: 1024 lanes x 8
+struct TsneAffinityArgs {
+    const float* x;             // [N, ldx], D channels used
+    double* p;                  // [N, N]: distances, then p_{j|i}, then p_ij, each in place
+    double* beta;               // [N]
+    int32_t* search_iters;      // [N], or NULL
+    int64_t ldx;
+    float perplexity;
+    int N, D;
+};
+hipError_t gt_launch_style_affinities(const TsneAffinityArgs& a, hipStream_t stream);
+
+struct TsneMapArgs {
+    const double* p;            // [N, N]
+    double* y;                  // [N, 2], as velocity and gains
+    double* velocity;
+    double* gains;
+    double* partials;           // [5 N + 1] workspace: S, A_x, A_y, B_x, B_y per row, and Z for the KL
+    double* kl;                 // [1], or NULL
+    double exaggeration, momentum, final_momentum, eta;
+    int N, first_iter, iters, stop_lying_iter, mom_switch_iter;
+};
+hipError_t gt_launch_style_map(const TsneMapArgs& a, hipStream_t stream);

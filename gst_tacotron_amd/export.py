@@ -61,3 +61,33 @@ def export_gst(path, wav_List, tag_List, gst_List):
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     with open(path, "w") as f:
         f.write("\n".join(lines))
+
+
+def export_gst_map(path, wav_List, tag_List, y):
+    """The style map beside export_gst's table: tab-separated Wav, Tag, TSNE_x, TSNE_y (the data frame reference R_Script/TSNE.R plots),
+    formatted as export_gst formats."""
+    y = np.asarray(y, dtype=np.float64)
+    lines = ["\t".join(["Wav", "Tag", "TSNE_x", "TSNE_y"])]
+    for wav_path, tag, point in zip(wav_List, tag_List, y):
+        lines.append("\t".join(["{}".format(x) for x in [wav_path, tag] + list(point)]))
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "w") as f:
+        f.write("\n".join(lines))
+
+
+def plot_gst_map(path, tag_List, y):
+    """The figure reference R_Script/TSNE.R saves: the map's points coloured by tag, titled "GST t-SNE".  Needs matplotlib."""
+    import matplotlib
+    matplotlib.use("Agg")
+    import matplotlib.pyplot as plt
+    y = np.asarray(y, dtype=np.float64)
+    tags = [str(t) for t in tag_List]
+    fig, ax = plt.subplots(figsize=(8, 6), dpi=100)
+    for tag in sorted(set(tags)):
+        rows = [i for i, t in enumerate(tags) if t == tag]
+        ax.scatter(y[rows, 0], y[rows, 1], label=tag)
+    ax.set_title("GST t-SNE")
+    ax.legend(title="Data_Tag", loc="center left", bbox_to_anchor=(1.0, 0.5))
+    fig.tight_layout()
+    fig.savefig(path)
+    plt.close(fig)

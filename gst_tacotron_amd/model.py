@@ -63,6 +63,11 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def style_map_init(n, seed=0):
+    """Where ``Style_Map`` starts without an ``init``: N x 2 normal draws of the host's generator, scaled by 1e-4 (bhtsne's scale)."""
+    return np.random.default_rng(seed).standard_normal((n, 2)) * 1e-4
+
+
 class GST_Tacotron:
     def __init__(self, is_Training=False, hyper_parameters=None, device=None,
                  max_batch=32, max_tokens=256, max_ref_frames=1025, max_wav_seconds=20.0, resample="device"):
@@ -570,16 +575,96 @@ class GST_Tacotron:
             result.update(pitch_per_utterance=evaluate.combine_pitch(counts, sums), f0=f0, ref_f0=ref_f0)
         return result
 
-    def Inference_GST(self, wav_List, tag_List=None, label=None):
+    def Inference_GST(self, wav_List, tag_List=None, label=None, style_map=False):
         """reference Model.py:427-446: style embeddings [B, Attention.Size] of the wavs; with ``tag_List`` the table
-        of Model.py:448-459 is written too."""
+        of Model.py:448-459 is written too.  ``style_map`` (extension; True or a dict of ``Style_Map`` keywords): the embeddings go
+        on to ``Style_Map`` without leaving the device and the method returns (gsts, map dict); with ``tag_List`` the map is written
+        beside the table as GST/<label>.GST.MAP.TXT and, where matplotlib imports, drawn as GST/<label>.GST.PNG -- the figure
+        reference R_Script/TSNE.R makes of the table."""
         if not self.hp_Dict["GST"]["Use"]:
             raise NotImplementedError("GST is not used")
         print("GST Inference running...")
         gsts = self.Inference_GST_Step(**self.feeder.Get_Inference_GST_Pattern(wav_List))
+        label = label or datetime.now().strftime("%Y%m%d.%H%M%S")
         if tag_List is not None:
-            self.Export_GST(wav_List, tag_List, gsts, label or datetime.now().strftime("%Y%m%d.%H%M%S"))
-        return gsts
+            self.Export_GST(wav_List, tag_List, gsts, label)
+        if style_map is False or style_map is None:
+            return gsts
+        result = self.Style_Map(gsts, **({} if style_map is True else dict(style_map)))
+        if tag_List is not None:
+            self.Export_GST_Map(wav_List, tag_List, result["y"], label)
+        return gsts, result
+
+    def Style_Affinities(self, embeddings, perplexity=5.0):
+        """Extension: the symmetric affinities of exact t-SNE (``gsttaco_style_affinities``) over ``embeddings`` [N, D] -- what
+        ``Inference_GST_Step`` returns, or any float array; a device tensor whose rows are dense is read where it lies.  Returns
+        (p float64 [N, N], beta float64 [N], search_iters int32 [N]) on the device.  ``perplexity`` lies in (1, N - 1).  The affinities
+        do not depend on the embeddings' scale: every point's bandwidth is searched for.  Works before Restore."""
+        if not torch.cuda.is_available():
+            raise capi.GstTacoError(-2, "no HIP device: the gfx950 kernels are the only compute path (no CPU fallback)")
+        x = embeddings
+        if not (isinstance(x, torch.Tensor) and x.device == self.device and x.dtype == torch.float32 and x.dim() == 2
+                and x.stride(1) == 1 and x.stride(0) >= x.shape[1]):
+            x = self._dev(x, torch.float32)
+        if x.dim() != 2:
+            raise ValueError("embeddings must be [points, channels]")
+        N, D = int(x.shape[0]), int(x.shape[1])
+        p = torch.empty((N, N), dtype=torch.float64, device=self.device)
+        beta = torch.empty((N,), dtype=torch.float64, device=self.device)
+        rounds = torch.empty((N,), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            self.ctx.check(self.ctx.lib.gsttaco_style_affinities(self.ctx.handle, _ptr(x), N, D, int(x.stride(0)), float(perplexity), _ptr(p),
+                                                                 _ptr(beta), _ptr(rounds), self._stream()))
+        return p, beta, rounds
+
+    def Style_Map(self, embeddings=None, affinities=None, perplexity=5.0, iters=1000, seed=0, init=None, state=None, exaggeration=12.0,
+                  stop_lying_iter=250, mom_switch_iter=250, momentum=0.5, final_momentum=0.8, eta=200.0):
+        """Extension: the style map -- exact (theta = 0) t-SNE of style embeddings into two dimensions on the device
+        (``gsttaco_style_map``), with the defaults of reference R_Script/TSNE.R and Rtsne (perplexity 5, 1000 iterations).  Exactly one
+        of ``embeddings`` [N, D] (``Style_Affinities`` runs first) and ``affinities`` [N, N] float64 is given; with ``state`` -- a
+        previous result -- neither need be: the state's own affinities are used and the descent continues at its ``iter`` for ``iters``
+        more steps, bitwise as one longer run would.  The map starts at ``init`` [N, 2], by default ``style_map_init(N, seed)``: drawn
+        on the host.  Returns a dict: ``y`` [N, 2], ``velocity``, ``gains`` (float64, on the device), ``iter``, ``kl`` (the KL
+        divergence at ``y``, a float64 device scalar), ``affinities`` and ``beta`` (None where the affinities were given).
+        Not Rtsne's picture point for point: TSNE.R runs the Barnes-Hut form (theta = 0.5) after a PCA to 50 dimensions, this is the
+        exact form on all D channels, and a t-SNE map depends on its seed.  Works before Restore."""
+        if embeddings is not None and affinities is not None:
+            raise ValueError("give embeddings or affinities, not both")
+        if not torch.cuda.is_available():
+            raise capi.GstTacoError(-2, "no HIP device: the gfx950 kernels are the only compute path (no CPU fallback)")
+        beta = None
+        if embeddings is not None:
+            affinities, beta, _ = self.Style_Affinities(embeddings, perplexity)
+        elif affinities is None:
+            if state is None:
+                raise ValueError("give embeddings or affinities (or a state, whose affinities are then used)")
+            affinities, beta = state["affinities"], state.get("beta")
+        elif state is not None and affinities is state.get("affinities"):
+            beta = state.get("beta")
+        p = self._dev(affinities, torch.float64)
+        if p.dim() != 2 or p.shape[0] != p.shape[1]:
+            raise ValueError("affinities must be [N, N]")
+        N = int(p.shape[0])
+        if state is not None:
+            if init is not None:
+                raise ValueError("give init or state, not both")
+            y, velocity, gains = (self._dev(state[k], torch.float64).clone() for k in ("y", "velocity", "gains"))
+            first = int(state["iter"])
+        else:
+            y = self._dev(style_map_init(N, seed) if init is None else np.asarray(init.cpu() if torch.is_tensor(init) else init, dtype=np.float64),
+                          torch.float64)
+            velocity = torch.zeros((N, 2), dtype=torch.float64, device=self.device)
+            gains = torch.ones((N, 2), dtype=torch.float64, device=self.device)
+            first = 0
+        for name, t in (("init / state y", y), ("velocity", velocity), ("gains", gains)):
+            if tuple(t.shape) != (N, 2):
+                raise ValueError(name + " must be [N, 2]")
+        kl = torch.empty((), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            self.ctx.check(self.ctx.lib.gsttaco_style_map(self.ctx.handle, _ptr(p), N, _ptr(y), _ptr(velocity), _ptr(gains), first, int(iters),
+                                                          float(exaggeration), int(stop_lying_iter), int(mom_switch_iter), float(momentum),
+                                                          float(final_momentum), float(eta), _ptr(kl), self._stream()))
+        return dict(y=y, velocity=velocity, gains=gains, iter=first + int(iters), kl=kl, affinities=p, beta=beta)
 
     def Inference_GST_Step(self, mels_for_gst, mel_lengths_for_gst, return_attention=False):
         """reference Model.py:257-265.  ``return_attention=True`` (extension): returns (gst, style_token_weights [B, Head, Style_Token.Size],
@@ -987,6 +1072,20 @@ class GST_Tacotron:
         gst = np.asarray(gst_List.cpu() if torch.is_tensor(gst_List) else gst_List)
         path = os.path.join(self.hp_Dict["Inference_Path"], "GST", "{}.GST.TXT".format(label))
         export.export_gst(path, wav_List, tag_List, gst)
+        return path
+
+    def Export_GST_Map(self, wav_List, tag_List, y, label):
+        """The style map of ``Inference_GST(..., style_map=...)`` as GST/<label>.GST.MAP.TXT and, where matplotlib imports,
+        GST/<label>.GST.PNG (what reference R_Script/TSNE.R saves).  Returns the table's path."""
+        from . import export
+        y = np.asarray(y.cpu() if torch.is_tensor(y) else y, dtype=np.float64)
+        root = os.path.join(self.hp_Dict["Inference_Path"], "GST")
+        path = os.path.join(root, "{}.GST.MAP.TXT".format(label))
+        export.export_gst_map(path, wav_List, tag_List, y)
+        try:
+            export.plot_gst_map(os.path.join(root, "{}.GST.PNG".format(label)), tag_List, y)
+        except ImportError:
+            pass                                  # matplotlib is optional
         return path
 
     # ------------------------------------------------------------------ per-phase entry points (tests / profiling)

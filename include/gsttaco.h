@@ -507,6 +507,55 @@ int gsttaco_pitch_errors(gsttaco_ctx* ctx, const float* f0_x, const int32_t* x_l
                          const int32_t* path, const int32_t* path_len, int path_cap,
                          int B, float gross, int32_t* counts, double* sums, void* stream);
 
+/* The symmetric affinities of exact t-SNE over N style embeddings (EXTENSION, DESIGN row A21; van der Maaten & Hinton, JMLR 9, 2008, with
+ * the perplexity search as bhtsne / Rtsne run it, restated here).  Needs a created context only, no weights.
+ *   x : [N, ldx] float32 (DEVICE), the first D channels of a row are the embedding -- what gsttaco_gst writes, ldx = D = Attention.Size
+ *   p : [N, N] DOUBLE   beta : [N] DOUBLE   search_iters : [N] int32 or NULL
+ * Distances, in double: d_ij = sum_k (x_ik - x_jk)^2, each x converted to double first, one accumulator per pair, ascending k, the
+ * square and the sum each rounded (no fused multiply-add) -- direct differences, not the Gram form: identical rows give exactly 0,
+ * d_ij == d_ji bitwise, and d is the same double on any IEEE machine.
+ * Row i: delta_j = d_ij - min_{j != i} d_ij for j != i (the shift changes nothing mathematically and keeps s >= 1 for embeddings of any
+ * scale: no 0 / 0).  The search: beta = 1, lo = -inf, hi = +inf; a round computes w_j = exp(-beta delta_j) for j != i, s = sum_j w_j,
+ * H = log(s) + beta (sum_j delta_j w_j) / s and Hd = H - log(perplexity) (the log in double of the float argument); it stops the search
+ * when |Hd| < 1e-5; else if Hd > 0: lo = beta, then beta = 2 beta while hi is +inf, else (beta + hi) / 2; otherwise: hi = beta, then
+ * beta = beta / 2 while lo is -inf, else (beta + lo) / 2.  At most 200 rounds.  search_iters[i] = the rounds run (1 .. 200, the
+ * stopping round included), beta[i] = the beta the search ended with: the stopping round's, or the one the 200th round's update left.
+ * p_{j|i} = w_j / s at THAT beta (after 200 undecided rounds w and s are evaluated once more at it); p_ij = (p_{j|i} + p_{i|j}) / (2N),
+ * p_ii = 0, p_ij == p_ji bitwise, no floor on p.  Rows with duplicates, or a perplexity below a point's number of duplicates, end with
+ * a large finite beta (up to 2^200) and finite p.  The sums over j have a fixed order (not ascending j), so two calls are bitwise equal.
+ * Three launches on the caller's stream, everything in the caller's buffers: p holds the distances, then p_{j|i}, then p_ij; no
+ * workspace.  A non-finite x makes the result unspecified; every loop stays bounded and the call finishes.
+ * GSTTACO_E_INVALID, before anything is enqueued or written: NULL x / p / beta; N < 3; D < 1; ldx < D; a perplexity that is not finite
+ * or lies outside the open interval (1, N - 1) -- log(N - 1) is the entropy no beta exceeds.
+ * GSTTACO_E_CAPACITY: N > 8192 (a row of distances stays in the registers of one workgroup: 1024 lanes x 8). */
+int gsttaco_style_affinities(gsttaco_ctx* ctx, const float* x, int N, int D, int64_t ldx, float perplexity,
+                             double* p, double* beta, int32_t* search_iters, void* stream);
+
+/* The descent of exact (theta = 0) t-SNE into two dimensions as bhtsne / Rtsne run it (EXTENSION, DESIGN row A21), double throughout;
+ * the float arguments are converted to double as they are.  Needs a created context only.
+ *   p : [N, N] DOUBLE as gsttaco_style_affinities writes it   y, velocity, gains : [N, 2] DOUBLE each, read AND written
+ * For t = first_iter .. first_iter + iters - 1:
+ *   e = exaggeration while t < stop_lying_iter, else 1;  m = momentum while t < mom_switch_iter, else final_momentum
+ *   n_ij = 1 / (1 + |y_i - y_j|^2) for i != j;  Z = sum_{i != j} n_ij
+ *   g_i = sum_j (e p_ij - n_ij / Z) n_ij (y_i - y_j), computed as e A_i - B_i / Z with S_i = sum_j n_ij, A_i = sum_j p_ij n_ij (y_i - y_j),
+ *         B_i = sum_j n_ij^2 (y_i - y_j) and Z = sum_i S_i -- no factor 4: bhtsne's exact gradient has none and its eta = 200 assumes that
+ *   per component: gains = gains + 0.2 where sign(g) != sign(velocity), else gains * 0.8, sign in {-1, 0, +1}; gains = max(gains, 0.01);
+ *         velocity = m velocity - eta gains g;  y = y + velocity
+ *   then the column means of y are subtracted from y.
+ * kl (DOUBLE [1] or NULL), after the last step: sum over p_ij > 0 of p_ij log(p_ij / q_ij), q_ij = n_ij / Z at the final y, no exaggeration.
+ * The state is (y, velocity, gains, first_iter) and nothing else: one call of 1000 steps equals two of 500 bitwise (the second with
+ * first_iter = 500), and iters = 0 with kl only evaluates the divergence.  A fresh run starts at gains = 1, velocity = 0.
+ * Per step two plain launches on the caller's stream (the pair terms, a wave per row with y tiled through LDS; then one workgroup that
+ * sums Z, updates and recentres), four more for kl; every sum has one fixed order (not ascending j), no floating-point atomics, no
+ * workgroup waits on another: two calls are bitwise equal.  Workspace: 5 * 8192 + 1 doubles, allocated by the first call and kept.
+ * A non-finite input makes the result unspecified; every loop is bounded by N and iters and the call finishes.
+ * GSTTACO_E_INVALID, before anything is enqueued or written: NULL p / y / velocity / gains; N < 3; iters < 0; first_iter < 0; an eta or
+ * exaggeration that is not finite and positive; momentum or final_momentum outside [0, 1).
+ * GSTTACO_E_CAPACITY: N > 8192 (the cap of gsttaco_style_affinities). */
+int gsttaco_style_map(gsttaco_ctx* ctx, const double* p, int N, double* y, double* velocity, double* gains,
+                      int first_iter, int iters, float exaggeration, int stop_lying_iter, int mom_switch_iter,
+                      float momentum, float final_momentum, float eta, double* kl, void* stream);
+
 /* hipGraph cache policy.  Every entry point replays one cached graph executable per (entry, B, Tv, Tref1, steps, flags) key.
  * The cache is LRU-bounded to `max_cached` executables (default 16 -- an Inference_Step replays two or three: encoder segment, GST + decode + postnet, vocoder; GSTTACO_GRAPH_CACHE; 0 = no graphs, everything is
  * enqueued eagerly on the caller's stream); the least recently used one is destroyed when a new shape is captured.
