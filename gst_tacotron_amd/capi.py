@@ -41,7 +41,13 @@ EXPORTED_SYMBOLS = (
     "gsttaco_resample",
     "gsttaco_pitch", "gsttaco_pitch_errors",
     "gsttaco_style_affinities", "gsttaco_style_map",
+    "gsttaco_melgan_configure", "gsttaco_melgan_num_weights", "gsttaco_melgan_weight_info", "gsttaco_melgan_load_weight",
+    "gsttaco_melgan_finalize", "gsttaco_melgan", "gsttaco_melgan_plan", "gsttaco_melgan_debug_stage",
 )
+# gsttaco_melgan_plan: ints per launch (kind, channels, tile, form, rate, lds), the launch kinds, and the size of its array
+MELGAN_PLAN_FIELDS = ("kind", "channels", "tile", "form", "rate", "lds")
+MELGAN_KINDS = ("in", "up", "res", "out")
+MELGAN_PLAN_INTS = 3 + 6 * 74
 # GSTTACO_PLAN_*: the fields gsttaco_decode_plan_fields fills, in order
 PLAN_FIELDS = ("persist", "persist_bf16", "fused", "lean_front", "lean_rec", "z0", "fuse12", "lean_x0", "lean_x1", "co_tiles", "lean_proj",
                "mirror", "dec_padded", "pj_tiles")
@@ -114,6 +120,11 @@ class Config(ctypes.Structure):
     ]
 
 
+class MelganConfig(ctypes.Structure):
+    _fields_ = [("mel_dim", ctypes.c_int32), ("base", ctypes.c_int32), ("n_ratios", ctypes.c_int32), ("ratios", _I32A),
+                ("n_res", ctypes.c_int32), ("slope", ctypes.c_float), ("max_batch", ctypes.c_int32), ("max_frames", ctypes.c_int32)]
+
+
 class GstTacoError(RuntimeError):
     def __init__(self, code, message):
         super().__init__("gsttaco error {}: {}".format(code, message))
@@ -173,6 +184,18 @@ def load_library(path=None):
     lib.gsttaco_style_affinities.restype = ctypes.c_int
     lib.gsttaco_style_map.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, f32, i32, i32, f32, f32, f32, vp, vp]
     lib.gsttaco_style_map.restype = ctypes.c_int
+    lib.gsttaco_melgan_configure.argtypes = [vp, ctypes.POINTER(MelganConfig)]
+    lib.gsttaco_melgan_num_weights.argtypes = [vp]
+    lib.gsttaco_melgan_weight_info.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_int64 * 4), ctypes.POINTER(ctypes.c_int)]
+    lib.gsttaco_melgan_load_weight.argtypes = [vp, ctypes.c_char_p, f32p, ctypes.POINTER(ctypes.c_int64), i32]
+    lib.gsttaco_melgan_finalize.argtypes = [vp]
+    lib.gsttaco_melgan.argtypes = [vp, vp, vp, i32, i32, vp, vp, i32, vp]
+    lib.gsttaco_melgan_plan.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
+    lib.gsttaco_melgan_debug_stage.argtypes = [vp, i32, vp, vp, i32, i32, vp, i32, vp]
+    lib.gsttaco_melgan_debug_stage.restype = ctypes.c_int
+    for fn in ("gsttaco_melgan_configure", "gsttaco_melgan_num_weights", "gsttaco_melgan_weight_info", "gsttaco_melgan_load_weight",
+               "gsttaco_melgan_finalize", "gsttaco_melgan", "gsttaco_melgan_plan"):
+        getattr(lib, fn).restype = ctypes.c_int
     lib.gsttaco_postnet.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.gsttaco_vocoder.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.gsttaco_inference_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
@@ -338,3 +361,49 @@ class Context:
 
     def finalize(self):
         self.check(self.lib.gsttaco_finalize_weights(self.handle))
+
+    # ---- the neural vocoder (gsttaco_melgan_*): one per context
+    def melgan_configure(self, cfg, max_batch, max_frames):
+        """``cfg``: a melgan.MelGANConfig (or anything with its fields)."""
+        m = MelganConfig()
+        m.mel_dim, m.base, m.n_res, m.slope = int(cfg.mel_dim), int(cfg.base), int(cfg.n_res), float(cfg.slope)
+        if len(cfg.ratios) > MAX_LAYERS:
+            raise ValueError("at most {} upsampling ratios".format(MAX_LAYERS))
+        m.n_ratios = len(cfg.ratios)
+        for i, r in enumerate(cfg.ratios):
+            m.ratios[i] = int(r)
+        m.max_batch, m.max_frames = int(max_batch), int(max_frames)
+        self.check(self.lib.gsttaco_melgan_configure(self.handle, ctypes.byref(m)))
+
+    def melgan_manifest(self):
+        out = {}
+        for i in range(self.lib.gsttaco_melgan_num_weights(self.handle)):
+            name, shape, nd = ctypes.c_char_p(), (ctypes.c_int64 * 4)(), ctypes.c_int()
+            self.check(self.lib.gsttaco_melgan_weight_info(self.handle, i, ctypes.byref(name), ctypes.byref(shape), ctypes.byref(nd)))
+            out[name.value.decode()] = tuple(shape[k] for k in range(nd.value))
+        return out
+
+    def melgan_load_weight(self, name, array):
+        a = np.ascontiguousarray(np.asarray(array, dtype=np.float32))
+        shape = (ctypes.c_int64 * max(a.ndim, 1))(*a.shape)
+        self.check(self.lib.gsttaco_melgan_load_weight(self.handle, name.encode(), a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), shape, a.ndim))
+
+    def melgan_load_weights(self, weights):
+        for name in self.melgan_manifest():
+            if name not in weights:
+                raise KeyError("missing weight '{}'".format(name))
+            self.melgan_load_weight(name, weights[name])
+
+    def melgan_finalize(self):
+        self.check(self.lib.gsttaco_melgan_finalize(self.handle))
+
+    def melgan_plan(self):
+        """(min_frames, hop, [one dict of MELGAN_PLAN_FIELDS per launch, ``kind`` as a name of MELGAN_KINDS])."""
+        f = (ctypes.c_int32 * MELGAN_PLAN_INTS)()
+        self.check(self.lib.gsttaco_melgan_plan(self.handle, f))
+        stages = []
+        for i in range(f[0]):
+            row = dict(zip(MELGAN_PLAN_FIELDS, f[3 + 6 * i: 9 + 6 * i]))
+            row["kind"] = MELGAN_KINDS[row["kind"]]
+            stages.append(row)
+        return int(f[1]), int(f[2]), stages

@@ -218,6 +218,16 @@ struct gsttaco_ctx {
     std::map<int, double*> dtw_basis;
     // The style map (gsttaco_style_map): the per-row partial sums [5 * GT_TSNE_MAX_N + 1], allocated by the first call
     double* w_tsne = nullptr;
+    // The neural vocoder (gsttaco_melgan_*): its own manifest, the plan whose stages hold the device operands once finalized, and the
+    // ping-pong activations for the capacity
+    struct Melgan {
+        bool configured = false, finalized = false;
+        gsttaco_melgan_config cfg{};
+        MgPlan plan{};
+        std::vector<HostTensor> tensors;
+        std::map<std::string, int> index;
+        float* ws[2] = {nullptr, nullptr};
+    } mg;
     // Resampling (gsttaco_resample): the tables of up to GT_RS_MAX_PAIRS rate pairs, least recently used evicted (ensure_resample_pair).
     // A slot's device memory and pinned host image are allocated at its first use and reused by the pairs that follow in it; `uploaded`
     // is recorded behind a slot's upload, and waited for before its host image is rewritten.
@@ -3151,6 +3161,184 @@ int gsttaco_style_map(gsttaco_ctx* c, const double* p, int N, double* y, double*
     a.exaggeration = (double)exaggeration; a.momentum = (double)momentum; a.final_momentum = (double)final_momentum; a.eta = (double)eta;
     a.N = N; a.first_iter = first_iter; a.iters = iters; a.stop_lying_iter = stop_lying_iter; a.mom_switch_iter = mom_switch_iter;
     HIPCHECK(c, gt_launch_style_map(a, (hipStream_t)stream));
+    return 0;
+}
+
+// ---- the neural vocoder (melgan.hip).  Configure and the manifest need no device; finalize uploads and allocates once.
+int gsttaco_melgan_configure(gsttaco_ctx* c, const gsttaco_melgan_config* m) {
+    if (!c) return GSTTACO_E_INVALID;
+    if (!m) return fail(c, GSTTACO_E_INVALID, "null argument");
+    gsttaco_ctx::Melgan& g = c->mg;
+    if (g.configured) return fail(c, GSTTACO_E_INVALID, "melgan: the context's vocoder is configured already");
+    if (m->n_ratios < 1 || m->n_ratios > GSTTACO_MAX_LAYERS) return fail(c, GSTTACO_E_INVALID, "melgan: between 1 and 8 upsampling ratios");
+    if (m->max_batch < 1 || m->max_frames < 1) return fail(c, GSTTACO_E_INVALID, "melgan: max_batch and max_frames must be at least 1");
+    MgPlan plan;
+    const char* why = gt_melgan_make_plan(m->mel_dim, m->base, m->n_ratios, m->ratios, m->n_res, m->slope, &plan);
+    if (why) return fail(c, GSTTACO_E_INVALID, std::string("melgan: ") + why);
+    if ((double)m->max_batch * m->max_frames * plan.hop > 2147483647.0)
+        return fail(c, GSTTACO_E_INVALID, "melgan: max_batch * max_frames * hop exceeds 2^31 - 1 samples");
+    g.cfg = *m;
+    g.plan = plan;
+    auto add = [&](const std::string& name, std::vector<int64_t> shape) {
+        HostTensor t;
+        t.name = name;
+        t.shape = std::move(shape);
+        g.index[name] = (int)g.tensors.size();
+        g.tensors.push_back(std::move(t));
+    };
+    int up = -1, res = 0;
+    for (int i = 0; i < plan.n_stages; ++i) {
+        const MgStage& s = plan.st[i];
+        if (s.kind == GT_MG_IN) { add("melgan/in/kernel", {(int64_t)7 * s.cin, s.cout}); add("melgan/in/bias", {s.cout}); }
+        else if (s.kind == GT_MG_UP) {
+            ++up; res = 0;
+            const std::string p = "melgan/up" + std::to_string(up);
+            add(p + "/kernel", {(int64_t)2 * s.r, s.cin, s.cout});
+            add(p + "/bias", {s.cout});
+        } else if (s.kind == GT_MG_RES) {
+            const std::string p = "melgan/up" + std::to_string(up) + "/res" + std::to_string(res++);
+            add(p + "/conv3/kernel", {(int64_t)3 * s.cin, s.cout}); add(p + "/conv3/bias", {s.cout});
+            add(p + "/conv1/kernel", {s.cin, s.cout}); add(p + "/conv1/bias", {s.cout});
+            add(p + "/shortcut/kernel", {s.cin, s.cout}); add(p + "/shortcut/bias", {s.cout});
+        } else { add("melgan/out/kernel", {(int64_t)7 * s.cin, 1}); add("melgan/out/bias", {1}); }
+    }
+    g.configured = true;
+    return 0;
+}
+
+int gsttaco_melgan_num_weights(const gsttaco_ctx* c) { return c ? (int)c->mg.tensors.size() : GSTTACO_E_INVALID; }
+
+int gsttaco_melgan_weight_info(const gsttaco_ctx* c, int i, const char** name, int64_t shape[4], int* ndim) {
+    if (!c || i < 0 || i >= (int)c->mg.tensors.size()) return GSTTACO_E_INVALID;
+    const HostTensor& t = c->mg.tensors[i];
+    if (name) *name = t.name.c_str();
+    if (ndim) *ndim = (int)t.shape.size();
+    if (shape)
+        for (size_t d = 0; d < 4; ++d) shape[d] = d < t.shape.size() ? t.shape[d] : 1;
+    return 0;
+}
+
+int gsttaco_melgan_load_weight(gsttaco_ctx* c, const char* name, const float* host, const int64_t* shape, int ndim) {
+    if (!c || !name || !host || !shape) return fail(c, GSTTACO_E_INVALID, "null argument");
+    gsttaco_ctx::Melgan& g = c->mg;
+    if (!g.configured) return fail(c, GSTTACO_E_WEIGHTS, "melgan: not configured (gsttaco_melgan_configure)");
+    if (g.finalized) return fail(c, GSTTACO_E_WEIGHTS, "melgan: weights already finalized");
+    auto it = g.index.find(name);
+    if (it == g.index.end()) return fail(c, GSTTACO_E_WEIGHTS, std::string("melgan: unknown weight '") + name + "'");
+    HostTensor& t = g.tensors[it->second];
+    bool ok = ndim == (int)t.shape.size();
+    for (int d = 0; ok && d < ndim; ++d) ok = shape[d] == t.shape[d];
+    if (!ok) return fail(c, GSTTACO_E_WEIGHTS, std::string("melgan: weight '") + name + "' has the wrong shape");
+    t.data.assign(host, host + t.numel());
+    t.loaded = true;
+    return 0;
+}
+
+int gsttaco_melgan_finalize(gsttaco_ctx* c) {
+    if (!c) return GSTTACO_E_INVALID;
+    gsttaco_ctx::Melgan& g = c->mg;
+    if (!g.configured) return fail(c, GSTTACO_E_WEIGHTS, "melgan: not configured (gsttaco_melgan_configure)");
+    if (g.finalized) return fail(c, GSTTACO_E_WEIGHTS, "melgan: weights already finalized");
+    for (const HostTensor& t : g.tensors)
+        if (!t.loaded) return fail(c, GSTTACO_E_WEIGHTS, "melgan: weight '" + t.name + "' was not loaded");
+    int rc = ensure_device(c);
+    if (rc) return rc;
+    HIPCHECK(c, gt_melgan_prepare());
+    auto host = [&](const std::string& name) -> const std::vector<float>& { return g.tensors[g.index[name]].data; };
+    std::vector<float> buf;
+    auto packed = [&](const float** dst, const std::string& name, int taps, int cin, int cout) {
+        const int cin_p = (cin + 15) / 16 * 16, n_p = (cout + 15) / 16 * 16;
+        buf.resize((size_t)taps * cin_p * n_p);
+        gt_melgan_pack(host(name).data(), taps, cin, cout, buf.data());
+        float* d = nullptr;
+        int e = upload(c, &d, buf.data(), buf.size());
+        *dst = d;
+        return e;
+    };
+    auto bias = [&](const float** dst, const std::string& name, const std::string& plus, int n_p) {
+        buf.assign(n_p, 0.f);
+        const std::vector<float>& b = host(name);
+        for (size_t i = 0; i < b.size(); ++i) buf[i] = b[i];
+        if (!plus.empty()) {
+            const std::vector<float>& b2 = host(plus);
+            for (size_t i = 0; i < b2.size(); ++i) buf[i] += b2[i];
+        }
+        float* d = nullptr;
+        int e = upload(c, &d, buf.data(), buf.size());
+        *dst = d;
+        return e;
+    };
+    int up = -1, res = 0;
+    for (int i = 0; i < g.plan.n_stages; ++i) {
+        MgStage& s = g.plan.st[i];
+        if (s.kind == GT_MG_IN) {
+            if ((rc = packed(&s.w0, "melgan/in/kernel", 7, s.cin, s.cout)) || (rc = bias(&s.b0, "melgan/in/bias", "", s.n_p))) return rc;
+        } else if (s.kind == GT_MG_UP) {
+            ++up; res = 0;
+            const std::string p = "melgan/up" + std::to_string(up);
+            if ((rc = packed(&s.w0, p + "/kernel", 2 * s.r, s.cin, s.cout)) || (rc = bias(&s.b0, p + "/bias", "", s.n_p))) return rc;
+        } else if (s.kind == GT_MG_RES) {
+            const std::string p = "melgan/up" + std::to_string(up) + "/res" + std::to_string(res++);
+            if ((rc = packed(&s.w0, p + "/conv3/kernel", 3, s.cin, s.cout)) || (rc = bias(&s.b0, p + "/conv3/bias", "", s.n_p))) return rc;
+            if ((rc = packed(&s.w1, p + "/shortcut/kernel", 1, s.cin, s.cout)) || (rc = packed(&s.w2, p + "/conv1/kernel", 1, s.cin, s.cout))) return rc;
+            if ((rc = bias(&s.b1, p + "/shortcut/bias", p + "/conv1/bias", s.n_p))) return rc;
+        } else {
+            float* d = nullptr;
+            if ((rc = upload(c, &d, host("melgan/out/kernel").data(), (size_t)7 * s.cin))) return rc;
+            s.w0 = d;
+            if ((rc = bias(&s.b0, "melgan/out/bias", "", 1))) return rc;
+        }
+    }
+    const size_t ws = (size_t)g.cfg.max_batch * g.cfg.max_frames * g.plan.ws_floats_per_frame * sizeof(float);
+    for (int k = 0; k < 2; ++k)
+        if ((rc = dev_alloc(c, (void**)&g.ws[k], ws))) return rc;
+    g.finalized = true;
+    return 0;
+}
+
+namespace { int melgan_call(gsttaco_ctx* c, const float* mel, const int32_t* frames, int B, int T, float* wav, int32_t* wav_lengths, int ld_wav,
+                            int only, void* stream); }
+
+int gsttaco_melgan(gsttaco_ctx* c, const float* mel, const int32_t* frames, int B, int T, float* wav, int32_t* wav_lengths, int ld_wav,
+                   void* stream) {
+    return melgan_call(c, mel, frames, B, T, wav, wav_lengths, ld_wav, -1, stream);
+}
+
+int gsttaco_melgan_debug_stage(gsttaco_ctx* c, int stage, const float* mel, const int32_t* frames, int B, int T, float* wav, int ld_wav,
+                               void* stream) {
+    if (!c) return GSTTACO_E_INVALID;
+    if (stage < 0 || stage >= c->mg.plan.n_stages) return fail(c, GSTTACO_E_INVALID, "melgan: no such launch");
+    return melgan_call(c, mel, frames, B, T, wav, nullptr, ld_wav, stage, stream);
+}
+
+namespace {
+int melgan_call(gsttaco_ctx* c, const float* mel, const int32_t* frames, int B, int T, float* wav, int32_t* wav_lengths, int ld_wav,
+                int only, void* stream) {
+    if (!c) return GSTTACO_E_INVALID;
+    const gsttaco_ctx::Melgan& g = c->mg;
+    if (!g.finalized) return fail(c, GSTTACO_E_WEIGHTS, "melgan: weights not finalized (gsttaco_melgan_finalize)");
+    if (!mel || !wav) return fail(c, GSTTACO_E_INVALID, "null argument");
+    if (B < 1 || T < 1) return fail(c, GSTTACO_E_INVALID, "bad B / T");
+    if (B > g.cfg.max_batch || T > g.cfg.max_frames) return fail(c, GSTTACO_E_CAPACITY, "melgan: B or T exceeds the capacity given at configure");
+    if ((int64_t)ld_wav < (int64_t)T * g.plan.hop) return fail(c, GSTTACO_E_INVALID, "ld_wav must be >= T * hop");
+    MgCall a{};
+    a.mel = mel; a.frames = frames; a.wav = wav; a.wav_lengths = wav_lengths; a.ws[0] = g.ws[0]; a.ws[1] = g.ws[1];
+    a.B = B; a.T = T; a.ld_wav = ld_wav; a.only = only;
+    HIPCHECK(c, gt_launch_melgan(g.plan, a, (hipStream_t)stream));
+    return 0;
+}
+}  // namespace
+
+int gsttaco_melgan_plan(const gsttaco_ctx* c, int32_t fields[]) {
+    if (!c || !fields) return GSTTACO_E_INVALID;
+    const gsttaco_ctx::Melgan& g = c->mg;
+    if (!g.configured) return fail(c, GSTTACO_E_WEIGHTS, "melgan: not configured (gsttaco_melgan_configure)");
+    fields[0] = g.plan.n_stages; fields[1] = g.plan.min_frames; fields[2] = g.plan.hop;
+    for (int i = 0; i < g.plan.n_stages; ++i) {
+        const MgStage& s = g.plan.st[i];
+        int32_t* f = fields + 3 + GSTTACO_MELGAN_PLAN_STRIDE * i;
+        f[0] = s.kind; f[1] = s.cout; f[2] = s.tile; f[3] = s.form; f[4] = s.kind == GT_MG_UP ? s.rate_in : s.rate_out; f[5] = (int32_t)s.lds;
+    }
     return 0;
 }
 

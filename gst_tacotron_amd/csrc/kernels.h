@@ -640,3 +640,46 @@ struct TsneMapArgs {
     int N, first_iter, iters, stop_lying_iter, mom_switch_iter;
 };
 hipError_t gt_launch_style_map(const TsneMapArgs& a, hipStream_t stream);
+
+
+// ---------------------------------------------------------------- melgan.hip
+// The neural vocoder: the MelGAN generator, mel -> waveform (the contract: gsttaco_melgan in include/gsttaco.h).
+#define GT_MG_MAX_RATIOS 8
+#define GT_MG_MAX_RES 8
+#define GT_MG_MAX_STAGES (2 + GT_MG_MAX_RATIOS * (1 + GT_MG_MAX_RES))
+#define GT_MG_LDS_MAX (160 * 1024)
+enum { GT_MG_IN = 0, GT_MG_UP = 1, GT_MG_RES = 2, GT_MG_OUT = 3 };
+// One launch of the chain.  Channel counts with _p are the padded ones (multiples of 16) the fragment packs and the workspace use.
+struct MgStage {
+    int kind;
+    int cin, cout;              // the network's channel counts
+    int cin_p, n_p;
+    int rate_in, rate_out;      // samples per mel frame of the stage's input and output
+    int r, dil;                 // GT_MG_UP: the ratio;  GT_MG_RES: the dilation
+    int tile, form;             // time tile (GT_MG_UP: in input positions, else in output samples); form: N-tiles a wave item owns (GT_MG_OUT: 0)
+    size_t lds;                 // dynamic LDS of a workgroup, bytes
+    // device operands (gsttaco_melgan_finalize).  GT_MG_RES: w0 / b0 = conv3, w1 = shortcut, w2 = conv1, b1 = the two biases summed
+    const float *w0, *b0, *w1, *w2, *b1;
+};
+struct MgPlan {
+    int n_stages;
+    MgStage st[GT_MG_MAX_STAGES];
+    int mel_dim, hop, min_frames;
+    float slope;
+    size_t ws_floats_per_frame;     // the largest activation of the chain, floats per mel frame of one row
+};
+// Fills the plan's shapes, tiles and LDS sizes (no device use).  Returns NULL, or the reason the configuration cannot run.
+const char* gt_melgan_make_plan(int mel_dim, int base, int n_ratios, const int* ratios, int n_res, float slope, MgPlan* plan);
+// [taps * cin, cout] (row stride cout) -> the fragment pack [taps][cin_p / 16][n_p][4][4] the kernels read, zero padded
+void gt_melgan_pack(const float* w, int taps, int cin, int cout, float* out);
+hipError_t gt_melgan_prepare();
+struct MgCall {
+    const float* mel;           // [B, T, mel_dim]
+    const int32_t* frames;      // [B] or NULL
+    float* wav;                 // [B, ld_wav]
+    int32_t* wav_lengths;       // [B] or NULL
+    float* ws[2];               // ping-pong activations, B * T * ws_floats_per_frame floats each
+    int B, T, ld_wav;
+    int only;                   // -1: the whole chain; else that launch alone, on what the workspace holds (timing: gsttaco_melgan_debug_stage)
+};
+hipError_t gt_launch_melgan(const MgPlan& plan, const MgCall& call, hipStream_t stream);

@@ -8,6 +8,9 @@ flattened into the handful of integers the C-ABI ``gsttaco_config`` needs.
 Additive keys (absent in the reference, defaults reproduce it):
   Tacotron2.Decoder.Attention.Sigmoid_Noise  -- SMA default 2.0 (Steps.py:212),
                                                  BMA default 0.0 (Steps.py:58)
+  Vocoder_MelGAN                              -- optional: {"Base_Filters": 32, "Upsample_Ratios": [8, 8, 2, 2],
+                                                 "Residual_Layers": 3, "Checkpoint_Path": null}, the neural vocoder
+                                                 (gst_tacotron_amd.melgan); absent, nothing changes
 """
 import copy
 import json
@@ -29,9 +32,27 @@ def load_hp(source=None):
     if source is None:
         source = DEFAULT_HP_PATH
     if isinstance(source, dict):
-        return copy.deepcopy(source)
-    with open(source, "r") as f:
-        return json.load(f)
+        hp = copy.deepcopy(source)
+    else:
+        with open(source, "r") as f:
+            hp = json.load(f)
+    check_melgan_section(hp)
+    return hp
+
+
+def check_melgan_section(hp):
+    """The optional Vocoder_MelGAN section: its upsampling ratios must multiply to Sound.Frame_Shift, or the waveform would not
+    have the mel frames' hop."""
+    sec = hp.get("Vocoder_MelGAN")
+    if sec is None:
+        return
+    ratios = [int(r) for r in sec.get("Upsample_Ratios", [8, 8, 2, 2])]
+    prod = 1
+    for r in ratios:
+        prod *= r
+    shift = int(hp["Sound"]["Frame_Shift"])
+    if prod != shift:
+        raise ValueError("Vocoder_MelGAN.Upsample_Ratios {} multiply to {}, Sound.Frame_Shift is {}".format(ratios, prod, shift))
 
 
 def load_token_dict(hp=None, base_dir=None):

@@ -88,6 +88,7 @@ class GST_Tacotron:
                                 max_batch=max_batch, max_tokens=max_tokens, max_ref_frames=max_ref_frames,
                                 max_wav_seconds=max_wav_seconds if self.dims.audio else 0.0)
         self._ready = False
+        self._melgan = None                 # the loaded neural vocoder's MelGANConfig (Load_Neural_Vocoder)
         self.seed = 0
 
     # ------------------------------------------------------------------ weights
@@ -884,7 +885,7 @@ class GST_Tacotron:
         return mels[:, :n + 1].contiguous(), specs[:, :n + 1].contiguous(), out_len
 
     def Inference(self, sentence_List, wav_List_for_GST=None, label=None, export=False, style_embeddings=None,
-                  style_token_weights=None, seeds=None, **kwargs):
+                  style_token_weights=None, seeds=None, vocoder="griffin_lim", **kwargs):
         """reference Model.py:342-367.  ``wav_List_for_GST`` holds wav paths / 1-D sample arrays like the reference's,
         or precomputed mels [T, Mel_Dim].  The reference always starts its export thread; here ``export=True`` asks for
         it (it needs the CBHG vocoder and Griffin-Lim, which are off the mel-frame metric) and runs it synchronously.
@@ -892,7 +893,10 @@ class GST_Tacotron:
         ``style_token_weights`` [Head, Style_Token.Size], [1, Head, Size] or [B, Head, Size] -- composed with no query
         (``Style_Compose``: outside the training distribution, see there) and then used as embeddings.
         ``seeds`` [B] (extension): per-utterance seeds (see ``Inference_Step``); the call then runs with ``masked=True`` -- without
-        masking the batch's padding reaches every utterance, which is what the seeds exist to rule out."""
+        masking the batch's padding reaches every utterance, which is what the seeds exist to rule out.
+        ``vocoder`` (extension): what ``export=True`` makes the WAVs with -- "griffin_lim" (the reference's, the default) or "melgan"
+        (``Load_Neural_Vocoder`` first; see ``Export_Inference``)."""
+        self._check_vocoder(vocoder)
         print("Inference running...")
         if seeds is not None:
             kwargs["seeds"], kwargs["masked"] = seeds, True
@@ -920,8 +924,65 @@ class GST_Tacotron:
         self.synchronize()                     # the reference returns finished arrays; also where a give-up of this call surfaces
         if export:
             self.Export_Inference(sentence_List, out[0], out[1], out[2], out[3],
-                                  label or datetime.now().strftime("%Y%m%d.%H%M%S"))
+                                  label or datetime.now().strftime("%Y%m%d.%H%M%S"), vocoder=vocoder)
         return out
+
+    # ------------------------------------------------------------------ the neural vocoder
+    def _check_vocoder(self, vocoder):
+        if vocoder not in ("griffin_lim", "melgan"):
+            raise ValueError("vocoder must be 'griffin_lim' or 'melgan'")
+        if vocoder == "melgan" and self._melgan is None:
+            raise capi.GstTacoError(-4, "vocoder='melgan' needs Load_Neural_Vocoder first")
+
+    def Load_Neural_Vocoder(self, weights_or_path=None, config=None, max_frames=None):
+        """Extension: loads the MelGAN generator (``gsttaco_melgan_*``, gst_tacotron_amd.melgan) into this model's context, once.
+        ``weights_or_path``: named folded arrays (``melgan.synthetic_weights`` / ``melgan.from_state_dict``) or the path of a
+        generator checkpoint in the public layout (``melgan.load``; None: ``Vocoder_MelGAN.Checkpoint_Path``).  ``config``: a ``melgan.MelGANConfig``; by default the
+        Hyper_Parameters' ``Vocoder_MelGAN`` section, else what the arrays' shapes say.  ``max_frames``: the longest mel a call may
+        bring (default Max_Step); the batch capacity is the model's.  Its Mel_Dim must be the model's and, where the Sound section
+        is complete, its hop Sound.Frame_Shift."""
+        from . import melgan
+        if weights_or_path is None:
+            weights_or_path = (self.hp_Dict.get("Vocoder_MelGAN") or {}).get("Checkpoint_Path")
+            if weights_or_path is None:
+                raise ValueError("no weights given and Hyper_Parameters has no Vocoder_MelGAN.Checkpoint_Path")
+        weights = melgan.load(weights_or_path) if isinstance(weights_or_path, (str, os.PathLike)) else weights_or_path
+        cfg = config or melgan.from_hp(self.hp_Dict) or melgan.infer_config(weights)
+        if cfg.mel_dim != self.dims.mel:
+            raise ValueError("the vocoder's mel_dim {} is not Sound.Mel_Dim {}".format(cfg.mel_dim, self.dims.mel))
+        if self.dims.audio and cfg.hop != self.dims.frame_shift:
+            raise ValueError("the vocoder's ratios multiply to {}, Sound.Frame_Shift is {}".format(cfg.hop, self.dims.frame_shift))
+        melgan.check_weights(cfg, weights)
+        if not torch.cuda.is_available():
+            raise capi.GstTacoError(-2, "no HIP device: the gfx950 kernels are the only compute path (no CPU fallback)")
+        self.ctx.melgan_configure(cfg, self.ctx.cfg.max_batch, int(max_frames or self.dims.max_step))
+        self.ctx.melgan_load_weights(weights)
+        with torch.cuda.device(self.device):
+            self.ctx.melgan_finalize()
+        self._melgan = cfg
+        return self
+
+    def Neural_Vocoder(self, mels, mel_lengths=None):
+        """Extension: mels [B, T, Mel_Dim], normalised exactly as ``Inference_Step`` and ``Inference_GTA`` produce them (what a vocoder
+        trained on GTA mels sees: no de-normalisation), torch or numpy, with ``mel_lengths`` [B] or None (all frames) ->
+        (wav float32 [B, T * hop] in [-1, 1], wav_lengths int32 [B]) on the device (``gsttaco_melgan``).  Row b uses its own
+        ``mel_lengths[b]`` frames everywhere -- its samples are bitwise those of the row run alone -- and is zero beyond
+        ``wav_lengths[b] = mel_lengths[b] * hop``; rows shorter than the vocoder's ``min_frames`` come out with length 0."""
+        if self._melgan is None:
+            raise capi.GstTacoError(-4, "no neural vocoder loaded (call Load_Neural_Vocoder first)")
+        x = self._dev(mels, torch.float32)
+        if x.dim() != 3 or x.shape[2] != self._melgan.mel_dim or x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError("mels must be [batch, frames >= 1, Mel_Dim]")
+        B, T = int(x.shape[0]), int(x.shape[1])
+        fr = self._dev(mel_lengths, torch.int32)
+        if fr is not None and tuple(fr.shape) != (B,):
+            raise ValueError("mel_lengths must be [batch]")
+        ld = T * self._melgan.hop
+        wav = torch.empty((B, ld), dtype=torch.float32, device=self.device)
+        lens = torch.empty((B,), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            self.ctx.check(self.ctx.lib.gsttaco_melgan(self.ctx.handle, _ptr(x), _ptr(fr), B, T, _ptr(wav), _ptr(lens), ld, self._stream()))
+        return wav, lens
 
     def Inference_Checked(self, sentence_List, wav_List_for_GST=None, style_embeddings=None, style_token_weights=None, seeds=None,
                           max_attempts=3, accept=None, export=False, label=None, **kwargs):
@@ -1039,17 +1100,24 @@ class GST_Tacotron:
                 self._stream()))
         return wav, lens
 
-    def Export_Inference(self, sentence_List, mel_List, stop_List, spectrogram_List, alignment_List, label, plot=True):
+    def Export_Inference(self, sentence_List, mel_List, stop_List, spectrogram_List, alignment_List, label, plot=True, vocoder="griffin_lim"):
         """reference Model.py:369-427: per utterance a figure (Plot/<label>.IDX_<i>.PNG) and the Griffin-Lim wav of the
-        spectrogram cut at the stop token (Wav/<label>.IDX_<i>.WAV) under Inference_Path.  Returns the wav paths."""
+        spectrogram cut at the stop token (Wav/<label>.IDX_<i>.WAV) under Inference_Path.  Returns the wav paths.
+        ``vocoder="melgan"`` (extension): the WAVs are ``Neural_Vocoder`` of the post-net mels, cut at the ``frames`` column of
+        ``Utterance_Report``, in place of Griffin-Lim; the figures are unchanged."""
         from . import export
+        self._check_vocoder(vocoder)
         root = self.hp_Dict["Inference_Path"]
         os.makedirs(os.path.join(root, "Plot"), exist_ok=True)
         os.makedirs(os.path.join(root, "Wav"), exist_ok=True)
         stops = np.asarray(stop_List.cpu() if torch.is_tensor(stop_List) else stop_List, dtype=np.float32)
         slice_idx = [export.stop_slice_index(s) for s in stops]
         frames = np.array([max(1, i) * self.dims.r for i in slice_idx], dtype=np.int32)           # Model.py:415
-        wav, lens = self.Inv_Spectrogram(spectrogram_List, frames=frames)
+        if vocoder == "melgan":
+            report, _ = self.Utterance_Report(stop_List, alignment_List)
+            wav, lens = self.Neural_Vocoder(mel_List, report[:, 1].contiguous())
+        else:
+            wav, lens = self.Inv_Spectrogram(spectrogram_List, frames=frames)
         wav, lens = wav.cpu().numpy(), lens.cpu().numpy()
         to_np = lambda a: np.asarray(a.cpu() if torch.is_tensor(a) else a, dtype=np.float32)
         mels, specs, aligns = to_np(mel_List), to_np(spectrogram_List), to_np(alignment_List)

@@ -556,6 +556,73 @@ int gsttaco_style_map(gsttaco_ctx* ctx, const double* p, int N, double* y, doubl
                       int first_iter, int iters, float exaggeration, int stop_lying_iter, int mom_switch_iter,
                       float momentum, float final_momentum, float eta, double* kl, void* stream);
 
+/* The neural vocoder: the MelGAN generator, mel -> waveform (EXTENSION, DESIGN row A22; Kumar et al., NeurIPS 2019, and its public
+ * implementation).  One per context, owned by it and freed by gsttaco_destroy; gsttaco_config and the model's manifest know nothing of it.
+ * The network, with mult = 2^n_ratios, x [T, mel_dim] and L(.) = LeakyReLU(slope):
+ *   input    reflection-pad 3 each side, Conv1D mel_dim -> mult * base, 7 taps, bias
+ *   per ratio r (C the channels so far): L; ConvTranspose1D C -> C/2, kernel 2r, stride r, padding r/2, bias: the output length is exactly
+ *            r * len, every output sample has two taps, and beyond its ends the input counts as absent (zero), not reflected.  Then
+ *            n_res residual blocks, block j = 0 .. n_res - 1 at dilation d = 3^j:
+ *              y = shortcut(x) + conv1(L(conv3_d(reflect_pad_d(L(x)))))
+ *            shortcut and conv1 1-tap convs C/2 -> C/2, conv3_d a 3-tap conv at dilation d, all three with bias.
+ *   output   L, reflection-pad 3, Conv1D base -> 1, 7 taps, bias, tanh
+ * T frames give exactly T * prod(ratios) samples in [-1, 1].  Weight normalisation is folded on the host; the device sees plain weights.
+ * Rows have lengths: row b uses frames[b] frames, and every reflection and every transposed-conv edge is taken at the row's own length
+ * at that stage, frames[b] * prod(ratios so far).  A row's samples are bitwise those of the row run alone, whatever batch, T or
+ * capacity it ran in: every output has one summation order (bias, taps ascending, channels ascending in groups of 16; fp32 MFMA, no
+ * atomics).  A row shorter than min_frames = max(4, floor(3^(n_res-1) / ratios[0]) + 1) -- reflection needs pad < length -- gets
+ * length 0; frames[b] > T counts as T.  Samples beyond a row's length, up to ld_wav, are written as zeros. */
+typedef struct gsttaco_melgan_config {
+    int32_t mel_dim;            /* 80 */
+    int32_t base;               /* 32: channels in front of the output conv (ngf) */
+    int32_t n_ratios;           /* 4 */
+    int32_t ratios[GSTTACO_MAX_LAYERS];     /* 8, 8, 2, 2: even, their product is the hop */
+    int32_t n_res;              /* 3 */
+    float slope;                /* 0.2 */
+    int32_t max_batch, max_frames;          /* capacity of a call */
+} gsttaco_melgan_config;
+
+/* Fixes the sizes and builds the vocoder's manifest.  No GPU use.  GSTTACO_E_INVALID with a message: an odd ratio (it would need
+ * output_padding), mel_dim / base / n_res / a capacity < 1, n_res > 8, more than 8 ratios, a slope outside [0, 1], a stage whose
+ * tile cannot fit in 160 KB of LDS, or a context whose vocoder is configured already. */
+int gsttaco_melgan_configure(gsttaco_ctx* ctx, const gsttaco_melgan_config* cfg);
+
+/* The vocoder's own manifest (gsttaco_num_weights of the model is unchanged), plain folded fp32 in the [taps * cin, cout] convention:
+ *   melgan/in/kernel [7 * mel_dim, mult * base]      melgan/in/bias [mult * base]
+ *   melgan/up<i>/kernel [2r, cin, cout]               melgan/up<i>/bias [cout]            (i = 0 .. n_ratios - 1; tap k, as torch's [cin, cout, k])
+ *   melgan/up<i>/res<j>/conv3/kernel [3 * C, C], .../conv1/kernel [C, C], .../shortcut/kernel [C, C], each with .../bias [C]
+ *   melgan/out/kernel [7 * base, 1]                   melgan/out/bias [1]
+ * GSTTACO_E_WEIGHTS: an unknown name, a wrong shape, a load before configure or after finalize. */
+int gsttaco_melgan_num_weights(const gsttaco_ctx* ctx);
+int gsttaco_melgan_weight_info(const gsttaco_ctx* ctx, int i, const char** name, int64_t shape[4], int* ndim);
+int gsttaco_melgan_load_weight(gsttaco_ctx* ctx, const char* name, const float* host, const int64_t* shape, int ndim);
+
+/* Repacks the weights into the kernels' fragment order (channel counts zero-padded to multiples of 16), uploads them and allocates the
+ * workspace for the capacity: 2 * max_batch * max_frames * (the widest activation, 8192 floats per frame at the defaults) floats.
+ * GSTTACO_E_WEIGHTS when a tensor was not loaded. */
+int gsttaco_melgan_finalize(gsttaco_ctx* ctx);
+
+/* mel : [B, T, mel_dim] float32 (DEVICE), normalised as gsttaco_inference_step writes it   frames : [B] int32 (DEVICE) or NULL = T
+ * wav : [B, ld_wav] float32 (DEVICE), ld_wav >= T * hop   wav_lengths : [B] int32 (DEVICE) or NULL, written
+ * 2 + n_ratios * (1 + n_res) plain launches on the caller's stream: no allocation, no synchronisation, capturable in a graph.
+ * GSTTACO_E_WEIGHTS before gsttaco_melgan_finalize; GSTTACO_E_CAPACITY: B > max_batch or T > max_frames; GSTTACO_E_INVALID: a NULL
+ * mel / wav, B or T < 1, ld_wav < T * hop. */
+int gsttaco_melgan(gsttaco_ctx* ctx, const float* mel, const int32_t* frames, int B, int T, float* wav, int32_t* wav_lengths,
+                   int ld_wav, void* stream);
+
+/* Test support: what the launches of a configured vocoder are.  fields[0] = the number of launches S, fields[1] = min_frames,
+ * fields[2] = hop; then per launch GSTTACO_MELGAN_PLAN_STRIDE ints: kind (0 input conv, 1 transposed conv, 2 residual block, 3 output
+ * conv), output channels, the time tile (kind 1: in input positions 0 .. len inclusive; else in output samples), the kernel form
+ * (N-tiles of 16 channels a wave owns per item; 0 for kind 3), samples per frame of the tile's unit, dynamic LDS bytes.
+ * fields holds GSTTACO_MELGAN_PLAN_INTS ints.  Launches nothing.
+ * gsttaco_melgan_debug_stage (timing support, tools/melgan_time.py): launch `stage` (0 .. S - 1) of gsttaco_melgan alone, with the
+ * same arguments and checks, on whatever activations the workspace holds from an earlier whole call of the same B and T. */
+int gsttaco_melgan_debug_stage(gsttaco_ctx* ctx, int stage, const float* mel, const int32_t* frames, int B, int T, float* wav, int ld_wav,
+                               void* stream);
+#define GSTTACO_MELGAN_PLAN_STRIDE 6
+#define GSTTACO_MELGAN_PLAN_INTS (3 + 6 * 74)
+int gsttaco_melgan_plan(const gsttaco_ctx* ctx, int32_t fields[]);
+
 /* hipGraph cache policy.  Every entry point replays one cached graph executable per (entry, B, Tv, Tref1, steps, flags) key.
  * The cache is LRU-bounded to `max_cached` executables (default 16 -- an Inference_Step replays two or three: encoder segment, GST + decode + postnet, vocoder; GSTTACO_GRAPH_CACHE; 0 = no graphs, everything is
  * enqueued eagerly on the caller's stream); the least recently used one is destroyed when a new shape is captured.
