@@ -43,7 +43,13 @@ EXPORTED_SYMBOLS = (
     "gsttaco_style_affinities", "gsttaco_style_map",
     "gsttaco_melgan_configure", "gsttaco_melgan_num_weights", "gsttaco_melgan_weight_info", "gsttaco_melgan_load_weight",
     "gsttaco_melgan_finalize", "gsttaco_melgan", "gsttaco_melgan_plan", "gsttaco_melgan_debug_stage",
+    "gsttaco_waveglow_configure", "gsttaco_waveglow_num_weights", "gsttaco_waveglow_weight_info", "gsttaco_waveglow_load_weight",
+    "gsttaco_waveglow_finalize", "gsttaco_waveglow_noise", "gsttaco_waveglow", "gsttaco_waveglow_plan", "gsttaco_waveglow_debug_stage",
 )
+# gsttaco_waveglow_plan: ints per launch (kind, channels, tile, form, unit, lds), the launch kinds, and the size of its array
+WAVEGLOW_PLAN_FIELDS = ("kind", "channels", "tile", "form", "unit", "lds")
+WAVEGLOW_KINDS = ("up", "layer", "flow")
+WAVEGLOW_PLAN_INTS = 3 + 6 * 354
 # gsttaco_melgan_plan: ints per launch (kind, channels, tile, form, rate, lds), the launch kinds, and the size of its array
 MELGAN_PLAN_FIELDS = ("kind", "channels", "tile", "form", "rate", "lds")
 MELGAN_KINDS = ("in", "up", "res", "out")
@@ -125,6 +131,11 @@ class MelganConfig(ctypes.Structure):
                 ("n_res", ctypes.c_int32), ("slope", ctypes.c_float), ("max_batch", ctypes.c_int32), ("max_frames", ctypes.c_int32)]
 
 
+class WaveglowConfig(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_int32) for name in ("mel_dim", "hop", "win", "n_group", "n_flows", "n_early_every", "n_early_size",
+                                                    "n_layers", "n_channels", "kernel", "max_batch", "max_frames")]
+
+
 class GstTacoError(RuntimeError):
     def __init__(self, code, message):
         super().__init__("gsttaco error {}: {}".format(code, message))
@@ -195,6 +206,18 @@ def load_library(path=None):
     lib.gsttaco_melgan_debug_stage.restype = ctypes.c_int
     for fn in ("gsttaco_melgan_configure", "gsttaco_melgan_num_weights", "gsttaco_melgan_weight_info", "gsttaco_melgan_load_weight",
                "gsttaco_melgan_finalize", "gsttaco_melgan", "gsttaco_melgan_plan"):
+        getattr(lib, fn).restype = ctypes.c_int
+    lib.gsttaco_waveglow_configure.argtypes = [vp, ctypes.POINTER(WaveglowConfig)]
+    lib.gsttaco_waveglow_num_weights.argtypes = [vp]
+    lib.gsttaco_waveglow_weight_info.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_int64 * 4), ctypes.POINTER(ctypes.c_int)]
+    lib.gsttaco_waveglow_load_weight.argtypes = [vp, ctypes.c_char_p, f32p, ctypes.POINTER(ctypes.c_int64), i32]
+    lib.gsttaco_waveglow_finalize.argtypes = [vp]
+    lib.gsttaco_waveglow_noise.argtypes = [vp, vp, i32, i32, vp, vp]
+    lib.gsttaco_waveglow.argtypes = [vp, vp, vp, i32, i32, f32, vp, vp, vp, vp, i32, vp]
+    lib.gsttaco_waveglow_plan.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
+    lib.gsttaco_waveglow_debug_stage.argtypes = [vp, i32, vp, vp, i32, i32, f32, vp, vp, vp, i32, vp]
+    for fn in ("gsttaco_waveglow_configure", "gsttaco_waveglow_num_weights", "gsttaco_waveglow_weight_info", "gsttaco_waveglow_load_weight",
+               "gsttaco_waveglow_finalize", "gsttaco_waveglow_noise", "gsttaco_waveglow", "gsttaco_waveglow_plan", "gsttaco_waveglow_debug_stage"):
         getattr(lib, fn).restype = ctypes.c_int
     lib.gsttaco_postnet.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.gsttaco_vocoder.argtypes = [vp, vp, i32, i32, vp, vp]
@@ -405,5 +428,47 @@ class Context:
         for i in range(f[0]):
             row = dict(zip(MELGAN_PLAN_FIELDS, f[3 + 6 * i: 9 + 6 * i]))
             row["kind"] = MELGAN_KINDS[row["kind"]]
+            stages.append(row)
+        return int(f[1]), int(f[2]), stages
+
+    # ---- the flow vocoder (gsttaco_waveglow_*): one per context
+    def waveglow_configure(self, cfg, max_batch, max_frames):
+        """``cfg``: a waveglow.WaveGlowConfig (or anything with its fields)."""
+        m = WaveglowConfig()
+        for name in ("mel_dim", "hop", "win", "n_group", "n_flows", "n_early_every", "n_early_size", "n_layers", "n_channels", "kernel"):
+            setattr(m, name, int(getattr(cfg, name)))
+        m.max_batch, m.max_frames = int(max_batch), int(max_frames)
+        self.check(self.lib.gsttaco_waveglow_configure(self.handle, ctypes.byref(m)))
+
+    def waveglow_manifest(self):
+        out = {}
+        for i in range(self.lib.gsttaco_waveglow_num_weights(self.handle)):
+            name, shape, nd = ctypes.c_char_p(), (ctypes.c_int64 * 4)(), ctypes.c_int()
+            self.check(self.lib.gsttaco_waveglow_weight_info(self.handle, i, ctypes.byref(name), ctypes.byref(shape), ctypes.byref(nd)))
+            out[name.value.decode()] = tuple(shape[k] for k in range(nd.value))
+        return out
+
+    def waveglow_load_weight(self, name, array):
+        a = np.ascontiguousarray(np.asarray(array, dtype=np.float32))
+        shape = (ctypes.c_int64 * max(a.ndim, 1))(*a.shape)
+        self.check(self.lib.gsttaco_waveglow_load_weight(self.handle, name.encode(), a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), shape, a.ndim))
+
+    def waveglow_load_weights(self, weights):
+        for name in self.waveglow_manifest():
+            if name not in weights:
+                raise KeyError("missing weight '{}'".format(name))
+            self.waveglow_load_weight(name, weights[name])
+
+    def waveglow_finalize(self):
+        self.check(self.lib.gsttaco_waveglow_finalize(self.handle))
+
+    def waveglow_plan(self):
+        """(hop, n_group, [one dict of WAVEGLOW_PLAN_FIELDS per launch, ``kind`` as a name of WAVEGLOW_KINDS])."""
+        f = (ctypes.c_int32 * WAVEGLOW_PLAN_INTS)()
+        self.check(self.lib.gsttaco_waveglow_plan(self.handle, f))
+        stages = []
+        for i in range(f[0]):
+            row = dict(zip(WAVEGLOW_PLAN_FIELDS, f[3 + 6 * i: 9 + 6 * i]))
+            row["kind"] = WAVEGLOW_KINDS[row["kind"]]
             stages.append(row)
         return int(f[1]), int(f[2]), stages

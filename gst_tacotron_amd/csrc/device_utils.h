@@ -185,6 +185,7 @@ __device__ __forceinline__ float gt_drop_keep(uint64_t seed, uint32_t step, uint
 // stream ids for the Philox counter's 4th word
 #define GT_RNG_PRENET0 0x1000u
 #define GT_RNG_NOISE   0x2000u
+#define GT_RNG_WAVEGLOW 0x8000u     // the flow vocoder's z: counter (column l, channel g, 0, this)
 
 __device__ __forceinline__ float gt_drop_keep(uint64_t seed, uint32_t step, uint32_t layer, uint32_t row, uint32_t col, uint32_t ncols,
                                              float rate) {

@@ -228,6 +228,16 @@ struct gsttaco_ctx {
         std::map<std::string, int> index;
         float* ws[2] = {nullptr, nullptr};
     } mg;
+    // The flow vocoder (gsttaco_waveglow_*): its own manifest, the plan that holds the device operands once finalized, and the
+    // workspace for the capacity (spect, the two hid, out, audio)
+    struct Waveglow {
+        bool configured = false, finalized = false;
+        gsttaco_waveglow_config cfg{};
+        WgPlan plan{};
+        std::vector<HostTensor> tensors;
+        std::map<std::string, int> index;
+        float *spect = nullptr, *hid[2] = {nullptr, nullptr}, *out = nullptr, *audio = nullptr;
+    } wg;
     // Resampling (gsttaco_resample): the tables of up to GT_RS_MAX_PAIRS rate pairs, least recently used evicted (ensure_resample_pair).
     // A slot's device memory and pinned host image are allocated at its first use and reused by the pairs that follow in it; `uploaded`
     // is recorded behind a slot's upload, and waited for before its host image is rewritten.
@@ -3339,6 +3349,250 @@ int gsttaco_melgan_plan(const gsttaco_ctx* c, int32_t fields[]) {
         int32_t* f = fields + 3 + GSTTACO_MELGAN_PLAN_STRIDE * i;
         f[0] = s.kind; f[1] = s.cout; f[2] = s.tile; f[3] = s.form; f[4] = s.kind == GT_MG_UP ? s.rate_in : s.rate_out; f[5] = (int32_t)s.lds;
     }
+    return 0;
+}
+
+// ---- the flow vocoder (waveglow.hip).  Configure and the manifest need no device; finalize inverts, repacks, uploads and allocates once.
+int gsttaco_waveglow_configure(gsttaco_ctx* c, const gsttaco_waveglow_config* m) {
+    if (!c) return GSTTACO_E_INVALID;
+    if (!m) return fail(c, GSTTACO_E_INVALID, "null argument");
+    gsttaco_ctx::Waveglow& g = c->wg;
+    if (g.configured) return fail(c, GSTTACO_E_INVALID, "waveglow: the context's flow vocoder is configured already");
+    if (m->kernel != 3) return fail(c, GSTTACO_E_INVALID, "waveglow: kernel must be 3 (the WN layers' taps are fixed)");
+    if (m->max_batch < 1) return fail(c, GSTTACO_E_INVALID, "waveglow: max_batch must be at least 1");
+    if (m->max_frames < 1) return fail(c, GSTTACO_E_INVALID, "waveglow: max_frames must be at least 1");
+    WgPlan plan;
+    const char* why = gt_waveglow_make_plan(m->mel_dim, m->hop, m->win, m->n_group, m->n_flows, m->n_early_every, m->n_early_size,
+                                            m->n_layers, m->n_channels, &plan);
+    if (why) return fail(c, GSTTACO_E_INVALID, std::string("waveglow: ") + why);
+    if ((double)m->max_batch * m->max_frames * plan.hop > 2147483647.0)
+        return fail(c, GSTTACO_E_INVALID, "waveglow: max_batch * max_frames * hop exceeds 2^31 - 1 samples");
+    g.cfg = *m;
+    g.plan = plan;
+    auto add = [&](const std::string& name, std::vector<int64_t> shape) {
+        HostTensor t;
+        t.name = name;
+        t.shape = std::move(shape);
+        g.index[name] = (int)g.tensors.size();
+        g.tensors.push_back(std::move(t));
+    };
+    const int64_t C = plan.C;
+    add("waveglow/up/kernel", {plan.win, plan.mel_dim, plan.mel_dim});
+    add("waveglow/up/bias", {plan.mel_dim});
+    for (int k = 0; k < plan.F; ++k) {
+        const std::string p = "waveglow/flow" + std::to_string(k);
+        const int64_t ck = plan.ck[k];
+        add(p + "/W", {ck, ck});
+        add(p + "/start/kernel", {ck / 2, C}); add(p + "/start/bias", {C});
+        add(p + "/end/kernel", {C, ck}); add(p + "/end/bias", {ck});
+        for (int i = 0; i < plan.NL; ++i) {
+            const std::string q = p + "/layer" + std::to_string(i);
+            const int64_t nrs = i == plan.NL - 1 ? C : 2 * C;
+            add(q + "/in/kernel", {3 * C, 2 * C}); add(q + "/in/bias", {2 * C});
+            add(q + "/cond/kernel", {plan.S, 2 * C}); add(q + "/cond/bias", {2 * C});
+            add(q + "/res_skip/kernel", {C, nrs}); add(q + "/res_skip/bias", {nrs});
+        }
+    }
+    g.configured = true;
+    return 0;
+}
+
+int gsttaco_waveglow_num_weights(const gsttaco_ctx* c) { return c ? (int)c->wg.tensors.size() : GSTTACO_E_INVALID; }
+
+int gsttaco_waveglow_weight_info(const gsttaco_ctx* c, int i, const char** name, int64_t shape[4], int* ndim) {
+    if (!c || i < 0 || i >= (int)c->wg.tensors.size()) return GSTTACO_E_INVALID;
+    const HostTensor& t = c->wg.tensors[i];
+    if (name) *name = t.name.c_str();
+    if (ndim) *ndim = (int)t.shape.size();
+    if (shape)
+        for (size_t d = 0; d < 4; ++d) shape[d] = d < t.shape.size() ? t.shape[d] : 1;
+    return 0;
+}
+
+int gsttaco_waveglow_load_weight(gsttaco_ctx* c, const char* name, const float* host, const int64_t* shape, int ndim) {
+    if (!c || !name || !host || !shape) return fail(c, GSTTACO_E_INVALID, "null argument");
+    gsttaco_ctx::Waveglow& g = c->wg;
+    if (!g.configured) return fail(c, GSTTACO_E_WEIGHTS, "waveglow: not configured (gsttaco_waveglow_configure)");
+    if (g.finalized) return fail(c, GSTTACO_E_WEIGHTS, "waveglow: weights already finalized");
+    auto it = g.index.find(name);
+    if (it == g.index.end()) return fail(c, GSTTACO_E_WEIGHTS, std::string("waveglow: unknown weight '") + name + "'");
+    HostTensor& t = g.tensors[it->second];
+    bool ok = ndim == (int)t.shape.size();
+    for (int d = 0; ok && d < ndim; ++d) ok = shape[d] == t.shape[d];
+    if (!ok) return fail(c, GSTTACO_E_WEIGHTS, std::string("waveglow: weight '") + name + "' has the wrong shape");
+    t.data.assign(host, host + t.numel());
+    t.loaded = true;
+    return 0;
+}
+
+namespace {
+// inverse of the n x n matrix w (row-major) in float64 by Gauss-Jordan elimination with partial pivoting; false: singular
+bool invert_f64(const float* w, int n, std::vector<double>& inv) {
+    std::vector<double> a((size_t)n * n);
+    for (int i = 0; i < n * n; ++i) a[i] = w[i];
+    inv.assign((size_t)n * n, 0.0);
+    for (int i = 0; i < n; ++i) inv[(size_t)i * n + i] = 1.0;
+    for (int col = 0; col < n; ++col) {
+        int piv = col;
+        for (int r = col + 1; r < n; ++r)
+            if (std::fabs(a[(size_t)r * n + col]) > std::fabs(a[(size_t)piv * n + col])) piv = r;
+        const double p = a[(size_t)piv * n + col];
+        if (!(std::fabs(p) > 0.0) || !std::isfinite(p)) return false;
+        if (piv != col)
+            for (int j = 0; j < n; ++j) { std::swap(a[(size_t)piv * n + j], a[(size_t)col * n + j]); std::swap(inv[(size_t)piv * n + j], inv[(size_t)col * n + j]); }
+        for (int j = 0; j < n; ++j) { a[(size_t)col * n + j] /= p; inv[(size_t)col * n + j] /= p; }
+        for (int r = 0; r < n; ++r) {
+            const double f = a[(size_t)r * n + col];
+            if (r == col || f == 0.0) continue;
+            for (int j = 0; j < n; ++j) { a[(size_t)r * n + j] -= f * a[(size_t)col * n + j]; inv[(size_t)r * n + j] -= f * inv[(size_t)col * n + j]; }
+        }
+    }
+    return true;
+}
+}  // namespace
+
+int gsttaco_waveglow_finalize(gsttaco_ctx* c) {
+    if (!c) return GSTTACO_E_INVALID;
+    gsttaco_ctx::Waveglow& g = c->wg;
+    if (!g.configured) return fail(c, GSTTACO_E_WEIGHTS, "waveglow: not configured (gsttaco_waveglow_configure)");
+    if (g.finalized) return fail(c, GSTTACO_E_WEIGHTS, "waveglow: weights already finalized");
+    for (const HostTensor& t : g.tensors)
+        if (!t.loaded) return fail(c, GSTTACO_E_WEIGHTS, "waveglow: weight '" + t.name + "' was not loaded");
+    int rc = ensure_device(c);
+    if (rc) return rc;
+    HIPCHECK(c, gt_waveglow_prepare());
+    WgPlan& P = g.plan;
+    auto host = [&](const std::string& name) -> const std::vector<float>& { return g.tensors[g.index[name]].data; };
+    std::vector<float> buf, bbuf;
+    auto up = [&](const float** dst, const std::vector<float>& v) {
+        float* d = nullptr;
+        int e = upload(c, &d, v.data(), v.size());
+        *dst = d;
+        return e;
+    };
+    const int C = P.C, C_p = P.C_p, n2 = 2 * C_p;
+    buf.resize((size_t)P.win * P.mel_p * P.mel_p);
+    gt_melgan_pack(host("waveglow/up/kernel").data(), P.win, P.mel_dim, P.mel_dim, buf.data());
+    if ((rc = up(&P.w_up, buf))) return rc;
+    buf.assign(P.mel_p, 0.f);
+    std::copy(host("waveglow/up/bias").begin(), host("waveglow/up/bias").end(), buf.begin());
+    if ((rc = up(&P.b_up, buf))) return rc;
+    std::vector<double> inv;
+    for (int k = 0; k < P.F; ++k) {
+        const std::string p = "waveglow/flow" + std::to_string(k);
+        const int ck = P.ck[k], h = ck / 2;
+        WgFlowOps& f = P.flow[k];
+        if (!invert_f64(host(p + "/W").data(), ck, inv)) return fail(c, GSTTACO_E_WEIGHTS, "waveglow: weight '" + p + "/W' is singular");
+        buf.assign(16 * 16, 0.f);
+        for (int i = 0; i < ck; ++i)
+            for (int j = 0; j < ck; ++j) buf[i * 16 + j] = (float)inv[(size_t)i * ck + j];
+        if ((rc = up(&f.winv, buf))) return rc;
+        buf.assign((size_t)h * C_p, 0.f);
+        for (int q = 0; q < h; ++q)
+            for (int n = 0; n < C; ++n) buf[(size_t)q * C_p + n] = host(p + "/start/kernel")[(size_t)q * C + n];
+        if ((rc = up(&f.w_start, buf))) return rc;
+        buf.assign(C_p, 0.f);
+        std::copy(host(p + "/start/bias").begin(), host(p + "/start/bias").end(), buf.begin());
+        if ((rc = up(&f.b_start, buf))) return rc;
+        buf.assign((size_t)C * 16, 0.f);
+        for (int n = 0; n < C; ++n)
+            for (int j = 0; j < ck; ++j) buf[(size_t)n * 16 + j] = host(p + "/end/kernel")[(size_t)n * ck + j];
+        if ((rc = up(&f.w_end, buf))) return rc;
+        buf.assign(16, 0.f);
+        std::copy(host(p + "/end/bias").begin(), host(p + "/end/bias").end(), buf.begin());
+        if ((rc = up(&f.b_end, buf))) return rc;
+        for (int i = 0; i < P.NL; ++i) {
+            const std::string q = p + "/layer" + std::to_string(i);
+            WgLayerOps& o = P.layer[k][i];
+            const bool last = i == P.NL - 1;
+            buf.resize((size_t)3 * C_p * n2);
+            gt_waveglow_pack_gate(host(q + "/in/kernel").data(), 3, C, C, buf.data());
+            if ((rc = up(&o.w_in, buf))) return rc;
+            buf.resize((size_t)P.S_p * n2);
+            gt_waveglow_pack_gate(host(q + "/cond/kernel").data(), 1, P.S, C, buf.data());
+            if ((rc = up(&o.w_cond, buf))) return rc;
+            buf.resize(n2);
+            gt_waveglow_gate_bias(host(q + "/in/bias").data(), host(q + "/cond/bias").data(), C, buf.data());
+            if ((rc = up(&o.b_ac, buf))) return rc;
+            const int nB = last ? C_p : n2;
+            buf.resize((size_t)C_p * nB);
+            bbuf.resize(nB);
+            gt_waveglow_pack_rs(host(q + "/res_skip/kernel").data(), host(q + "/res_skip/bias").data(), C, last, buf.data(), bbuf.data());
+            if ((rc = up(&o.w_rs, buf)) || (rc = up(&o.b_rs, bbuf))) return rc;
+        }
+    }
+    // the workspace for the capacity: max_batch * max_frames * hop / n_group columns of spect S_p, two hid C_p, out C_p and audio 16
+    const size_t cols = (size_t)g.cfg.max_batch * g.cfg.max_frames * (P.hop / P.G);
+    if ((rc = dev_alloc(c, (void**)&g.spect, cols * P.S_p * sizeof(float))) || (rc = dev_alloc(c, (void**)&g.hid[0], cols * C_p * sizeof(float))) ||
+        (rc = dev_alloc(c, (void**)&g.hid[1], cols * C_p * sizeof(float))) || (rc = dev_alloc(c, (void**)&g.out, cols * C_p * sizeof(float))) ||
+        (rc = dev_alloc(c, (void**)&g.audio, cols * 16 * sizeof(float)))) return rc;
+    g.finalized = true;
+    return 0;
+}
+
+int gsttaco_waveglow_noise(gsttaco_ctx* c, const uint64_t* seeds, int B, int T, float* z, void* stream) {
+    if (!c) return GSTTACO_E_INVALID;
+    const gsttaco_ctx::Waveglow& g = c->wg;
+    if (!g.configured) return fail(c, GSTTACO_E_WEIGHTS, "waveglow: not configured (gsttaco_waveglow_configure)");
+    if (!seeds || !z) return fail(c, GSTTACO_E_INVALID, "null argument");
+    if (B < 1 || T < 1) return fail(c, GSTTACO_E_INVALID, "bad B / T");
+    if ((double)B * T * g.plan.hop > 2147483647.0) return fail(c, GSTTACO_E_CAPACITY, "waveglow: B * T * hop exceeds 2^31 - 1 samples");
+    int rc = ensure_device(c);
+    if (rc) return rc;
+    HIPCHECK(c, gt_launch_waveglow_noise(seeds, z, B, T * g.plan.hop, g.plan.G, (hipStream_t)stream));
+    return 0;
+}
+
+namespace {
+int waveglow_call(gsttaco_ctx* c, const float* mel, const int32_t* frames, int B, int T, float sigma, const uint64_t* seeds, const float* z,
+                  float* wav, int32_t* wav_lengths, int ld_wav, int only, void* stream) {
+    if (!c) return GSTTACO_E_INVALID;
+    const gsttaco_ctx::Waveglow& g = c->wg;
+    if (!g.finalized) return fail(c, GSTTACO_E_WEIGHTS, "waveglow: weights not finalized (gsttaco_waveglow_finalize)");
+    if (!mel || !wav) return fail(c, GSTTACO_E_INVALID, "null argument");
+    if ((seeds != nullptr) == (z != nullptr)) return fail(c, GSTTACO_E_INVALID, "waveglow: exactly one of seeds and z must be given");
+    if (B < 1 || T < 1) return fail(c, GSTTACO_E_INVALID, "bad B / T");
+    if (!(sigma >= 0.f) || !std::isfinite(sigma)) return fail(c, GSTTACO_E_INVALID, "sigma must be finite and at least 0");
+    if (B > g.cfg.max_batch || T > g.cfg.max_frames) return fail(c, GSTTACO_E_CAPACITY, "waveglow: B or T exceeds the capacity given at configure");
+    if ((int64_t)ld_wav < (int64_t)T * g.plan.hop) return fail(c, GSTTACO_E_INVALID, "ld_wav must be >= T * hop");
+    WgCall a{};
+    a.mel = mel; a.frames = frames; a.seeds = seeds; a.z = z; a.wav = wav; a.wav_lengths = wav_lengths;
+    a.spect = g.spect; a.hid[0] = g.hid[0]; a.hid[1] = g.hid[1]; a.out = g.out; a.audio = g.audio;
+    a.B = B; a.T = T; a.ld_wav = ld_wav; a.sigma = sigma; a.only = only;
+    HIPCHECK(c, gt_launch_waveglow(g.plan, a, (hipStream_t)stream));
+    return 0;
+}
+}  // namespace
+
+int gsttaco_waveglow(gsttaco_ctx* c, const float* mel, const int32_t* frames, int B, int T, float sigma, const uint64_t* seeds, const float* z,
+                     float* wav, int32_t* wav_lengths, int ld_wav, void* stream) {
+    return waveglow_call(c, mel, frames, B, T, sigma, seeds, z, wav, wav_lengths, ld_wav, -1, stream);
+}
+
+int gsttaco_waveglow_debug_stage(gsttaco_ctx* c, int stage, const float* mel, const int32_t* frames, int B, int T, float sigma,
+                                 const uint64_t* seeds, const float* z, float* wav, int ld_wav, void* stream) {
+    if (!c) return GSTTACO_E_INVALID;
+    if (!c->wg.configured || stage < 0 || stage >= 2 + c->wg.plan.F * (c->wg.plan.NL + 1)) return fail(c, GSTTACO_E_INVALID, "waveglow: no such launch");
+    return waveglow_call(c, mel, frames, B, T, sigma, seeds, z, wav, nullptr, ld_wav, stage, stream);
+}
+
+int gsttaco_waveglow_plan(const gsttaco_ctx* c, int32_t fields[]) {
+    if (!c || !fields) return GSTTACO_E_INVALID;
+    const gsttaco_ctx::Waveglow& g = c->wg;
+    if (!g.configured) return fail(c, GSTTACO_E_WEIGHTS, "waveglow: not configured (gsttaco_waveglow_configure)");
+    const WgPlan& P = g.plan;
+    int n = 0;
+    auto put = [&](int kind, int channels, int tile, int form, int unit, size_t lds) {
+        int32_t* f = fields + 3 + GSTTACO_WAVEGLOW_PLAN_STRIDE * n++;
+        f[0] = kind; f[1] = channels; f[2] = tile; f[3] = form; f[4] = unit; f[5] = (int32_t)lds;
+    };
+    put(GT_WG_UP, P.mel_dim, P.up_tile, P.up_form, P.hop, P.up_lds);
+    put(GT_WG_FLOW, P.n_rem, GT_WG_FLOW_TILE, 0, P.G, P.flow_lds);
+    for (int k = P.F - 1; k >= 0; --k) {
+        for (int i = 0; i < P.NL; ++i) put(GT_WG_LAYER, P.C, P.tile, P.form, P.G, P.lds);
+        put(GT_WG_FLOW, P.ck[k], GT_WG_FLOW_TILE, 0, P.G, P.flow_lds);
+    }
+    fields[0] = n; fields[1] = P.hop; fields[2] = P.G;
     return 0;
 }
 

@@ -683,3 +683,54 @@ struct MgCall {
     int only;                   // -1: the whole chain; else that launch alone, on what the workspace holds (timing: gsttaco_melgan_debug_stage)
 };
 hipError_t gt_launch_melgan(const MgPlan& plan, const MgCall& call, hipStream_t stream);
+
+
+// ---------------------------------------------------------------- waveglow.hip
+// The flow vocoder: WaveGlow inference, mel -> waveform (the contract: gsttaco_waveglow in include/gsttaco.h).
+#define GT_WG_MAX_FLOWS 32
+#define GT_WG_MAX_LAYERS 10
+#define GT_WG_MAX_GROUP 16
+#define GT_WG_FLOW_TILE 64      // columns of a workgroup of gt_wg_flow_kernel
+enum { GT_WG_UP = 0, GT_WG_LAYER = 1, GT_WG_FLOW = 2 };
+// device operands (gsttaco_waveglow_finalize).  w_in / w_cond / b_ac: the gate GEMM's, columns in pair order (gt_waveglow_pack_gate),
+// b_ac the two biases summed;  w_rs / b_rs: res_skip, [res | skip] each padded to C_p (the last layer: skip only)
+struct WgLayerOps { const float *w_in, *w_cond, *b_ac, *w_rs, *b_rs; };
+// w_start [c_k / 2][C_p], b_start [C_p];  w_end [C][16], b_end [16];  winv [16][16] = inverse(W_k), zero padded
+struct WgFlowOps { const float *w_start, *b_start, *w_end, *b_end, *winv; };
+struct WgPlan {
+    int mel_dim, hop, win, G, F, EE, ES, NL, C;
+    int mel_p, C_p, S, S_p, n_rem;      // S = mel_dim * G; _p: rounded up to 16
+    int ck[GT_WG_MAX_FLOWS];            // channels of flow k
+    int up_tile, up_form;               // the upsampler: frames of a workgroup, N-tiles a wave item owns
+    int tile, form, kc;                 // the WN layer: columns of a workgroup, N-tiles of the gate GEMM a wave item owns, K chunk
+    size_t up_lds, lds, flow_lds;       // dynamic LDS of a workgroup, bytes
+    size_t ws_floats_per_column;        // spect S_p + hid 2 C_p + out C_p + audio 16
+    const float *w_up, *b_up;
+    WgFlowOps flow[GT_WG_MAX_FLOWS];
+    WgLayerOps layer[GT_WG_MAX_FLOWS][GT_WG_MAX_LAYERS];
+};
+// c_k = G - ES * #{j : 0 < j <= k, j % EE == 0}
+int gt_waveglow_flow_channels(int G, int EE, int ES, int k);
+// Fills the plan's shapes, tiles and LDS sizes (no device use).  Returns NULL, or the reason, which starts with the field's name.
+const char* gt_waveglow_make_plan(int mel_dim, int hop, int win, int G, int F, int EE, int ES, int NL, int C, WgPlan* plan);
+// in / cond [taps * cin, 2 C] -> the fragment pack of [taps][cin_p][2 C_p] with the columns in pair order: N-tile 2 j holds the tanh
+// half's channels 16 j .. 16 j + 15, N-tile 2 j + 1 the sigmoid half's; gate_bias: b_in + b_cond in that order [2 C_p]
+void gt_waveglow_pack_gate(const float* w, int taps, int cin, int C, float* out);
+void gt_waveglow_gate_bias(const float* b_in, const float* b_cond, int C, float* out);
+// res_skip [C, 2 C] (last: [C, C]) and its bias -> the fragment pack of [C_p][2 C_p] (last: [C_p][C_p]) and the padded bias
+void gt_waveglow_pack_rs(const float* w, const float* bias, int C, bool last, float* out, float* bias_out);
+hipError_t gt_waveglow_prepare();
+hipError_t gt_launch_waveglow_noise(const uint64_t* seeds, float* z, int B, int n, int G, hipStream_t stream);
+struct WgCall {
+    const float* mel;           // [B, T, mel_dim]
+    const int32_t* frames;      // [B] or NULL
+    const uint64_t* seeds;      // [B], or
+    const float* z;             // [B, T * hop]
+    float* wav;                 // [B, ld_wav]
+    int32_t* wav_lengths;       // [B] or NULL
+    float *spect, *hid[2], *out, *audio;        // the workspace, B * T * hop / G columns each
+    int B, T, ld_wav;
+    float sigma;
+    int only;                   // -1: the whole chain; else that launch alone (timing: gsttaco_waveglow_debug_stage)
+};
+hipError_t gt_launch_waveglow(const WgPlan& plan, const WgCall& call, hipStream_t stream);

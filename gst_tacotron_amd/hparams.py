@@ -11,6 +11,9 @@ Additive keys (absent in the reference, defaults reproduce it):
   Vocoder_MelGAN                              -- optional: {"Base_Filters": 32, "Upsample_Ratios": [8, 8, 2, 2],
                                                  "Residual_Layers": 3, "Checkpoint_Path": null}, the neural vocoder
                                                  (gst_tacotron_amd.melgan); absent, nothing changes
+  Vocoder_WaveGlow                            -- optional: {"Flows": 12, "Group": 8, "Early_Every": 4, "Early_Size": 2, "Layers": 8,
+                                                 "Channels": 256, "Upsample_Kernel": 1024, "Checkpoint_Path": null}, the flow
+                                                 vocoder (gst_tacotron_amd.waveglow; its hop is Sound.Frame_Shift); absent, nothing changes
 """
 import copy
 import json

@@ -89,6 +89,7 @@ class GST_Tacotron:
                                 max_wav_seconds=max_wav_seconds if self.dims.audio else 0.0)
         self._ready = False
         self._melgan = None                 # the loaded neural vocoder's MelGANConfig (Load_Neural_Vocoder)
+        self._waveglow = None               # the loaded flow vocoder's WaveGlowConfig (Load_WaveGlow)
         self.seed = 0
 
     # ------------------------------------------------------------------ weights
@@ -894,8 +895,9 @@ class GST_Tacotron:
         (``Style_Compose``: outside the training distribution, see there) and then used as embeddings.
         ``seeds`` [B] (extension): per-utterance seeds (see ``Inference_Step``); the call then runs with ``masked=True`` -- without
         masking the batch's padding reaches every utterance, which is what the seeds exist to rule out.
-        ``vocoder`` (extension): what ``export=True`` makes the WAVs with -- "griffin_lim" (the reference's, the default) or "melgan"
-        (``Load_Neural_Vocoder`` first; see ``Export_Inference``)."""
+        ``vocoder`` (extension): what ``export=True`` makes the WAVs with -- "griffin_lim" (the reference's, the default), "melgan"
+        (``Load_Neural_Vocoder`` first) or "waveglow" (``Load_WaveGlow`` first; an utterance's decode seed is also its vocoder seed,
+        without ``seeds`` every row's is 0); see ``Export_Inference``."""
         self._check_vocoder(vocoder)
         print("Inference running...")
         if seeds is not None:
@@ -924,15 +926,17 @@ class GST_Tacotron:
         self.synchronize()                     # the reference returns finished arrays; also where a give-up of this call surfaces
         if export:
             self.Export_Inference(sentence_List, out[0], out[1], out[2], out[3],
-                                  label or datetime.now().strftime("%Y%m%d.%H%M%S"), vocoder=vocoder)
+                                  label or datetime.now().strftime("%Y%m%d.%H%M%S"), vocoder=vocoder, seeds=seeds)
         return out
 
     # ------------------------------------------------------------------ the neural vocoder
     def _check_vocoder(self, vocoder):
-        if vocoder not in ("griffin_lim", "melgan"):
-            raise ValueError("vocoder must be 'griffin_lim' or 'melgan'")
+        if vocoder not in ("griffin_lim", "melgan", "waveglow"):
+            raise ValueError("vocoder must be 'griffin_lim', 'melgan' or 'waveglow'")
         if vocoder == "melgan" and self._melgan is None:
             raise capi.GstTacoError(-4, "vocoder='melgan' needs Load_Neural_Vocoder first")
+        if vocoder == "waveglow" and self._waveglow is None:
+            raise capi.GstTacoError(-4, "vocoder='waveglow' needs Load_WaveGlow first")
 
     def Load_Neural_Vocoder(self, weights_or_path=None, config=None, max_frames=None):
         """Extension: loads the MelGAN generator (``gsttaco_melgan_*``, gst_tacotron_amd.melgan) into this model's context, once.
@@ -982,6 +986,78 @@ class GST_Tacotron:
         lens = torch.empty((B,), dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
             self.ctx.check(self.ctx.lib.gsttaco_melgan(self.ctx.handle, _ptr(x), _ptr(fr), B, T, _ptr(wav), _ptr(lens), ld, self._stream()))
+        return wav, lens
+
+    # ------------------------------------------------------------------ the flow vocoder
+    def Load_WaveGlow(self, weights_or_path=None, config=None, max_frames=None):
+        """Extension: loads WaveGlow (``gsttaco_waveglow_*``, gst_tacotron_amd.waveglow) into this model's context, once, beside or
+        without the MelGAN generator.  ``weights_or_path``: named folded arrays (``waveglow.synthetic_weights`` /
+        ``waveglow.from_state_dict``) or the path of a file that holds a ``state_dict`` in the public layout (``waveglow.load``; None:
+        ``Vocoder_WaveGlow.Checkpoint_Path``).  ``config``: a ``waveglow.WaveGlowConfig``; by default the Hyper_Parameters'
+        ``Vocoder_WaveGlow`` section, else what the arrays' shapes say at hop = Sound.Frame_Shift.  ``max_frames``: the longest mel a
+        call may bring (default Max_Step); the batch capacity is the model's.  Its Mel_Dim must be the model's and, where the Sound
+        section is complete, its hop Sound.Frame_Shift."""
+        from . import waveglow
+        if weights_or_path is None:
+            weights_or_path = (self.hp_Dict.get("Vocoder_WaveGlow") or {}).get("Checkpoint_Path")
+            if weights_or_path is None:
+                raise ValueError("no weights given and Hyper_Parameters has no Vocoder_WaveGlow.Checkpoint_Path")
+        weights = waveglow.load(weights_or_path) if isinstance(weights_or_path, (str, os.PathLike)) else weights_or_path
+        cfg = config or waveglow.from_hp(self.hp_Dict) or waveglow.infer_config(weights, hop=int(self.hp_Dict["Sound"]["Frame_Shift"]))
+        cfg.check()
+        if cfg.mel_dim != self.dims.mel:
+            raise ValueError("the vocoder's mel_dim {} is not Sound.Mel_Dim {}".format(cfg.mel_dim, self.dims.mel))
+        if self.dims.audio and cfg.hop != self.dims.frame_shift:
+            raise ValueError("the vocoder's hop {} is not Sound.Frame_Shift {}".format(cfg.hop, self.dims.frame_shift))
+        waveglow.check_weights(cfg, weights)
+        if not torch.cuda.is_available():
+            raise capi.GstTacoError(-2, "no HIP device: the gfx950 kernels are the only compute path (no CPU fallback)")
+        self.ctx.waveglow_configure(cfg, self.ctx.cfg.max_batch, int(max_frames or self.dims.max_step))
+        self.ctx.waveglow_load_weights(weights)
+        with torch.cuda.device(self.device):
+            self.ctx.waveglow_finalize()
+        self._waveglow = cfg
+        return self
+
+    def WaveGlow(self, mels, mel_lengths=None, sigma=0.6, seeds=None, z=None):
+        """Extension: mels [B, T, Mel_Dim], normalised exactly as ``Inference_Step`` and ``Inference_GTA`` produce them, torch or numpy,
+        with ``mel_lengths`` [B] or None (all frames) -> (wav float32 [B, T * hop], wav_lengths int32 [B]) on the device
+        (``gsttaco_waveglow``).  The waveform is sampled: ``sigma`` is the temperature, and the noise is either drawn on the device from
+        ``seeds`` [B] (integers mod 2^64; None: 0 for every row) or given as ``z`` [B, T * hop] -- not both.  A row's noise depends on its
+        seed and the sample's position only, and row b uses its own ``mel_lengths[b]`` frames everywhere: its samples are bitwise those
+        of the row run alone.  The output is NOT bounded by 1 (a flow has no tanh); the WAV writer clips.  Beyond
+        ``wav_lengths[b] = mel_lengths[b] * hop`` a row is zeros."""
+        if self._waveglow is None:
+            raise capi.GstTacoError(-4, "no flow vocoder loaded (call Load_WaveGlow first)")
+        if seeds is not None and z is not None:
+            raise ValueError("seeds and z are mutually exclusive")
+        x = self._dev(mels, torch.float32)
+        if x.dim() != 3 or x.shape[2] != self._waveglow.mel_dim or x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError("mels must be [batch, frames >= 1, Mel_Dim]")
+        B, T = int(x.shape[0]), int(x.shape[1])
+        fr = self._dev(mel_lengths, torch.int32)
+        if fr is not None and tuple(fr.shape) != (B,):
+            raise ValueError("mel_lengths must be [batch]")
+        ld = T * self._waveglow.hop
+        dev_seeds = None
+        if z is not None:
+            z = self._dev(z, torch.float32)
+            if tuple(z.shape) != (B, ld):
+                raise ValueError("z must be [batch, frames * hop]")
+        else:
+            if seeds is None:
+                seeds = [0] * B
+            if torch.is_tensor(seeds):
+                seeds = seeds.cpu().numpy()
+            vals = [int(v) & checked.MASK64 for v in np.asarray(seeds, dtype=object).reshape(-1)]
+            if np.ndim(seeds) != 1 or len(vals) != B:
+                raise ValueError("seeds must be [batch]")
+            dev_seeds = torch.from_numpy(np.array(vals, dtype=np.uint64).view(np.int64)).to(self.device)      # (the same 64 bits)
+        wav = torch.empty((B, ld), dtype=torch.float32, device=self.device)
+        lens = torch.empty((B,), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            self.ctx.check(self.ctx.lib.gsttaco_waveglow(self.ctx.handle, _ptr(x), _ptr(fr), B, T, ctypes.c_float(float(sigma)),
+                                                         _ptr(dev_seeds), _ptr(z), _ptr(wav), _ptr(lens), ld, self._stream()))
         return wav, lens
 
     def Inference_Checked(self, sentence_List, wav_List_for_GST=None, style_embeddings=None, style_token_weights=None, seeds=None,
@@ -1100,11 +1176,13 @@ class GST_Tacotron:
                 self._stream()))
         return wav, lens
 
-    def Export_Inference(self, sentence_List, mel_List, stop_List, spectrogram_List, alignment_List, label, plot=True, vocoder="griffin_lim"):
+    def Export_Inference(self, sentence_List, mel_List, stop_List, spectrogram_List, alignment_List, label, plot=True, vocoder="griffin_lim",
+                         seeds=None):
         """reference Model.py:369-427: per utterance a figure (Plot/<label>.IDX_<i>.PNG) and the Griffin-Lim wav of the
         spectrogram cut at the stop token (Wav/<label>.IDX_<i>.WAV) under Inference_Path.  Returns the wav paths.
         ``vocoder="melgan"`` (extension): the WAVs are ``Neural_Vocoder`` of the post-net mels, cut at the ``frames`` column of
-        ``Utterance_Report``, in place of Griffin-Lim; the figures are unchanged."""
+        ``Utterance_Report``, in place of Griffin-Lim; the figures are unchanged.  ``vocoder="waveglow"``: ``WaveGlow`` of the same cut
+        mels at its default temperature, row b's noise drawn from ``seeds[b]`` (None: 0 for every row)."""
         from . import export
         self._check_vocoder(vocoder)
         root = self.hp_Dict["Inference_Path"]
@@ -1116,6 +1194,9 @@ class GST_Tacotron:
         if vocoder == "melgan":
             report, _ = self.Utterance_Report(stop_List, alignment_List)
             wav, lens = self.Neural_Vocoder(mel_List, report[:, 1].contiguous())
+        elif vocoder == "waveglow":
+            report, _ = self.Utterance_Report(stop_List, alignment_List)
+            wav, lens = self.WaveGlow(mel_List, report[:, 1].contiguous(), seeds=seeds)
         else:
             wav, lens = self.Inv_Spectrogram(spectrogram_List, frames=frames)
         wav, lens = wav.cpu().numpy(), lens.cpu().numpy()

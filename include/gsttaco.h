@@ -623,6 +623,96 @@ int gsttaco_melgan_debug_stage(gsttaco_ctx* ctx, int stage, const float* mel, co
 #define GSTTACO_MELGAN_PLAN_INTS (3 + 6 * 74)
 int gsttaco_melgan_plan(const gsttaco_ctx* ctx, int32_t fields[]);
 
+/* The flow vocoder: WaveGlow inference, mel -> waveform, sampled from noise under a temperature (EXTENSION, DESIGN row A23; Prenger,
+ * Valle & Catanzaro, ICASSP 2019).  One per context, owned by it and freed by gsttaco_destroy; gsttaco_config, the model's manifest and the
+ * MelGAN state know nothing of it.  With G = n_group, F = n_flows, EE = n_early_every, ES = n_early_size, NL = n_layers, C = n_channels:
+ *   c_k   = G - ES * #{j : 0 < j <= k, j % EE == 0}, the channels of flow k (the defaults: 8 for flows 0..3, 6 for 4..7, 4 for 8..11);
+ *   n_rem = c_{F-1};   L = frames * hop / G, the columns of a row of `frames` frames.
+ * Inference of one row, at the row's own length, zeros beyond it:
+ *   1. up: ConvTranspose1D mel_dim -> mel_dim, kernel win, stride hop, bias, cropped to the first frames * hop samples: sample
+ *      q * hop + p sums taps p + j * hop of frames q - j, j = 0 .. win / hop - 1; frames below 0 are absent.  Later frames never reach an
+ *      earlier sample, so the crop is exact for a padded batch.
+ *   2. group: spect[l, m * G + g] = up[l * G + g, m], giving [L, mel_dim * G].
+ *   3. noise: audio = sigma * z[:, 0:n_rem], giving [L, n_rem].
+ *   4. for k = F-1 down to 0, h = c_k / 2, a0 = audio[:, :h], a1 = audio[:, h:]:
+ *        hid = start_k of a0 (one tap, h -> C);  out = 0
+ *        for layer i = 0 .. NL-1 at dilation 2^i, zero "same" padding at the row's ends:
+ *          acts = in_{k,i} of hid (three taps, C -> 2C) + cond_{k,i} of spect (one tap, mel_dim * G -> 2C)
+ *          g = tanh(acts[:, :C]) * sigmoid(acts[:, C:]);  rs = res_skip_{k,i} of g (one tap, C -> 2C; at the last layer C -> C)
+ *          every layer but the last: hid += rs[:, :C], out += rs[:, C:];  the last: out += rs
+ *        o = end_k of out (one tap, C -> 2h), b = o[:, :h], s = o[:, h:];  a1 = (a1 - b) * exp(-s)
+ *        audio = [a0 | a1] @ inverse(W_k)^T
+ *        if k % EE == 0 and k > 0: audio = [sigma * z[:, next ES columns] | audio]
+ *   5. wav[l * G + g] = audio[l, g].  It is NOT bounded by 1; a WAV writer clips.
+ * The G columns of z are each used exactly once: n_rem first, then ES per early injection in the order inference meets them.
+ * inverse(W_k) is computed once at finalize, in float64 on the host.  Row b uses frames[b] frames (above T: T; below 1: length 0, all zeros);
+ * its samples are bitwise those of the row run alone, whatever batch, T or capacity it ran in: one summation order per output (fp32
+ * MFMA, no atomics), and z[b, l * G + g] depends on (seed, l, g) only. */
+typedef struct gsttaco_waveglow_config {
+    int32_t mel_dim;            /* 80 */
+    int32_t hop;                /* 256 = Sound.Frame_Shift */
+    int32_t win;                /* 1024: the upsampler's kernel, a multiple of hop */
+    int32_t n_group;            /* 8: even, divides hop, at most 16 */
+    int32_t n_flows;            /* 12, at most 32 */
+    int32_t n_early_every;      /* 4 */
+    int32_t n_early_size;       /* 2: even */
+    int32_t n_layers;           /* 8, at most 10 */
+    int32_t n_channels;         /* 256 */
+    int32_t kernel;             /* 3, fixed: the WN layers' taps */
+    int32_t max_batch, max_frames;          /* capacity of a call */
+} gsttaco_waveglow_config;
+
+/* Fixes the sizes and builds the flow vocoder's manifest.  No GPU use.  GSTTACO_E_INVALID with a message that names the field: win % hop,
+ * hop % n_group, n_group % 2, n_early_size % 2 or any c_k % 2 nonzero; n_rem < 2; any size below 1; n_layers > 10, n_flows > 32,
+ * n_group > 16; kernel other than 3; a tile that cannot fit the 160 KB of LDS; max_batch * max_frames * hop above 2^31 - 1; a context
+ * whose flow vocoder is configured already. */
+int gsttaco_waveglow_configure(gsttaco_ctx* ctx, const gsttaco_waveglow_config* cfg);
+
+/* The flow vocoder's own manifest, plain folded fp32 in the [taps * cin, cout] convention:
+ *   waveglow/up/kernel [win, mel_dim, mel_dim] (tap t, as torch's [cin, cout, t])       waveglow/up/bias [mel_dim]
+ *   waveglow/flow<k>/W [c_k, c_k]
+ *   waveglow/flow<k>/start/kernel [c_k / 2, C]      .../start/bias [C]      waveglow/flow<k>/end/kernel [C, c_k]     .../end/bias [c_k]
+ *   waveglow/flow<k>/layer<i>/in/kernel [3 * C, 2 * C], .../cond/kernel [mel_dim * G, 2 * C], .../res_skip/kernel [C, 2 * C] (the last
+ *   layer: [C, C]), each with .../bias
+ * GSTTACO_E_WEIGHTS: an unknown name, a wrong shape, a load before configure or after finalize. */
+int gsttaco_waveglow_num_weights(const gsttaco_ctx* ctx);
+int gsttaco_waveglow_weight_info(const gsttaco_ctx* ctx, int i, const char** name, int64_t shape[4], int* ndim);
+int gsttaco_waveglow_load_weight(gsttaco_ctx* ctx, const char* name, const float* host, const int64_t* shape, int ndim);
+
+/* Inverts every W_k (float64), repacks the weights into the kernels' fragment order (channel counts zero-padded to multiples of 16),
+ * uploads them and allocates the workspace for the capacity:
+ *   max_batch * max_frames * (hop / G) * (S_p + 3 * C_p + 16) floats
+ * -- spect, two hid, out and audio per column; S_p and C_p are mel_dim * G and C rounded up to 16; 45 568 floats per frame at the defaults.
+ * GSTTACO_E_WEIGHTS when a tensor was not loaded or a W_k is singular; a failed allocation is GSTTACO_E_HIP. */
+int gsttaco_waveglow_finalize(gsttaco_ctx* ctx);
+
+/* seeds : [B] uint64 (DEVICE)   z : [B, T * hop] float32 (DEVICE), written:  z[b, l * G + g] = gt_normal of the Philox words of counter
+ * (l, g, 0, 0x8000) under seeds[b] -- a sample depends on (seed, position, channel) only, not on the batch, on T or on the capacity.
+ * Needs a configured context (hop and G).  GSTTACO_E_INVALID: a NULL, B or T < 1. */
+int gsttaco_waveglow_noise(gsttaco_ctx* ctx, const uint64_t* seeds, int B, int T, float* z, void* stream);
+
+/* mel : [B, T, mel_dim] float32 (DEVICE), normalised as gsttaco_inference_step writes it   frames : [B] int32 (DEVICE) or NULL = T
+ * seeds : [B] uint64 (DEVICE) or z : [B, T * hop] float32 (DEVICE) -- exactly one of the two; with seeds the call is bitwise the call
+ * with z = what gsttaco_waveglow_noise writes for them.   sigma >= 0: the temperature.
+ * wav : [B, ld_wav] float32 (DEVICE), ld_wav >= T * hop   wav_lengths : [B] int32 (DEVICE) or NULL, written: frames[b] * hop
+ * 2 + F * (NL + 1) plain launches on the caller's stream: no allocation, no synchronisation, capturable in a graph.
+ * GSTTACO_E_WEIGHTS before gsttaco_waveglow_finalize; GSTTACO_E_CAPACITY: B > max_batch or T > max_frames; GSTTACO_E_INVALID: a NULL
+ * mel / wav, B or T < 1, ld_wav < T * hop, both or neither of seeds / z, sigma < 0 or not finite. */
+int gsttaco_waveglow(gsttaco_ctx* ctx, const float* mel, const int32_t* frames, int B, int T, float sigma,
+                     const uint64_t* seeds, const float* z, float* wav, int32_t* wav_lengths, int ld_wav, void* stream);
+
+/* Test support: what the launches of a configured flow vocoder are.  fields[0] = the number of launches S, fields[1] = hop,
+ * fields[2] = G; then per launch GSTTACO_WAVEGLOW_PLAN_STRIDE ints: kind (0 upsampler, 1 WN layer, 2 flow tail), channels, the time tile
+ * (kind 0: in frames; else in columns of G samples), the kernel form (N-tiles of 16 channels a wave owns per item; 0 for kind 2),
+ * samples per unit of the tile (hop or G), dynamic LDS bytes.  fields holds GSTTACO_WAVEGLOW_PLAN_INTS ints.  Launches nothing.
+ * gsttaco_waveglow_debug_stage (timing support, tools/waveglow_time.py): launch `stage` (0 .. S - 1) of gsttaco_waveglow alone, with
+ * the same arguments and checks, on whatever the workspace holds from an earlier whole call of the same B and T. */
+int gsttaco_waveglow_debug_stage(gsttaco_ctx* ctx, int stage, const float* mel, const int32_t* frames, int B, int T, float sigma,
+                                 const uint64_t* seeds, const float* z, float* wav, int ld_wav, void* stream);
+#define GSTTACO_WAVEGLOW_PLAN_STRIDE 6
+#define GSTTACO_WAVEGLOW_PLAN_INTS (3 + 6 * 354)
+int gsttaco_waveglow_plan(const gsttaco_ctx* ctx, int32_t fields[]);
+
 /* hipGraph cache policy.  Every entry point replays one cached graph executable per (entry, B, Tv, Tref1, steps, flags) key.
  * The cache is LRU-bounded to `max_cached` executables (default 16 -- an Inference_Step replays two or three: encoder segment, GST + decode + postnet, vocoder; GSTTACO_GRAPH_CACHE; 0 = no graphs, everything is
  * enqueued eagerly on the caller's stream); the least recently used one is destroyed when a new shape is captured.
