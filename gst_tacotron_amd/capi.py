@@ -45,7 +45,14 @@ EXPORTED_SYMBOLS = (
     "gsttaco_melgan_finalize", "gsttaco_melgan", "gsttaco_melgan_plan", "gsttaco_melgan_debug_stage",
     "gsttaco_waveglow_configure", "gsttaco_waveglow_num_weights", "gsttaco_waveglow_weight_info", "gsttaco_waveglow_load_weight",
     "gsttaco_waveglow_finalize", "gsttaco_waveglow_noise", "gsttaco_waveglow", "gsttaco_waveglow_plan", "gsttaco_waveglow_debug_stage",
+    "gsttaco_hifigan_configure", "gsttaco_hifigan_num_weights", "gsttaco_hifigan_weight_info", "gsttaco_hifigan_load_weight",
+    "gsttaco_hifigan_finalize", "gsttaco_hifigan", "gsttaco_hifigan_plan", "gsttaco_hifigan_debug_stage",
 )
+# gsttaco_hifigan_plan: ints per launch (kind, channels, taps, dilation, tile, form, rate, lds), the launch kinds, and the size of its array
+HIFIGAN_PLAN_FIELDS = ("kind", "channels", "taps", "dilation", "tile", "form", "rate", "lds")
+HIFIGAN_KINDS = ("in", "up", "conv", "out")
+HIFIGAN_PLAN_INTS = 3 + 8 * 522
+HIFIGAN_MAX_DILATIONS = 4
 # gsttaco_waveglow_plan: ints per launch (kind, channels, tile, form, unit, lds), the launch kinds, and the size of its array
 WAVEGLOW_PLAN_FIELDS = ("kind", "channels", "tile", "form", "unit", "lds")
 WAVEGLOW_KINDS = ("up", "layer", "flow")
@@ -136,6 +143,13 @@ class WaveglowConfig(ctypes.Structure):
                                                     "n_layers", "n_channels", "kernel", "max_batch", "max_frames")]
 
 
+class HifiganConfig(ctypes.Structure):
+    _fields_ = [("mel_dim", ctypes.c_int32), ("initial", ctypes.c_int32), ("n_rates", ctypes.c_int32), ("rates", _I32A),
+                ("resblock", ctypes.c_int32), ("n_kernels", ctypes.c_int32), ("kernels", _I32A), ("n_dilations", _I32A),
+                ("dilations", (ctypes.c_int32 * HIFIGAN_MAX_DILATIONS) * MAX_LAYERS),
+                ("slope", ctypes.c_float), ("out_slope", ctypes.c_float), ("max_batch", ctypes.c_int32), ("max_frames", ctypes.c_int32)]
+
+
 class GstTacoError(RuntimeError):
     def __init__(self, code, message):
         super().__init__("gsttaco error {}: {}".format(code, message))
@@ -218,6 +232,17 @@ def load_library(path=None):
     lib.gsttaco_waveglow_debug_stage.argtypes = [vp, i32, vp, vp, i32, i32, f32, vp, vp, vp, i32, vp]
     for fn in ("gsttaco_waveglow_configure", "gsttaco_waveglow_num_weights", "gsttaco_waveglow_weight_info", "gsttaco_waveglow_load_weight",
                "gsttaco_waveglow_finalize", "gsttaco_waveglow_noise", "gsttaco_waveglow", "gsttaco_waveglow_plan", "gsttaco_waveglow_debug_stage"):
+        getattr(lib, fn).restype = ctypes.c_int
+    lib.gsttaco_hifigan_configure.argtypes = [vp, ctypes.POINTER(HifiganConfig)]
+    lib.gsttaco_hifigan_num_weights.argtypes = [vp]
+    lib.gsttaco_hifigan_weight_info.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_int64 * 4), ctypes.POINTER(ctypes.c_int)]
+    lib.gsttaco_hifigan_load_weight.argtypes = [vp, ctypes.c_char_p, f32p, ctypes.POINTER(ctypes.c_int64), i32]
+    lib.gsttaco_hifigan_finalize.argtypes = [vp]
+    lib.gsttaco_hifigan.argtypes = [vp, vp, vp, i32, i32, vp, vp, i32, vp]
+    lib.gsttaco_hifigan_plan.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
+    lib.gsttaco_hifigan_debug_stage.argtypes = [vp, i32, vp, vp, i32, i32, vp, i32, vp]
+    for fn in ("gsttaco_hifigan_configure", "gsttaco_hifigan_num_weights", "gsttaco_hifigan_weight_info", "gsttaco_hifigan_load_weight",
+               "gsttaco_hifigan_finalize", "gsttaco_hifigan", "gsttaco_hifigan_plan", "gsttaco_hifigan_debug_stage"):
         getattr(lib, fn).restype = ctypes.c_int
     lib.gsttaco_postnet.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.gsttaco_vocoder.argtypes = [vp, vp, i32, i32, vp, vp]
@@ -470,5 +495,60 @@ class Context:
         for i in range(f[0]):
             row = dict(zip(WAVEGLOW_PLAN_FIELDS, f[3 + 6 * i: 9 + 6 * i]))
             row["kind"] = WAVEGLOW_KINDS[row["kind"]]
+            stages.append(row)
+        return int(f[1]), int(f[2]), stages
+
+    # ---- the HiFi-GAN vocoder (gsttaco_hifigan_*): one per context
+    def hifigan_configure(self, cfg, max_batch, max_frames):
+        """``cfg``: a hifigan.HiFiGANConfig (or anything with its fields)."""
+        m = HifiganConfig()
+        m.mel_dim, m.initial, m.resblock = int(cfg.mel_dim), int(cfg.initial), int(cfg.resblock)
+        m.slope, m.out_slope = float(cfg.slope), float(cfg.out_slope)
+        if len(cfg.rates) > MAX_LAYERS:
+            raise ValueError("at most {} upsampling rates".format(MAX_LAYERS))
+        if len(cfg.kernels) > MAX_LAYERS:
+            raise ValueError("at most {} residual kernels".format(MAX_LAYERS))
+        if len(cfg.dilations) != len(cfg.kernels):
+            raise ValueError("one dilation list per residual kernel")
+        m.n_rates, m.n_kernels = len(cfg.rates), len(cfg.kernels)
+        for i, r in enumerate(cfg.rates):
+            m.rates[i] = int(r)
+        for j, (k, dils) in enumerate(zip(cfg.kernels, cfg.dilations)):
+            m.kernels[j], m.n_dilations[j] = int(k), len(dils)
+            for n, d in enumerate(dils[:HIFIGAN_MAX_DILATIONS]):
+                m.dilations[j][n] = int(d)
+        m.max_batch, m.max_frames = int(max_batch), int(max_frames)
+        self.check(self.lib.gsttaco_hifigan_configure(self.handle, ctypes.byref(m)))
+
+    def hifigan_manifest(self):
+        out = {}
+        for i in range(self.lib.gsttaco_hifigan_num_weights(self.handle)):
+            name, shape, nd = ctypes.c_char_p(), (ctypes.c_int64 * 4)(), ctypes.c_int()
+            self.check(self.lib.gsttaco_hifigan_weight_info(self.handle, i, ctypes.byref(name), ctypes.byref(shape), ctypes.byref(nd)))
+            out[name.value.decode()] = tuple(shape[k] for k in range(nd.value))
+        return out
+
+    def hifigan_load_weight(self, name, array):
+        a = np.ascontiguousarray(np.asarray(array, dtype=np.float32))
+        shape = (ctypes.c_int64 * max(a.ndim, 1))(*a.shape)
+        self.check(self.lib.gsttaco_hifigan_load_weight(self.handle, name.encode(), a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), shape, a.ndim))
+
+    def hifigan_load_weights(self, weights):
+        for name in self.hifigan_manifest():
+            if name not in weights:
+                raise KeyError("missing weight '{}'".format(name))
+            self.hifigan_load_weight(name, weights[name])
+
+    def hifigan_finalize(self):
+        self.check(self.lib.gsttaco_hifigan_finalize(self.handle))
+
+    def hifigan_plan(self):
+        """(min_frames, hop, [one dict of HIFIGAN_PLAN_FIELDS per launch, ``kind`` as a name of HIFIGAN_KINDS])."""
+        f = (ctypes.c_int32 * HIFIGAN_PLAN_INTS)()
+        self.check(self.lib.gsttaco_hifigan_plan(self.handle, f))
+        stages = []
+        for i in range(f[0]):
+            row = dict(zip(HIFIGAN_PLAN_FIELDS, f[3 + 8 * i: 11 + 8 * i]))
+            row["kind"] = HIFIGAN_KINDS[row["kind"]]
             stages.append(row)
         return int(f[1]), int(f[2]), stages

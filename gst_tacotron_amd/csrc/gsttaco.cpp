@@ -238,6 +238,16 @@ struct gsttaco_ctx {
         std::map<std::string, int> index;
         float *spect = nullptr, *hid[2] = {nullptr, nullptr}, *out = nullptr, *audio = nullptr;
     } wg;
+    // The HiFi-GAN vocoder (gsttaco_hifigan_*): its own manifest, the plan whose launches hold the device operands once finalized, and
+    // the four activation buffers for the capacity
+    struct Hifigan {
+        bool configured = false, finalized = false;
+        gsttaco_hifigan_config cfg{};
+        HgPlan plan{};
+        std::vector<HostTensor> tensors;
+        std::map<std::string, int> index;
+        float* ws[GT_HG_BUFS] = {nullptr, nullptr, nullptr, nullptr};
+    } hg;
     // Resampling (gsttaco_resample): the tables of up to GT_RS_MAX_PAIRS rate pairs, least recently used evicted (ensure_resample_pair).
     // A slot's device memory and pinned host image are allocated at its first use and reused by the pairs that follow in it; `uploaded`
     // is recorded behind a slot's upload, and waited for before its host image is rewritten.
@@ -3593,6 +3603,177 @@ int gsttaco_waveglow_plan(const gsttaco_ctx* c, int32_t fields[]) {
         put(GT_WG_FLOW, P.ck[k], GT_WG_FLOW_TILE, 0, P.G, P.flow_lds);
     }
     fields[0] = n; fields[1] = P.hop; fields[2] = P.G;
+    return 0;
+}
+
+// ---- the HiFi-GAN vocoder (hifigan.hip).  Configure and the manifest need no device; finalize uploads and allocates once.
+namespace {
+// the manifest's name of a launch's weights, without the /kernel or /bias leaf
+std::string hifigan_name(const HgStage& s) {
+    if (s.kind == GT_HG_IN) return "hifigan/in";
+    if (s.kind == GT_HG_OUT) return "hifigan/out";
+    std::string p = "hifigan/up" + std::to_string(s.up);
+    if (s.kind == GT_HG_UP) return p;
+    return p + "/res" + std::to_string(s.block) + "/unit" + std::to_string(s.unit) + (s.conv ? "/conv2" : "/conv1");
+}
+}  // namespace
+
+int gsttaco_hifigan_configure(gsttaco_ctx* c, const gsttaco_hifigan_config* m) {
+    if (!c) return GSTTACO_E_INVALID;
+    if (!m) return fail(c, GSTTACO_E_INVALID, "null argument");
+    gsttaco_ctx::Hifigan& g = c->hg;
+    if (g.configured) return fail(c, GSTTACO_E_INVALID, "hifigan: the context's HiFi-GAN is configured already");
+    if (m->n_rates < 1 || m->n_rates > GSTTACO_MAX_LAYERS) return fail(c, GSTTACO_E_INVALID, "hifigan: n_rates: between 1 and 8 upsampling rates");
+    if (m->n_kernels < 1 || m->n_kernels > GSTTACO_MAX_LAYERS) return fail(c, GSTTACO_E_INVALID, "hifigan: n_kernels: between 1 and 8 residual kernels");
+    if (m->max_batch < 1 || m->max_frames < 1) return fail(c, GSTTACO_E_INVALID, "hifigan: max_batch and max_frames must be at least 1");
+    HgConfig hc{};
+    hc.mel_dim = m->mel_dim; hc.initial = m->initial; hc.n_rates = m->n_rates; hc.resblock = m->resblock; hc.n_kernels = m->n_kernels;
+    hc.slope = m->slope; hc.out_slope = m->out_slope;
+    for (int i = 0; i < m->n_rates; ++i) hc.rates[i] = m->rates[i];
+    for (int j = 0; j < m->n_kernels; ++j) {
+        hc.kernels[j] = m->kernels[j];
+        hc.n_dilations[j] = m->n_dilations[j];
+        for (int k = 0; k < GSTTACO_HIFIGAN_MAX_DILATIONS; ++k) hc.dilations[j][k] = m->dilations[j][k];
+    }
+    const char* why = gt_hifigan_make_plan(hc, &g.plan);
+    if (why) {
+        g.plan = HgPlan{};
+        return fail(c, GSTTACO_E_INVALID, std::string("hifigan: ") + why);
+    }
+    if ((double)m->max_batch * m->max_frames * g.plan.hop > 2147483647.0) {
+        g.plan = HgPlan{};
+        return fail(c, GSTTACO_E_INVALID, "hifigan: max_batch * max_frames * hop exceeds 2^31 - 1 samples");
+    }
+    g.cfg = *m;
+    auto add = [&](const std::string& name, std::vector<int64_t> shape) {
+        HostTensor t;
+        t.name = name;
+        t.shape = std::move(shape);
+        g.index[name] = (int)g.tensors.size();
+        g.tensors.push_back(std::move(t));
+    };
+    for (int i = 0; i < g.plan.n_stages; ++i) {
+        const HgStage& s = g.plan.st[i];
+        const std::string p = hifigan_name(s);
+        if (s.kind == GT_HG_UP) add(p + "/kernel", {(int64_t)s.taps, s.cin, s.cout});
+        else add(p + "/kernel", {(int64_t)s.taps * s.cin, s.cout});
+        add(p + "/bias", {s.cout});
+    }
+    g.configured = true;
+    return 0;
+}
+
+int gsttaco_hifigan_num_weights(const gsttaco_ctx* c) { return c ? (int)c->hg.tensors.size() : GSTTACO_E_INVALID; }
+
+int gsttaco_hifigan_weight_info(const gsttaco_ctx* c, int i, const char** name, int64_t shape[4], int* ndim) {
+    if (!c || i < 0 || i >= (int)c->hg.tensors.size()) return GSTTACO_E_INVALID;
+    const HostTensor& t = c->hg.tensors[i];
+    if (name) *name = t.name.c_str();
+    if (ndim) *ndim = (int)t.shape.size();
+    if (shape)
+        for (size_t d = 0; d < 4; ++d) shape[d] = d < t.shape.size() ? t.shape[d] : 1;
+    return 0;
+}
+
+int gsttaco_hifigan_load_weight(gsttaco_ctx* c, const char* name, const float* host, const int64_t* shape, int ndim) {
+    if (!c || !name || !host || !shape) return fail(c, GSTTACO_E_INVALID, "null argument");
+    gsttaco_ctx::Hifigan& g = c->hg;
+    if (!g.configured) return fail(c, GSTTACO_E_WEIGHTS, "hifigan: not configured (gsttaco_hifigan_configure)");
+    if (g.finalized) return fail(c, GSTTACO_E_WEIGHTS, "hifigan: weights already finalized");
+    auto it = g.index.find(name);
+    if (it == g.index.end()) return fail(c, GSTTACO_E_WEIGHTS, std::string("hifigan: unknown weight '") + name + "'");
+    HostTensor& t = g.tensors[it->second];
+    bool ok = ndim == (int)t.shape.size();
+    for (int d = 0; ok && d < ndim; ++d) ok = shape[d] == t.shape[d];
+    if (!ok) return fail(c, GSTTACO_E_WEIGHTS, std::string("hifigan: weight '") + name + "' has the wrong shape");
+    t.data.assign(host, host + t.numel());
+    t.loaded = true;
+    return 0;
+}
+
+int gsttaco_hifigan_finalize(gsttaco_ctx* c) {
+    if (!c) return GSTTACO_E_INVALID;
+    gsttaco_ctx::Hifigan& g = c->hg;
+    if (!g.configured) return fail(c, GSTTACO_E_WEIGHTS, "hifigan: not configured (gsttaco_hifigan_configure)");
+    if (g.finalized) return fail(c, GSTTACO_E_WEIGHTS, "hifigan: weights already finalized");
+    for (const HostTensor& t : g.tensors)
+        if (!t.loaded) return fail(c, GSTTACO_E_WEIGHTS, "hifigan: weight '" + t.name + "' was not loaded");
+    int rc = ensure_device(c);
+    if (rc) return rc;
+    HIPCHECK(c, gt_hifigan_prepare());
+    auto host = [&](const std::string& name) -> const std::vector<float>& { return g.tensors[g.index[name]].data; };
+    std::vector<float> buf;
+    for (int i = 0; i < g.plan.n_stages; ++i) {
+        HgStage& s = g.plan.st[i];
+        const std::string p = hifigan_name(s);
+        float* d = nullptr;
+        if (s.kind == GT_HG_OUT) {
+            if ((rc = upload(c, &d, host(p + "/kernel").data(), (size_t)s.taps * s.cin))) return rc;
+        } else {
+            buf.resize((size_t)s.taps * s.cin_p * s.n_p);
+            gt_hifigan_pack(host(p + "/kernel").data(), s.taps, s.cin, s.cout, buf.data());
+            if ((rc = upload(c, &d, buf.data(), buf.size()))) return rc;
+        }
+        s.w0 = d;
+        buf.assign(s.kind == GT_HG_OUT ? 1 : s.n_p, 0.f);
+        const std::vector<float>& b = host(p + "/bias");
+        for (size_t k = 0; k < b.size(); ++k) buf[k] = b[k];
+        d = nullptr;
+        if ((rc = upload(c, &d, buf.data(), buf.size()))) return rc;
+        s.b0 = d;
+    }
+    const size_t ws = (size_t)g.cfg.max_batch * g.cfg.max_frames * g.plan.ws_floats_per_frame * sizeof(float);
+    for (int k = 0; k < GT_HG_BUFS; ++k)
+        if ((rc = dev_alloc(c, (void**)&g.ws[k], ws))) return rc;
+    g.finalized = true;
+    return 0;
+}
+
+namespace { int hifigan_call(gsttaco_ctx* c, const float* mel, const int32_t* frames, int B, int T, float* wav, int32_t* wav_lengths, int ld_wav,
+                             int only, void* stream); }
+
+int gsttaco_hifigan(gsttaco_ctx* c, const float* mel, const int32_t* frames, int B, int T, float* wav, int32_t* wav_lengths, int ld_wav,
+                    void* stream) {
+    return hifigan_call(c, mel, frames, B, T, wav, wav_lengths, ld_wav, -1, stream);
+}
+
+int gsttaco_hifigan_debug_stage(gsttaco_ctx* c, int stage, const float* mel, const int32_t* frames, int B, int T, float* wav, int ld_wav,
+                                void* stream) {
+    if (!c) return GSTTACO_E_INVALID;
+    if (stage < 0 || stage >= c->hg.plan.n_stages) return fail(c, GSTTACO_E_INVALID, "hifigan: no such launch");
+    return hifigan_call(c, mel, frames, B, T, wav, nullptr, ld_wav, stage, stream);
+}
+
+namespace {
+int hifigan_call(gsttaco_ctx* c, const float* mel, const int32_t* frames, int B, int T, float* wav, int32_t* wav_lengths, int ld_wav,
+                 int only, void* stream) {
+    if (!c) return GSTTACO_E_INVALID;
+    const gsttaco_ctx::Hifigan& g = c->hg;
+    if (!g.finalized) return fail(c, GSTTACO_E_WEIGHTS, "hifigan: weights not finalized (gsttaco_hifigan_finalize)");
+    if (!mel || !wav) return fail(c, GSTTACO_E_INVALID, "null argument");
+    if (B < 1 || T < 1) return fail(c, GSTTACO_E_INVALID, "bad B / T");
+    if (B > g.cfg.max_batch || T > g.cfg.max_frames) return fail(c, GSTTACO_E_CAPACITY, "hifigan: B or T exceeds the capacity given at configure");
+    if ((int64_t)ld_wav < (int64_t)T * g.plan.hop) return fail(c, GSTTACO_E_INVALID, "ld_wav must be >= T * hop");
+    HgCall a{};
+    a.mel = mel; a.frames = frames; a.wav = wav; a.wav_lengths = wav_lengths;
+    for (int k = 0; k < GT_HG_BUFS; ++k) a.ws[k] = g.ws[k];
+    a.B = B; a.T = T; a.ld_wav = ld_wav; a.only = only;
+    HIPCHECK(c, gt_launch_hifigan(g.plan, a, (hipStream_t)stream));
+    return 0;
+}
+}  // namespace
+
+int gsttaco_hifigan_plan(const gsttaco_ctx* c, int32_t fields[]) {
+    if (!c || !fields) return GSTTACO_E_INVALID;
+    const gsttaco_ctx::Hifigan& g = c->hg;
+    if (!g.configured) return fail(c, GSTTACO_E_WEIGHTS, "hifigan: not configured (gsttaco_hifigan_configure)");
+    fields[0] = g.plan.n_stages; fields[1] = g.plan.min_frames; fields[2] = g.plan.hop;
+    for (int i = 0; i < g.plan.n_stages; ++i) {
+        const HgStage& s = g.plan.st[i];
+        int32_t* f = fields + 3 + GSTTACO_HIFIGAN_PLAN_STRIDE * i;
+        f[0] = s.kind; f[1] = s.cout; f[2] = s.taps; f[3] = s.dil; f[4] = s.tile; f[5] = s.form;
+        f[6] = s.kind == GT_HG_UP ? s.rate_in : s.rate_out; f[7] = (int32_t)s.lds;
+    }
     return 0;
 }
 

@@ -734,3 +734,62 @@ struct WgCall {
     int only;                   // -1: the whole chain; else that launch alone (timing: gsttaco_waveglow_debug_stage)
 };
 hipError_t gt_launch_waveglow(const WgPlan& plan, const WgCall& call, hipStream_t stream);
+
+
+// ---------------------------------------------------------------- hifigan.hip
+// The HiFi-GAN generator, mel -> waveform (the contract: gsttaco_hifigan in include/gsttaco.h).
+#define GT_HG_MAX_RATES 8
+#define GT_HG_MAX_KERNELS 8
+#define GT_HG_MAX_DILATIONS 4
+#define GT_HG_MAX_TAPS 11
+#define GT_HG_MAX_STAGES (2 + GT_HG_MAX_RATES * (1 + GT_HG_MAX_KERNELS * GT_HG_MAX_DILATIONS * 2))
+#define GT_HG_LDS_MAX (160 * 1024)
+enum { GT_HG_IN = 0, GT_HG_UP = 1, GT_HG_CONV = 2, GT_HG_OUT = 3 };
+// The four activation buffers of the workspace: the fused sum (a stage's output, the next stage's input), the transposed conv's output
+// (every residual block's input), and the two a block's chain alternates between.
+enum { GT_HG_BUF_SUM = 0, GT_HG_BUF_UP = 1, GT_HG_BUF_A = 2, GT_HG_BUF_B = 3, GT_HG_BUFS = 4 };
+// What a GT_HG_CONV launch does with its result v (bias + taps, then + residual): GT_HG_SUM_NONE writes v to dst; the last unit of block j
+// writes the fused sum instead: sum = v (j = 0) or sum += v, times `scale` = 1 / n_k on the last block.
+enum { GT_HG_SUM_NONE = 0, GT_HG_SUM_SET = 1, GT_HG_SUM_ADD = 2 };
+// One launch of the chain.  Channel counts with _p are the padded ones (multiples of 16) the fragment packs and the workspace use.
+struct HgStage {
+    int kind;
+    int cin, cout, cin_p, n_p;
+    int rate_in, rate_out;      // samples per mel frame of the stage's input and output
+    int r;                      // GT_HG_UP: the rate
+    int taps, dil;              // GT_HG_CONV: kernel size and dilation (GT_HG_IN / GT_HG_OUT: 7, 1)
+    int src, res, dst;          // GT_HG_CONV: buffers read through the LeakyReLU, added raw in the epilogue (-1: none), written (-1: the sum alone)
+    int sum;                    // GT_HG_SUM_*
+    float scale;                // on the fused sum's last write, 1 / n_k; else 1
+    int up, block, unit, conv;  // where the launch sits: stage i, residual block j, unit m, conv 0 / 1 (the manifest's names)
+    int tile, form;             // time tile (GT_HG_UP: in input positions, else in output samples); form: N-tiles a wave item owns (GT_HG_OUT: 0)
+    size_t lds;                 // dynamic LDS of a workgroup, bytes
+    const float *w0, *b0;       // device operands (gsttaco_hifigan_finalize)
+};
+struct HgConfig {
+    int mel_dim, initial, n_rates, rates[GT_HG_MAX_RATES], resblock, n_kernels, kernels[GT_HG_MAX_KERNELS];
+    int n_dilations[GT_HG_MAX_KERNELS], dilations[GT_HG_MAX_KERNELS][GT_HG_MAX_DILATIONS];
+    float slope, out_slope;
+};
+struct HgPlan {
+    int n_stages;
+    HgStage st[GT_HG_MAX_STAGES];
+    int mel_dim, hop, min_frames;
+    float slope, out_slope;
+    size_t ws_floats_per_frame;     // the largest activation of the chain, floats per mel frame of one row
+};
+// Fills the plan's shapes, tiles and LDS sizes (no device use).  Returns NULL, or the reason the configuration cannot run.
+const char* gt_hifigan_make_plan(const HgConfig& cfg, HgPlan* plan);
+// [taps * cin, cout] (row stride cout) -> the fragment pack [taps][cin_p / 16][n_p][4][4] the kernels read, zero padded
+void gt_hifigan_pack(const float* w, int taps, int cin, int cout, float* out);
+hipError_t gt_hifigan_prepare();
+struct HgCall {
+    const float* mel;           // [B, T, mel_dim]
+    const int32_t* frames;      // [B] or NULL
+    float* wav;                 // [B, ld_wav]
+    int32_t* wav_lengths;       // [B] or NULL
+    float* ws[GT_HG_BUFS];      // B * T * ws_floats_per_frame floats each
+    int B, T, ld_wav;
+    int only;                   // -1: the whole chain; else that launch alone, on what the workspace holds (timing: gsttaco_hifigan_debug_stage)
+};
+hipError_t gt_launch_hifigan(const HgPlan& plan, const HgCall& call, hipStream_t stream);

@@ -14,6 +14,10 @@ Additive keys (absent in the reference, defaults reproduce it):
   Vocoder_WaveGlow                            -- optional: {"Flows": 12, "Group": 8, "Early_Every": 4, "Early_Size": 2, "Layers": 8,
                                                  "Channels": 256, "Upsample_Kernel": 1024, "Checkpoint_Path": null}, the flow
                                                  vocoder (gst_tacotron_amd.waveglow; its hop is Sound.Frame_Shift); absent, nothing changes
+  Vocoder_HiFiGAN                             -- optional: {"Initial_Filters": 512, "Upsample_Rates": [8, 8, 2, 2], "Resblock": 1,
+                                                 "Resblock_Kernel_Sizes": [3, 7, 11], "Resblock_Dilation_Sizes": [[1, 3, 5], [1, 3, 5],
+                                                 [1, 3, 5]], "Checkpoint_Path": null}, the HiFi-GAN generator
+                                                 (gst_tacotron_amd.hifigan); absent, nothing changes
 """
 import copy
 import json
@@ -40,6 +44,7 @@ def load_hp(source=None):
         with open(source, "r") as f:
             hp = json.load(f)
     check_melgan_section(hp)
+    check_hifigan_section(hp)
     return hp
 
 
@@ -56,6 +61,27 @@ def check_melgan_section(hp):
     shift = int(hp["Sound"]["Frame_Shift"])
     if prod != shift:
         raise ValueError("Vocoder_MelGAN.Upsample_Ratios {} multiply to {}, Sound.Frame_Shift is {}".format(ratios, prod, shift))
+
+
+def check_hifigan_section(hp):
+    """The optional Vocoder_HiFiGAN section: its upsampling rates must multiply to Sound.Frame_Shift, or the waveform would not have
+    the mel frames' hop; there is one dilation list per residual kernel, and ``Resblock`` is 1 or 2."""
+    sec = hp.get("Vocoder_HiFiGAN")
+    if sec is None:
+        return
+    rates = [int(r) for r in sec.get("Upsample_Rates", [8, 8, 2, 2])]
+    prod = 1
+    for r in rates:
+        prod *= r
+    shift = int(hp["Sound"]["Frame_Shift"])
+    if prod != shift:
+        raise ValueError("Vocoder_HiFiGAN.Upsample_Rates {} multiply to {}, Sound.Frame_Shift is {}".format(rates, prod, shift))
+    if int(sec.get("Resblock", 1)) not in (1, 2):
+        raise ValueError("Vocoder_HiFiGAN.Resblock must be 1 or 2")
+    kernels = sec.get("Resblock_Kernel_Sizes", [3, 7, 11])
+    dilations = sec.get("Resblock_Dilation_Sizes", [[1, 3, 5]] * 3)
+    if len(kernels) != len(dilations):
+        raise ValueError("Vocoder_HiFiGAN: {} Resblock_Kernel_Sizes but {} Resblock_Dilation_Sizes".format(len(kernels), len(dilations)))
 
 
 def load_token_dict(hp=None, base_dir=None):

@@ -90,6 +90,7 @@ class GST_Tacotron:
         self._ready = False
         self._melgan = None                 # the loaded neural vocoder's MelGANConfig (Load_Neural_Vocoder)
         self._waveglow = None               # the loaded flow vocoder's WaveGlowConfig (Load_WaveGlow)
+        self._hifigan = None                # the loaded HiFi-GAN's HiFiGANConfig (Load_HiFiGAN)
         self.seed = 0
 
     # ------------------------------------------------------------------ weights
@@ -896,8 +897,8 @@ class GST_Tacotron:
         ``seeds`` [B] (extension): per-utterance seeds (see ``Inference_Step``); the call then runs with ``masked=True`` -- without
         masking the batch's padding reaches every utterance, which is what the seeds exist to rule out.
         ``vocoder`` (extension): what ``export=True`` makes the WAVs with -- "griffin_lim" (the reference's, the default), "melgan"
-        (``Load_Neural_Vocoder`` first) or "waveglow" (``Load_WaveGlow`` first; an utterance's decode seed is also its vocoder seed,
-        without ``seeds`` every row's is 0); see ``Export_Inference``."""
+        (``Load_Neural_Vocoder`` first), "waveglow" (``Load_WaveGlow`` first; an utterance's decode seed is also its vocoder seed,
+        without ``seeds`` every row's is 0) or "hifigan" (``Load_HiFiGAN`` first); see ``Export_Inference``."""
         self._check_vocoder(vocoder)
         print("Inference running...")
         if seeds is not None:
@@ -931,12 +932,14 @@ class GST_Tacotron:
 
     # ------------------------------------------------------------------ the neural vocoder
     def _check_vocoder(self, vocoder):
-        if vocoder not in ("griffin_lim", "melgan", "waveglow"):
-            raise ValueError("vocoder must be 'griffin_lim', 'melgan' or 'waveglow'")
+        if vocoder not in ("griffin_lim", "melgan", "waveglow", "hifigan"):
+            raise ValueError("vocoder must be 'griffin_lim', 'melgan', 'waveglow' or 'hifigan'")
         if vocoder == "melgan" and self._melgan is None:
             raise capi.GstTacoError(-4, "vocoder='melgan' needs Load_Neural_Vocoder first")
         if vocoder == "waveglow" and self._waveglow is None:
             raise capi.GstTacoError(-4, "vocoder='waveglow' needs Load_WaveGlow first")
+        if vocoder == "hifigan" and self._hifigan is None:
+            raise capi.GstTacoError(-4, "vocoder='hifigan' needs Load_HiFiGAN first")
 
     def Load_Neural_Vocoder(self, weights_or_path=None, config=None, max_frames=None):
         """Extension: loads the MelGAN generator (``gsttaco_melgan_*``, gst_tacotron_amd.melgan) into this model's context, once.
@@ -989,6 +992,57 @@ class GST_Tacotron:
         return wav, lens
 
     # ------------------------------------------------------------------ the flow vocoder
+    def Load_HiFiGAN(self, weights_or_path=None, config=None, max_frames=None):
+        """Extension: loads the HiFi-GAN generator (``gsttaco_hifigan_*``, gst_tacotron_amd.hifigan) into this model's context, once,
+        beside or without the MelGAN generator and WaveGlow.  ``weights_or_path``: named folded arrays (``hifigan.synthetic_weights``
+        / ``hifigan.from_state_dict``) or the path of a file that holds a generator ``state_dict`` in the public layout
+        (``hifigan.load``; None: ``Vocoder_HiFiGAN.Checkpoint_Path``).  ``config``: a ``hifigan.HiFiGANConfig``; by default the
+        Hyper_Parameters' ``Vocoder_HiFiGAN`` section, else what the arrays' shapes say (the dilations only for the shipped shapes).
+        ``max_frames``: the longest mel a call may bring (default Max_Step); the batch capacity is the model's.  Its Mel_Dim must be
+        the model's and, where the Sound section is complete, its hop Sound.Frame_Shift."""
+        from . import hifigan
+        if weights_or_path is None:
+            weights_or_path = (self.hp_Dict.get("Vocoder_HiFiGAN") or {}).get("Checkpoint_Path")
+            if weights_or_path is None:
+                raise ValueError("no weights given and Hyper_Parameters has no Vocoder_HiFiGAN.Checkpoint_Path")
+        weights = hifigan.load(weights_or_path) if isinstance(weights_or_path, (str, os.PathLike)) else weights_or_path
+        cfg = config or hifigan.from_hp(self.hp_Dict) or hifigan.infer_config(weights)
+        if cfg.mel_dim != self.dims.mel:
+            raise ValueError("the vocoder's mel_dim {} is not Sound.Mel_Dim {}".format(cfg.mel_dim, self.dims.mel))
+        if self.dims.audio and cfg.hop != self.dims.frame_shift:
+            raise ValueError("the vocoder's rates multiply to {}, Sound.Frame_Shift is {}".format(cfg.hop, self.dims.frame_shift))
+        hifigan.check_weights(cfg, weights)
+        if not torch.cuda.is_available():
+            raise capi.GstTacoError(-2, "no HIP device: the gfx950 kernels are the only compute path (no CPU fallback)")
+        self.ctx.hifigan_configure(cfg, self.ctx.cfg.max_batch, int(max_frames or self.dims.max_step))
+        self.ctx.hifigan_load_weights(weights)
+        with torch.cuda.device(self.device):
+            self.ctx.hifigan_finalize()
+        self._hifigan = cfg
+        return self
+
+    def HiFiGAN(self, mels, mel_lengths=None):
+        """Extension: mels [B, T, Mel_Dim], normalised exactly as ``Inference_Step`` and ``Inference_GTA`` produce them (what a vocoder
+        trained on GTA mels sees: no de-normalisation), torch or numpy, with ``mel_lengths`` [B] or None (all frames) ->
+        (wav float32 [B, T * hop] in [-1, 1], wav_lengths int32 [B]) on the device (``gsttaco_hifigan``).  Row b uses its own
+        ``mel_lengths[b]`` frames everywhere -- its samples are bitwise those of the row run alone -- and is zero beyond
+        ``wav_lengths[b] = mel_lengths[b] * hop``; one frame is enough, a row of 0 frames comes out with length 0."""
+        if self._hifigan is None:
+            raise capi.GstTacoError(-4, "no HiFi-GAN loaded (call Load_HiFiGAN first)")
+        x = self._dev(mels, torch.float32)
+        if x.dim() != 3 or x.shape[2] != self._hifigan.mel_dim or x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError("mels must be [batch, frames >= 1, Mel_Dim]")
+        B, T = int(x.shape[0]), int(x.shape[1])
+        fr = self._dev(mel_lengths, torch.int32)
+        if fr is not None and tuple(fr.shape) != (B,):
+            raise ValueError("mel_lengths must be [batch]")
+        ld = T * self._hifigan.hop
+        wav = torch.empty((B, ld), dtype=torch.float32, device=self.device)
+        lens = torch.empty((B,), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            self.ctx.check(self.ctx.lib.gsttaco_hifigan(self.ctx.handle, _ptr(x), _ptr(fr), B, T, _ptr(wav), _ptr(lens), ld, self._stream()))
+        return wav, lens
+
     def Load_WaveGlow(self, weights_or_path=None, config=None, max_frames=None):
         """Extension: loads WaveGlow (``gsttaco_waveglow_*``, gst_tacotron_amd.waveglow) into this model's context, once, beside or
         without the MelGAN generator.  ``weights_or_path``: named folded arrays (``waveglow.synthetic_weights`` /
@@ -1182,7 +1236,8 @@ class GST_Tacotron:
         spectrogram cut at the stop token (Wav/<label>.IDX_<i>.WAV) under Inference_Path.  Returns the wav paths.
         ``vocoder="melgan"`` (extension): the WAVs are ``Neural_Vocoder`` of the post-net mels, cut at the ``frames`` column of
         ``Utterance_Report``, in place of Griffin-Lim; the figures are unchanged.  ``vocoder="waveglow"``: ``WaveGlow`` of the same cut
-        mels at its default temperature, row b's noise drawn from ``seeds[b]`` (None: 0 for every row)."""
+        mels at its default temperature, row b's noise drawn from ``seeds[b]`` (None: 0 for every row).  ``vocoder="hifigan"``:
+        ``HiFiGAN`` of the same cut mels."""
         from . import export
         self._check_vocoder(vocoder)
         root = self.hp_Dict["Inference_Path"]
@@ -1197,6 +1252,9 @@ class GST_Tacotron:
         elif vocoder == "waveglow":
             report, _ = self.Utterance_Report(stop_List, alignment_List)
             wav, lens = self.WaveGlow(mel_List, report[:, 1].contiguous(), seeds=seeds)
+        elif vocoder == "hifigan":
+            report, _ = self.Utterance_Report(stop_List, alignment_List)
+            wav, lens = self.HiFiGAN(mel_List, report[:, 1].contiguous())
         else:
             wav, lens = self.Inv_Spectrogram(spectrogram_List, frames=frames)
         wav, lens = wav.cpu().numpy(), lens.cpu().numpy()

@@ -713,6 +713,88 @@ int gsttaco_waveglow_debug_stage(gsttaco_ctx* ctx, int stage, const float* mel, 
 #define GSTTACO_WAVEGLOW_PLAN_INTS (3 + 6 * 354)
 int gsttaco_waveglow_plan(const gsttaco_ctx* ctx, int32_t fields[]);
 
+/* The HiFi-GAN vocoder: the generator of Kong, Kim & Bae (NeurIPS 2020) and its public implementation, mel -> waveform (EXTENSION,
+ * DESIGN row A24).  One per context, beside or without the MelGAN generator and WaveGlow, owned by the context and freed by
+ * gsttaco_destroy; gsttaco_config and the model's manifest know nothing of it.
+ * The network, with x [T, mel_dim] and L(.) = LeakyReLU(slope):
+ *   input    Conv1D mel_dim -> initial, 7 taps, zero padding 3, bias
+ *   per rate u_i (C the channels so far): L; ConvTranspose1D C -> C/2, kernel 2 u_i, stride u_i, padding u_i / 2, bias: the output
+ *            length is exactly u_i * len, every output sample has two taps, and beyond its ends the input counts as absent (zero).
+ *            Then the fusion  y = (1 / n_kernels) * sum_j ResBlock_j(x)  over residual blocks of kernel size k_j = kernels[j] and
+ *            dilations D_j = dilations[j][0 .. n_dilations[j] - 1], the sum taken in the order j = 0, 1, ...:
+ *              resblock = 1, for every d in D_j in order:  x = x + conv_{k_j, 1}(L(conv_{k_j, d}(L(x))))
+ *              resblock = 2, for every d in D_j in order:  x = x + conv_{k_j, d}(L(x))
+ *            every conv C/2 -> C/2 with bias and zero padding (k_j - 1) / 2 * d.
+ *   output   LeakyReLU(out_slope) -- 0.01, NOT slope: the public code calls F.leaky_relu with its default there --, Conv1D C_last -> 1,
+ *            7 taps, zero padding 3, bias, tanh
+ * T frames give exactly T * prod(rates) samples in [-1, 1].  Weight normalisation is folded on the host; the device sees plain weights.
+ * The shipped configurations: V1 initial 512, rates 8 8 2 2, resblock 1, kernels 3 7 11, dilations 1 3 5 each; V2 the same at initial
+ * 128; V3 initial 256, rates 8 8 4, resblock 2, kernels 3 5 7, dilations {1 2} {2 6} {3 12}.
+ * Rows have lengths: row b uses frames[b] frames, and every zero pad and every transposed-conv edge is taken at the row's own length at
+ * that stage, frames[b] * prod(rates so far); workspace beyond a row's end is never read as data.  A row's samples are bitwise those
+ * of the row run alone, whatever batch, T or capacity it ran in: every output has one summation order (bias, taps ascending, channels
+ * ascending in groups of 16, the residual, the blocks in order; fp32 MFMA, no atomics).  min_frames is 1 (zero padding needs no
+ * length): a row of 0 frames has length 0; frames[b] > T counts as T.  Samples beyond a row's length, up to ld_wav, are written as zeros. */
+#define GSTTACO_HIFIGAN_MAX_DILATIONS 4
+typedef struct gsttaco_hifigan_config {
+    int32_t mel_dim;            /* 80 */
+    int32_t initial;            /* 512 (V1): channels behind the input conv; a multiple of 2^n_rates */
+    int32_t n_rates;            /* 4 */
+    int32_t rates[GSTTACO_MAX_LAYERS];      /* 8, 8, 2, 2: even, their product is the hop; the transposed kernel is twice the rate */
+    int32_t resblock;           /* 1 or 2 */
+    int32_t n_kernels;          /* 3 */
+    int32_t kernels[GSTTACO_MAX_LAYERS];    /* 3, 7, 11: odd, at most 11 */
+    int32_t n_dilations[GSTTACO_MAX_LAYERS];                                /* 3, 3, 3: 1 .. 4 per kernel */
+    int32_t dilations[GSTTACO_MAX_LAYERS][GSTTACO_HIFIGAN_MAX_DILATIONS];   /* 1, 3, 5 each */
+    float slope;                /* 0.1 */
+    float out_slope;            /* 0.01 */
+    int32_t max_batch, max_frames;          /* capacity of a call */
+} gsttaco_hifigan_config;
+
+/* Fixes the sizes and builds the vocoder's manifest.  No GPU use.  GSTTACO_E_INVALID with a message that names the field: mel_dim /
+ * initial / a capacity < 1, n_rates or n_kernels outside 1 .. 8, a rate that is odd or < 2, initial not a multiple of 2^n_rates,
+ * resblock other than 1 or 2, a kernel that is even or above 11, n_dilations outside 1 .. 4, a dilation < 1, a slope or out_slope
+ * outside [0, 1], a launch whose smallest tile cannot fit in 160 KB of LDS, or a context whose HiFi-GAN is configured already. */
+int gsttaco_hifigan_configure(gsttaco_ctx* ctx, const gsttaco_hifigan_config* cfg);
+
+/* The vocoder's own manifest (gsttaco_num_weights of the model is unchanged), plain folded fp32 in the [taps * cin, cout] convention:
+ *   hifigan/in/kernel [7 * mel_dim, initial]          hifigan/in/bias [initial]
+ *   hifigan/up<i>/kernel [2 u_i, cin, cout]            hifigan/up<i>/bias [cout]           (i = 0 .. n_rates - 1; tap k, as torch's [cin, cout, k])
+ *   hifigan/up<i>/res<j>/unit<m>/conv1/kernel [k_j * C, C], .../conv1/bias [C]: the conv at dilation D_j[m]; and under resblock = 1
+ *   hifigan/up<i>/res<j>/unit<m>/conv2/kernel [k_j * C, C], .../conv2/bias [C]: the unit's closing conv at dilation 1
+ *   hifigan/out/kernel [7 * C_last, 1]                 hifigan/out/bias [1]
+ * GSTTACO_E_WEIGHTS: an unknown name, a wrong shape, a load before configure or after finalize. */
+int gsttaco_hifigan_num_weights(const gsttaco_ctx* ctx);
+int gsttaco_hifigan_weight_info(const gsttaco_ctx* ctx, int i, const char** name, int64_t shape[4], int* ndim);
+int gsttaco_hifigan_load_weight(gsttaco_ctx* ctx, const char* name, const float* host, const int64_t* shape, int ndim);
+
+/* Repacks the weights into the kernels' fragment order (channel counts zero-padded to multiples of 16), uploads them and allocates the
+ * workspace for the capacity: 4 * max_batch * max_frames * (the widest activation, 8192 floats per frame at V1) floats.
+ * GSTTACO_E_WEIGHTS when a tensor was not loaded. */
+int gsttaco_hifigan_finalize(gsttaco_ctx* ctx);
+
+/* mel : [B, T, mel_dim] float32 (DEVICE), normalised as gsttaco_inference_step writes it   frames : [B] int32 (DEVICE) or NULL = T
+ * wav : [B, ld_wav] float32 (DEVICE), ld_wav >= T * hop   wav_lengths : [B] int32 (DEVICE) or NULL, written
+ * One launch per convolution (2 + n_rates + the residual convs: 78 at V1), plain launches on the caller's stream: no allocation, no
+ * synchronisation, capturable in a graph.
+ * GSTTACO_E_WEIGHTS before gsttaco_hifigan_finalize; GSTTACO_E_CAPACITY: B > max_batch or T > max_frames; GSTTACO_E_INVALID: a NULL
+ * mel / wav, B or T < 1, ld_wav < T * hop. */
+int gsttaco_hifigan(gsttaco_ctx* ctx, const float* mel, const int32_t* frames, int B, int T, float* wav, int32_t* wav_lengths,
+                    int ld_wav, void* stream);
+
+/* Test support: what the launches of a configured HiFi-GAN are.  fields[0] = the number of launches S, fields[1] = min_frames,
+ * fields[2] = hop; then per launch GSTTACO_HIFIGAN_PLAN_STRIDE ints: kind (0 input conv, 1 transposed conv, 2 residual conv, 3 output
+ * conv), output channels, taps, dilation, the time tile (kind 1: in input positions 0 .. len inclusive; else in output samples), the
+ * kernel form (N-tiles of 16 channels a wave owns per item; 0 for kind 3), samples per frame of the tile's unit (kind 1: the rate of
+ * its input), dynamic LDS bytes.  fields holds GSTTACO_HIFIGAN_PLAN_INTS ints.  Launches nothing.
+ * gsttaco_hifigan_debug_stage is timing support (tools/hifigan_time.py): launch `stage` (0 .. S - 1) of gsttaco_hifigan alone, with
+ * the same arguments and checks, on whatever activations the workspace holds from an earlier whole call of the same B and T. */
+int gsttaco_hifigan_debug_stage(gsttaco_ctx* ctx, int stage, const float* mel, const int32_t* frames, int B, int T, float* wav, int ld_wav,
+                                void* stream);
+#define GSTTACO_HIFIGAN_PLAN_STRIDE 8
+#define GSTTACO_HIFIGAN_PLAN_INTS (3 + 8 * 522)
+int gsttaco_hifigan_plan(const gsttaco_ctx* ctx, int32_t fields[]);
+
 /* hipGraph cache policy.  Every entry point replays one cached graph executable per (entry, B, Tv, Tref1, steps, flags) key.
  * The cache is LRU-bounded to `max_cached` executables (default 16 -- an Inference_Step replays two or three: encoder segment, GST + decode + postnet, vocoder; GSTTACO_GRAPH_CACHE; 0 = no graphs, everything is
  * enqueued eagerly on the caller's stream); the least recently used one is destroyed when a new shape is captured.
