@@ -47,12 +47,16 @@ EXPORTED_SYMBOLS = (
     "gsttaco_waveglow_finalize", "gsttaco_waveglow_noise", "gsttaco_waveglow", "gsttaco_waveglow_plan", "gsttaco_waveglow_debug_stage",
     "gsttaco_hifigan_configure", "gsttaco_hifigan_num_weights", "gsttaco_hifigan_weight_info", "gsttaco_hifigan_load_weight",
     "gsttaco_hifigan_finalize", "gsttaco_hifigan", "gsttaco_hifigan_plan", "gsttaco_hifigan_debug_stage",
+    "gsttaco_hifigan_set_operands", "gsttaco_hifigan_debug_buffer",
 )
 # gsttaco_hifigan_plan: ints per launch (kind, channels, taps, dilation, tile, form, rate, lds), the launch kinds, and the size of its array
 HIFIGAN_PLAN_FIELDS = ("kind", "channels", "taps", "dilation", "tile", "form", "rate", "lds")
 HIFIGAN_KINDS = ("in", "up", "conv", "out")
 HIFIGAN_PLAN_INTS = 3 + 8 * 522
 HIFIGAN_MAX_DILATIONS = 4
+# gsttaco_hifigan_set_operands: the MFMA's operand form, by the name Load_HiFiGAN takes, and gsttaco_hifigan_debug_buffer's buffers
+HIFIGAN_OPERANDS = {"float32": 0, "bfloat16": 1, "float16": 2}
+HIFIGAN_BUFFERS = ("sum", "up", "a", "b")
 # gsttaco_waveglow_plan: ints per launch (kind, channels, tile, form, unit, lds), the launch kinds, and the size of its array
 WAVEGLOW_PLAN_FIELDS = ("kind", "channels", "tile", "form", "unit", "lds")
 WAVEGLOW_KINDS = ("up", "layer", "flow")
@@ -241,8 +245,11 @@ def load_library(path=None):
     lib.gsttaco_hifigan.argtypes = [vp, vp, vp, i32, i32, vp, vp, i32, vp]
     lib.gsttaco_hifigan_plan.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
     lib.gsttaco_hifigan_debug_stage.argtypes = [vp, i32, vp, vp, i32, i32, vp, i32, vp]
+    lib.gsttaco_hifigan_set_operands.argtypes = [vp, i32]
+    lib.gsttaco_hifigan_debug_buffer.argtypes = [vp, i32, vp, ctypes.c_int64, i32, vp]
     for fn in ("gsttaco_hifigan_configure", "gsttaco_hifigan_num_weights", "gsttaco_hifigan_weight_info", "gsttaco_hifigan_load_weight",
-               "gsttaco_hifigan_finalize", "gsttaco_hifigan", "gsttaco_hifigan_plan", "gsttaco_hifigan_debug_stage"):
+               "gsttaco_hifigan_finalize", "gsttaco_hifigan", "gsttaco_hifigan_plan", "gsttaco_hifigan_debug_stage",
+               "gsttaco_hifigan_set_operands", "gsttaco_hifigan_debug_buffer"):
         getattr(lib, fn).restype = ctypes.c_int
     lib.gsttaco_postnet.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.gsttaco_vocoder.argtypes = [vp, vp, i32, i32, vp, vp]
@@ -539,8 +546,19 @@ class Context:
                 raise KeyError("missing weight '{}'".format(name))
             self.hifigan_load_weight(name, weights[name])
 
+    def hifigan_set_operands(self, operands):
+        """``operands``: a name of HIFIGAN_OPERANDS ("float32", "bfloat16", "float16") or its number; between configure and finalize."""
+        self.check(self.lib.gsttaco_hifigan_set_operands(self.handle, int(HIFIGAN_OPERANDS.get(operands, operands))))
+
     def hifigan_finalize(self):
         self.check(self.lib.gsttaco_hifigan_finalize(self.handle))
+
+    def hifigan_debug_buffer(self, buffer, tensor, write, stream=None):
+        """Test support: copies the float32 device ``tensor`` into (``write``) or out of the start of workspace buffer ``buffer`` (0 .. 3
+        or a name of HIFIGAN_BUFFERS) on ``stream`` (a raw stream handle; None: the null stream)."""
+        k = HIFIGAN_BUFFERS.index(buffer) if isinstance(buffer, str) else int(buffer)
+        self.check(self.lib.gsttaco_hifigan_debug_buffer(self.handle, k, ctypes.c_void_p(tensor.data_ptr()), int(tensor.numel()),
+                                                         1 if write else 0, stream))
 
     def hifigan_plan(self):
         """(min_frames, hop, [one dict of HIFIGAN_PLAN_FIELDS per launch, ``kind`` as a name of HIFIGAN_KINDS])."""

@@ -247,6 +247,7 @@ struct gsttaco_ctx {
         std::vector<HostTensor> tensors;
         std::map<std::string, int> index;
         float* ws[GT_HG_BUFS] = {nullptr, nullptr, nullptr, nullptr};
+        int operands = GSTTACO_HIFIGAN_F32;     // gsttaco_hifigan_set_operands: the form finalize packs for (the plan's copy is what runs)
     } hg;
     // Resampling (gsttaco_resample): the tables of up to GT_RS_MAX_PAIRS rate pairs, least recently used evicted (ensure_resample_pair).
     // A slot's device memory and pinned host image are allocated at its first use and reused by the pairs that follow in it; `uploaded`
@@ -3659,7 +3660,20 @@ int gsttaco_hifigan_configure(gsttaco_ctx* c, const gsttaco_hifigan_config* m) {
         else add(p + "/kernel", {(int64_t)s.taps * s.cin, s.cout});
         add(p + "/bias", {s.cout});
     }
+    g.operands = GSTTACO_HIFIGAN_F32;           // a configure starts at the fp32 form, whatever was selected before it
     g.configured = true;
+    return 0;
+}
+
+int gsttaco_hifigan_set_operands(gsttaco_ctx* c, int operands) {
+    if (!c) return GSTTACO_E_INVALID;
+    gsttaco_ctx::Hifigan& g = c->hg;
+    if (operands != GSTTACO_HIFIGAN_F32 && operands != GSTTACO_HIFIGAN_BF16 && operands != GSTTACO_HIFIGAN_F16)
+        return fail(c, GSTTACO_E_INVALID, "hifigan: operands must be GSTTACO_HIFIGAN_F32, _BF16 or _F16");
+    if (!g.configured) return fail(c, GSTTACO_E_WEIGHTS, "hifigan: not configured (gsttaco_hifigan_configure)");
+    if (g.finalized) return fail(c, GSTTACO_E_WEIGHTS, "hifigan: weights already finalized (the operand form is chosen before gsttaco_hifigan_finalize)");
+    g.operands = operands;
+    gt_hifigan_set_operands(&g.plan, operands);
     return 0;
 }
 
@@ -3698,10 +3712,25 @@ int gsttaco_hifigan_finalize(gsttaco_ctx* c) {
     if (g.finalized) return fail(c, GSTTACO_E_WEIGHTS, "hifigan: weights already finalized");
     for (const HostTensor& t : g.tensors)
         if (!t.loaded) return fail(c, GSTTACO_E_WEIGHTS, "hifigan: weight '" + t.name + "' was not loaded");
+    auto host = [&](const std::string& name) -> const std::vector<float>& { return g.tensors[g.index[name]].data; };
+    // The 16-bit packs first, on the host alone: a weight that fp16 cannot hold refuses the finalize before anything is uploaded, and
+    // the context stays as it was (another form can be selected, or the tensor loaded again).
+    static_assert(GSTTACO_HIFIGAN_F32 == GT_HG_OP_F32 && GSTTACO_HIFIGAN_BF16 == GT_HG_OP_BF16 && GSTTACO_HIFIGAN_F16 == GT_HG_OP_F16, "operand forms");
+    std::vector<std::vector<float>> packs16(g.plan.n_stages);       // 16-bit words, two to a float
+    if (g.operands != GSTTACO_HIFIGAN_F32)
+        for (int i = 0; i < g.plan.n_stages; ++i) {
+            const HgStage& s = g.plan.st[i];
+            if (s.kind == GT_HG_OUT) continue;
+            const std::string p = hifigan_name(s);
+            packs16[i].resize(gt_hifigan_pack16_words(s.taps, s.cin, s.cout) / 2);
+            const int64_t bad = gt_hifigan_pack16(host(p + "/kernel").data(), s.taps, s.cin, s.cout, g.operands, reinterpret_cast<uint16_t*>(packs16[i].data()));
+            if (bad >= 0)
+                return fail(c, GSTTACO_E_WEIGHTS, "hifigan: weight '" + p + "/kernel' is not finite in float16 (element " + std::to_string(bad) +
+                                                  "): use the bfloat16 or float32 operands");
+        }
     int rc = ensure_device(c);
     if (rc) return rc;
     HIPCHECK(c, gt_hifigan_prepare());
-    auto host = [&](const std::string& name) -> const std::vector<float>& { return g.tensors[g.index[name]].data; };
     std::vector<float> buf;
     for (int i = 0; i < g.plan.n_stages; ++i) {
         HgStage& s = g.plan.st[i];
@@ -3709,6 +3738,8 @@ int gsttaco_hifigan_finalize(gsttaco_ctx* c) {
         float* d = nullptr;
         if (s.kind == GT_HG_OUT) {
             if ((rc = upload(c, &d, host(p + "/kernel").data(), (size_t)s.taps * s.cin))) return rc;
+        } else if (g.operands != GSTTACO_HIFIGAN_F32) {
+            if ((rc = upload(c, &d, packs16[i].data(), packs16[i].size()))) return rc;
         } else {
             buf.resize((size_t)s.taps * s.cin_p * s.n_p);
             gt_hifigan_pack(host(p + "/kernel").data(), s.taps, s.cin, s.cout, buf.data());
@@ -3742,6 +3773,19 @@ int gsttaco_hifigan_debug_stage(gsttaco_ctx* c, int stage, const float* mel, con
     if (!c) return GSTTACO_E_INVALID;
     if (stage < 0 || stage >= c->hg.plan.n_stages) return fail(c, GSTTACO_E_INVALID, "hifigan: no such launch");
     return hifigan_call(c, mel, frames, B, T, wav, nullptr, ld_wav, stage, stream);
+}
+
+int gsttaco_hifigan_debug_buffer(gsttaco_ctx* c, int buffer, float* device, int64_t floats, int write, void* stream) {
+    if (!c) return GSTTACO_E_INVALID;
+    const gsttaco_ctx::Hifigan& g = c->hg;
+    if (!g.finalized) return fail(c, GSTTACO_E_WEIGHTS, "hifigan: weights not finalized (gsttaco_hifigan_finalize)");
+    if (buffer < 0 || buffer >= GT_HG_BUFS) return fail(c, GSTTACO_E_INVALID, "hifigan: no such workspace buffer (0 sum, 1 up, 2 A, 3 B)");
+    const int64_t size = (int64_t)g.cfg.max_batch * g.cfg.max_frames * (int64_t)g.plan.ws_floats_per_frame;
+    if (!device || floats < 0 || floats > size) return fail(c, GSTTACO_E_INVALID, "hifigan: a NULL array, or more floats than the workspace buffer holds");
+    if (floats == 0) return 0;
+    HIPCHECK(c, hipMemcpyAsync(write ? (void*)g.ws[buffer] : (void*)device, write ? (const void*)device : (const void*)g.ws[buffer],
+                               (size_t)floats * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
 }
 
 namespace {

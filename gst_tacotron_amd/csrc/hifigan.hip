@@ -32,7 +32,19 @@
 // order -- that depends on neither the batch nor the call's T nor the capacity: a row's samples are bitwise those of the row run alone.
 // Every global access is bounded by the row's length at that stage (<= T * rate), every LDS access by the tile the plan sized; nothing
 // waits on another workgroup.
+//
+// The 16-bit operand forms (gsttaco_hifigan_set_operands; GT_HG_OP_BF16 / GT_HG_OP_F16) run the same three GEMM kernels on
+// v_mfma_f32_16x16x32_{bf16,f16}: one template over the operand type, the two instructions share their lane maps (lane l holds
+// A[row l & 15][k = 8 (l >> 4) + j] and B[k = 8 (l >> 4) + j][col l & 15], j = 0 .. 7; C as the fp32 16x16x4 form, so the epilogues are
+// the same code).  HBM is untouched: activations stay fp32 at C_p = round16(C).  hg_stage applies its bounds and the LeakyReLU in fp32,
+// then rounds to nearest even once (fp16 saturating to +-65504) into a 16-bit LDS tile whose rows are padded with exact zeros to a
+// multiple of 32 k, plus 8 elements: the row stride is then an odd number of 16-byte slots, and the 16 rows of a ds_read_b128 lane group
+// (8 at one k quarter, 8 at the next) fall on 16-byte slots at worst 2-way.  The weights are rounded once on the host (gt_hifigan_pack16)
+// into [tap][k / 32][n][q = (k % 32) / 8][j = k % 8]: one 16-byte load per lane and 32 k.  k advances in blocks of 32; a sample's order
+// is bias, taps ascending, k ascending in blocks of 32 (inside a block the MFMA's own), the residual, the fused sum -- still independent
+// of batch, T and capacity.  The output conv stays fp32 on the VALU in every form.
 #include <algorithm>
+#include <string.h>
 #include <math.h>
 
 #include "kernels.h"
@@ -45,6 +57,17 @@
 #define HG_TAPS_IO 7
 
 namespace {
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+// The operand type of the MFMA: K the k block an MFMA group consumes (the LDS row and the weight pack are padded to it), Q = K / 4 the
+// elements a lane holds of it, PAD the row padding in elements (16 bytes in every form).
+template <typename OP> struct HgOp;
+template <> struct HgOp<float> { static constexpr int K = 16, Q = 4, PAD = 4; };
+template <> struct HgOp<__bf16> { static constexpr int K = 32, Q = 8, PAD = 8; typedef bf16x8 frag; };
+template <> struct HgOp<_Float16> { static constexpr int K = 32, Q = 8, PAD = 8; typedef f16x8 frag; };
+template <typename OP> __host__ __device__ __forceinline__ int hg_kpad(int c) { return (c + HgOp<OP>::K - 1) / HgOp<OP>::K * HgOp<OP>::K; }
 
 struct HgArgs {
     const float* x;             // the launch's input
@@ -68,25 +91,41 @@ __device__ __forceinline__ float hg_leaky(float v, float slope) { return v > 0.f
 
 // Positions [p0, p0 + rows) of one row's input (len valid positions, row stride ldx) into xs[rows][cs], channels [0, cin_p).  A position
 // outside [0, len), and every channel >= cin, is 0.
-template <bool LEAKY>
-__device__ __forceinline__ void hg_stage(const HgArgs& a, const float* xb, float* xs, int cs, int p0, int rows, int len, bool vec) {
+// fp32 -> the operand type, to nearest even; fp16 saturates instead of overflowing to inf (a NaN stays a NaN)
+template <typename OP> __device__ __forceinline__ OP hg_cvt(float v) { return (OP)v; }
+template <> __device__ __forceinline__ _Float16 hg_cvt<_Float16>(float v) {
+    v = v > 65504.f ? 65504.f : (v < -65504.f ? -65504.f : v);
+    return (_Float16)v;
+}
+__device__ __forceinline__ void hg_store4(float* dst, const float4& v) { *reinterpret_cast<float4*>(dst) = v; }
+template <typename OP>
+__device__ __forceinline__ void hg_store4(OP* dst, const float4& v) {
+    typedef OP op4 __attribute__((ext_vector_type(4)));
+    const op4 o = {hg_cvt<OP>(v.x), hg_cvt<OP>(v.y), hg_cvt<OP>(v.z), hg_cvt<OP>(v.w)};
+    *reinterpret_cast<op4*>(dst) = o;                       // 8 bytes: cs and c are multiples of 4 elements
+}
+
+// The same for the operand type OP: the fp32 value, bounds and LeakyReLU first, then rounded once; channels [cin_p, hg_kpad(cin_p)) are 0.
+template <typename OP, bool LEAKY>
+__device__ __forceinline__ void hg_stage(const HgArgs& a, const float* xb, OP* xs, int cs, int p0, int rows, int len, bool vec) {
+    const int ck = hg_kpad<OP>(a.cin_p);
     if (vec) {
-        const int c4n = a.cin_p >> 2;
+        const int c4n = ck >> 2;
         for (int e = threadIdx.x; e < rows * c4n; e += HG_THREADS) {
             const int i = e / c4n, c = (e - i * c4n) << 2;
             const int p = p0 + i;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (p >= 0 && p < len) v = *reinterpret_cast<const float4*>(xb + (size_t)p * a.ldx + c);
+            if (p >= 0 && p < len && c < a.cin_p) v = *reinterpret_cast<const float4*>(xb + (size_t)p * a.ldx + c);
             if (LEAKY) { v.x = hg_leaky(v.x, a.slope); v.y = hg_leaky(v.y, a.slope); v.z = hg_leaky(v.z, a.slope); v.w = hg_leaky(v.w, a.slope); }
-            *reinterpret_cast<float4*>(xs + i * cs + c) = v;
+            hg_store4(xs + i * cs + c, v);
         }
     } else {
-        for (int e = threadIdx.x; e < rows * a.cin_p; e += HG_THREADS) {
-            const int i = e / a.cin_p, c = e - i * a.cin_p;
+        for (int e = threadIdx.x; e < rows * ck; e += HG_THREADS) {
+            const int i = e / ck, c = e - i * ck;
             const int p = p0 + i;
             float v = 0.f;
             if (p >= 0 && p < len && c < a.cin) v = xb[(size_t)p * a.ldx + c];
-            xs[i * cs + c] = LEAKY ? hg_leaky(v, a.slope) : v;
+            xs[i * cs + c] = hg_cvt<OP>(LEAKY ? hg_leaky(v, a.slope) : v);
         }
     }
 }
@@ -117,6 +156,26 @@ __device__ __forceinline__ void hg_gemm(f32x4 (&acc)[4][NT], const float* a_lane
     }
 }
 
+// The 16-bit form: acc[mt][nt] += A[64 rows, 32 nkb] * W[32 nkb, 16 NT].  a_lane: this lane's row l & 15 of M-tile 0, k offset 8 (l >> 4);
+// w_lane: this lane's column and k quarter of N-tile 0 in the 16-bit pack.  One MFMA per M-tile, N-tile and 32 k.
+__device__ __forceinline__ f32x4 hg_mfma16(const bf16x8& a, const bf16x8& b, const f32x4& c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f32x4 hg_mfma16(const f16x8& a, const f16x8& b, const f32x4& c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+template <int NT, typename OP>
+__device__ __forceinline__ void hg_gemm(f32x4 (&acc)[4][NT], const OP* a_lane, int cs, const OP* w_lane, int nkb, int n_p) {
+    typedef typename HgOp<OP>::frag frag;
+    for (int kb = 0; kb < nkb; ++kb) {
+        frag av[4], bv[NT];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) bv[nt] = *reinterpret_cast<const frag*>(w_lane + ((size_t)kb * n_p + nt * 16) * 32);
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) av[mt] = *reinterpret_cast<const frag*>(a_lane + mt * 16 * cs + kb * 32);
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = hg_mfma16(av[mt], bv[nt], acc[mt][nt]);
+    }
+}
+
 template <int NT>
 __device__ __forceinline__ void hg_bias(f32x4 (&acc)[4][NT], const float* bias, int n0, int col) {
 #pragma unroll
@@ -128,25 +187,28 @@ __device__ __forceinline__ void hg_bias(f32x4 (&acc)[4][NT], const float* bias, 
 }
 
 // ------------------------------------------------------------------------------------------------ the input conv
-template <int NT>
+template <int NT, typename OP>
 __global__ __launch_bounds__(HG_THREADS) void gt_hg_in_kernel(HgArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float hg_lds[];
+    extern __shared__ __attribute__((aligned(16))) unsigned char hg_lds_raw[];
+    OP* hg_lds = reinterpret_cast<OP*>(hg_lds_raw);
+    constexpr int KB = HgOp<OP>::K, Q = HgOp<OP>::Q;
+    const OP* w0 = reinterpret_cast<const OP*>(a.w0);
     const int b = blockIdx.y, len = hg_row_frames(a, b), t0 = blockIdx.x * a.tile;
     if (t0 >= len) return;
-    const int cs = a.cin_p + 4, pad = HG_TAPS_IO / 2;
+    const int ck = hg_kpad<OP>(a.cin_p), cs = ck + HgOp<OP>::PAD, pad = HG_TAPS_IO / 2;
     const float* xb = a.x + (size_t)b * a.T * a.ldx;
     float* yb = a.y + (size_t)b * a.T * a.n_p;
-    hg_stage<false>(a, xb, hg_lds, cs, t0 - pad, a.tile + 2 * pad, len, false);
+    hg_stage<OP, false>(a, xb, hg_lds, cs, t0 - pad, a.tile + 2 * pad, len, false);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, g = lane >> 4;
-    const int nkb = a.cin_p >> 4, ngroups = (a.n_p >> 4) / NT, items = (a.tile / HG_ROWS) * ngroups;
+    const int nkb = ck / KB, ngroups = (a.n_p >> 4) / NT, items = (a.tile / HG_ROWS) * ngroups;
     for (int item = wave; item < items; item += HG_WAVES) {
         const int mg = item / ngroups, n0 = (item - mg * ngroups) * NT * 16;
         f32x4 acc[4][NT];
         hg_bias<NT>(acc, a.b0, n0, col);
         for (int tap = 0; tap < HG_TAPS_IO; ++tap)
-            hg_gemm<NT>(acc, hg_lds + (mg * HG_ROWS + tap + col) * cs + 4 * g, cs,
-                        a.w0 + (size_t)tap * a.cin_p * a.n_p + (size_t)(n0 + col) * 16 + 4 * g, nkb, a.n_p);
+            hg_gemm<NT>(acc, hg_lds + (mg * HG_ROWS + tap + col) * cs + Q * g, cs,
+                        w0 + (size_t)tap * ck * a.n_p + (size_t)(n0 + col) * KB + Q * g, nkb, a.n_p);
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
@@ -161,27 +223,30 @@ __global__ __launch_bounds__(HG_THREADS) void gt_hg_in_kernel(HgArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ the transposed conv
-template <int NT>
+template <int NT, typename OP>
 __global__ __launch_bounds__(HG_THREADS) void gt_hg_up_kernel(HgArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float hg_lds[];
+    extern __shared__ __attribute__((aligned(16))) unsigned char hg_lds_raw[];
+    OP* hg_lds = reinterpret_cast<OP*>(hg_lds_raw);
+    constexpr int KB = HgOp<OP>::K, Q = HgOp<OP>::Q;
+    const OP* w0 = reinterpret_cast<const OP*>(a.w0);
     const int b = blockIdx.y, len = hg_row_frames(a, b) * a.rate_in, q0 = blockIdx.x * a.tile;
     if (len == 0 || q0 > len) return;                       // q runs over [0, len]: position len still feeds the last r / 2 samples
-    const int cs = a.cin_p + 4;
+    const int ck = hg_kpad<OP>(a.cin_p), cs = ck + HgOp<OP>::PAD;
     const float* xb = a.x + (size_t)b * a.T * a.rate_in * a.ldx;
     float* yb = a.y + (size_t)b * a.T * a.rate_out * a.n_p;
-    hg_stage<true>(a, xb, hg_lds, cs, q0 - 1, a.tile + 1, len, true);       // xs[i] = LeakyReLU(x[q0 - 1 + i]), 0 where absent
+    hg_stage<OP, true>(a, xb, hg_lds, cs, q0 - 1, a.tile + 1, len, true);       // xs[i] = LeakyReLU(x[q0 - 1 + i]), 0 where absent
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, g = lane >> 4;
-    const int nkb = a.cin_p >> 4, ngroups = (a.n_p >> 4) / NT, per_phase = (a.tile / HG_ROWS) * ngroups, items = per_phase * a.r;
+    const int nkb = ck / KB, ngroups = (a.n_p >> 4) / NT, per_phase = (a.tile / HG_ROWS) * ngroups, items = per_phase * a.r;
     const int len_out = len * a.r, half = a.r >> 1;
-    const size_t tap_stride = (size_t)a.cin_p * a.n_p;
+    const size_t tap_stride = (size_t)ck * a.n_p;
     for (int item = wave; item < items; item += HG_WAVES) {
         const int p = item / per_phase, rest = item - p * per_phase, mg = rest / ngroups, n0 = (rest - mg * ngroups) * NT * 16;
         f32x4 acc[4][NT];
         hg_bias<NT>(acc, a.b0, n0, col);
-        const size_t wl = (size_t)(n0 + col) * 16 + 4 * g;
-        hg_gemm<NT>(acc, hg_lds + (mg * HG_ROWS + 1 + col) * cs + 4 * g, cs, a.w0 + p * tap_stride + wl, nkb, a.n_p);
-        hg_gemm<NT>(acc, hg_lds + (mg * HG_ROWS + col) * cs + 4 * g, cs, a.w0 + (p + a.r) * tap_stride + wl, nkb, a.n_p);
+        const size_t wl = (size_t)(n0 + col) * KB + Q * g;
+        hg_gemm<NT>(acc, hg_lds + (mg * HG_ROWS + 1 + col) * cs + Q * g, cs, w0 + p * tap_stride + wl, nkb, a.n_p);
+        hg_gemm<NT>(acc, hg_lds + (mg * HG_ROWS + col) * cs + Q * g, cs, w0 + (p + a.r) * tap_stride + wl, nkb, a.n_p);
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
@@ -197,28 +262,31 @@ __global__ __launch_bounds__(HG_THREADS) void gt_hg_up_kernel(HgArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ one residual conv
-template <int NT>
+template <int NT, typename OP>
 __global__ __launch_bounds__(HG_THREADS) void gt_hg_conv_kernel(HgArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float hg_lds[];
+    extern __shared__ __attribute__((aligned(16))) unsigned char hg_lds_raw[];
+    OP* hg_lds = reinterpret_cast<OP*>(hg_lds_raw);
+    constexpr int KB = HgOp<OP>::K, Q = HgOp<OP>::Q;
+    const OP* w0 = reinterpret_cast<const OP*>(a.w0);
     const int b = blockIdx.y, len = hg_row_frames(a, b) * a.rate_in, t0 = blockIdx.x * a.tile;
     if (t0 >= len) return;
-    const int cs = a.cin_p + 4, d = a.dil, halo = (a.taps >> 1) * d;
+    const int ck = hg_kpad<OP>(a.cin_p), cs = ck + HgOp<OP>::PAD, d = a.dil, halo = (a.taps >> 1) * d;
     const size_t row0 = (size_t)b * a.T * a.rate_in * a.n_p;            // cin_p == n_p: every buffer of the stage has this shape
-    hg_stage<true>(a, a.x + row0, hg_lds, cs, t0 - halo, a.tile + 2 * halo, len, true);
+    hg_stage<OP, true>(a, a.x + row0, hg_lds, cs, t0 - halo, a.tile + 2 * halo, len, true);
     __syncthreads();
     const float* rb = a.res ? a.res + row0 : nullptr;
     float* yb = a.y ? a.y + row0 : nullptr;
     float* sb = a.sum + row0;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, g = lane >> 4;
-    const int nkb = a.cin_p >> 4, ngroups = (a.n_p >> 4) / NT, items = (a.tile / HG_ROWS) * ngroups;
-    const size_t tap_stride = (size_t)a.cin_p * a.n_p;
+    const int nkb = ck / KB, ngroups = (a.n_p >> 4) / NT, items = (a.tile / HG_ROWS) * ngroups;
+    const size_t tap_stride = (size_t)ck * a.n_p;
     for (int item = wave; item < items; item += HG_WAVES) {
         const int mg = item / ngroups, n0 = (item - mg * ngroups) * NT * 16;
         f32x4 acc[4][NT];
         hg_bias<NT>(acc, a.b0, n0, col);
-        const size_t wl = (size_t)(n0 + col) * 16 + 4 * g;
+        const size_t wl = (size_t)(n0 + col) * KB + Q * g;
         for (int tap = 0; tap < a.taps; ++tap)
-            hg_gemm<NT>(acc, hg_lds + (mg * HG_ROWS + tap * d + col) * cs + 4 * g, cs, a.w0 + tap * tap_stride + wl, nkb, a.n_p);
+            hg_gemm<NT>(acc, hg_lds + (mg * HG_ROWS + tap * d + col) * cs + Q * g, cs, w0 + tap * tap_stride + wl, nkb, a.n_p);
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
@@ -283,24 +351,56 @@ void hg_tile_form(int n_p, int* tile, int* form) {
     *form = nt;
 }
 
-size_t hg_lds_bytes(const HgStage& s) {
-    const size_t cs = (size_t)s.cin_p + 4;
+// op_bytes: the size of an MFMA operand, 4 (fp32: rows of cin_p + 4) or 2 (16-bit: rows of round32(cin_p) + 8); the output conv is fp32 always
+size_t hg_lds_bytes(const HgStage& s, size_t op_bytes) {
+    const size_t cs = op_bytes == 4 ? (size_t)s.cin_p + HgOp<float>::PAD : (size_t)hg_kpad<__bf16>(s.cin_p) + HgOp<__bf16>::PAD;
     switch (s.kind) {
-    case GT_HG_IN: return (size_t)(s.tile + HG_TAPS_IO - 1) * cs * sizeof(float);
-    case GT_HG_UP: return (size_t)(s.tile + 1) * cs * sizeof(float);
-    case GT_HG_CONV: return ((size_t)s.tile + (size_t)(s.taps - 1) * s.dil) * cs * sizeof(float);
+    case GT_HG_IN: return (size_t)(s.tile + HG_TAPS_IO - 1) * cs * op_bytes;
+    case GT_HG_UP: return (size_t)(s.tile + 1) * cs * op_bytes;
+    case GT_HG_CONV: return ((size_t)s.tile + (size_t)(s.taps - 1) * s.dil) * cs * op_bytes;
     default: return ((size_t)(HG_OUT_TILE + HG_TAPS_IO - 1) * (s.cin | 1) + (size_t)HG_TAPS_IO * s.cin) * sizeof(float);
     }
 }
 
-template <int NT>
+template <int NT, typename OP>
 hipError_t hg_launch_form(const HgStage& s, const HgArgs& a, dim3 grid, hipStream_t stream) {
     switch (s.kind) {
-    case GT_HG_IN: gt_hg_in_kernel<NT><<<grid, HG_THREADS, s.lds, stream>>>(a); break;
-    case GT_HG_UP: gt_hg_up_kernel<NT><<<grid, HG_THREADS, s.lds, stream>>>(a); break;
-    default: gt_hg_conv_kernel<NT><<<grid, HG_THREADS, s.lds, stream>>>(a); break;
+    case GT_HG_IN: gt_hg_in_kernel<NT, OP><<<grid, HG_THREADS, s.lds, stream>>>(a); break;
+    case GT_HG_UP: gt_hg_up_kernel<NT, OP><<<grid, HG_THREADS, s.lds, stream>>>(a); break;
+    default: gt_hg_conv_kernel<NT, OP><<<grid, HG_THREADS, s.lds, stream>>>(a); break;
     }
     return hipGetLastError();
+}
+
+template <typename OP>
+hipError_t hg_launch_op(const HgStage& s, const HgArgs& a, dim3 grid, hipStream_t stream) {
+    return s.form == 4 ? hg_launch_form<4, OP>(s, a, grid, stream) : s.form == 2 ? hg_launch_form<2, OP>(s, a, grid, stream)
+                                                                                 : hg_launch_form<1, OP>(s, a, grid, stream);
+}
+
+template <typename OP>
+hipError_t hg_prepare_op() {
+    hipError_t e = hipSuccess;
+#define HG_ATTR(K) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, GT_HG_LDS_MAX)
+    HG_ATTR((gt_hg_in_kernel<1, OP>)); HG_ATTR((gt_hg_in_kernel<2, OP>)); HG_ATTR((gt_hg_in_kernel<4, OP>));
+    HG_ATTR((gt_hg_up_kernel<1, OP>)); HG_ATTR((gt_hg_up_kernel<2, OP>)); HG_ATTR((gt_hg_up_kernel<4, OP>));
+    HG_ATTR((gt_hg_conv_kernel<1, OP>)); HG_ATTR((gt_hg_conv_kernel<2, OP>)); HG_ATTR((gt_hg_conv_kernel<4, OP>));
+#undef HG_ATTR
+    return e;
+}
+
+// fp32 -> bf16 / fp16 bits, to nearest even, as the device's conversion does it
+uint16_t hg_bf16_bits(float v) {
+    uint32_t u;
+    memcpy(&u, &v, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x0040u);       // NaN stays a (quiet) NaN
+    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+uint16_t hg_f16_bits(float v) {
+    const _Float16 h = (_Float16)v;
+    uint16_t u;
+    memcpy(&u, &h, 2);
+    return u;
 }
 
 }  // namespace
@@ -339,7 +439,7 @@ const char* gt_hifigan_make_plan(const HgConfig& cfg, HgPlan* plan) {
         s.src = s.res = s.dst = -1; s.sum = GT_HG_SUM_NONE; s.scale = 1.f; s.up = s.block = s.unit = s.conv = -1;
         if (kind == GT_HG_OUT) { s.tile = HG_OUT_TILE; s.form = 0; }
         else hg_tile_form(s.n_p, &s.tile, &s.form);
-        while ((s.lds = hg_lds_bytes(s)) > GT_HG_LDS_MAX && kind != GT_HG_OUT && s.tile > HG_ROWS) s.tile >>= 1;
+        while ((s.lds = hg_lds_bytes(s, sizeof(float))) > GT_HG_LDS_MAX && kind != GT_HG_OUT && s.tile > HG_ROWS) s.tile >>= 1;
         if (kind != GT_HG_OUT) P.ws_floats_per_frame = std::max(P.ws_floats_per_frame, (size_t)rate_out * s.n_p);
         return s.lds <= GT_HG_LDS_MAX ? &s : nullptr;
     };
@@ -393,13 +493,36 @@ void gt_hifigan_pack(const float* w, int taps, int cin, int cout, float* out) {
                 out[(size_t)tap * cin_p * n_p + ((size_t)(k >> 4) * n_p + nn) * 16 + (k & 15)] = w[((size_t)tap * cin + k) * cout + nn];
 }
 
+void gt_hifigan_set_operands(HgPlan* plan, int operands) {
+    plan->operands = operands;
+    for (int i = 0; i < plan->n_stages; ++i) plan->st[i].lds = hg_lds_bytes(plan->st[i], operands == GT_HG_OP_F32 ? 4 : 2);
+}
+
+size_t gt_hifigan_pack16_words(int taps, int cin, int cout) { return (size_t)taps * hg_kpad<__bf16>(hg_pad16(cin)) * hg_pad16(cout); }
+
+int64_t gt_hifigan_pack16(const float* w, int taps, int cin, int cout, int operands, uint16_t* out) {
+    const int ck = hg_kpad<__bf16>(hg_pad16(cin)), n_p = hg_pad16(cout);
+    std::fill(out, out + (size_t)taps * ck * n_p, (uint16_t)0);
+    int64_t bad = -1;
+    for (int tap = 0; tap < taps; ++tap)
+        for (int k = 0; k < cin; ++k)
+            for (int nn = 0; nn < cout; ++nn) {
+                const size_t src = ((size_t)tap * cin + k) * cout + nn;
+                uint16_t bits;
+                if (operands == GT_HG_OP_F16) {
+                    bits = hg_f16_bits(w[src]);
+                    if ((bits & 0x7c00u) == 0x7c00u && bad < 0) bad = (int64_t)src;     // inf or NaN after rounding
+                } else bits = hg_bf16_bits(w[src]);
+                out[(size_t)tap * ck * n_p + ((size_t)(k >> 5) * n_p + nn) * 32 + (k & 31)] = bits;
+            }
+    return bad;
+}
+
 hipError_t gt_hifigan_prepare() {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gt_hg_out_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, GT_HG_LDS_MAX);
-#define HG_ATTR(K) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, GT_HG_LDS_MAX)
-    HG_ATTR(gt_hg_in_kernel<1>); HG_ATTR(gt_hg_in_kernel<2>); HG_ATTR(gt_hg_in_kernel<4>);
-    HG_ATTR(gt_hg_up_kernel<1>); HG_ATTR(gt_hg_up_kernel<2>); HG_ATTR(gt_hg_up_kernel<4>);
-    HG_ATTR(gt_hg_conv_kernel<1>); HG_ATTR(gt_hg_conv_kernel<2>); HG_ATTR(gt_hg_conv_kernel<4>);
-#undef HG_ATTR
+    if (e == hipSuccess) e = hg_prepare_op<float>();
+    if (e == hipSuccess) e = hg_prepare_op<__bf16>();
+    if (e == hipSuccess) e = hg_prepare_op<_Float16>();
     return e;
 }
 
@@ -435,8 +558,8 @@ hipError_t gt_launch_hifigan(const HgPlan& P, const HgCall& c, hipStream_t strea
             gt_hg_out_kernel<<<grid, HG_OUT_TILE, s.lds, stream>>>(a);
             e = hipGetLastError();
         } else {
-            e = s.form == 4 ? hg_launch_form<4>(s, a, grid, stream) : s.form == 2 ? hg_launch_form<2>(s, a, grid, stream)
-                                                                                  : hg_launch_form<1>(s, a, grid, stream);
+            e = P.operands == GT_HG_OP_BF16 ? hg_launch_op<__bf16>(s, a, grid, stream)
+              : P.operands == GT_HG_OP_F16 ? hg_launch_op<_Float16>(s, a, grid, stream) : hg_launch_op<float>(s, a, grid, stream);
         }
         if (e != hipSuccess) return e;
     }

@@ -667,6 +667,7 @@ struct MgPlan {
     int mel_dim, hop, min_frames;
     float slope;
     size_t ws_floats_per_frame;     // the largest activation of the chain, floats per mel frame of one row
+    int operands;                   // GT_HG_OP_*: gt_hifigan_make_plan leaves fp32, gt_hifigan_set_operands changes it
 };
 // Fills the plan's shapes, tiles and LDS sizes (no device use).  Returns NULL, or the reason the configuration cannot run.
 const char* gt_melgan_make_plan(int mel_dim, int base, int n_ratios, const int* ratios, int n_res, float slope, MgPlan* plan);
@@ -751,6 +752,9 @@ enum { GT_HG_BUF_SUM = 0, GT_HG_BUF_UP = 1, GT_HG_BUF_A = 2, GT_HG_BUF_B = 3, GT
 // What a GT_HG_CONV launch does with its result v (bias + taps, then + residual): GT_HG_SUM_NONE writes v to dst; the last unit of block j
 // writes the fused sum instead: sum = v (j = 0) or sum += v, times `scale` = 1 / n_k on the last block.
 enum { GT_HG_SUM_NONE = 0, GT_HG_SUM_SET = 1, GT_HG_SUM_ADD = 2 };
+// The MFMA's operand form (gsttaco_hifigan_set_operands): fp32 on v_mfma_f32_16x16x4_f32, or the staged tile and the weight pack rounded
+// to bf16 / fp16 on v_mfma_f32_16x16x32_{bf16,f16}.  Activations, biases, accumulators and epilogues are fp32 in every form.
+enum { GT_HG_OP_F32 = 0, GT_HG_OP_BF16 = 1, GT_HG_OP_F16 = 2 };
 // One launch of the chain.  Channel counts with _p are the padded ones (multiples of 16) the fragment packs and the workspace use.
 struct HgStage {
     int kind;
@@ -764,7 +768,7 @@ struct HgStage {
     int up, block, unit, conv;  // where the launch sits: stage i, residual block j, unit m, conv 0 / 1 (the manifest's names)
     int tile, form;             // time tile (GT_HG_UP: in input positions, else in output samples); form: N-tiles a wave item owns (GT_HG_OUT: 0)
     size_t lds;                 // dynamic LDS of a workgroup, bytes
-    const float *w0, *b0;       // device operands (gsttaco_hifigan_finalize)
+    const float *w0, *b0;       // device operands (gsttaco_hifigan_finalize); w0 holds 16-bit words under GT_HG_OP_BF16 / _F16 (not GT_HG_OUT)
 };
 struct HgConfig {
     int mel_dim, initial, n_rates, rates[GT_HG_MAX_RATES], resblock, n_kernels, kernels[GT_HG_MAX_KERNELS];
@@ -777,11 +781,21 @@ struct HgPlan {
     int mel_dim, hop, min_frames;
     float slope, out_slope;
     size_t ws_floats_per_frame;     // the largest activation of the chain, floats per mel frame of one row
+    int operands;                   // GT_HG_OP_*: gt_hifigan_make_plan leaves fp32, gt_hifigan_set_operands changes it
 };
 // Fills the plan's shapes, tiles and LDS sizes (no device use).  Returns NULL, or the reason the configuration cannot run.
 const char* gt_hifigan_make_plan(const HgConfig& cfg, HgPlan* plan);
 // [taps * cin, cout] (row stride cout) -> the fragment pack [taps][cin_p / 16][n_p][4][4] the kernels read, zero padded
 void gt_hifigan_pack(const float* w, int taps, int cin, int cout, float* out);
+// The plan's operand form: the launches, tiles and forms stay the fp32 plan's, only every launch's LDS bytes are recomputed for the
+// operand size (they shrink: a 16-bit row of round32(cin_p) + 8 elements is never longer than an fp32 row of cin_p + 4).
+void gt_hifigan_set_operands(HgPlan* plan, int operands);
+// Words of the 16-bit pack of a [taps * cin, cout] kernel: taps * round32(cin) * round16(cout)
+size_t gt_hifigan_pack16_words(int taps, int cin, int cout);
+// The 16-bit fragment pack [taps][cin_p32 / 32][n_p][4][8], zero padded, each weight rounded to nearest even once (operands: GT_HG_OP_BF16
+// or GT_HG_OP_F16): one 16-byte load per lane and 32 k.  Returns -1, or under GT_HG_OP_F16 the index in w of the first weight that is
+// not finite after rounding (the pack is then unusable).
+int64_t gt_hifigan_pack16(const float* w, int taps, int cin, int cout, int operands, uint16_t* out);
 hipError_t gt_hifigan_prepare();
 struct HgCall {
     const float* mel;           // [B, T, mel_dim]

@@ -8,6 +8,9 @@ Weights are named, plain (weight norm folded) float32 arrays in the project's ``
 unit's dilation) and, under ``resblock = 1``, ``.../conv2/kernel`` (the unit's closing conv at dilation 1), ``hifigan/out/kernel``,
 each with ``.../bias``.
 
+``round_operand`` states, in NumPy, the one rounding the optional 16-bit operand forms apply (``Load_HiFiGAN(precision=)``, the
+section's ``Precision`` key, ``gsttaco_hifigan_set_operands``): the two operands of each matrix product, nothing else.
+
 The loader's layout is NOT verified against a trained public checkpoint (none is at hand): it is pinned to torch's own modules,
 built as the public generator, on the CPU (tests/test_hifigan_cases.py).  Public checkpoints were trained on natural-log mels at
 another scale than this project's normalised ones and will not sound right here; the use is a vocoder trained on ``Inference_GTA``
@@ -56,8 +59,42 @@ class HiFiGANConfig:
         return cls(mel_dim=mel_dim, initial=256, rates=[8, 8, 4], resblock=2, kernels=[3, 5, 7], dilations=[[1, 2], [2, 6], [3, 12]])
 
 
+PRECISIONS = ("float32", "bfloat16", "float16")
+
+
+def check_precision(precision):
+    if precision not in PRECISIONS:
+        raise ValueError("precision must be 'float32', 'bfloat16' or 'float16', not {!r}".format(precision))
+    return precision
+
+
+def precision_from_hp(hp):
+    """The section's optional ``Precision`` key (the operand type of the matrix products), "float32" where it or the section is absent."""
+    return check_precision((hp.get("Vocoder_HiFiGAN") or {}).get("Precision") or "float32")
+
+
+def round_operand(x, precision):
+    """What ``gsttaco_hifigan_set_operands`` does to an operand of a matrix product, stated on the host: ``x`` (any float array) is
+    rounded once to ``precision`` and returned in x's own dtype (every bfloat16 and float16 is exact in float32 and float64).
+    "float32" returns x unchanged.  "bfloat16": to nearest, ties to even, on the float32 bits (a float64 x is first rounded to
+    float32, as the device only ever sees float32); NaN stays NaN.  "float16": clipped to +-65504 (the device saturates where the
+    plain conversion would give inf), then ``np.float16``'s conversion, nearest even with subnormals."""
+    check_precision(precision)
+    x = np.asarray(x)
+    if precision == "float32":
+        return x
+    if precision == "float16":
+        return np.clip(x, -65504.0, 65504.0).astype(np.float16).astype(x.dtype)
+    f = np.ascontiguousarray(x, dtype=np.float32)
+    u = f.view(np.uint32)
+    r = ((u.astype(np.uint64) + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000).astype(np.uint32)
+    r = np.where(np.isnan(f), (u & np.uint32(0xFFFF0000)) | np.uint32(0x00400000), r).astype(np.uint32)
+    return r.view(np.float32).reshape(x.shape).astype(x.dtype)
+
+
 def from_hp(hp):
-    """The configuration of Hyper_Parameters' optional ``Vocoder_HiFiGAN`` section (V1 where a key is absent), or None without it."""
+    """The configuration of Hyper_Parameters' optional ``Vocoder_HiFiGAN`` section (V1 where a key is absent), or None without it.
+    The section's ``Precision`` and ``Checkpoint_Path`` are no part of the network: see ``precision_from_hp``."""
     sec = hp.get("Vocoder_HiFiGAN")
     if sec is None:
         return None

@@ -16,8 +16,10 @@ Additive keys (absent in the reference, defaults reproduce it):
                                                  vocoder (gst_tacotron_amd.waveglow; its hop is Sound.Frame_Shift); absent, nothing changes
   Vocoder_HiFiGAN                             -- optional: {"Initial_Filters": 512, "Upsample_Rates": [8, 8, 2, 2], "Resblock": 1,
                                                  "Resblock_Kernel_Sizes": [3, 7, 11], "Resblock_Dilation_Sizes": [[1, 3, 5], [1, 3, 5],
-                                                 [1, 3, 5]], "Checkpoint_Path": null}, the HiFi-GAN generator
-                                                 (gst_tacotron_amd.hifigan); absent, nothing changes
+                                                 [1, 3, 5]], "Checkpoint_Path": null, "Precision": "float32"}, the HiFi-GAN
+                                                 generator (gst_tacotron_amd.hifigan); absent, nothing changes.  "Precision" is the
+                                                 operand type of its matrix products ("float32", "bfloat16" or "float16", fp32 sums);
+                                                 Use_Mixed_Precision does not touch the vocoder
 """
 import copy
 import json
@@ -82,6 +84,8 @@ def check_hifigan_section(hp):
     dilations = sec.get("Resblock_Dilation_Sizes", [[1, 3, 5]] * 3)
     if len(kernels) != len(dilations):
         raise ValueError("Vocoder_HiFiGAN: {} Resblock_Kernel_Sizes but {} Resblock_Dilation_Sizes".format(len(kernels), len(dilations)))
+    if sec.get("Precision") is not None and sec["Precision"] not in ("float32", "bfloat16", "float16"):
+        raise ValueError("Vocoder_HiFiGAN.Precision must be 'float32', 'bfloat16' or 'float16', not {!r}".format(sec["Precision"]))
 
 
 def load_token_dict(hp=None, base_dir=None):

@@ -91,6 +91,7 @@ class GST_Tacotron:
         self._melgan = None                 # the loaded neural vocoder's MelGANConfig (Load_Neural_Vocoder)
         self._waveglow = None               # the loaded flow vocoder's WaveGlowConfig (Load_WaveGlow)
         self._hifigan = None                # the loaded HiFi-GAN's HiFiGANConfig (Load_HiFiGAN)
+        self._hifigan_precision = None      # and the operand type it was loaded with
         self.seed = 0
 
     # ------------------------------------------------------------------ weights
@@ -992,15 +993,20 @@ class GST_Tacotron:
         return wav, lens
 
     # ------------------------------------------------------------------ the flow vocoder
-    def Load_HiFiGAN(self, weights_or_path=None, config=None, max_frames=None):
+    def Load_HiFiGAN(self, weights_or_path=None, config=None, max_frames=None, precision=None):
         """Extension: loads the HiFi-GAN generator (``gsttaco_hifigan_*``, gst_tacotron_amd.hifigan) into this model's context, once,
         beside or without the MelGAN generator and WaveGlow.  ``weights_or_path``: named folded arrays (``hifigan.synthetic_weights``
         / ``hifigan.from_state_dict``) or the path of a file that holds a generator ``state_dict`` in the public layout
         (``hifigan.load``; None: ``Vocoder_HiFiGAN.Checkpoint_Path``).  ``config``: a ``hifigan.HiFiGANConfig``; by default the
         Hyper_Parameters' ``Vocoder_HiFiGAN`` section, else what the arrays' shapes say (the dilations only for the shipped shapes).
         ``max_frames``: the longest mel a call may bring (default Max_Step); the batch capacity is the model's.  Its Mel_Dim must be
-        the model's and, where the Sound section is complete, its hop Sound.Frame_Shift."""
+        the model's and, where the Sound section is complete, its hop Sound.Frame_Shift.
+        ``precision``: the operand type of the generator's matrix products, "float32" (the default), "bfloat16" or "float16"
+        (``gsttaco_hifigan_set_operands``: 16-bit MFMA operands, everything else fp32; None: ``Vocoder_HiFiGAN.Precision``, else
+        "float32").  ``Use_Mixed_Precision`` does not switch it.  ``HiFiGAN``, ``Inference(..., vocoder="hifigan")`` and
+        ``Export_Inference`` use whatever was loaded; their outputs are float32 in [-1, 1] in every form."""
         from . import hifigan
+        precision = hifigan.precision_from_hp(self.hp_Dict) if precision is None else hifigan.check_precision(precision)
         if weights_or_path is None:
             weights_or_path = (self.hp_Dict.get("Vocoder_HiFiGAN") or {}).get("Checkpoint_Path")
             if weights_or_path is None:
@@ -1015,10 +1021,13 @@ class GST_Tacotron:
         if not torch.cuda.is_available():
             raise capi.GstTacoError(-2, "no HIP device: the gfx950 kernels are the only compute path (no CPU fallback)")
         self.ctx.hifigan_configure(cfg, self.ctx.cfg.max_batch, int(max_frames or self.dims.max_step))
+        if precision != "float32":
+            self.ctx.hifigan_set_operands(precision)
         self.ctx.hifigan_load_weights(weights)
         with torch.cuda.device(self.device):
             self.ctx.hifigan_finalize()
         self._hifigan = cfg
+        self._hifigan_precision = precision
         return self
 
     def HiFiGAN(self, mels, mel_lengths=None):

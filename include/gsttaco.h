@@ -795,6 +795,49 @@ int gsttaco_hifigan_debug_stage(gsttaco_ctx* ctx, int stage, const float* mel, c
 #define GSTTACO_HIFIGAN_PLAN_INTS (3 + 8 * 522)
 int gsttaco_hifigan_plan(const gsttaco_ctx* ctx, int32_t fields[]);
 
+/* The operand form of the HiFi-GAN's matrix products (EXTENSION; new symbols only, no struct and no signature changes).
+ * GSTTACO_HIFIGAN_F32, the default, is everything above, bit for bit, uploaded bytes included.  Under GSTTACO_HIFIGAN_BF16 /
+ * GSTTACO_HIFIGAN_F16 the input conv, the transposed convs and the residual convs run on v_mfma_f32_16x16x32_bf16 / _f16: the MFMA's
+ * two operands are 16-bit, nothing else is.
+ *   - Activations stay fp32 in the workspace (the residual stream and the fusion sums are never rounded); the workspace, its four
+ *     buffers, the launches, tiles and forms are those of the fp32 plan.  gsttaco_hifigan_plan reports the same table, the dynamic LDS
+ *     bytes excepted: they are those of the 16-bit tile, never more than the fp32 tile's.
+ *   - A launch's input is taken in fp32 at its bounds (zero outside the row), passed through the LeakyReLU in fp32, then rounded once,
+ *     to nearest even, on its way into the staged tile; fp16 saturates to +-65504 instead of producing inf.  The input conv's mel
+ *     is rounded the same way (no LeakyReLU).
+ *   - A kernel weight is rounded once, to nearest even, on the host at gsttaco_hifigan_finalize.  An fp16 weight that is not finite
+ *     after rounding refuses the finalize with GSTTACO_E_WEIGHTS and a message that names the tensor; nothing was uploaded, and the
+ *     context may select another form, load the tensor again and finalize.
+ *   - Products are exact and summed in fp32 by the MFMA; the accumulator, the bias (fp32), the residual add, the fused sum and the
+ *     whole output conv (fp32 weights, VALU) are as in the fp32 form.  One summation order per output sample -- bias, taps ascending,
+ *     channels ascending in blocks of 32, the residual, the blocks in order -- that depends on neither batch, T nor capacity: a row
+ *     is still bitwise the row run alone, and the call is still capturable.
+ * Valid between gsttaco_hifigan_configure and gsttaco_hifigan_finalize: GSTTACO_E_INVALID for another value, GSTTACO_E_WEIGHTS
+ * before configure or after finalize.  gsttaco_hifigan_configure always starts a context at GSTTACO_HIFIGAN_F32.
+ * Pinned to a float64 restatement with rounded operands on synthetic weights (tests/hifigan_half_cases.py); no trained checkpoint
+ * has been run in any form.  MelGAN and WaveGlow have no such setting. */
+#define GSTTACO_HIFIGAN_F32 0
+#define GSTTACO_HIFIGAN_BF16 1
+#define GSTTACO_HIFIGAN_F16 2
+int gsttaco_hifigan_set_operands(gsttaco_ctx* ctx, int operands);
+
+/* Test support: copies `floats` floats between the START of workspace buffer `buffer` (0 the fused sum, 1 the transposed conv's output,
+ * 2 and 3 the two a residual block alternates between) and `device` (DEVICE memory), device to device on `stream`; write != 0 copies
+ * into the workspace.  With gsttaco_hifigan_debug_stage it runs one launch on inputs the caller chose and reads its result back.
+ * What a launch of a call (B, T) addresses, with R samples per frame and C_p = round16(channels) at that side of the launch: row b
+ * starts at float b * T * R * C_p of the buffer, position t of the row at + t * C_p, channel c at + c; channels [C, C_p) hold zeros.
+ *   kind 0 (input conv)       reads mel [B, T, mel_dim] (the call's argument, no workspace), writes buffer 0 at R = 1
+ *   kind 1 (transposed conv)  reads buffer 0 at its input rate, writes buffer 1 at its output rate
+ *   kind 2 (residual conv)    reads its source through the LeakyReLU, adds its residual raw, writes its destination, or -- the last
+ *                             conv of a residual block -- sets (block 0) or adds to (later blocks) buffer 0, times 1 / n_kernels on
+ *                             the last block.  resblock = 1: a unit's first conv reads x (buffer 1 in the block's first unit, 3 after)
+ *                             and writes 2; its second reads 2, adds x and writes 3.  resblock = 2: a unit reads and adds x (buffer 1,
+ *                             then 2, 3, 2, ...) and writes the other of 2 and 3 (2 first).
+ *   kind 3 (output conv)      reads buffer 0, writes wav [B, ld_wav]
+ * Only positions below a row's own length are read or written.  GSTTACO_E_INVALID: a buffer outside 0 .. 3, a NULL array, floats < 0
+ * or beyond the buffer's size (max_batch * max_frames * the widest activation per frame); GSTTACO_E_WEIGHTS before finalize. */
+int gsttaco_hifigan_debug_buffer(gsttaco_ctx* ctx, int buffer, float* device, int64_t floats, int write, void* stream);
+
 /* hipGraph cache policy.  Every entry point replays one cached graph executable per (entry, B, Tv, Tref1, steps, flags) key.
  * The cache is LRU-bounded to `max_cached` executables (default 16 -- an Inference_Step replays two or three: encoder segment, GST + decode + postnet, vocoder; GSTTACO_GRAPH_CACHE; 0 = no graphs, everything is
  * enqueued eagerly on the caller's stream); the least recently used one is destroyed when a new shape is captured.
