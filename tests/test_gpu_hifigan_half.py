@@ -110,15 +110,21 @@ def _launch_rows(name, stage_row):
     return frames + ([] if 0 in frames else [0])
 
 
-def _run_one_launch(v, i, l, frames, rng, precision):
-    """Launch i of the plan on seeded inputs -> (device error, e32_launch), both max-abs over the launch's rows."""
+def _normal(rng, shape):
+    return rng.normal(0.0, 1.0, shape).astype(np.float32)
+
+
+def _run_one_launch(v, i, l, frames, rng, precision, *, draw=_normal, beyond=BEYOND):
+    """Launch i of the plan on seeded inputs -> (device error, e32_launch), both max-abs over the launch's rows.  ``draw(rng, shape)``
+    generates every input of the launch, ``beyond`` is what every buffer and the mel hold beyond a row's length (it may be NaN: the
+    buffers are compared by their bits)."""
     import torch
     cfg = v.cfg
     B, T = len(frames), max(max(frames), 1)
     assert B <= v.max_batch and T <= v.max_frames
     wpf = H.ws_floats_per_frame(cfg)
-    image = [torch.full((B * T * wpf,), BEYOND, dtype=torch.float32, device="cuda") for _ in range(4)]
-    normal = lambda n, rate, ch: rng.normal(0.0, 1.0, (n * rate, ch)).astype(np.float32)
+    image = [torch.full((B * T * wpf,), beyond, dtype=torch.float32, device="cuda") for _ in range(4)]
+    normal = lambda n, rate, ch: draw(rng, (n * rate, ch))
 
     def rows_of(buf, rate, ch):
         """views [n * rate, C_p] of the rows of workspace buffer ``buf`` at this call's T"""
@@ -131,7 +137,7 @@ def _run_one_launch(v, i, l, frames, rng, precision):
             view[:, ch:] = 0.0                      # the padding channels are exact zeros
 
     ins = {}
-    mel = torch.full((B, T, cfg.mel_dim), BEYOND, dtype=torch.float32, device="cuda")
+    mel = torch.full((B, T, cfg.mel_dim), beyond, dtype=torch.float32, device="cuda")
     ld = T * cfg.hop
     wav = torch.full((B, ld), float("nan"), dtype=torch.float32, device="cuda")
     if l.kind == "in":
@@ -184,7 +190,7 @@ def _run_one_launch(v, i, l, frames, rng, precision):
         err = max(err, float(np.abs(g.astype(np.float64) - want[b]).max()))
         e32 = max(e32, float(np.abs(want32[b].astype(np.float64) - want[b]).max()))
     for k in range(4):
-        assert torch.equal(after[k], expect[k]), ("launch", i, "wrote buffer", k, "beyond a row's length or outside its output")
+        assert torch.equal(after[k].view(torch.int32), expect[k].view(torch.int32)), ("launch", i, "wrote buffer", k, "beyond a row's length or outside its output")
     return err, e32
 
 

@@ -165,6 +165,47 @@ def test_the_call_is_captured_in_a_graph_and_replays_bitwise():
         assert np.array_equal(wav.cpu().numpy(), eager) and np.array_equal(lens.cpu().numpy(), eager_len)
 
 
+def _nan_beyond(mel, frames, min_frames):
+    """the mel with NaN beyond each row's frames, and in the whole mel of a row too short to run"""
+    out = np.array(mel, dtype=np.float32)
+    for b, n in enumerate(frames):
+        out[b, (n if n >= min_frames else 0):] = np.nan
+    return out
+
+
+def test_nan_beyond_a_row_reaches_no_sample():
+    """What lies beyond a row's frames -- in Inference(..., vocoder=) the decoder's free run past the stop token -- may be NaN: a
+    bound taken as a product passes a finite filler and fails this.  The wav and the lengths are bitwise those of the plain call."""
+    c = M.CASES["tiny"]
+    v = _vocoder("tiny")
+    bits = lambda a: np.ascontiguousarray(a).view(np.int32)
+    for frames in (c.frames_array, np.asarray([0, c.cfg.min_frames - 1, 6], dtype=np.int32)):
+        wav, lengths = v(c.mel, frames)
+        mel = _nan_beyond(c.mel, frames, c.cfg.min_frames)
+        assert np.isnan(mel).any() and np.abs(wav).max() > 0
+        got, got_len = v(mel, frames)
+        assert np.array_equal(got_len, lengths) and np.array_equal(bits(got), bits(wav))
+        for b, n in enumerate(lengths):
+            assert not got[b, n:].any(), b
+
+
+def test_a_row_of_nan_leaves_its_neighbours_bitwise_alone():
+    """One row's mel is NaN inside its own length: every other row is bitwise the row run alone; the bad row may hold anything up
+    to its length and holds zeros beyond it."""
+    c = M.CASES["tiny"]
+    v = _vocoder("tiny")
+    mel, frames = c.mel.copy(), c.frames_array.copy()
+    frames[0] = c.frames[0] - 1                                 # the bad row is the longest: leave room beyond it
+    mel[0, frames[0] // 2, 1] = np.nan
+    wav, lengths = v(mel, frames)
+    assert np.array_equal(lengths, frames * c.cfg.hop) and not wav[0, lengths[0]:].any()
+    for b in range(1, len(frames)):
+        n = int(frames[b])
+        alone, alone_len = v(c.mel[b:b + 1, :n])
+        assert alone_len[0] == lengths[b] and np.array_equal(alone[0].view(np.int32), wav[b, :lengths[b]].view(np.int32)), b
+        assert not wav[b, lengths[b]:].any()
+
+
 # ---------------------------------------------------------------------------------------------------- 3. refusals through the C ABI
 def test_refusals_come_through_the_c_abi():
     import torch

@@ -214,6 +214,44 @@ def test_seeds_are_the_noise_they_stand_for():
     assert not np.array_equal(other[0], by_seed[0])
 
 
+def test_nan_beyond_a_row_reaches_no_sample():
+    """What lies beyond a row's frames (mel) and samples (z) may be NaN -- in Inference(..., vocoder=) the decoder's free run past the
+    stop token is what sits there: a bound taken as a product passes a finite filler and fails this.  The wav and the lengths are
+    bitwise those of the plain call."""
+    c = M.CASES["tiny"]
+    v = _vocoder("tiny")
+    hop = c.cfg.hop
+    wav, lengths = v(c.mel, c.frames_array, z=c.z, sigma=c.sigma)
+    mel, z = c.mel.copy(), c.z.copy()
+    for b, n in enumerate(c.frames):
+        mel[b, n:] = np.nan                                     # the whole mel and z of the row of 0 frames
+        z[b, n * hop:] = np.nan
+    assert 0 in c.frames and np.isnan(mel[:, -1]).sum() > 0 and np.abs(wav).max() > 0
+    got, got_len = v(mel, c.frames_array, z=z, sigma=c.sigma)
+    assert np.array_equal(got_len, lengths) and np.array_equal(got.view(np.int32), wav.view(np.int32))
+    for b, n in enumerate(lengths):
+        assert not got[b, n:].any(), b
+
+
+def test_a_row_of_nan_leaves_its_neighbours_bitwise_alone():
+    """One row's mel is NaN inside its own length: every other row is bitwise the row run alone; the bad row may hold anything up
+    to its length and holds zeros beyond it."""
+    c = M.CASES["tiny"]
+    v = _vocoder("tiny")
+    hop = c.cfg.hop
+    mel, frames = c.mel.copy(), c.frames_array.copy()
+    frames[0] = c.frames[0] - 1                                 # the bad row is the longest: leave room beyond it
+    mel[0, frames[0] // 2, 1] = np.nan
+    wav, lengths = v(mel, frames, z=c.z, sigma=c.sigma)
+    assert np.array_equal(lengths, frames * hop) and not wav[0, lengths[0]:].any()
+    for b in range(1, len(frames)):
+        n = int(frames[b])
+        assert not wav[b, lengths[b]:].any()
+        if n >= 1:
+            alone, alone_len = v(c.mel[b:b + 1, :n], z=c.z[b:b + 1, :n * hop], sigma=c.sigma)
+            assert alone_len[0] == lengths[b] and np.array_equal(alone[0].view(np.int32), wav[b, :lengths[b]].view(np.int32)), b
+
+
 # ---------------------------------------------------------------------------------------------------- 3. the noise
 def test_the_noise_is_the_host_box_muller():
     """z[b, l * G + g] = Box-Muller of the x and y words of Philox counter (l, g, 0, 0x8000) under seeds[b]: oracle/rng_np.py's words,
