@@ -213,44 +213,21 @@ def load_library(path=None):
     lib.gsttaco_style_affinities.restype = ctypes.c_int
     lib.gsttaco_style_map.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, f32, i32, i32, f32, f32, f32, vp, vp]
     lib.gsttaco_style_map.restype = ctypes.c_int
-    lib.gsttaco_melgan_configure.argtypes = [vp, ctypes.POINTER(MelganConfig)]
-    lib.gsttaco_melgan_num_weights.argtypes = [vp]
-    lib.gsttaco_melgan_weight_info.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_int64 * 4), ctypes.POINTER(ctypes.c_int)]
-    lib.gsttaco_melgan_load_weight.argtypes = [vp, ctypes.c_char_p, f32p, ctypes.POINTER(ctypes.c_int64), i32]
-    lib.gsttaco_melgan_finalize.argtypes = [vp]
-    lib.gsttaco_melgan.argtypes = [vp, vp, vp, i32, i32, vp, vp, i32, vp]
-    lib.gsttaco_melgan_plan.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
-    lib.gsttaco_melgan_debug_stage.argtypes = [vp, i32, vp, vp, i32, i32, vp, i32, vp]
-    lib.gsttaco_melgan_debug_stage.restype = ctypes.c_int
-    for fn in ("gsttaco_melgan_configure", "gsttaco_melgan_num_weights", "gsttaco_melgan_weight_info", "gsttaco_melgan_load_weight",
-               "gsttaco_melgan_finalize", "gsttaco_melgan", "gsttaco_melgan_plan"):
-        getattr(lib, fn).restype = ctypes.c_int
-    lib.gsttaco_waveglow_configure.argtypes = [vp, ctypes.POINTER(WaveglowConfig)]
-    lib.gsttaco_waveglow_num_weights.argtypes = [vp]
-    lib.gsttaco_waveglow_weight_info.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_int64 * 4), ctypes.POINTER(ctypes.c_int)]
-    lib.gsttaco_waveglow_load_weight.argtypes = [vp, ctypes.c_char_p, f32p, ctypes.POINTER(ctypes.c_int64), i32]
-    lib.gsttaco_waveglow_finalize.argtypes = [vp]
-    lib.gsttaco_waveglow_noise.argtypes = [vp, vp, i32, i32, vp, vp]
-    lib.gsttaco_waveglow.argtypes = [vp, vp, vp, i32, i32, f32, vp, vp, vp, vp, i32, vp]
-    lib.gsttaco_waveglow_plan.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
-    lib.gsttaco_waveglow_debug_stage.argtypes = [vp, i32, vp, vp, i32, i32, f32, vp, vp, vp, i32, vp]
-    for fn in ("gsttaco_waveglow_configure", "gsttaco_waveglow_num_weights", "gsttaco_waveglow_weight_info", "gsttaco_waveglow_load_weight",
-               "gsttaco_waveglow_finalize", "gsttaco_waveglow_noise", "gsttaco_waveglow", "gsttaco_waveglow_plan", "gsttaco_waveglow_debug_stage"):
-        getattr(lib, fn).restype = ctypes.c_int
-    lib.gsttaco_hifigan_configure.argtypes = [vp, ctypes.POINTER(HifiganConfig)]
-    lib.gsttaco_hifigan_num_weights.argtypes = [vp]
-    lib.gsttaco_hifigan_weight_info.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_int64 * 4), ctypes.POINTER(ctypes.c_int)]
-    lib.gsttaco_hifigan_load_weight.argtypes = [vp, ctypes.c_char_p, f32p, ctypes.POINTER(ctypes.c_int64), i32]
-    lib.gsttaco_hifigan_finalize.argtypes = [vp]
-    lib.gsttaco_hifigan.argtypes = [vp, vp, vp, i32, i32, vp, vp, i32, vp]
-    lib.gsttaco_hifigan_plan.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
-    lib.gsttaco_hifigan_debug_stage.argtypes = [vp, i32, vp, vp, i32, i32, vp, i32, vp]
-    lib.gsttaco_hifigan_set_operands.argtypes = [vp, i32]
-    lib.gsttaco_hifigan_debug_buffer.argtypes = [vp, i32, vp, ctypes.c_int64, i32, vp]
-    for fn in ("gsttaco_hifigan_configure", "gsttaco_hifigan_num_weights", "gsttaco_hifigan_weight_info", "gsttaco_hifigan_load_weight",
-               "gsttaco_hifigan_finalize", "gsttaco_hifigan", "gsttaco_hifigan_plan", "gsttaco_hifigan_debug_stage",
-               "gsttaco_hifigan_set_operands", "gsttaco_hifigan_debug_buffer"):
-        getattr(lib, fn).restype = ctypes.c_int
+    # the three vocoders: five signatures in common, then each one's own
+    for prefix, config in (("melgan", MelganConfig), ("waveglow", WaveglowConfig), ("hifigan", HifiganConfig)):
+        sig = {"configure": [vp, ctypes.POINTER(config)], "num_weights": [vp], "finalize": [vp], "plan": [vp, ctypes.POINTER(ctypes.c_int32)],
+               "weight_info": [vp, i32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_int64 * 4), ctypes.POINTER(ctypes.c_int)],
+               "load_weight": [vp, ctypes.c_char_p, f32p, ctypes.POINTER(ctypes.c_int64), i32]}
+        for name, argtypes in sig.items():
+            fn = getattr(lib, "gsttaco_{}_{}".format(prefix, name))
+            fn.argtypes, fn.restype = argtypes, ctypes.c_int
+    for name, argtypes in (("melgan", [vp, vp, vp, i32, i32, vp, vp, i32, vp]), ("melgan_debug_stage", [vp, i32, vp, vp, i32, i32, vp, i32, vp]),
+                           ("waveglow_noise", [vp, vp, i32, i32, vp, vp]), ("waveglow", [vp, vp, vp, i32, i32, f32, vp, vp, vp, vp, i32, vp]),
+                           ("waveglow_debug_stage", [vp, i32, vp, vp, i32, i32, f32, vp, vp, vp, i32, vp]),
+                           ("hifigan", [vp, vp, vp, i32, i32, vp, vp, i32, vp]), ("hifigan_debug_stage", [vp, i32, vp, vp, i32, i32, vp, i32, vp]),
+                           ("hifigan_set_operands", [vp, i32]), ("hifigan_debug_buffer", [vp, i32, vp, ctypes.c_int64, i32, vp])):
+        fn = getattr(lib, "gsttaco_" + name)
+        fn.argtypes, fn.restype = argtypes, ctypes.c_int
     lib.gsttaco_postnet.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.gsttaco_vocoder.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.gsttaco_inference_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
@@ -417,6 +394,43 @@ class Context:
     def finalize(self):
         self.check(self.lib.gsttaco_finalize_weights(self.handle))
 
+    # ---- what the three vocoders' bindings share; ``prefix`` is "melgan", "waveglow" or "hifigan"
+    def _voc_fn(self, prefix, name):
+        return getattr(self.lib, "gsttaco_{}_{}".format(prefix, name))
+
+    def _voc_manifest(self, prefix):
+        out = {}
+        for i in range(self._voc_fn(prefix, "num_weights")(self.handle)):
+            name, shape, nd = ctypes.c_char_p(), (ctypes.c_int64 * 4)(), ctypes.c_int()
+            self.check(self._voc_fn(prefix, "weight_info")(self.handle, i, ctypes.byref(name), ctypes.byref(shape), ctypes.byref(nd)))
+            out[name.value.decode()] = tuple(shape[k] for k in range(nd.value))
+        return out
+
+    def _voc_load_weight(self, prefix, name, array):
+        a = np.ascontiguousarray(np.asarray(array, dtype=np.float32))
+        shape = (ctypes.c_int64 * max(a.ndim, 1))(*a.shape)
+        self.check(self._voc_fn(prefix, "load_weight")(self.handle, name.encode(), a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), shape, a.ndim))
+
+    def _voc_load_weights(self, prefix, weights):
+        for name in self._voc_manifest(prefix):
+            if name not in weights:
+                raise KeyError("missing weight '{}'".format(name))
+            self._voc_load_weight(prefix, name, weights[name])
+
+    def _voc_finalize(self, prefix):
+        self.check(self._voc_fn(prefix, "finalize")(self.handle))
+
+    def _voc_plan(self, prefix, ints, stride, fields, kinds):
+        """(the plan's two leading numbers, [one dict of ``fields`` per launch, ``kind`` as a name of ``kinds``])"""
+        f = (ctypes.c_int32 * ints)()
+        self.check(self._voc_fn(prefix, "plan")(self.handle, f))
+        stages = []
+        for i in range(f[0]):
+            row = dict(zip(fields, f[3 + stride * i: 3 + stride * (i + 1)]))
+            row["kind"] = kinds[row["kind"]]
+            stages.append(row)
+        return int(f[1]), int(f[2]), stages
+
     # ---- the neural vocoder (gsttaco_melgan_*): one per context
     def melgan_configure(self, cfg, max_batch, max_frames):
         """``cfg``: a melgan.MelGANConfig (or anything with its fields)."""
@@ -431,37 +445,20 @@ class Context:
         self.check(self.lib.gsttaco_melgan_configure(self.handle, ctypes.byref(m)))
 
     def melgan_manifest(self):
-        out = {}
-        for i in range(self.lib.gsttaco_melgan_num_weights(self.handle)):
-            name, shape, nd = ctypes.c_char_p(), (ctypes.c_int64 * 4)(), ctypes.c_int()
-            self.check(self.lib.gsttaco_melgan_weight_info(self.handle, i, ctypes.byref(name), ctypes.byref(shape), ctypes.byref(nd)))
-            out[name.value.decode()] = tuple(shape[k] for k in range(nd.value))
-        return out
+        return self._voc_manifest("melgan")
 
     def melgan_load_weight(self, name, array):
-        a = np.ascontiguousarray(np.asarray(array, dtype=np.float32))
-        shape = (ctypes.c_int64 * max(a.ndim, 1))(*a.shape)
-        self.check(self.lib.gsttaco_melgan_load_weight(self.handle, name.encode(), a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), shape, a.ndim))
+        self._voc_load_weight("melgan", name, array)
 
     def melgan_load_weights(self, weights):
-        for name in self.melgan_manifest():
-            if name not in weights:
-                raise KeyError("missing weight '{}'".format(name))
-            self.melgan_load_weight(name, weights[name])
+        self._voc_load_weights("melgan", weights)
 
     def melgan_finalize(self):
-        self.check(self.lib.gsttaco_melgan_finalize(self.handle))
+        self._voc_finalize("melgan")
 
     def melgan_plan(self):
         """(min_frames, hop, [one dict of MELGAN_PLAN_FIELDS per launch, ``kind`` as a name of MELGAN_KINDS])."""
-        f = (ctypes.c_int32 * MELGAN_PLAN_INTS)()
-        self.check(self.lib.gsttaco_melgan_plan(self.handle, f))
-        stages = []
-        for i in range(f[0]):
-            row = dict(zip(MELGAN_PLAN_FIELDS, f[3 + 6 * i: 9 + 6 * i]))
-            row["kind"] = MELGAN_KINDS[row["kind"]]
-            stages.append(row)
-        return int(f[1]), int(f[2]), stages
+        return self._voc_plan("melgan", MELGAN_PLAN_INTS, 6, MELGAN_PLAN_FIELDS, MELGAN_KINDS)
 
     # ---- the flow vocoder (gsttaco_waveglow_*): one per context
     def waveglow_configure(self, cfg, max_batch, max_frames):
@@ -473,37 +470,20 @@ class Context:
         self.check(self.lib.gsttaco_waveglow_configure(self.handle, ctypes.byref(m)))
 
     def waveglow_manifest(self):
-        out = {}
-        for i in range(self.lib.gsttaco_waveglow_num_weights(self.handle)):
-            name, shape, nd = ctypes.c_char_p(), (ctypes.c_int64 * 4)(), ctypes.c_int()
-            self.check(self.lib.gsttaco_waveglow_weight_info(self.handle, i, ctypes.byref(name), ctypes.byref(shape), ctypes.byref(nd)))
-            out[name.value.decode()] = tuple(shape[k] for k in range(nd.value))
-        return out
+        return self._voc_manifest("waveglow")
 
     def waveglow_load_weight(self, name, array):
-        a = np.ascontiguousarray(np.asarray(array, dtype=np.float32))
-        shape = (ctypes.c_int64 * max(a.ndim, 1))(*a.shape)
-        self.check(self.lib.gsttaco_waveglow_load_weight(self.handle, name.encode(), a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), shape, a.ndim))
+        self._voc_load_weight("waveglow", name, array)
 
     def waveglow_load_weights(self, weights):
-        for name in self.waveglow_manifest():
-            if name not in weights:
-                raise KeyError("missing weight '{}'".format(name))
-            self.waveglow_load_weight(name, weights[name])
+        self._voc_load_weights("waveglow", weights)
 
     def waveglow_finalize(self):
-        self.check(self.lib.gsttaco_waveglow_finalize(self.handle))
+        self._voc_finalize("waveglow")
 
     def waveglow_plan(self):
         """(hop, n_group, [one dict of WAVEGLOW_PLAN_FIELDS per launch, ``kind`` as a name of WAVEGLOW_KINDS])."""
-        f = (ctypes.c_int32 * WAVEGLOW_PLAN_INTS)()
-        self.check(self.lib.gsttaco_waveglow_plan(self.handle, f))
-        stages = []
-        for i in range(f[0]):
-            row = dict(zip(WAVEGLOW_PLAN_FIELDS, f[3 + 6 * i: 9 + 6 * i]))
-            row["kind"] = WAVEGLOW_KINDS[row["kind"]]
-            stages.append(row)
-        return int(f[1]), int(f[2]), stages
+        return self._voc_plan("waveglow", WAVEGLOW_PLAN_INTS, 6, WAVEGLOW_PLAN_FIELDS, WAVEGLOW_KINDS)
 
     # ---- the HiFi-GAN vocoder (gsttaco_hifigan_*): one per context
     def hifigan_configure(self, cfg, max_batch, max_frames):
@@ -528,30 +508,20 @@ class Context:
         self.check(self.lib.gsttaco_hifigan_configure(self.handle, ctypes.byref(m)))
 
     def hifigan_manifest(self):
-        out = {}
-        for i in range(self.lib.gsttaco_hifigan_num_weights(self.handle)):
-            name, shape, nd = ctypes.c_char_p(), (ctypes.c_int64 * 4)(), ctypes.c_int()
-            self.check(self.lib.gsttaco_hifigan_weight_info(self.handle, i, ctypes.byref(name), ctypes.byref(shape), ctypes.byref(nd)))
-            out[name.value.decode()] = tuple(shape[k] for k in range(nd.value))
-        return out
+        return self._voc_manifest("hifigan")
 
     def hifigan_load_weight(self, name, array):
-        a = np.ascontiguousarray(np.asarray(array, dtype=np.float32))
-        shape = (ctypes.c_int64 * max(a.ndim, 1))(*a.shape)
-        self.check(self.lib.gsttaco_hifigan_load_weight(self.handle, name.encode(), a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), shape, a.ndim))
+        self._voc_load_weight("hifigan", name, array)
 
     def hifigan_load_weights(self, weights):
-        for name in self.hifigan_manifest():
-            if name not in weights:
-                raise KeyError("missing weight '{}'".format(name))
-            self.hifigan_load_weight(name, weights[name])
+        self._voc_load_weights("hifigan", weights)
 
     def hifigan_set_operands(self, operands):
         """``operands``: a name of HIFIGAN_OPERANDS ("float32", "bfloat16", "float16") or its number; between configure and finalize."""
         self.check(self.lib.gsttaco_hifigan_set_operands(self.handle, int(HIFIGAN_OPERANDS.get(operands, operands))))
 
     def hifigan_finalize(self):
-        self.check(self.lib.gsttaco_hifigan_finalize(self.handle))
+        self._voc_finalize("hifigan")
 
     def hifigan_debug_buffer(self, buffer, tensor, write, stream=None):
         """Test support: copies the float32 device ``tensor`` into (``write``) or out of the start of workspace buffer ``buffer`` (0 .. 3
@@ -562,11 +532,4 @@ class Context:
 
     def hifigan_plan(self):
         """(min_frames, hop, [one dict of HIFIGAN_PLAN_FIELDS per launch, ``kind`` as a name of HIFIGAN_KINDS])."""
-        f = (ctypes.c_int32 * HIFIGAN_PLAN_INTS)()
-        self.check(self.lib.gsttaco_hifigan_plan(self.handle, f))
-        stages = []
-        for i in range(f[0]):
-            row = dict(zip(HIFIGAN_PLAN_FIELDS, f[3 + 8 * i: 11 + 8 * i]))
-            row["kind"] = HIFIGAN_KINDS[row["kind"]]
-            stages.append(row)
-        return int(f[1]), int(f[2]), stages
+        return self._voc_plan("hifigan", HIFIGAN_PLAN_INTS, 8, HIFIGAN_PLAN_FIELDS, HIFIGAN_KINDS)

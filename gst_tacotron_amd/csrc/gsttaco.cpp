@@ -21,22 +21,12 @@
 
 #include "../../include/gsttaco.h"
 #include "kernels.h"
+#include "manifest.h"
+#include "vocoder_common.h"
 
 namespace {
 
 constexpr float kBnEps = 1e-3f;   // tf.keras.layers.BatchNormalization default epsilon
-
-struct HostTensor {
-    std::string name;
-    std::vector<int64_t> shape;
-    std::vector<float> data;
-    bool loaded = false;
-    int64_t numel() const {
-        int64_t n = 1;
-        for (auto s : shape) n *= s;
-        return n;
-    }
-};
 
 struct PackedLinear {       // skinny-GEMM operand set
     float* wp = nullptr;
@@ -127,8 +117,7 @@ std::map<int, FusedInFlight> g_fused_event;
 
 struct gsttaco_ctx {
     gsttaco_config cfg{};
-    std::vector<HostTensor> tensors;
-    std::map<std::string, int> index;
+    Manifest weights;
     // Decoder sizes below the ones the persistent decode kernels are written for (prenet 256 / 256, attention 128, LSTM 1024 / 1024) are
     // ZERO-PADDED up to them at finalize (pad_decoder): the padded copies of the decoder's tensors, consulted by T() in front of `tensors`
     // (whose shapes stay the caller's: gsttaco_weight_info).  cfg keeps the caller's sizes; P0 .. att below are the padded ones once dec_padded.
@@ -224,8 +213,7 @@ struct gsttaco_ctx {
         bool configured = false, finalized = false;
         gsttaco_melgan_config cfg{};
         MgPlan plan{};
-        std::vector<HostTensor> tensors;
-        std::map<std::string, int> index;
+        Manifest man;
         float* ws[2] = {nullptr, nullptr};
     } mg;
     // The flow vocoder (gsttaco_waveglow_*): its own manifest, the plan that holds the device operands once finalized, and the
@@ -234,8 +222,7 @@ struct gsttaco_ctx {
         bool configured = false, finalized = false;
         gsttaco_waveglow_config cfg{};
         WgPlan plan{};
-        std::vector<HostTensor> tensors;
-        std::map<std::string, int> index;
+        Manifest man;
         float *spect = nullptr, *hid[2] = {nullptr, nullptr}, *out = nullptr, *audio = nullptr;
     } wg;
     // The HiFi-GAN vocoder (gsttaco_hifigan_*): its own manifest, the plan whose launches hold the device operands once finalized, and
@@ -244,8 +231,7 @@ struct gsttaco_ctx {
         bool configured = false, finalized = false;
         gsttaco_hifigan_config cfg{};
         HgPlan plan{};
-        std::vector<HostTensor> tensors;
-        std::map<std::string, int> index;
+        Manifest man;
         float* ws[GT_HG_BUFS] = {nullptr, nullptr, nullptr, nullptr};
         int operands = GSTTACO_HIFIGAN_F32;     // gsttaco_hifigan_set_operands: the form finalize packs for (the plan's copy is what runs)
     } hg;
@@ -333,13 +319,15 @@ struct gsttaco_ctx {
     std::vector<hipEvent_t> prof_ev[5];     // pairs (start, stop) per bracketed launch
 };
 
-namespace {
-
-int fail(const gsttaco_ctx* c, int code, const std::string& msg) {
+int gt_fail(const gsttaco_ctx* c, int code, const std::string& msg) {
     if (c) c->err = msg;
     else g_create_error = msg;
     return code;
 }
+
+namespace {
+
+int fail(const gsttaco_ctx* c, int code, const std::string& msg) { return gt_fail(c, code, msg); }
 
 #define HIPCHECK(ctx, expr)                                                                   \
     do {                                                                                      \
@@ -348,13 +336,7 @@ int fail(const gsttaco_ctx* c, int code, const std::string& msg) {
             return fail(ctx, GSTTACO_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
     } while (0)
 
-void add_tensor(gsttaco_ctx* c, const std::string& name, std::vector<int64_t> shape) {
-    HostTensor t;
-    t.name = name;
-    t.shape = std::move(shape);
-    c->index[name] = (int)c->tensors.size();
-    c->tensors.push_back(std::move(t));
-}
+void add_tensor(gsttaco_ctx* c, const std::string& name, std::vector<int64_t> shape) { c->weights.add(name, std::move(shape)); }
 
 void add_bn(gsttaco_ctx* c, const std::string& prefix, int64_t n) {
     for (const char* f : {"gamma", "beta", "moving_mean", "moving_variance"}) add_tensor(c, prefix + ".bn." + f, {n});
@@ -484,7 +466,7 @@ void build_manifest(gsttaco_ctx* c) {
 
 const HostTensor& T(const gsttaco_ctx* c, const std::string& name) {
     auto it = c->padded.find(name);
-    return it != c->padded.end() ? it->second : c->tensors[c->index.at(name)];
+    return it != c->padded.end() ? it->second : c->weights.tensors[c->weights.index.at(name)];
 }
 
 // A decoder smaller than the reference's (Taco2.py:61-89 builds every layer from hp_Dict: any prenet / attention / LSTM size) used to leave
@@ -513,7 +495,7 @@ void pad_decoder(gsttaco_ctx* c) {
     if (!c->pad_dec || !decoder_pads(c->cfg)) return;
     // dst[rmap(r)][cmap(cc)] = src[r][cc]
     auto embed = [&](const std::string& name, int rows_out, int cols_out, auto rmap, auto cmap) {
-        const HostTensor& src = c->tensors[c->index.at(name)];
+        const HostTensor& src = c->weights.tensors[c->weights.index.at(name)];
         const int rows = src.shape.size() == 2 ? (int)src.shape[0] : 1, cols = (int)src.shape.back();
         HostTensor t;
         t.name = name; t.loaded = true;
@@ -2284,30 +2266,16 @@ void gsttaco_destroy(gsttaco_ctx* c) {
     delete c;
 }
 
-int gsttaco_num_weights(const gsttaco_ctx* c) { return c ? (int)c->tensors.size() : GSTTACO_E_INVALID; }
+int gsttaco_num_weights(const gsttaco_ctx* c) { return c ? (int)c->weights.tensors.size() : GSTTACO_E_INVALID; }
 
 int gsttaco_weight_info(const gsttaco_ctx* c, int i, const char** name, int64_t shape[4], int* ndim) {
-    if (!c || i < 0 || i >= (int)c->tensors.size()) return GSTTACO_E_INVALID;
-    const HostTensor& t = c->tensors[i];
-    if (name) *name = t.name.c_str();
-    if (ndim) *ndim = (int)t.shape.size();
-    if (shape)
-        for (size_t d = 0; d < 4; ++d) shape[d] = d < t.shape.size() ? t.shape[d] : 1;
-    return 0;
+    return c ? c->weights.info(i, name, shape, ndim) : GSTTACO_E_INVALID;
 }
 
 int gsttaco_load_weight(gsttaco_ctx* c, const char* name, const float* host, const int64_t* shape, int ndim) {
     if (!c || !name || !host) return fail(c, GSTTACO_E_INVALID, "null argument");
     if (c->finalized) return fail(c, GSTTACO_E_WEIGHTS, "weights already finalized");
-    auto it = c->index.find(name);
-    if (it == c->index.end()) return fail(c, GSTTACO_E_WEIGHTS, std::string("unknown weight '") + name + "'");
-    HostTensor& t = c->tensors[it->second];
-    bool ok = ndim == (int)t.shape.size();
-    for (int d = 0; ok && d < ndim; ++d) ok = shape[d] == t.shape[d];
-    if (!ok) return fail(c, GSTTACO_E_WEIGHTS, std::string("weight '") + name + "' has the wrong shape");
-    t.data.assign(host, host + t.numel());
-    t.loaded = true;
-    return 0;
+    return c->weights.load(c, "", name, host, shape, ndim);
 }
 
 }  // extern "C"
@@ -2484,8 +2452,8 @@ int finalize_vocoder(gsttaco_ctx* c) {
         const HostTensor &k = T(c, name + ".kernel"), &b = T(c, name + ".bias");
         return upload_dense(c, L, k.data.data(), (int)k.shape[0], (int)k.shape[1], (int)k.shape[1], b.data.data(), false);
     };
-    if (c->index.count("vocoder.proj_dense.kernel") && (rc = dense(&c->voc_pd, "vocoder.proj_dense"))) return rc;
-    if (c->index.count("vocoder.highway_in.kernel") && (rc = dense(&c->voc_hin, "vocoder.highway_in"))) return rc;
+    if (c->weights.index.count("vocoder.proj_dense.kernel") && (rc = dense(&c->voc_pd, "vocoder.proj_dense"))) return rc;
+    if (c->weights.index.count("vocoder.highway_in.kernel") && (rc = dense(&c->voc_hin, "vocoder.highway_in"))) return rc;
     const int S = g.highway_size;
     c->voc_hw.resize(g.highway_count);
     for (int i = 0; i < g.highway_count; ++i) {
@@ -2623,6 +2591,92 @@ int alloc_workspace(gsttaco_ctx* c) {
     return 0;
 }
 
+// ---- what the three vocoders (gsttaco_melgan_* / _waveglow_* / _hifigan_*) share.  V is the context's member for one of them
+// (configured, finalized, cfg, plan, man); `model` its name, which starts every message ("melgan: ...").
+template <typename V>
+int voc_not_open(const gsttaco_ctx* c, const V& g, const char* model) {        // what load_weight and finalize refuse first
+    if (!g.configured) return fail(c, GSTTACO_E_WEIGHTS, std::string(model) + ": not configured (gsttaco_" + model + "_configure)");
+    if (g.finalized) return fail(c, GSTTACO_E_WEIGHTS, std::string(model) + ": weights already finalized");
+    return 0;
+}
+
+template <typename V>
+int voc_load_weight(gsttaco_ctx* c, V gsttaco_ctx::*which, const char* model, const char* name, const float* host, const int64_t* shape, int ndim) {
+    if (!c || !name || !host || !shape) return fail(c, GSTTACO_E_INVALID, "null argument");
+    V& g = c->*which;
+    if (int rc = voc_not_open(c, g, model)) return rc;
+    return g.man.load(c, (std::string(model) + ": ").c_str(), name, host, shape, ndim);
+}
+
+// finalize's prologue: configured, not yet finalized, every tensor loaded
+template <typename V>
+int voc_begin_finalize(gsttaco_ctx* c, const V& g, const char* model) {
+    if (int rc = voc_not_open(c, g, model)) return rc;
+    if (const HostTensor* t = g.man.first_unloaded()) return fail(c, GSTTACO_E_WEIGHTS, std::string(model) + ": weight '" + t->name + "' was not loaded");
+    return 0;
+}
+
+int upload_vec(gsttaco_ctx* c, const float** dst, const std::vector<float>& v) {
+    float* d = nullptr;
+    int e = upload(c, &d, v.data(), v.size());
+    *dst = d;
+    return e;
+}
+
+// the bias `name` (plus the bias `plus`, unless empty) zero-padded to n_p floats, on the device
+int upload_padded_bias(gsttaco_ctx* c, const Manifest& man, const float** dst, const std::string& name, const std::string& plus, int n_p) {
+    std::vector<float> buf(n_p, 0.f);
+    const std::vector<float>& b = man.host(name);
+    for (size_t i = 0; i < b.size(); ++i) buf[i] = b[i];
+    if (!plus.empty()) {
+        const std::vector<float>& b2 = man.host(plus);
+        for (size_t i = 0; i < b2.size(); ++i) buf[i] += b2[i];
+    }
+    return upload_vec(c, dst, buf);
+}
+
+// [taps * cin, cout] as the fp32 fragment pack (voc_pack_f32), on the device
+int upload_packed(gsttaco_ctx* c, const float** dst, const std::vector<float>& w, int taps, int cin, int cout) {
+    std::vector<float> buf((size_t)taps * voc_pad16(cin) * voc_pad16(cout));
+    voc_pack_f32(w.data(), taps, cin, cout, buf.data());
+    return upload_vec(c, dst, buf);
+}
+
+// HiFi-GAN: the manifest's name of a launch's weights, without the /kernel or /bias leaf
+std::string hifigan_name(const HgStage& s) {
+    if (s.kind == GT_HG_IN) return "hifigan/in";
+    if (s.kind == GT_HG_OUT) return "hifigan/out";
+    std::string p = "hifigan/up" + std::to_string(s.up);
+    if (s.kind == GT_HG_UP) return p;
+    return p + "/res" + std::to_string(s.block) + "/unit" + std::to_string(s.unit) + (s.conv ? "/conv2" : "/conv1");
+}
+
+// What every vocoder call refuses, in the order it always has.  after_null / after_bt: a further refusal of the caller's own
+// (GSTTACO_E_INVALID with that text) at the place where it fires, NULL where there is none.
+template <typename V>
+int voc_check_call(const gsttaco_ctx* c, const V& g, const char* model, const float* mel, const float* wav, int B, int T, int ld_wav,
+                   const char* after_null = nullptr, const char* after_bt = nullptr) {
+    if (!g.finalized) return fail(c, GSTTACO_E_WEIGHTS, std::string(model) + ": weights not finalized (gsttaco_" + model + "_finalize)");
+    if (!mel || !wav) return fail(c, GSTTACO_E_INVALID, "null argument");
+    if (after_null) return fail(c, GSTTACO_E_INVALID, after_null);
+    if (B < 1 || T < 1) return fail(c, GSTTACO_E_INVALID, "bad B / T");
+    if (after_bt) return fail(c, GSTTACO_E_INVALID, after_bt);
+    if (B > g.cfg.max_batch || T > g.cfg.max_frames) return fail(c, GSTTACO_E_CAPACITY, std::string(model) + ": B or T exceeds the capacity given at configure");
+    if ((int64_t)ld_wav < (int64_t)T * g.plan.hop) return fail(c, GSTTACO_E_INVALID, "ld_wav must be >= T * hop");
+    return 0;
+}
+
+// The call of a chain with `ws` buffers (MgCall / HgCall) behind voc_check_call
+template <typename Call, typename V>
+int voc_chain_call(const gsttaco_ctx* c, const V& g, const char* model, Call* a, const float* mel, const int32_t* frames, int B, int T, float* wav,
+                   int32_t* wav_lengths, int ld_wav, int only) {
+    if (int rc = voc_check_call(c, g, model, mel, wav, B, T, ld_wav)) return rc;
+    a->mel = mel; a->frames = frames; a->wav = wav; a->wav_lengths = wav_lengths;
+    for (size_t k = 0; k < sizeof(g.ws) / sizeof(g.ws[0]); ++k) a->ws[k] = g.ws[k];
+    a->B = B; a->T = T; a->ld_wav = ld_wav; a->only = only;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2630,7 +2684,7 @@ extern "C" {
 int gsttaco_finalize_weights(gsttaco_ctx* c) {
     if (!c) return GSTTACO_E_INVALID;
     if (c->finalized) return 0;
-    for (auto& t : c->tensors)
+    for (auto& t : c->weights.tensors)
         if (!t.loaded) return fail(c, GSTTACO_E_WEIGHTS, "missing weight '" + t.name + "'");
     const gsttaco_config& g = c->cfg;
     int rc = ensure_device(c);
@@ -2666,7 +2720,7 @@ int gsttaco_finalize_weights(gsttaco_ctx* c) {
                            " workgroups, " + std::to_string(c->fuse12_slots[0]) + " resident): the two LSTM cells run as two launches";
     HIPCHECK(c, hipDeviceSynchronize());
     // host copies are no longer needed
-    for (auto& t : c->tensors) std::vector<float>().swap(t.data);
+    for (auto& t : c->weights.tensors) std::vector<float>().swap(t.data);
     c->padded.clear();
     c->finalized = true;
     return 0;
@@ -3200,13 +3254,7 @@ int gsttaco_melgan_configure(gsttaco_ctx* c, const gsttaco_melgan_config* m) {
         return fail(c, GSTTACO_E_INVALID, "melgan: max_batch * max_frames * hop exceeds 2^31 - 1 samples");
     g.cfg = *m;
     g.plan = plan;
-    auto add = [&](const std::string& name, std::vector<int64_t> shape) {
-        HostTensor t;
-        t.name = name;
-        t.shape = std::move(shape);
-        g.index[name] = (int)g.tensors.size();
-        g.tensors.push_back(std::move(t));
-    };
+    auto add = [&](const std::string& name, std::vector<int64_t> shape) { g.man.add(name, std::move(shape)); };
     int up = -1, res = 0;
     for (int i = 0; i < plan.n_stages; ++i) {
         const MgStage& s = plan.st[i];
@@ -3227,67 +3275,27 @@ int gsttaco_melgan_configure(gsttaco_ctx* c, const gsttaco_melgan_config* m) {
     return 0;
 }
 
-int gsttaco_melgan_num_weights(const gsttaco_ctx* c) { return c ? (int)c->mg.tensors.size() : GSTTACO_E_INVALID; }
+int gsttaco_melgan_num_weights(const gsttaco_ctx* c) { return c ? (int)c->mg.man.tensors.size() : GSTTACO_E_INVALID; }
 
 int gsttaco_melgan_weight_info(const gsttaco_ctx* c, int i, const char** name, int64_t shape[4], int* ndim) {
-    if (!c || i < 0 || i >= (int)c->mg.tensors.size()) return GSTTACO_E_INVALID;
-    const HostTensor& t = c->mg.tensors[i];
-    if (name) *name = t.name.c_str();
-    if (ndim) *ndim = (int)t.shape.size();
-    if (shape)
-        for (size_t d = 0; d < 4; ++d) shape[d] = d < t.shape.size() ? t.shape[d] : 1;
-    return 0;
+    return c ? c->mg.man.info(i, name, shape, ndim) : GSTTACO_E_INVALID;
 }
 
 int gsttaco_melgan_load_weight(gsttaco_ctx* c, const char* name, const float* host, const int64_t* shape, int ndim) {
-    if (!c || !name || !host || !shape) return fail(c, GSTTACO_E_INVALID, "null argument");
-    gsttaco_ctx::Melgan& g = c->mg;
-    if (!g.configured) return fail(c, GSTTACO_E_WEIGHTS, "melgan: not configured (gsttaco_melgan_configure)");
-    if (g.finalized) return fail(c, GSTTACO_E_WEIGHTS, "melgan: weights already finalized");
-    auto it = g.index.find(name);
-    if (it == g.index.end()) return fail(c, GSTTACO_E_WEIGHTS, std::string("melgan: unknown weight '") + name + "'");
-    HostTensor& t = g.tensors[it->second];
-    bool ok = ndim == (int)t.shape.size();
-    for (int d = 0; ok && d < ndim; ++d) ok = shape[d] == t.shape[d];
-    if (!ok) return fail(c, GSTTACO_E_WEIGHTS, std::string("melgan: weight '") + name + "' has the wrong shape");
-    t.data.assign(host, host + t.numel());
-    t.loaded = true;
-    return 0;
+    return voc_load_weight(c, &gsttaco_ctx::mg, "melgan", name, host, shape, ndim);
 }
 
 int gsttaco_melgan_finalize(gsttaco_ctx* c) {
     if (!c) return GSTTACO_E_INVALID;
     gsttaco_ctx::Melgan& g = c->mg;
-    if (!g.configured) return fail(c, GSTTACO_E_WEIGHTS, "melgan: not configured (gsttaco_melgan_configure)");
-    if (g.finalized) return fail(c, GSTTACO_E_WEIGHTS, "melgan: weights already finalized");
-    for (const HostTensor& t : g.tensors)
-        if (!t.loaded) return fail(c, GSTTACO_E_WEIGHTS, "melgan: weight '" + t.name + "' was not loaded");
-    int rc = ensure_device(c);
-    if (rc) return rc;
+    int rc = voc_begin_finalize(c, g, "melgan");
+    if (rc || (rc = ensure_device(c))) return rc;
     HIPCHECK(c, gt_melgan_prepare());
-    auto host = [&](const std::string& name) -> const std::vector<float>& { return g.tensors[g.index[name]].data; };
-    std::vector<float> buf;
     auto packed = [&](const float** dst, const std::string& name, int taps, int cin, int cout) {
-        const int cin_p = (cin + 15) / 16 * 16, n_p = (cout + 15) / 16 * 16;
-        buf.resize((size_t)taps * cin_p * n_p);
-        gt_melgan_pack(host(name).data(), taps, cin, cout, buf.data());
-        float* d = nullptr;
-        int e = upload(c, &d, buf.data(), buf.size());
-        *dst = d;
-        return e;
+        return upload_packed(c, dst, g.man.host(name), taps, cin, cout);
     };
     auto bias = [&](const float** dst, const std::string& name, const std::string& plus, int n_p) {
-        buf.assign(n_p, 0.f);
-        const std::vector<float>& b = host(name);
-        for (size_t i = 0; i < b.size(); ++i) buf[i] = b[i];
-        if (!plus.empty()) {
-            const std::vector<float>& b2 = host(plus);
-            for (size_t i = 0; i < b2.size(); ++i) buf[i] += b2[i];
-        }
-        float* d = nullptr;
-        int e = upload(c, &d, buf.data(), buf.size());
-        *dst = d;
-        return e;
+        return upload_padded_bias(c, g.man, dst, name, plus, n_p);
     };
     int up = -1, res = 0;
     for (int i = 0; i < g.plan.n_stages; ++i) {
@@ -3304,10 +3312,7 @@ int gsttaco_melgan_finalize(gsttaco_ctx* c) {
             if ((rc = packed(&s.w1, p + "/shortcut/kernel", 1, s.cin, s.cout)) || (rc = packed(&s.w2, p + "/conv1/kernel", 1, s.cin, s.cout))) return rc;
             if ((rc = bias(&s.b1, p + "/shortcut/bias", p + "/conv1/bias", s.n_p))) return rc;
         } else {
-            float* d = nullptr;
-            if ((rc = upload(c, &d, host("melgan/out/kernel").data(), (size_t)7 * s.cin))) return rc;
-            s.w0 = d;
-            if ((rc = bias(&s.b0, "melgan/out/bias", "", 1))) return rc;
+            if ((rc = upload_vec(c, &s.w0, g.man.host("melgan/out/kernel"))) || (rc = bias(&s.b0, "melgan/out/bias", "", 1))) return rc;
         }
     }
     const size_t ws = (size_t)g.cfg.max_batch * g.cfg.max_frames * g.plan.ws_floats_per_frame * sizeof(float);
@@ -3337,14 +3342,8 @@ int melgan_call(gsttaco_ctx* c, const float* mel, const int32_t* frames, int B, 
                 int only, void* stream) {
     if (!c) return GSTTACO_E_INVALID;
     const gsttaco_ctx::Melgan& g = c->mg;
-    if (!g.finalized) return fail(c, GSTTACO_E_WEIGHTS, "melgan: weights not finalized (gsttaco_melgan_finalize)");
-    if (!mel || !wav) return fail(c, GSTTACO_E_INVALID, "null argument");
-    if (B < 1 || T < 1) return fail(c, GSTTACO_E_INVALID, "bad B / T");
-    if (B > g.cfg.max_batch || T > g.cfg.max_frames) return fail(c, GSTTACO_E_CAPACITY, "melgan: B or T exceeds the capacity given at configure");
-    if ((int64_t)ld_wav < (int64_t)T * g.plan.hop) return fail(c, GSTTACO_E_INVALID, "ld_wav must be >= T * hop");
     MgCall a{};
-    a.mel = mel; a.frames = frames; a.wav = wav; a.wav_lengths = wav_lengths; a.ws[0] = g.ws[0]; a.ws[1] = g.ws[1];
-    a.B = B; a.T = T; a.ld_wav = ld_wav; a.only = only;
+    if (int rc = voc_chain_call(c, g, "melgan", &a, mel, frames, B, T, wav, wav_lengths, ld_wav, only)) return rc;
     HIPCHECK(c, gt_launch_melgan(g.plan, a, (hipStream_t)stream));
     return 0;
 }
@@ -3380,13 +3379,7 @@ int gsttaco_waveglow_configure(gsttaco_ctx* c, const gsttaco_waveglow_config* m)
         return fail(c, GSTTACO_E_INVALID, "waveglow: max_batch * max_frames * hop exceeds 2^31 - 1 samples");
     g.cfg = *m;
     g.plan = plan;
-    auto add = [&](const std::string& name, std::vector<int64_t> shape) {
-        HostTensor t;
-        t.name = name;
-        t.shape = std::move(shape);
-        g.index[name] = (int)g.tensors.size();
-        g.tensors.push_back(std::move(t));
-    };
+    auto add = [&](const std::string& name, std::vector<int64_t> shape) { g.man.add(name, std::move(shape)); };
     const int64_t C = plan.C;
     add("waveglow/up/kernel", {plan.win, plan.mel_dim, plan.mel_dim});
     add("waveglow/up/bias", {plan.mel_dim});
@@ -3408,32 +3401,14 @@ int gsttaco_waveglow_configure(gsttaco_ctx* c, const gsttaco_waveglow_config* m)
     return 0;
 }
 
-int gsttaco_waveglow_num_weights(const gsttaco_ctx* c) { return c ? (int)c->wg.tensors.size() : GSTTACO_E_INVALID; }
+int gsttaco_waveglow_num_weights(const gsttaco_ctx* c) { return c ? (int)c->wg.man.tensors.size() : GSTTACO_E_INVALID; }
 
 int gsttaco_waveglow_weight_info(const gsttaco_ctx* c, int i, const char** name, int64_t shape[4], int* ndim) {
-    if (!c || i < 0 || i >= (int)c->wg.tensors.size()) return GSTTACO_E_INVALID;
-    const HostTensor& t = c->wg.tensors[i];
-    if (name) *name = t.name.c_str();
-    if (ndim) *ndim = (int)t.shape.size();
-    if (shape)
-        for (size_t d = 0; d < 4; ++d) shape[d] = d < t.shape.size() ? t.shape[d] : 1;
-    return 0;
+    return c ? c->wg.man.info(i, name, shape, ndim) : GSTTACO_E_INVALID;
 }
 
 int gsttaco_waveglow_load_weight(gsttaco_ctx* c, const char* name, const float* host, const int64_t* shape, int ndim) {
-    if (!c || !name || !host || !shape) return fail(c, GSTTACO_E_INVALID, "null argument");
-    gsttaco_ctx::Waveglow& g = c->wg;
-    if (!g.configured) return fail(c, GSTTACO_E_WEIGHTS, "waveglow: not configured (gsttaco_waveglow_configure)");
-    if (g.finalized) return fail(c, GSTTACO_E_WEIGHTS, "waveglow: weights already finalized");
-    auto it = g.index.find(name);
-    if (it == g.index.end()) return fail(c, GSTTACO_E_WEIGHTS, std::string("waveglow: unknown weight '") + name + "'");
-    HostTensor& t = g.tensors[it->second];
-    bool ok = ndim == (int)t.shape.size();
-    for (int d = 0; ok && d < ndim; ++d) ok = shape[d] == t.shape[d];
-    if (!ok) return fail(c, GSTTACO_E_WEIGHTS, std::string("waveglow: weight '") + name + "' has the wrong shape");
-    t.data.assign(host, host + t.numel());
-    t.loaded = true;
-    return 0;
+    return voc_load_weight(c, &gsttaco_ctx::wg, "waveglow", name, host, shape, ndim);
 }
 
 namespace {
@@ -3465,29 +3440,16 @@ bool invert_f64(const float* w, int n, std::vector<double>& inv) {
 int gsttaco_waveglow_finalize(gsttaco_ctx* c) {
     if (!c) return GSTTACO_E_INVALID;
     gsttaco_ctx::Waveglow& g = c->wg;
-    if (!g.configured) return fail(c, GSTTACO_E_WEIGHTS, "waveglow: not configured (gsttaco_waveglow_configure)");
-    if (g.finalized) return fail(c, GSTTACO_E_WEIGHTS, "waveglow: weights already finalized");
-    for (const HostTensor& t : g.tensors)
-        if (!t.loaded) return fail(c, GSTTACO_E_WEIGHTS, "waveglow: weight '" + t.name + "' was not loaded");
-    int rc = ensure_device(c);
-    if (rc) return rc;
+    int rc = voc_begin_finalize(c, g, "waveglow");
+    if (rc || (rc = ensure_device(c))) return rc;
     HIPCHECK(c, gt_waveglow_prepare());
     WgPlan& P = g.plan;
-    auto host = [&](const std::string& name) -> const std::vector<float>& { return g.tensors[g.index[name]].data; };
+    auto host = [&](const std::string& name) -> const std::vector<float>& { return g.man.host(name); };
     std::vector<float> buf, bbuf;
-    auto up = [&](const float** dst, const std::vector<float>& v) {
-        float* d = nullptr;
-        int e = upload(c, &d, v.data(), v.size());
-        *dst = d;
-        return e;
-    };
+    auto up = [&](const float** dst, const std::vector<float>& v) { return upload_vec(c, dst, v); };
     const int C = P.C, C_p = P.C_p, n2 = 2 * C_p;
-    buf.resize((size_t)P.win * P.mel_p * P.mel_p);
-    gt_melgan_pack(host("waveglow/up/kernel").data(), P.win, P.mel_dim, P.mel_dim, buf.data());
-    if ((rc = up(&P.w_up, buf))) return rc;
-    buf.assign(P.mel_p, 0.f);
-    std::copy(host("waveglow/up/bias").begin(), host("waveglow/up/bias").end(), buf.begin());
-    if ((rc = up(&P.b_up, buf))) return rc;
+    if ((rc = upload_packed(c, &P.w_up, host("waveglow/up/kernel"), P.win, P.mel_dim, P.mel_dim))) return rc;
+    if ((rc = upload_padded_bias(c, g.man, &P.b_up, "waveglow/up/bias", "", P.mel_p))) return rc;
     std::vector<double> inv;
     for (int k = 0; k < P.F; ++k) {
         const std::string p = "waveglow/flow" + std::to_string(k);
@@ -3502,16 +3464,12 @@ int gsttaco_waveglow_finalize(gsttaco_ctx* c) {
         for (int q = 0; q < h; ++q)
             for (int n = 0; n < C; ++n) buf[(size_t)q * C_p + n] = host(p + "/start/kernel")[(size_t)q * C + n];
         if ((rc = up(&f.w_start, buf))) return rc;
-        buf.assign(C_p, 0.f);
-        std::copy(host(p + "/start/bias").begin(), host(p + "/start/bias").end(), buf.begin());
-        if ((rc = up(&f.b_start, buf))) return rc;
+        if ((rc = upload_padded_bias(c, g.man, &f.b_start, p + "/start/bias", "", C_p))) return rc;
         buf.assign((size_t)C * 16, 0.f);
         for (int n = 0; n < C; ++n)
             for (int j = 0; j < ck; ++j) buf[(size_t)n * 16 + j] = host(p + "/end/kernel")[(size_t)n * ck + j];
         if ((rc = up(&f.w_end, buf))) return rc;
-        buf.assign(16, 0.f);
-        std::copy(host(p + "/end/bias").begin(), host(p + "/end/bias").end(), buf.begin());
-        if ((rc = up(&f.b_end, buf))) return rc;
+        if ((rc = upload_padded_bias(c, g.man, &f.b_end, p + "/end/bias", "", 16))) return rc;
         for (int i = 0; i < P.NL; ++i) {
             const std::string q = p + "/layer" + std::to_string(i);
             WgLayerOps& o = P.layer[k][i];
@@ -3559,13 +3517,9 @@ int waveglow_call(gsttaco_ctx* c, const float* mel, const int32_t* frames, int B
                   float* wav, int32_t* wav_lengths, int ld_wav, int only, void* stream) {
     if (!c) return GSTTACO_E_INVALID;
     const gsttaco_ctx::Waveglow& g = c->wg;
-    if (!g.finalized) return fail(c, GSTTACO_E_WEIGHTS, "waveglow: weights not finalized (gsttaco_waveglow_finalize)");
-    if (!mel || !wav) return fail(c, GSTTACO_E_INVALID, "null argument");
-    if ((seeds != nullptr) == (z != nullptr)) return fail(c, GSTTACO_E_INVALID, "waveglow: exactly one of seeds and z must be given");
-    if (B < 1 || T < 1) return fail(c, GSTTACO_E_INVALID, "bad B / T");
-    if (!(sigma >= 0.f) || !std::isfinite(sigma)) return fail(c, GSTTACO_E_INVALID, "sigma must be finite and at least 0");
-    if (B > g.cfg.max_batch || T > g.cfg.max_frames) return fail(c, GSTTACO_E_CAPACITY, "waveglow: B or T exceeds the capacity given at configure");
-    if ((int64_t)ld_wav < (int64_t)T * g.plan.hop) return fail(c, GSTTACO_E_INVALID, "ld_wav must be >= T * hop");
+    if (int rc = voc_check_call(c, g, "waveglow", mel, wav, B, T, ld_wav,
+                                (seeds != nullptr) == (z != nullptr) ? "waveglow: exactly one of seeds and z must be given" : nullptr,
+                                !(sigma >= 0.f) || !std::isfinite(sigma) ? "sigma must be finite and at least 0" : nullptr)) return rc;
     WgCall a{};
     a.mel = mel; a.frames = frames; a.seeds = seeds; a.z = z; a.wav = wav; a.wav_lengths = wav_lengths;
     a.spect = g.spect; a.hid[0] = g.hid[0]; a.hid[1] = g.hid[1]; a.out = g.out; a.audio = g.audio;
@@ -3608,17 +3562,6 @@ int gsttaco_waveglow_plan(const gsttaco_ctx* c, int32_t fields[]) {
 }
 
 // ---- the HiFi-GAN vocoder (hifigan.hip).  Configure and the manifest need no device; finalize uploads and allocates once.
-namespace {
-// the manifest's name of a launch's weights, without the /kernel or /bias leaf
-std::string hifigan_name(const HgStage& s) {
-    if (s.kind == GT_HG_IN) return "hifigan/in";
-    if (s.kind == GT_HG_OUT) return "hifigan/out";
-    std::string p = "hifigan/up" + std::to_string(s.up);
-    if (s.kind == GT_HG_UP) return p;
-    return p + "/res" + std::to_string(s.block) + "/unit" + std::to_string(s.unit) + (s.conv ? "/conv2" : "/conv1");
-}
-}  // namespace
-
 int gsttaco_hifigan_configure(gsttaco_ctx* c, const gsttaco_hifigan_config* m) {
     if (!c) return GSTTACO_E_INVALID;
     if (!m) return fail(c, GSTTACO_E_INVALID, "null argument");
@@ -3646,13 +3589,7 @@ int gsttaco_hifigan_configure(gsttaco_ctx* c, const gsttaco_hifigan_config* m) {
         return fail(c, GSTTACO_E_INVALID, "hifigan: max_batch * max_frames * hop exceeds 2^31 - 1 samples");
     }
     g.cfg = *m;
-    auto add = [&](const std::string& name, std::vector<int64_t> shape) {
-        HostTensor t;
-        t.name = name;
-        t.shape = std::move(shape);
-        g.index[name] = (int)g.tensors.size();
-        g.tensors.push_back(std::move(t));
-    };
+    auto add = [&](const std::string& name, std::vector<int64_t> shape) { g.man.add(name, std::move(shape)); };
     for (int i = 0; i < g.plan.n_stages; ++i) {
         const HgStage& s = g.plan.st[i];
         const std::string p = hifigan_name(s);
@@ -3677,42 +3614,22 @@ int gsttaco_hifigan_set_operands(gsttaco_ctx* c, int operands) {
     return 0;
 }
 
-int gsttaco_hifigan_num_weights(const gsttaco_ctx* c) { return c ? (int)c->hg.tensors.size() : GSTTACO_E_INVALID; }
+int gsttaco_hifigan_num_weights(const gsttaco_ctx* c) { return c ? (int)c->hg.man.tensors.size() : GSTTACO_E_INVALID; }
 
 int gsttaco_hifigan_weight_info(const gsttaco_ctx* c, int i, const char** name, int64_t shape[4], int* ndim) {
-    if (!c || i < 0 || i >= (int)c->hg.tensors.size()) return GSTTACO_E_INVALID;
-    const HostTensor& t = c->hg.tensors[i];
-    if (name) *name = t.name.c_str();
-    if (ndim) *ndim = (int)t.shape.size();
-    if (shape)
-        for (size_t d = 0; d < 4; ++d) shape[d] = d < t.shape.size() ? t.shape[d] : 1;
-    return 0;
+    return c ? c->hg.man.info(i, name, shape, ndim) : GSTTACO_E_INVALID;
 }
 
 int gsttaco_hifigan_load_weight(gsttaco_ctx* c, const char* name, const float* host, const int64_t* shape, int ndim) {
-    if (!c || !name || !host || !shape) return fail(c, GSTTACO_E_INVALID, "null argument");
-    gsttaco_ctx::Hifigan& g = c->hg;
-    if (!g.configured) return fail(c, GSTTACO_E_WEIGHTS, "hifigan: not configured (gsttaco_hifigan_configure)");
-    if (g.finalized) return fail(c, GSTTACO_E_WEIGHTS, "hifigan: weights already finalized");
-    auto it = g.index.find(name);
-    if (it == g.index.end()) return fail(c, GSTTACO_E_WEIGHTS, std::string("hifigan: unknown weight '") + name + "'");
-    HostTensor& t = g.tensors[it->second];
-    bool ok = ndim == (int)t.shape.size();
-    for (int d = 0; ok && d < ndim; ++d) ok = shape[d] == t.shape[d];
-    if (!ok) return fail(c, GSTTACO_E_WEIGHTS, std::string("hifigan: weight '") + name + "' has the wrong shape");
-    t.data.assign(host, host + t.numel());
-    t.loaded = true;
-    return 0;
+    return voc_load_weight(c, &gsttaco_ctx::hg, "hifigan", name, host, shape, ndim);
 }
 
 int gsttaco_hifigan_finalize(gsttaco_ctx* c) {
     if (!c) return GSTTACO_E_INVALID;
     gsttaco_ctx::Hifigan& g = c->hg;
-    if (!g.configured) return fail(c, GSTTACO_E_WEIGHTS, "hifigan: not configured (gsttaco_hifigan_configure)");
-    if (g.finalized) return fail(c, GSTTACO_E_WEIGHTS, "hifigan: weights already finalized");
-    for (const HostTensor& t : g.tensors)
-        if (!t.loaded) return fail(c, GSTTACO_E_WEIGHTS, "hifigan: weight '" + t.name + "' was not loaded");
-    auto host = [&](const std::string& name) -> const std::vector<float>& { return g.tensors[g.index[name]].data; };
+    int rc = voc_begin_finalize(c, g, "hifigan");
+    if (rc) return rc;
+    auto host = [&](const std::string& name) -> const std::vector<float>& { return g.man.host(name); };
     // The 16-bit packs first, on the host alone: a weight that fp16 cannot hold refuses the finalize before anything is uploaded, and
     // the context stays as it was (another form can be selected, or the tensor loaded again).
     static_assert(GSTTACO_HIFIGAN_F32 == GT_HG_OP_F32 && GSTTACO_HIFIGAN_BF16 == GT_HG_OP_BF16 && GSTTACO_HIFIGAN_F16 == GT_HG_OP_F16, "operand forms");
@@ -3728,30 +3645,15 @@ int gsttaco_hifigan_finalize(gsttaco_ctx* c) {
                 return fail(c, GSTTACO_E_WEIGHTS, "hifigan: weight '" + p + "/kernel' is not finite in float16 (element " + std::to_string(bad) +
                                                   "): use the bfloat16 or float32 operands");
         }
-    int rc = ensure_device(c);
-    if (rc) return rc;
+    if ((rc = ensure_device(c))) return rc;
     HIPCHECK(c, gt_hifigan_prepare());
-    std::vector<float> buf;
     for (int i = 0; i < g.plan.n_stages; ++i) {
         HgStage& s = g.plan.st[i];
         const std::string p = hifigan_name(s);
-        float* d = nullptr;
-        if (s.kind == GT_HG_OUT) {
-            if ((rc = upload(c, &d, host(p + "/kernel").data(), (size_t)s.taps * s.cin))) return rc;
-        } else if (g.operands != GSTTACO_HIFIGAN_F32) {
-            if ((rc = upload(c, &d, packs16[i].data(), packs16[i].size()))) return rc;
-        } else {
-            buf.resize((size_t)s.taps * s.cin_p * s.n_p);
-            gt_hifigan_pack(host(p + "/kernel").data(), s.taps, s.cin, s.cout, buf.data());
-            if ((rc = upload(c, &d, buf.data(), buf.size()))) return rc;
-        }
-        s.w0 = d;
-        buf.assign(s.kind == GT_HG_OUT ? 1 : s.n_p, 0.f);
-        const std::vector<float>& b = host(p + "/bias");
-        for (size_t k = 0; k < b.size(); ++k) buf[k] = b[k];
-        d = nullptr;
-        if ((rc = upload(c, &d, buf.data(), buf.size()))) return rc;
-        s.b0 = d;
+        if (s.kind == GT_HG_OUT) rc = upload_vec(c, &s.w0, host(p + "/kernel"));
+        else if (g.operands != GSTTACO_HIFIGAN_F32) rc = upload_vec(c, &s.w0, packs16[i]);
+        else rc = upload_packed(c, &s.w0, host(p + "/kernel"), s.taps, s.cin, s.cout);
+        if (rc || (rc = upload_padded_bias(c, g.man, &s.b0, p + "/bias", "", s.kind == GT_HG_OUT ? 1 : s.n_p))) return rc;
     }
     const size_t ws = (size_t)g.cfg.max_batch * g.cfg.max_frames * g.plan.ws_floats_per_frame * sizeof(float);
     for (int k = 0; k < GT_HG_BUFS; ++k)
@@ -3793,15 +3695,8 @@ int hifigan_call(gsttaco_ctx* c, const float* mel, const int32_t* frames, int B,
                  int only, void* stream) {
     if (!c) return GSTTACO_E_INVALID;
     const gsttaco_ctx::Hifigan& g = c->hg;
-    if (!g.finalized) return fail(c, GSTTACO_E_WEIGHTS, "hifigan: weights not finalized (gsttaco_hifigan_finalize)");
-    if (!mel || !wav) return fail(c, GSTTACO_E_INVALID, "null argument");
-    if (B < 1 || T < 1) return fail(c, GSTTACO_E_INVALID, "bad B / T");
-    if (B > g.cfg.max_batch || T > g.cfg.max_frames) return fail(c, GSTTACO_E_CAPACITY, "hifigan: B or T exceeds the capacity given at configure");
-    if ((int64_t)ld_wav < (int64_t)T * g.plan.hop) return fail(c, GSTTACO_E_INVALID, "ld_wav must be >= T * hop");
     HgCall a{};
-    a.mel = mel; a.frames = frames; a.wav = wav; a.wav_lengths = wav_lengths;
-    for (int k = 0; k < GT_HG_BUFS; ++k) a.ws[k] = g.ws[k];
-    a.B = B; a.T = T; a.ld_wav = ld_wav; a.only = only;
+    if (int rc = voc_chain_call(c, g, "hifigan", &a, mel, frames, B, T, wav, wav_lengths, ld_wav, only)) return rc;
     HIPCHECK(c, gt_launch_hifigan(g.plan, a, (hipStream_t)stream));
     return 0;
 }

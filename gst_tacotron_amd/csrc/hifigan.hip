@@ -12,31 +12,26 @@
 //   output   LeakyReLU of slope `out_slope`, Conv1D C_last -> 1, 7 taps, zero padding 3, bias, tanh
 // Row b has frames[b] frames; every zero pad and every edge of a transposed conv is taken at the row's own length at that stage.
 //
-// Activations are time-major [B, L, C_p], C_p = C rounded up to 16; the padding channels are exact zeros everywhere (zero weights, zero
-// bias, LeakyReLU(0) = 0, 0 + 0 = 0), so any channel count runs the same kernels.  Weights are repacked on the host (gt_hifigan_pack)
-// into the order the B operand is read in: [tap][k / 16][n][g = (k % 16) / 4][j = k % 4], one coalesced 16-byte load per lane and 16 k.
-//
-//   gt_hg_in_kernel    the 7-tap input conv: the mel tile plus 3 frames each side (zeros outside the row) staged in LDS, 7 GEMMs of K = mel_dim
-//   gt_hg_up_kernel    the transposed conv as a polyphase GEMM: output phase p of input position q takes taps p and p + r of positions
-//                      q and q - 1 (K = 2 C, no zero stuffing), LeakyReLU applied while staging; a workgroup owns a tile of q and
-//                      walks the r phases
+// The activation layout, the fragment packs, the wave items, the tap-GEMMs and the three kernels shared with MelGAN are
+// vocoder_common.h's (the padding channels stay exact zeros here too: LeakyReLU(0) = 0, 0 + 0 = 0):
+//   gt_voc_in_kernel<NT, OP, false>      the 7-tap input conv, zeros outside the row
+//   gt_voc_up_kernel<NT, OP>             the transposed conv as a polyphase GEMM
+//   gt_voc_out_kernel<false>             C_last -> 1 on the VALU with the tanh fused, LeakyReLU of `out_slope`
+// HiFi-GAN's own:
 //   gt_hg_conv_kernel  ONE launch per residual conv, at every width: the tile plus a halo of (k - 1) / 2 * d each side staged through the
 //                      LeakyReLU (zeros outside the row), k dilated tap-GEMMs into one accumulator, and an epilogue that adds the raw
 //                      residual and either writes the activation or, on the last unit of block j, the fused sum (sum = y for j = 0,
 //                      sum += y else, times 1 / n_k on the last block).  The sum's read-modify-write is done by the element's owner and
 //                      ordered by the stream: one order, no atomics.  (A fused pair would keep the intermediate in LDS, but at 256
 //                      channels, k = 11, d = 5 the two tiles need 206 KB; one form for every width was chosen -- DESIGN 3.5.)
-//   gt_hg_out_kernel   C_last -> 1: a 7 * C_last term dot product per sample on the VALU with the tanh fused; zeros beyond the row's length
-// A wave owns items of 64 time rows x NT N-tiles (the plan's `form`, by channel count); 256 threads a workgroup.  Every output sample
-// has one summation order -- bias, then taps ascending, k ascending in groups of 16, then the residual, then the fused sum in block
+// Every output sample has one summation order -- bias, then taps ascending, k ascending in groups of 16, then the residual, then the fused sum in block
 // order -- that depends on neither the batch nor the call's T nor the capacity: a row's samples are bitwise those of the row run alone.
 // Every global access is bounded by the row's length at that stage (<= T * rate), every LDS access by the tile the plan sized; nothing
 // waits on another workgroup.
 //
 // The 16-bit operand forms (gsttaco_hifigan_set_operands; GT_HG_OP_BF16 / GT_HG_OP_F16) run the same three GEMM kernels on
-// v_mfma_f32_16x16x32_{bf16,f16}: one template over the operand type, the two instructions share their lane maps (lane l holds
-// A[row l & 15][k = 8 (l >> 4) + j] and B[k = 8 (l >> 4) + j][col l & 15], j = 0 .. 7; C as the fp32 16x16x4 form, so the epilogues are
-// the same code).  HBM is untouched: activations stay fp32 at C_p = round16(C).  hg_stage applies its bounds and the LeakyReLU in fp32,
+// v_mfma_f32_16x16x32_{bf16,f16}: one template over the operand type (the lane maps: vocoder_common.h).  HBM is untouched: activations
+// stay fp32 at C_p = round16(C).  The staging (voc_stage; hg_stage below for the conv kernel) applies its bounds and the LeakyReLU in fp32,
 // then rounds to nearest even once (fp16 saturating to +-65504) into a 16-bit LDS tile whose rows are padded with exact zeros to a
 // multiple of 32 k, plus 8 elements: the row stride is then an odd number of 16-byte slots, and the 16 rows of a ds_read_b128 lane group
 // (8 at one k quarter, 8 at the next) fall on 16-byte slots at worst 2-way.  The weights are rounded once on the host (gt_hifigan_pack16)
@@ -47,251 +42,58 @@
 #include <string.h>
 #include <math.h>
 
-#include "kernels.h"
-#include "device_utils.h"
-
-#define HG_THREADS 256
-#define HG_WAVES (HG_THREADS / GT_WAVE)
-#define HG_ROWS 64              // time rows of a wave item: four M-tiles
-#define HG_OUT_TILE 256
-#define HG_TAPS_IO 7
+#include "vocoder_common.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-// The operand type of the MFMA: K the k block an MFMA group consumes (the LDS row and the weight pack are padded to it), Q = K / 4 the
-// elements a lane holds of it, PAD the row padding in elements (16 bytes in every form).
-template <typename OP> struct HgOp;
-template <> struct HgOp<float> { static constexpr int K = 16, Q = 4, PAD = 4; };
-template <> struct HgOp<__bf16> { static constexpr int K = 32, Q = 8, PAD = 8; typedef bf16x8 frag; };
-template <> struct HgOp<_Float16> { static constexpr int K = 32, Q = 8, PAD = 8; typedef f16x8 frag; };
-template <typename OP> __host__ __device__ __forceinline__ int hg_kpad(int c) { return (c + HgOp<OP>::K - 1) / HgOp<OP>::K * HgOp<OP>::K; }
-
-struct HgArgs {
-    const float* x;             // the launch's input
-    const float* res;           // GT_HG_CONV: the raw residual or NULL
-    float* y;                   // the activation written, or NULL (the sum alone)
-    float* sum;                 // GT_HG_CONV: the fused sum
-    const int32_t* frames;
-    int32_t* wav_lengths;
-    const float *w0, *b0;
-    int T, ldx, cin, cin_p, n_p, rate_in, rate_out, r, taps, dil, tile, ld_wav, sum_mode;
-    float slope, scale;
-};
-
-__device__ __forceinline__ int hg_row_frames(const HgArgs& a, int b) {
-    int f = a.frames ? a.frames[b] : a.T;
-    f = f < a.T ? f : a.T;
-    return f < 1 ? 0 : f;
-}
-
-__device__ __forceinline__ float hg_leaky(float v, float slope) { return v > 0.f ? v : v * slope; }
-
-// Positions [p0, p0 + rows) of one row's input (len valid positions, row stride ldx) into xs[rows][cs], channels [0, cin_p).  A position
-// outside [0, len), and every channel >= cin, is 0.
-// fp32 -> the operand type, to nearest even; fp16 saturates instead of overflowing to inf (a NaN stays a NaN)
-template <typename OP> __device__ __forceinline__ OP hg_cvt(float v) { return (OP)v; }
-template <> __device__ __forceinline__ _Float16 hg_cvt<_Float16>(float v) {
-    v = v > 65504.f ? 65504.f : (v < -65504.f ? -65504.f : v);
-    return (_Float16)v;
-}
-__device__ __forceinline__ void hg_store4(float* dst, const float4& v) { *reinterpret_cast<float4*>(dst) = v; }
+// gt_hg_conv_kernel's own staging: voc_stage<OP, true, false> at vec = true, with the arguments as a struct.  Positions [p0, p0 + rows)
+// of one row's input into xs[rows][cs] through the LeakyReLU, zeros outside [0, len) and in channels >= cin_p, rounded once to OP.  It is
+// kept apart because with the shared voc_stage the compiler biased the K loop's weight pointer by 0x800 and the 128-channel float32
+// launches ran 3.2 % slower ("shared core"); with this form the kernel's text is the one it had before the fold.
 template <typename OP>
-__device__ __forceinline__ void hg_store4(OP* dst, const float4& v) {
-    typedef OP op4 __attribute__((ext_vector_type(4)));
-    const op4 o = {hg_cvt<OP>(v.x), hg_cvt<OP>(v.y), hg_cvt<OP>(v.z), hg_cvt<OP>(v.w)};
-    *reinterpret_cast<op4*>(dst) = o;                       // 8 bytes: cs and c are multiples of 4 elements
-}
-
-// The same for the operand type OP: the fp32 value, bounds and LeakyReLU first, then rounded once; channels [cin_p, hg_kpad(cin_p)) are 0.
-template <typename OP, bool LEAKY>
-__device__ __forceinline__ void hg_stage(const HgArgs& a, const float* xb, OP* xs, int cs, int p0, int rows, int len, bool vec) {
-    const int ck = hg_kpad<OP>(a.cin_p);
-    if (vec) {
-        const int c4n = ck >> 2;
-        for (int e = threadIdx.x; e < rows * c4n; e += HG_THREADS) {
-            const int i = e / c4n, c = (e - i * c4n) << 2;
-            const int p = p0 + i;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (p >= 0 && p < len && c < a.cin_p) v = *reinterpret_cast<const float4*>(xb + (size_t)p * a.ldx + c);
-            if (LEAKY) { v.x = hg_leaky(v.x, a.slope); v.y = hg_leaky(v.y, a.slope); v.z = hg_leaky(v.z, a.slope); v.w = hg_leaky(v.w, a.slope); }
-            hg_store4(xs + i * cs + c, v);
-        }
-    } else {
-        for (int e = threadIdx.x; e < rows * ck; e += HG_THREADS) {
-            const int i = e / ck, c = e - i * ck;
-            const int p = p0 + i;
-            float v = 0.f;
-            if (p >= 0 && p < len && c < a.cin) v = xb[(size_t)p * a.ldx + c];
-            xs[i * cs + c] = hg_cvt<OP>(LEAKY ? hg_leaky(v, a.slope) : v);
-        }
-    }
-}
-
-// acc[mt][nt] += A[64 rows, 16 nkb] * W[16 nkb, 16 NT]: A from LDS (a_lane: this lane's row l & 15 of M-tile 0, k offset 4 (l >> 4)),
-// W from the fragment pack (w_lane: this lane's column and k group of N-tile 0).  k ascending in groups of 16; inside a group MFMA j
-// takes k = 4 g + j of the four lane groups g.
-template <int NT>
-__device__ __forceinline__ void hg_gemm(f32x4 (&acc)[4][NT], const float* a_lane, int cs, const float* w_lane, int nkb, int n_p) {
-    for (int kb = 0; kb < nkb; ++kb) {
-        float av[4][4], bv[NT][4];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const float4 t = *reinterpret_cast<const float4*>(w_lane + ((size_t)kb * n_p + nt * 16) * 16);
-            bv[nt][0] = t.x; bv[nt][1] = t.y; bv[nt][2] = t.z; bv[nt][3] = t.w;
-        }
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-            const float4 t = *reinterpret_cast<const float4*>(a_lane + mt * 16 * cs + kb * 16);
-            av[mt][0] = t.x; av[mt][1] = t.y; av[mt][2] = t.z; av[mt][3] = t.w;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt][j], bv[nt][j], acc[mt][nt], 0, 0, 0);
-    }
-}
-
-// The 16-bit form: acc[mt][nt] += A[64 rows, 32 nkb] * W[32 nkb, 16 NT].  a_lane: this lane's row l & 15 of M-tile 0, k offset 8 (l >> 4);
-// w_lane: this lane's column and k quarter of N-tile 0 in the 16-bit pack.  One MFMA per M-tile, N-tile and 32 k.
-__device__ __forceinline__ f32x4 hg_mfma16(const bf16x8& a, const bf16x8& b, const f32x4& c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x4 hg_mfma16(const f16x8& a, const f16x8& b, const f32x4& c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-template <int NT, typename OP>
-__device__ __forceinline__ void hg_gemm(f32x4 (&acc)[4][NT], const OP* a_lane, int cs, const OP* w_lane, int nkb, int n_p) {
-    typedef typename HgOp<OP>::frag frag;
-    for (int kb = 0; kb < nkb; ++kb) {
-        frag av[4], bv[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) bv[nt] = *reinterpret_cast<const frag*>(w_lane + ((size_t)kb * n_p + nt * 16) * 32);
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) av[mt] = *reinterpret_cast<const frag*>(a_lane + mt * 16 * cs + kb * 32);
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = hg_mfma16(av[mt], bv[nt], acc[mt][nt]);
-    }
-}
-
-template <int NT>
-__device__ __forceinline__ void hg_bias(f32x4 (&acc)[4][NT], const float* bias, int n0, int col) {
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const float b = bias[n0 + nt * 16 + col];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) acc[mt][nt] = f32x4{b, b, b, b};
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ the input conv
-template <int NT, typename OP>
-__global__ __launch_bounds__(HG_THREADS) void gt_hg_in_kernel(HgArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char hg_lds_raw[];
-    OP* hg_lds = reinterpret_cast<OP*>(hg_lds_raw);
-    constexpr int KB = HgOp<OP>::K, Q = HgOp<OP>::Q;
-    const OP* w0 = reinterpret_cast<const OP*>(a.w0);
-    const int b = blockIdx.y, len = hg_row_frames(a, b), t0 = blockIdx.x * a.tile;
-    if (t0 >= len) return;
-    const int ck = hg_kpad<OP>(a.cin_p), cs = ck + HgOp<OP>::PAD, pad = HG_TAPS_IO / 2;
-    const float* xb = a.x + (size_t)b * a.T * a.ldx;
-    float* yb = a.y + (size_t)b * a.T * a.n_p;
-    hg_stage<OP, false>(a, xb, hg_lds, cs, t0 - pad, a.tile + 2 * pad, len, false);
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, g = lane >> 4;
-    const int nkb = ck / KB, ngroups = (a.n_p >> 4) / NT, items = (a.tile / HG_ROWS) * ngroups;
-    for (int item = wave; item < items; item += HG_WAVES) {
-        const int mg = item / ngroups, n0 = (item - mg * ngroups) * NT * 16;
-        f32x4 acc[4][NT];
-        hg_bias<NT>(acc, a.b0, n0, col);
-        for (int tap = 0; tap < HG_TAPS_IO; ++tap)
-            hg_gemm<NT>(acc, hg_lds + (mg * HG_ROWS + tap + col) * cs + Q * g, cs,
-                        w0 + (size_t)tap * ck * a.n_p + (size_t)(n0 + col) * KB + Q * g, nkb, a.n_p);
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int t = t0 + mg * HG_ROWS + mt * 16 + g * 4 + i;
-                if (t < len) {
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) yb[(size_t)t * a.n_p + n0 + nt * 16 + col] = acc[mt][nt][i];
-                }
-            }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ the transposed conv
-template <int NT, typename OP>
-__global__ __launch_bounds__(HG_THREADS) void gt_hg_up_kernel(HgArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char hg_lds_raw[];
-    OP* hg_lds = reinterpret_cast<OP*>(hg_lds_raw);
-    constexpr int KB = HgOp<OP>::K, Q = HgOp<OP>::Q;
-    const OP* w0 = reinterpret_cast<const OP*>(a.w0);
-    const int b = blockIdx.y, len = hg_row_frames(a, b) * a.rate_in, q0 = blockIdx.x * a.tile;
-    if (len == 0 || q0 > len) return;                       // q runs over [0, len]: position len still feeds the last r / 2 samples
-    const int ck = hg_kpad<OP>(a.cin_p), cs = ck + HgOp<OP>::PAD;
-    const float* xb = a.x + (size_t)b * a.T * a.rate_in * a.ldx;
-    float* yb = a.y + (size_t)b * a.T * a.rate_out * a.n_p;
-    hg_stage<OP, true>(a, xb, hg_lds, cs, q0 - 1, a.tile + 1, len, true);       // xs[i] = LeakyReLU(x[q0 - 1 + i]), 0 where absent
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, g = lane >> 4;
-    const int nkb = ck / KB, ngroups = (a.n_p >> 4) / NT, per_phase = (a.tile / HG_ROWS) * ngroups, items = per_phase * a.r;
-    const int len_out = len * a.r, half = a.r >> 1;
-    const size_t tap_stride = (size_t)ck * a.n_p;
-    for (int item = wave; item < items; item += HG_WAVES) {
-        const int p = item / per_phase, rest = item - p * per_phase, mg = rest / ngroups, n0 = (rest - mg * ngroups) * NT * 16;
-        f32x4 acc[4][NT];
-        hg_bias<NT>(acc, a.b0, n0, col);
-        const size_t wl = (size_t)(n0 + col) * KB + Q * g;
-        hg_gemm<NT>(acc, hg_lds + (mg * HG_ROWS + 1 + col) * cs + Q * g, cs, w0 + p * tap_stride + wl, nkb, a.n_p);
-        hg_gemm<NT>(acc, hg_lds + (mg * HG_ROWS + col) * cs + Q * g, cs, w0 + (p + a.r) * tap_stride + wl, nkb, a.n_p);
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int q = q0 + mg * HG_ROWS + mt * 16 + g * 4 + i;
-                const int o = q * a.r + p - half;
-                if (q <= len && o >= 0 && o < len_out) {
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) yb[(size_t)o * a.n_p + n0 + nt * 16 + col] = acc[mt][nt][i];
-                }
-            }
+__device__ __forceinline__ void hg_stage(const VocArgs& a, const float* xb, OP* xs, int cs, int p0, int rows, int len) {
+    const int ck = voc_kpad<OP>(a.cin_p), c4n = ck >> 2;
+    for (int e = threadIdx.x; e < rows * c4n; e += VOC_THREADS) {
+        const int i = e / c4n, c = (e - i * c4n) << 2;
+        const int p = p0 + i;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (p >= 0 && p < len && c < a.cin_p) v = *reinterpret_cast<const float4*>(xb + (size_t)p * a.ldx + c);
+        v.x = voc_leaky(v.x, a.slope); v.y = voc_leaky(v.y, a.slope); v.z = voc_leaky(v.z, a.slope); v.w = voc_leaky(v.w, a.slope);
+        voc_store4(xs + i * cs + c, v);
     }
 }
 
 // ------------------------------------------------------------------------------------------------ one residual conv
 template <int NT, typename OP>
-__global__ __launch_bounds__(HG_THREADS) void gt_hg_conv_kernel(HgArgs a) {
+__global__ __launch_bounds__(VOC_THREADS) void gt_hg_conv_kernel(VocArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char hg_lds_raw[];
     OP* hg_lds = reinterpret_cast<OP*>(hg_lds_raw);
-    constexpr int KB = HgOp<OP>::K, Q = HgOp<OP>::Q;
+    constexpr int KB = VocOp<OP>::K, Q = VocOp<OP>::Q;
     const OP* w0 = reinterpret_cast<const OP*>(a.w0);
-    const int b = blockIdx.y, len = hg_row_frames(a, b) * a.rate_in, t0 = blockIdx.x * a.tile;
+    const int b = blockIdx.y, len = voc_row_frames(a.frames, b, a.T, 1) * a.rate_in, t0 = blockIdx.x * a.tile;      // (min_frames is 1: zero padding)
     if (t0 >= len) return;
-    const int ck = hg_kpad<OP>(a.cin_p), cs = ck + HgOp<OP>::PAD, d = a.dil, halo = (a.taps >> 1) * d;
+    const int ck = voc_kpad<OP>(a.cin_p), cs = ck + VocOp<OP>::PAD, d = a.dil, halo = (a.taps >> 1) * d;
     const size_t row0 = (size_t)b * a.T * a.rate_in * a.n_p;            // cin_p == n_p: every buffer of the stage has this shape
-    hg_stage<OP, true>(a, a.x + row0, hg_lds, cs, t0 - halo, a.tile + 2 * halo, len, true);
+    hg_stage<OP>(a, a.x + row0, hg_lds, cs, t0 - halo, a.tile + 2 * halo, len);
     __syncthreads();
     const float* rb = a.res ? a.res + row0 : nullptr;
     float* yb = a.y ? a.y + row0 : nullptr;
     float* sb = a.sum + row0;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, g = lane >> 4;
-    const int nkb = ck / KB, ngroups = (a.n_p >> 4) / NT, items = (a.tile / HG_ROWS) * ngroups;
+    const int nkb = ck / KB, ngroups = (a.n_p >> 4) / NT, items = (a.tile / VOC_ROWS) * ngroups;
     const size_t tap_stride = (size_t)ck * a.n_p;
-    for (int item = wave; item < items; item += HG_WAVES) {
+    for (int item = wave; item < items; item += VOC_WAVES) {
         const int mg = item / ngroups, n0 = (item - mg * ngroups) * NT * 16;
         f32x4 acc[4][NT];
-        hg_bias<NT>(acc, a.b0, n0, col);
+        voc_bias<NT>(acc, a.b0, n0, col);
         const size_t wl = (size_t)(n0 + col) * KB + Q * g;
         for (int tap = 0; tap < a.taps; ++tap)
-            hg_gemm<NT>(acc, hg_lds + (mg * HG_ROWS + tap * d + col) * cs + Q * g, cs, w0 + tap * tap_stride + wl, nkb, a.n_p);
+            voc_gemm<NT>(acc, hg_lds + (mg * VOC_ROWS + tap * d + col) * cs + Q * g, cs, w0 + tap * tap_stride + wl, nkb, a.n_p);
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const int t = t0 + mg * HG_ROWS + mt * 16 + g * 4 + i;
+                const int t = t0 + mg * VOC_ROWS + mt * 16 + g * 4 + i;
                 if (t < len) {
 #pragma unroll
                     for (int nt = 0; nt < NT; ++nt) {
@@ -309,85 +111,42 @@ __global__ __launch_bounds__(HG_THREADS) void gt_hg_conv_kernel(HgArgs a) {
     }
 }
 
-// ------------------------------------------------------------------------------------------------ the output conv
-__global__ __launch_bounds__(HG_OUT_TILE) void gt_hg_out_kernel(HgArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float hg_lds[];
-    const int b = blockIdx.y, len = hg_row_frames(a, b) * a.rate_in, t0 = blockIdx.x * HG_OUT_TILE, t = t0 + (int)threadIdx.x;
-    float* wb = a.y + (size_t)b * a.ld_wav;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && a.wav_lengths) a.wav_lengths[b] = len;
-    if (t0 >= len) {
-        if (t < a.ld_wav) wb[t] = 0.f;
-        return;
-    }
-    const int cs = a.cin | 1, pad = HG_TAPS_IO / 2, rows = HG_OUT_TILE + 2 * pad;
-    float* xs = hg_lds;                                     // [rows][cs], LeakyReLU (the output slope) applied
-    float* ws = hg_lds + rows * cs;                         // [7 * cin]
-    const float* xb = a.x + (size_t)b * a.T * a.rate_in * a.ldx;
-    for (int e = threadIdx.x; e < rows * a.cin; e += HG_OUT_TILE) {
-        const int i = e / a.cin, c = e - i * a.cin;
-        const int p = t0 - pad + i;
-        xs[i * cs + c] = (p >= 0 && p < len) ? hg_leaky(xb[(size_t)p * a.ldx + c], a.slope) : 0.f;
-    }
-    for (int e = threadIdx.x; e < HG_TAPS_IO * a.cin; e += HG_OUT_TILE) ws[e] = a.w0[e];
-    __syncthreads();
-    float acc = a.b0[0];
-    for (int tap = 0; tap < HG_TAPS_IO; ++tap) {
-        const float* xr = xs + (threadIdx.x + tap) * cs;
-        const float* wr = ws + tap * a.cin;
-        for (int c = 0; c < a.cin; ++c) acc = __builtin_fmaf(xr[c], wr[c], acc);
-    }
-    if (t < a.ld_wav) wb[t] = t < len ? fminf(1.f, fmaxf(-1.f, tanhf(acc))) : 0.f;
-}
-
-int hg_pad16(int c) { return (c + 15) / 16 * 16; }
-
-// N-tiles per wave item by channel count, and the time tile that gives the four waves an item each
-void hg_tile_form(int n_p, int* tile, int* form) {
-    const int ntiles = n_p / 16;
-    const int nt = (ntiles % 4 == 0 && ntiles >= 16) ? 4 : (ntiles % 2 == 0 ? 2 : 1);
-    const int ngroups = ntiles / nt;
-    const int mgroups = ngroups >= 4 ? 1 : (ngroups >= 2 ? 2 : 4);
-    *tile = HG_ROWS * mgroups;
-    *form = nt;
-}
-
 // op_bytes: the size of an MFMA operand, 4 (fp32: rows of cin_p + 4) or 2 (16-bit: rows of round32(cin_p) + 8); the output conv is fp32 always
 size_t hg_lds_bytes(const HgStage& s, size_t op_bytes) {
-    const size_t cs = op_bytes == 4 ? (size_t)s.cin_p + HgOp<float>::PAD : (size_t)hg_kpad<__bf16>(s.cin_p) + HgOp<__bf16>::PAD;
+    const size_t cs = op_bytes == 4 ? (size_t)s.cin_p + VocOp<float>::PAD : (size_t)voc_kpad<__bf16>(s.cin_p) + VocOp<__bf16>::PAD;
     switch (s.kind) {
-    case GT_HG_IN: return (size_t)(s.tile + HG_TAPS_IO - 1) * cs * op_bytes;
+    case GT_HG_IN: return (size_t)(s.tile + VOC_TAPS_IO - 1) * cs * op_bytes;
     case GT_HG_UP: return (size_t)(s.tile + 1) * cs * op_bytes;
     case GT_HG_CONV: return ((size_t)s.tile + (size_t)(s.taps - 1) * s.dil) * cs * op_bytes;
-    default: return ((size_t)(HG_OUT_TILE + HG_TAPS_IO - 1) * (s.cin | 1) + (size_t)HG_TAPS_IO * s.cin) * sizeof(float);
+    default: return voc_out_lds(s.cin);
     }
 }
 
 template <int NT, typename OP>
-hipError_t hg_launch_form(const HgStage& s, const HgArgs& a, dim3 grid, hipStream_t stream) {
+hipError_t hg_launch_form(const HgStage& s, const VocArgs& a, dim3 grid, hipStream_t stream) {
     switch (s.kind) {
-    case GT_HG_IN: gt_hg_in_kernel<NT, OP><<<grid, HG_THREADS, s.lds, stream>>>(a); break;
-    case GT_HG_UP: gt_hg_up_kernel<NT, OP><<<grid, HG_THREADS, s.lds, stream>>>(a); break;
-    default: gt_hg_conv_kernel<NT, OP><<<grid, HG_THREADS, s.lds, stream>>>(a); break;
+    case GT_HG_IN: gt_voc_in_kernel<NT, OP, false><<<grid, VOC_THREADS, s.lds, stream>>>(a); break;
+    case GT_HG_UP: gt_voc_up_kernel<NT, OP><<<grid, VOC_THREADS, s.lds, stream>>>(a); break;
+    default: gt_hg_conv_kernel<NT, OP><<<grid, VOC_THREADS, s.lds, stream>>>(a); break;
     }
     return hipGetLastError();
 }
 
 template <typename OP>
-hipError_t hg_launch_op(const HgStage& s, const HgArgs& a, dim3 grid, hipStream_t stream) {
+hipError_t hg_launch_op(const HgStage& s, const VocArgs& a, dim3 grid, hipStream_t stream) {
     return s.form == 4 ? hg_launch_form<4, OP>(s, a, grid, stream) : s.form == 2 ? hg_launch_form<2, OP>(s, a, grid, stream)
                                                                                  : hg_launch_form<1, OP>(s, a, grid, stream);
 }
 
-template <typename OP>
-hipError_t hg_prepare_op() {
-    hipError_t e = hipSuccess;
-#define HG_ATTR(K) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, GT_HG_LDS_MAX)
-    HG_ATTR((gt_hg_in_kernel<1, OP>)); HG_ATTR((gt_hg_in_kernel<2, OP>)); HG_ATTR((gt_hg_in_kernel<4, OP>));
-    HG_ATTR((gt_hg_up_kernel<1, OP>)); HG_ATTR((gt_hg_up_kernel<2, OP>)); HG_ATTR((gt_hg_up_kernel<4, OP>));
-    HG_ATTR((gt_hg_conv_kernel<1, OP>)); HG_ATTR((gt_hg_conv_kernel<2, OP>)); HG_ATTR((gt_hg_conv_kernel<4, OP>));
-#undef HG_ATTR
-    return e;
+template <int NT, typename OP>
+hipError_t hg_prepare_form(hipError_t e) {
+    e = voc_allow_lds(e, gt_voc_in_kernel<NT, OP, false>);
+    e = voc_allow_lds(e, gt_voc_up_kernel<NT, OP>);
+    return voc_allow_lds(e, gt_hg_conv_kernel<NT, OP>);
 }
+
+template <typename OP>
+hipError_t hg_prepare_op(hipError_t e) { return hg_prepare_form<4, OP>(hg_prepare_form<2, OP>(hg_prepare_form<1, OP>(e))); }
 
 // fp32 -> bf16 / fp16 bits, to nearest even, as the device's conversion does it
 uint16_t hg_bf16_bits(float v) {
@@ -430,21 +189,22 @@ const char* gt_hifigan_make_plan(const HgConfig& cfg, HgPlan* plan) {
     }
     HgPlan& P = *plan;
     P = HgPlan{};
+    // (min_frames must stay 1: the shared in / up / out kernels read it from the plan, gt_hg_conv_kernel has it as a literal)
     P.mel_dim = cfg.mel_dim; P.hop = (int)hop; P.slope = cfg.slope; P.out_slope = cfg.out_slope; P.min_frames = 1;
     int C = cfg.initial, rate = 1, n = 0;
     auto add = [&](int kind, int cin, int cout, int rate_in, int rate_out, int r, int taps, int dil) -> HgStage* {
         HgStage& s = P.st[n++];
-        s.kind = kind; s.cin = cin; s.cout = cout; s.cin_p = hg_pad16(cin); s.n_p = hg_pad16(cout);
+        s.kind = kind; s.cin = cin; s.cout = cout; s.cin_p = voc_pad16(cin); s.n_p = voc_pad16(cout);
         s.rate_in = rate_in; s.rate_out = rate_out; s.r = r; s.taps = taps; s.dil = dil;
         s.src = s.res = s.dst = -1; s.sum = GT_HG_SUM_NONE; s.scale = 1.f; s.up = s.block = s.unit = s.conv = -1;
-        if (kind == GT_HG_OUT) { s.tile = HG_OUT_TILE; s.form = 0; }
-        else hg_tile_form(s.n_p, &s.tile, &s.form);
-        while ((s.lds = hg_lds_bytes(s, sizeof(float))) > GT_HG_LDS_MAX && kind != GT_HG_OUT && s.tile > HG_ROWS) s.tile >>= 1;
+        if (kind == GT_HG_OUT) { s.tile = VOC_OUT_TILE; s.form = 0; }
+        else voc_tile_form(s.n_p, &s.tile, &s.form);
+        while ((s.lds = hg_lds_bytes(s, sizeof(float))) > GT_VOC_LDS_MAX && kind != GT_HG_OUT && s.tile > VOC_ROWS) s.tile >>= 1;
         if (kind != GT_HG_OUT) P.ws_floats_per_frame = std::max(P.ws_floats_per_frame, (size_t)rate_out * s.n_p);
-        return s.lds <= GT_HG_LDS_MAX ? &s : nullptr;
+        return s.lds <= GT_VOC_LDS_MAX ? &s : nullptr;
     };
     static const char* lds_msg = "a launch's smallest tile does not fit the 160 KB of LDS (initial: fewer channels, or dilations: a narrower halo)";
-    if (!add(GT_HG_IN, cfg.mel_dim, C, 1, 1, 0, HG_TAPS_IO, 1)) return lds_msg;
+    if (!add(GT_HG_IN, cfg.mel_dim, C, 1, 1, 0, VOC_TAPS_IO, 1)) return lds_msg;
     for (int i = 0; i < cfg.n_rates; ++i) {
         HgStage* u = add(GT_HG_UP, C, C / 2, rate, rate * cfg.rates[i], cfg.rates[i], 2 * cfg.rates[i], 1);
         if (!u) return lds_msg;
@@ -479,18 +239,9 @@ const char* gt_hifigan_make_plan(const HgConfig& cfg, HgPlan* plan) {
             }
         }
     }
-    if (!add(GT_HG_OUT, C, 1, rate, rate, 0, HG_TAPS_IO, 1)) return lds_msg;
+    if (!add(GT_HG_OUT, C, 1, rate, rate, 0, VOC_TAPS_IO, 1)) return lds_msg;
     P.n_stages = n;
     return nullptr;
-}
-
-void gt_hifigan_pack(const float* w, int taps, int cin, int cout, float* out) {
-    const int cin_p = hg_pad16(cin), n_p = hg_pad16(cout);
-    std::fill(out, out + (size_t)taps * cin_p * n_p, 0.f);
-    for (int tap = 0; tap < taps; ++tap)
-        for (int k = 0; k < cin; ++k)
-            for (int nn = 0; nn < cout; ++nn)
-                out[(size_t)tap * cin_p * n_p + ((size_t)(k >> 4) * n_p + nn) * 16 + (k & 15)] = w[((size_t)tap * cin + k) * cout + nn];
 }
 
 void gt_hifigan_set_operands(HgPlan* plan, int operands) {
@@ -498,10 +249,10 @@ void gt_hifigan_set_operands(HgPlan* plan, int operands) {
     for (int i = 0; i < plan->n_stages; ++i) plan->st[i].lds = hg_lds_bytes(plan->st[i], operands == GT_HG_OP_F32 ? 4 : 2);
 }
 
-size_t gt_hifigan_pack16_words(int taps, int cin, int cout) { return (size_t)taps * hg_kpad<__bf16>(hg_pad16(cin)) * hg_pad16(cout); }
+size_t gt_hifigan_pack16_words(int taps, int cin, int cout) { return (size_t)taps * voc_kpad<__bf16>(voc_pad16(cin)) * voc_pad16(cout); }
 
 int64_t gt_hifigan_pack16(const float* w, int taps, int cin, int cout, int operands, uint16_t* out) {
-    const int ck = hg_kpad<__bf16>(hg_pad16(cin)), n_p = hg_pad16(cout);
+    const int ck = voc_kpad<__bf16>(voc_pad16(cin)), n_p = voc_pad16(cout);
     std::fill(out, out + (size_t)taps * ck * n_p, (uint16_t)0);
     int64_t bad = -1;
     for (int tap = 0; tap < taps; ++tap)
@@ -519,10 +270,8 @@ int64_t gt_hifigan_pack16(const float* w, int taps, int cin, int cout, int opera
 }
 
 hipError_t gt_hifigan_prepare() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gt_hg_out_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, GT_HG_LDS_MAX);
-    if (e == hipSuccess) e = hg_prepare_op<float>();
-    if (e == hipSuccess) e = hg_prepare_op<__bf16>();
-    if (e == hipSuccess) e = hg_prepare_op<_Float16>();
+    hipError_t e = voc_allow_lds(hipSuccess, gt_voc_out_kernel<false>);
+    e = hg_prepare_op<float>(e); e = hg_prepare_op<__bf16>(e); e = hg_prepare_op<_Float16>(e);
     return e;
 }
 
@@ -530,11 +279,11 @@ hipError_t gt_launch_hifigan(const HgPlan& P, const HgCall& c, hipStream_t strea
     for (int i = 0; i < P.n_stages; ++i) {
         if (c.only >= 0 && c.only != i) continue;
         const HgStage& s = P.st[i];
-        HgArgs a{};
+        VocArgs a{};
         a.frames = c.frames; a.wav_lengths = c.wav_lengths;
         a.w0 = s.w0; a.b0 = s.b0;
         a.T = c.T; a.cin = s.cin; a.cin_p = s.cin_p; a.n_p = s.n_p; a.rate_in = s.rate_in; a.rate_out = s.rate_out;
-        a.r = s.r; a.taps = s.taps; a.dil = s.dil; a.tile = s.tile; a.ld_wav = c.ld_wav; a.sum_mode = s.sum;
+        a.r = s.r; a.taps = s.taps; a.dil = s.dil; a.tile = s.tile; a.min_frames = P.min_frames; a.ld_wav = c.ld_wav; a.sum_mode = s.sum;
         a.slope = s.kind == GT_HG_OUT ? P.out_slope : P.slope; a.scale = s.scale;
         a.sum = c.ws[GT_HG_BUF_SUM];
         dim3 grid(1, c.B);
@@ -551,11 +300,11 @@ hipError_t gt_launch_hifigan(const HgPlan& P, const HgCall& c, hipStream_t strea
             grid.x = (unsigned)(((int64_t)c.T * s.rate_out + s.tile - 1) / s.tile);
         } else {
             a.x = c.ws[GT_HG_BUF_SUM]; a.ldx = s.cin_p; a.y = c.wav;
-            grid.x = (c.ld_wav + HG_OUT_TILE - 1) / HG_OUT_TILE;
+            grid.x = (c.ld_wav + VOC_OUT_TILE - 1) / VOC_OUT_TILE;
         }
         hipError_t e;
         if (s.kind == GT_HG_OUT) {
-            gt_hg_out_kernel<<<grid, HG_OUT_TILE, s.lds, stream>>>(a);
+            gt_voc_out_kernel<false><<<grid, VOC_OUT_TILE, s.lds, stream>>>(a);
             e = hipGetLastError();
         } else {
             e = P.operands == GT_HG_OP_BF16 ? hg_launch_op<__bf16>(s, a, grid, stream)

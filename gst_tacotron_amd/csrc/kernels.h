@@ -647,7 +647,6 @@ hipError_t gt_launch_style_map(const TsneMapArgs& a, hipStream_t stream);
 #define GT_MG_MAX_RATIOS 8
 #define GT_MG_MAX_RES 8
 #define GT_MG_MAX_STAGES (2 + GT_MG_MAX_RATIOS * (1 + GT_MG_MAX_RES))
-#define GT_MG_LDS_MAX (160 * 1024)
 enum { GT_MG_IN = 0, GT_MG_UP = 1, GT_MG_RES = 2, GT_MG_OUT = 3 };
 // One launch of the chain.  Channel counts with _p are the padded ones (multiples of 16) the fragment packs and the workspace use.
 struct MgStage {
@@ -667,12 +666,9 @@ struct MgPlan {
     int mel_dim, hop, min_frames;
     float slope;
     size_t ws_floats_per_frame;     // the largest activation of the chain, floats per mel frame of one row
-    int operands;                   // GT_HG_OP_*: gt_hifigan_make_plan leaves fp32, gt_hifigan_set_operands changes it
 };
 // Fills the plan's shapes, tiles and LDS sizes (no device use).  Returns NULL, or the reason the configuration cannot run.
 const char* gt_melgan_make_plan(int mel_dim, int base, int n_ratios, const int* ratios, int n_res, float slope, MgPlan* plan);
-// [taps * cin, cout] (row stride cout) -> the fragment pack [taps][cin_p / 16][n_p][4][4] the kernels read, zero padded
-void gt_melgan_pack(const float* w, int taps, int cin, int cout, float* out);
 hipError_t gt_melgan_prepare();
 struct MgCall {
     const float* mel;           // [B, T, mel_dim]
@@ -744,7 +740,6 @@ hipError_t gt_launch_waveglow(const WgPlan& plan, const WgCall& call, hipStream_
 #define GT_HG_MAX_DILATIONS 4
 #define GT_HG_MAX_TAPS 11
 #define GT_HG_MAX_STAGES (2 + GT_HG_MAX_RATES * (1 + GT_HG_MAX_KERNELS * GT_HG_MAX_DILATIONS * 2))
-#define GT_HG_LDS_MAX (160 * 1024)
 enum { GT_HG_IN = 0, GT_HG_UP = 1, GT_HG_CONV = 2, GT_HG_OUT = 3 };
 // The four activation buffers of the workspace: the fused sum (a stage's output, the next stage's input), the transposed conv's output
 // (every residual block's input), and the two a block's chain alternates between.
@@ -785,8 +780,6 @@ struct HgPlan {
 };
 // Fills the plan's shapes, tiles and LDS sizes (no device use).  Returns NULL, or the reason the configuration cannot run.
 const char* gt_hifigan_make_plan(const HgConfig& cfg, HgPlan* plan);
-// [taps * cin, cout] (row stride cout) -> the fragment pack [taps][cin_p / 16][n_p][4][4] the kernels read, zero padded
-void gt_hifigan_pack(const float* w, int taps, int cin, int cout, float* out);
 // The plan's operand form: the launches, tiles and forms stay the fp32 plan's, only every launch's LDS bytes are recomputed for the
 // operand size (they shrink: a 16-bit row of round32(cin_p) + 8 elements is never longer than an fp32 row of cin_p + 4).
 void gt_hifigan_set_operands(HgPlan* plan, int operands);

@@ -12,7 +12,8 @@
 //   wav[l G + g] = audio[l, g]
 //
 // Activations are time-major [B, L, C_p], C_p = C rounded up to 16, the padding channels exact zeros (zero weights and biases, and
-// tanh(0) sigmoid(0) = 0), as in melgan.hip, whose fragment pack (gt_melgan_pack: [tap][k / 16][n][4][4]) the weights use.
+// tanh(0) sigmoid(0) = 0).  The fp32 tap-GEMM (voc_gemm, voc_bias), the row-length rule and the fragment pack the weights use
+// (voc_pack_f32: [tap][k / 16][n][4][4]) are vocoder_common.h's; wg_stage stages a column window of a row and is this file's own.
 //
 //   gt_wg_up_kernel     the transposed conv as a polyphase GEMM, K = (win / hop) mel_dim per sample: a workgroup owns a tile of frames
 //                       (staged with the win / hop - 1 frames in front of it) and walks the hop phases; stores into the grouped layout
@@ -33,62 +34,18 @@
 #include <math.h>
 #include <vector>
 
-#include "kernels.h"
-#include "device_utils.h"
+#include "vocoder_common.h"
 
-#define WG_THREADS 256
-#define WG_WAVES (WG_THREADS / GT_WAVE)
-#define WG_ROWS 64              // time rows of a wave item: four M-tiles
 #define WG_AW 16                // the audio buffer's row width (n_group <= 16)
 #define WG_OS (WG_AW + 1)       // row stride of the flow kernel's per-column LDS rows
 
 namespace {
 
-__device__ __forceinline__ int wg_row_frames(const int32_t* frames, int b, int T) {
-    int f = frames ? frames[b] : T;
-    f = f < T ? f : T;
-    return f < 1 ? 0 : f;
-}
-
-// acc[mt][nt] += A[64 rows, 16 nkb] * W[16 nkb, 16 NT] (melgan.hip's mg_gemm: A from LDS, W from the fragment pack, k ascending)
-template <int NT>
-__device__ __forceinline__ void wg_gemm(f32x4 (&acc)[4][NT], const float* a_lane, int cs, const float* w_lane, int nkb, int n_p) {
-    for (int kb = 0; kb < nkb; ++kb) {
-        float av[4][4], bv[NT][4];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const float4 t = *reinterpret_cast<const float4*>(w_lane + ((size_t)kb * n_p + nt * 16) * 16);
-            bv[nt][0] = t.x; bv[nt][1] = t.y; bv[nt][2] = t.z; bv[nt][3] = t.w;
-        }
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-            const float4 t = *reinterpret_cast<const float4*>(a_lane + mt * 16 * cs + kb * 16);
-            av[mt][0] = t.x; av[mt][1] = t.y; av[mt][2] = t.z; av[mt][3] = t.w;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt][j], bv[nt][j], acc[mt][nt], 0, 0, 0);
-    }
-}
-
-template <int NT>
-__device__ __forceinline__ void wg_bias(f32x4 (&acc)[4][NT], const float* bias, int n0, int col) {
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const float b = bias[n0 + nt * 16 + col];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) acc[mt][nt] = f32x4{b, b, b, b};
-    }
-}
-
 // Columns [k0, k0 + w) of positions [p0, p0 + rows) of one row's activation (len valid positions, row stride ld, w a multiple of 16)
 // into xs[rows][cs]; a position outside [0, len) is zeros.
 __device__ __forceinline__ void wg_stage(const float* xb, float* xs, int cs, int ld, int k0, int w, int p0, int rows, int len) {
     const int c4n = w >> 2;
-    for (int e = threadIdx.x; e < rows * c4n; e += WG_THREADS) {
+    for (int e = threadIdx.x; e < rows * c4n; e += VOC_THREADS) {
         const int i = e / c4n, c = (e - i * c4n) << 2, p = p0 + i;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (p >= 0 && p < len) v = *reinterpret_cast<const float4*>(xb + (size_t)p * ld + k0 + c);
@@ -106,35 +63,35 @@ struct WgUpArgs {
 };
 
 template <int NT>
-__global__ __launch_bounds__(WG_THREADS) void gt_wg_up_kernel(WgUpArgs a) {
+__global__ __launch_bounds__(VOC_THREADS) void gt_wg_up_kernel(WgUpArgs a) {
     extern __shared__ __attribute__((aligned(16))) float wg_lds[];
-    const int b = blockIdx.y, len = wg_row_frames(a.frames, b, a.T), q0 = blockIdx.x * a.tile;
+    const int b = blockIdx.y, len = voc_row_frames(a.frames, b, a.T, 1), q0 = blockIdx.x * a.tile;
     if (q0 >= len) return;
     const int cs = a.mel_p + 4, back = a.taps - 1, rows = a.tile + back;
     const float* xb = a.mel + (size_t)b * a.T * a.mel_dim;
-    for (int e = threadIdx.x; e < rows * a.mel_p; e += WG_THREADS) {        // xs[i] = mel[q0 - back + i], 0 where absent
+    for (int e = threadIdx.x; e < rows * a.mel_p; e += VOC_THREADS) {        // xs[i] = mel[q0 - back + i], 0 where absent
         const int i = e / a.mel_p, c = e - i * a.mel_p, p = q0 - back + i;
         wg_lds[i * cs + c] = (p >= 0 && p < len && c < a.mel_dim) ? xb[(size_t)p * a.mel_dim + c] : 0.f;
     }
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, g = lane >> 4;
-    const int nkb = a.mel_p >> 4, ngroups = (a.mel_p >> 4) / NT, per_phase = (a.tile / WG_ROWS) * ngroups, items = per_phase * a.hop;
+    const int nkb = a.mel_p >> 4, ngroups = (a.mel_p >> 4) / NT, per_phase = (a.tile / VOC_ROWS) * ngroups, items = per_phase * a.hop;
     const int cpf = a.hop / a.G;                            // columns per frame
     const size_t tap_stride = (size_t)a.mel_p * a.mel_p;
     float* sb = a.spect + (size_t)b * a.T * cpf * a.S_p;
-    for (int item = wave; item < items; item += WG_WAVES) {
+    for (int item = wave; item < items; item += VOC_WAVES) {
         const int p = item / per_phase, rest = item - p * per_phase, mg = rest / ngroups, n0 = (rest - mg * ngroups) * NT * 16;
         f32x4 acc[4][NT];
-        wg_bias<NT>(acc, a.b, n0, col);
+        voc_bias<NT>(acc, a.b, n0, col);
         const size_t wl = (size_t)(n0 + col) * 16 + 4 * g;
         for (int j = 0; j < a.taps; ++j)                    // tap p + j hop of frame q - j
-            wg_gemm<NT>(acc, wg_lds + (mg * WG_ROWS + back - j + col) * cs + 4 * g, cs, a.w + (size_t)(p + j * a.hop) * tap_stride + wl, nkb, a.mel_p);
+            voc_gemm<NT>(acc, wg_lds + (mg * VOC_ROWS + back - j + col) * cs + 4 * g, cs, a.w + (size_t)(p + j * a.hop) * tap_stride + wl, nkb, a.mel_p);
         const int lp = p / a.G, gp = p - lp * a.G;
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const int q = q0 + mg * WG_ROWS + mt * 16 + g * 4 + i;
+                const int q = q0 + mg * VOC_ROWS + mt * 16 + g * 4 + i;
                 if (q < len) {
                     float* row = sb + ((size_t)q * cpf + lp) * a.S_p + gp;
 #pragma unroll
@@ -148,7 +105,7 @@ __global__ __launch_bounds__(WG_THREADS) void gt_wg_up_kernel(WgUpArgs a) {
     const int npad = a.S_p - a.S;                           // the padding channels of the tile's columns: exact zeros
     if (npad) {
         const int l0 = q0 * cpf, l1 = min(q0 + a.tile, len) * cpf;
-        for (int e = threadIdx.x; e < (l1 - l0) * npad; e += WG_THREADS) {
+        for (int e = threadIdx.x; e < (l1 - l0) * npad; e += VOC_THREADS) {
             const int i = e / npad;
             sb[(size_t)(l0 + i) * a.S_p + a.S + (e - i * npad)] = 0.f;
         }
@@ -167,9 +124,9 @@ struct WgLayerArgs {
 // (two waves per SIMD: at NT = 8 the 128 accumulators and the fragments fit 256 registers without a spill, and a second workgroup on the
 // CU multiplies while this one stages)
 template <int NT>
-__global__ __launch_bounds__(WG_THREADS, 2) void gt_wg_layer_kernel(WgLayerArgs a) {
+__global__ __launch_bounds__(VOC_THREADS, 2) void gt_wg_layer_kernel(WgLayerArgs a) {
     extern __shared__ __attribute__((aligned(16))) float wg_lds[];
-    const int b = blockIdx.y, len = wg_row_frames(a.frames, b, a.T) * a.cpf, t0 = blockIdx.x * a.tile;
+    const int b = blockIdx.y, len = voc_row_frames(a.frames, b, a.T, 1) * a.cpf, t0 = blockIdx.x * a.tile;
     if (t0 >= len) return;
     const int xcs = a.kc + 4, gcs = a.C_p + 4, n2 = 2 * a.C_p;
     float* xs = wg_lds;                                     // [tile][xcs]: the K chunk in flight
@@ -179,13 +136,13 @@ __global__ __launch_bounds__(WG_THREADS, 2) void gt_wg_layer_kernel(WgLayerArgs 
     const float* sb = a.spect + rowbase * a.S_p;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, g = lane >> 4;
     {
-        const int ngroups = (n2 >> 4) / NT, items = (a.tile / WG_ROWS) * ngroups, passes = (items + WG_WAVES - 1) / WG_WAVES;
+        const int ngroups = (n2 >> 4) / NT, items = (a.tile / VOC_ROWS) * ngroups, passes = (items + VOC_WAVES - 1) / VOC_WAVES;
         for (int pass = 0; pass < passes; ++pass) {
-            const int item = pass * WG_WAVES + wave;
+            const int item = pass * VOC_WAVES + wave;
             const bool active = item < items;
             const int mg = active ? item / ngroups : 0, n0 = active ? (item - mg * ngroups) * NT * 16 : 0;
             f32x4 acc[4][NT];
-            wg_bias<NT>(acc, a.b_ac, n0, col);
+            voc_bias<NT>(acc, a.b_ac, n0, col);
             const size_t wl = (size_t)(n0 + col) * 16 + 4 * g;
             for (int src = 0; src < 4; ++src) {             // the taps at t - d, t, t + d of hid, then spect
                 const float* xb = src < 3 ? hb : sb;
@@ -196,7 +153,7 @@ __global__ __launch_bounds__(WG_THREADS, 2) void gt_wg_layer_kernel(WgLayerArgs 
                     __syncthreads();                        // the chunk before this one has been consumed
                     wg_stage(xb, xs, xcs, ld, k0, w, t0 + shift, a.tile, len);
                     __syncthreads();
-                    if (active) wg_gemm<NT>(acc, xs + (mg * WG_ROWS + col) * xcs + 4 * g, xcs, ws + (size_t)(k0 >> 4) * n2 * 16 + wl, w >> 4, n2);
+                    if (active) voc_gemm<NT>(acc, xs + (mg * VOC_ROWS + col) * xcs + 4 * g, xcs, ws + (size_t)(k0 >> 4) * n2 * 16 + wl, w >> 4, n2);
                 }
             }
             if (active) {
@@ -207,7 +164,7 @@ __global__ __launch_bounds__(WG_THREADS, 2) void gt_wg_layer_kernel(WgLayerArgs 
 #pragma unroll
                         for (int u = 0; u < NT / 2; ++u) {  // N-tile 2 u: tanh half, 2 u + 1: sigmoid half of the same 16 channels
                             const float sg = 1.0f / (1.0f + expf(-acc[mt][2 * u + 1][i]));
-                            gs[(mg * WG_ROWS + mt * 16 + g * 4 + i) * gcs + (n0 >> 1) + u * 16 + col] = gt_tanh(acc[mt][2 * u][i]) * sg;
+                            gs[(mg * VOC_ROWS + mt * 16 + g * 4 + i) * gcs + (n0 >> 1) + u * 16 + col] = gt_tanh(acc[mt][2 * u][i]) * sg;
                         }
             }
         }
@@ -215,19 +172,19 @@ __global__ __launch_bounds__(WG_THREADS, 2) void gt_wg_layer_kernel(WgLayerArgs 
     __syncthreads();
     {
         constexpr int NB = NT / 2;
-        const int nB = a.last ? a.C_p : n2, ngroups = (nB >> 4) / NB, items = (a.tile / WG_ROWS) * ngroups;
+        const int nB = a.last ? a.C_p : n2, ngroups = (nB >> 4) / NB, items = (a.tile / VOC_ROWS) * ngroups;
         float* ho = a.hid_out + rowbase * a.C_p;
         float* ob = a.out + rowbase * a.C_p;
-        for (int item = wave; item < items; item += WG_WAVES) {
+        for (int item = wave; item < items; item += VOC_WAVES) {
             const int mg = item / ngroups, n0 = (item - mg * ngroups) * NB * 16;
             f32x4 acc[4][NB];
-            wg_bias<NB>(acc, a.b_rs, n0, col);
-            wg_gemm<NB>(acc, gs + (mg * WG_ROWS + col) * gcs + 4 * g, gcs, a.w_rs + (size_t)(n0 + col) * 16 + 4 * g, a.C_p >> 4, nB);
+            voc_bias<NB>(acc, a.b_rs, n0, col);
+            voc_gemm<NB>(acc, gs + (mg * VOC_ROWS + col) * gcs + 4 * g, gcs, a.w_rs + (size_t)(n0 + col) * 16 + 4 * g, a.C_p >> 4, nB);
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const int t = t0 + mg * WG_ROWS + mt * 16 + g * 4 + i;
+                    const int t = t0 + mg * VOC_ROWS + mt * 16 + g * 4 + i;
                     if (t < len) {
 #pragma unroll
                         for (int nt = 0; nt < NB; ++nt) {
@@ -267,14 +224,14 @@ __device__ __forceinline__ float wg_z(const WgFlowArgs& a, int b, int l, int gco
     return gt_normal(r.x, r.y);
 }
 
-__global__ __launch_bounds__(WG_THREADS) void gt_wg_flow_kernel(WgFlowArgs a) {
+__global__ __launch_bounds__(VOC_THREADS) void gt_wg_flow_kernel(WgFlowArgs a) {
     extern __shared__ __attribute__((aligned(16))) float wg_lds[];
-    const int b = blockIdx.y, len = wg_row_frames(a.frames, b, a.T) * a.cpf, l0 = blockIdx.x * GT_WG_FLOW_TILE;
+    const int b = blockIdx.y, len = voc_row_frames(a.frames, b, a.T, 1) * a.cpf, l0 = blockIdx.x * GT_WG_FLOW_TILE;
     if (a.wav) {
         float* wb = a.wav + (size_t)b * a.ld_wav;
         if (blockIdx.x == 0 && threadIdx.x == 0 && a.wav_lengths) a.wav_lengths[b] = len * a.G;
         const int n0 = max(l0, len) * a.G, n1 = min((l0 + GT_WG_FLOW_TILE) * a.G, a.ld_wav);        // zeros beyond the row
-        for (int n = n0 + (int)threadIdx.x; n < n1; n += WG_THREADS) wb[n] = 0.f;
+        for (int n = n0 + (int)threadIdx.x; n < n1; n += VOC_THREADS) wb[n] = 0.f;
     }
     if (l0 >= len) return;
     const int xcs = a.C_p + 1, h = a.ck >> 1;
@@ -286,14 +243,14 @@ __global__ __launch_bounds__(WG_THREADS) void gt_wg_flow_kernel(WgFlowArgs a) {
     const size_t rowbase = (size_t)b * a.T * a.cpf;
     if (a.ck) {
         const float* ob = a.out + rowbase * a.C_p;
-        for (int e = threadIdx.x; e < GT_WG_FLOW_TILE * a.C_p; e += WG_THREADS) {
+        for (int e = threadIdx.x; e < GT_WG_FLOW_TILE * a.C_p; e += VOC_THREADS) {
             const int i = e / a.C_p, c = e - i * a.C_p, l = l0 + i;
             xs[i * xcs + c] = l < len ? ob[(size_t)l * a.C_p + c] : 0.f;
         }
-        for (int e = threadIdx.x; e < a.C * 16; e += WG_THREADS) we[e] = a.w_end[e];
+        for (int e = threadIdx.x; e < a.C * 16; e += VOC_THREADS) we[e] = a.w_end[e];
         __syncthreads();
         const int colr = threadIdx.x & (GT_WG_FLOW_TILE - 1);
-        for (int j = threadIdx.x / GT_WG_FLOW_TILE; j < a.ck; j += WG_THREADS / GT_WG_FLOW_TILE) {
+        for (int j = threadIdx.x / GT_WG_FLOW_TILE; j < a.ck; j += VOC_THREADS / GT_WG_FLOW_TILE) {
             float acc = a.b_end[j];
             const float* xr = xs + colr * xcs;
             for (int c = 0; c < a.C; ++c) acc = __builtin_fmaf(xr[c], we[c * 16 + j], acc);
@@ -328,7 +285,7 @@ __global__ __launch_bounds__(WG_THREADS) void gt_wg_flow_kernel(WgFlowArgs a) {
     if (a.wav) return;
     __syncthreads();
     float* hb = a.hid + rowbase * a.C_p;
-    for (int e = threadIdx.x; e < GT_WG_FLOW_TILE * a.C_p; e += WG_THREADS) {        // the next flow's start
+    for (int e = threadIdx.x; e < GT_WG_FLOW_TILE * a.C_p; e += VOC_THREADS) {        // the next flow's start
         const int i = e / a.C_p, n = e - i * a.C_p, l = l0 + i;
         if (l < len) {
             float v = a.b_start[n];
@@ -338,15 +295,13 @@ __global__ __launch_bounds__(WG_THREADS) void gt_wg_flow_kernel(WgFlowArgs a) {
     }
 }
 
-__global__ __launch_bounds__(WG_THREADS) void gt_wg_noise_kernel(const uint64_t* seeds, float* z, int n, int G) {
-    const int b = blockIdx.y, i = blockIdx.x * WG_THREADS + threadIdx.x;
+__global__ __launch_bounds__(VOC_THREADS) void gt_wg_noise_kernel(const uint64_t* seeds, float* z, int n, int G) {
+    const int b = blockIdx.y, i = blockIdx.x * VOC_THREADS + threadIdx.x;
     if (i >= n) return;
     const int l = i / G;
     const Philox4 r = gt_philox(seeds[b], (uint32_t)l, (uint32_t)(i - l * G), 0u, GT_RNG_WAVEGLOW);
     z[(size_t)b * n + i] = gt_normal(r.x, r.y);
 }
-
-int wg_pad16(int c) { return (c + 15) / 16 * 16; }
 
 size_t wg_flow_lds(int C, int C_p) {
     return ((size_t)GT_WG_FLOW_TILE * (3 * WG_OS + C_p + 1) + (size_t)C * 16) * sizeof(float);
@@ -354,7 +309,7 @@ size_t wg_flow_lds(int C, int C_p) {
 
 template <int NT>
 void wg_launch_layer(const WgLayerArgs& a, dim3 grid, size_t lds, hipStream_t stream) {
-    gt_wg_layer_kernel<NT><<<grid, WG_THREADS, lds, stream>>>(a);
+    gt_wg_layer_kernel<NT><<<grid, VOC_THREADS, lds, stream>>>(a);
 }
 
 }  // namespace
@@ -386,7 +341,7 @@ const char* gt_waveglow_make_plan(int mel_dim, int hop, int win, int G, int F, i
     WgPlan& P = *plan;
     P = WgPlan{};
     P.mel_dim = mel_dim; P.hop = hop; P.win = win; P.G = G; P.F = F; P.EE = EE; P.ES = ES; P.NL = NL; P.C = C;
-    P.mel_p = wg_pad16(mel_dim); P.C_p = wg_pad16(C); P.S = mel_dim * G; P.S_p = wg_pad16(P.S);
+    P.mel_p = voc_pad16(mel_dim); P.C_p = voc_pad16(C); P.S = mel_dim * G; P.S_p = voc_pad16(P.S);
     for (int k = 0; k < F; ++k) {
         P.ck[k] = gt_waveglow_flow_channels(G, EE, ES, k);
         if (P.ck[k] < 2) return "n_early_size: fewer than 2 channels remain (n_rem < 2)";
@@ -394,54 +349,51 @@ const char* gt_waveglow_make_plan(int mel_dim, int hop, int win, int G, int F, i
     }
     P.n_rem = P.ck[F - 1];
     static const char* lds_msg = "n_channels: a tile does not fit the 160 KB of LDS";
-    {   // the upsampler: melgan.hip's item form by channel count
-        const int ntiles = P.mel_p / 16;
-        P.up_form = (ntiles % 4 == 0 && ntiles >= 16) ? 4 : (ntiles % 2 == 0 ? 2 : 1);
-        const int ngroups = ntiles / P.up_form;
-        P.up_tile = WG_ROWS * (ngroups >= 4 ? 1 : (ngroups >= 2 ? 2 : 4));
+    {   // the upsampler: the shared item form by channel count
+        voc_tile_form(P.mel_p, &P.up_tile, &P.up_form);
         auto lds = [&]() { return (size_t)(P.up_tile + win / hop - 1) * (P.mel_p + 4) * sizeof(float); };
-        while ((P.up_lds = lds()) > GT_MG_LDS_MAX && P.up_tile > WG_ROWS) P.up_tile >>= 1;
-        if (P.up_lds > GT_MG_LDS_MAX) return "win: the upsampler's tile does not fit the 160 KB of LDS";
+        while ((P.up_lds = lds()) > GT_VOC_LDS_MAX && P.up_tile > VOC_ROWS) P.up_tile >>= 1;
+        if (P.up_lds > GT_VOC_LDS_MAX) return "win: the upsampler's tile does not fit the 160 KB of LDS";
     }
     {   // the WN layer: N-tiles a wave item owns in the gate GEMM (pairs of a tanh and a sigmoid tile), the time tile that gives four
         // waves an item each, and the widest K chunk with which two workgroups share a CU's LDS (else the widest that fits at all)
         const int pairs = P.C_p / 16;
         P.form = pairs % 4 == 0 ? 8 : (pairs % 2 == 0 ? 4 : 2);
         const int ngroups = 2 * pairs / P.form;
-        P.tile = WG_ROWS * (ngroups >= 4 ? 1 : (ngroups >= 2 ? 2 : 4));
+        P.tile = VOC_ROWS * (ngroups >= 4 ? 1 : (ngroups >= 2 ? 2 : 4));
         auto lds = [&](int kc) { return (size_t)P.tile * ((kc + 4) + (P.C_p + 4)) * sizeof(float); };
         P.kc = 0;
         for (int share = 2; share >= 1 && !P.kc; --share)
             for (int kc = 64; kc >= 16 && !P.kc; kc >>= 1)
-                if (lds(kc) * share <= GT_MG_LDS_MAX) P.kc = kc;
+                if (lds(kc) * share <= GT_VOC_LDS_MAX) P.kc = kc;
         if (!P.kc) return lds_msg;
         P.lds = lds(P.kc);
     }
     P.flow_lds = wg_flow_lds(C, P.C_p);
-    if (P.flow_lds > GT_MG_LDS_MAX) return lds_msg;
+    if (P.flow_lds > GT_VOC_LDS_MAX) return lds_msg;
     P.ws_floats_per_column = (size_t)P.S_p + 3 * (size_t)P.C_p + WG_AW;
     return nullptr;
 }
 
 void gt_waveglow_pack_gate(const float* w, int taps, int cin, int C, float* out) {
-    const int C_p = wg_pad16(C), n2 = 2 * C_p;
+    const int C_p = voc_pad16(C), n2 = 2 * C_p;
     std::vector<float> perm((size_t)taps * cin * n2, 0.f);
     for (int r = 0; r < taps * cin; ++r)
         for (int half = 0; half < 2; ++half)
             for (int ch = 0; ch < C; ++ch)
                 perm[(size_t)r * n2 + ((ch >> 4) * 2 + half) * 16 + (ch & 15)] = w[(size_t)r * 2 * C + half * C + ch];
-    gt_melgan_pack(perm.data(), taps, cin, n2, out);
+    voc_pack_f32(perm.data(), taps, cin, n2, out);
 }
 
 void gt_waveglow_gate_bias(const float* b_in, const float* b_cond, int C, float* out) {
-    const int C_p = wg_pad16(C);
+    const int C_p = voc_pad16(C);
     std::fill(out, out + 2 * C_p, 0.f);
     for (int half = 0; half < 2; ++half)
         for (int ch = 0; ch < C; ++ch) out[((ch >> 4) * 2 + half) * 16 + (ch & 15)] = b_in[half * C + ch] + b_cond[half * C + ch];
 }
 
 void gt_waveglow_pack_rs(const float* w, const float* bias, int C, bool last, float* out, float* bias_out) {
-    const int C_p = wg_pad16(C), halves = last ? 1 : 2, nB = halves * C_p;
+    const int C_p = voc_pad16(C), halves = last ? 1 : 2, nB = halves * C_p;
     std::vector<float> perm((size_t)C * nB, 0.f);
     std::fill(bias_out, bias_out + nB, 0.f);
     for (int half = 0; half < halves; ++half)
@@ -449,20 +401,18 @@ void gt_waveglow_pack_rs(const float* w, const float* bias, int C, bool last, fl
             for (int r = 0; r < C; ++r) perm[(size_t)r * nB + half * C_p + ch] = w[(size_t)r * halves * C + half * C + ch];
             bias_out[half * C_p + ch] = bias[half * C + ch];
         }
-    gt_melgan_pack(perm.data(), 1, C, nB, out);
+    voc_pack_f32(perm.data(), 1, C, nB, out);
 }
 
 hipError_t gt_waveglow_prepare() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gt_wg_flow_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, GT_MG_LDS_MAX);
-#define WG_ATTR(K) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, GT_MG_LDS_MAX)
-    WG_ATTR(gt_wg_up_kernel<1>); WG_ATTR(gt_wg_up_kernel<2>); WG_ATTR(gt_wg_up_kernel<4>);
-    WG_ATTR(gt_wg_layer_kernel<2>); WG_ATTR(gt_wg_layer_kernel<4>); WG_ATTR(gt_wg_layer_kernel<8>);
-#undef WG_ATTR
+    hipError_t e = voc_allow_lds(hipSuccess, gt_wg_flow_kernel);
+    e = voc_allow_lds(e, gt_wg_up_kernel<1>); e = voc_allow_lds(e, gt_wg_up_kernel<2>); e = voc_allow_lds(e, gt_wg_up_kernel<4>);
+    e = voc_allow_lds(e, gt_wg_layer_kernel<2>); e = voc_allow_lds(e, gt_wg_layer_kernel<4>); e = voc_allow_lds(e, gt_wg_layer_kernel<8>);
     return e;
 }
 
 hipError_t gt_launch_waveglow_noise(const uint64_t* seeds, float* z, int B, int n, int G, hipStream_t stream) {
-    gt_wg_noise_kernel<<<dim3((n + WG_THREADS - 1) / WG_THREADS, B), WG_THREADS, 0, stream>>>(seeds, z, n, G);
+    gt_wg_noise_kernel<<<dim3((n + VOC_THREADS - 1) / VOC_THREADS, B), VOC_THREADS, 0, stream>>>(seeds, z, n, G);
     return hipGetLastError();
 }
 
@@ -477,9 +427,9 @@ hipError_t gt_launch_waveglow(const WgPlan& P, const WgCall& c, hipStream_t stre
         a.T = c.T; a.mel_dim = P.mel_dim; a.mel_p = P.mel_p; a.hop = P.hop; a.taps = P.win / P.hop; a.G = P.G; a.S = P.S; a.S_p = P.S_p;
         a.tile = P.up_tile;
         const dim3 grid((c.T + P.up_tile - 1) / P.up_tile, c.B);
-        if (P.up_form == 4) gt_wg_up_kernel<4><<<grid, WG_THREADS, P.up_lds, stream>>>(a);
-        else if (P.up_form == 2) gt_wg_up_kernel<2><<<grid, WG_THREADS, P.up_lds, stream>>>(a);
-        else gt_wg_up_kernel<1><<<grid, WG_THREADS, P.up_lds, stream>>>(a);
+        if (P.up_form == 4) gt_wg_up_kernel<4><<<grid, VOC_THREADS, P.up_lds, stream>>>(a);
+        else if (P.up_form == 2) gt_wg_up_kernel<2><<<grid, VOC_THREADS, P.up_lds, stream>>>(a);
+        else gt_wg_up_kernel<1><<<grid, VOC_THREADS, P.up_lds, stream>>>(a);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -504,7 +454,7 @@ hipError_t gt_launch_waveglow(const WgPlan& P, const WgCall& c, hipStream_t stre
             grid.x = (unsigned)(((int64_t)(c.ld_wav + P.G - 1) / P.G + GT_WG_FLOW_TILE - 1) / GT_WG_FLOW_TILE);
         }
         if (!wanted()) return hipSuccess;
-        gt_wg_flow_kernel<<<grid, WG_THREADS, P.flow_lds, stream>>>(a);
+        gt_wg_flow_kernel<<<grid, VOC_THREADS, P.flow_lds, stream>>>(a);
         return hipGetLastError();
     };
     hipError_t e = flow(P.F);

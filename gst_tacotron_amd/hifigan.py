@@ -21,6 +21,9 @@ from typing import List
 
 import numpy as np
 
+from . import vocoder_common
+from .vocoder_common import _np, conv_kernel, fold_weight_norm      # (fold_weight_norm: part of this module's interface)
+
 
 @dataclass
 class HiFiGANConfig:
@@ -157,12 +160,7 @@ def synthetic_weights(cfg, seed=0, gain=1.0):
 
 
 def check_weights(cfg, weights):
-    for name, shape in manifest(cfg).items():
-        if name not in weights:
-            raise KeyError("missing weight '{}'".format(name))
-        got = tuple(np.shape(weights[name]))
-        if got != tuple(shape):
-            raise ValueError("weight '{}' has shape {}, expected {}".format(name, got, tuple(shape)))
+    vocoder_common.check_weights(manifest(cfg), weights)
 
 
 def infer_config(weights, dilations=None, slope=0.1, out_slope=0.01):
@@ -199,19 +197,6 @@ def infer_config(weights, dilations=None, slope=0.1, out_slope=0.01):
                          rates=rates, resblock=resblock, kernels=kernels, dilations=dilations, slope=slope, out_slope=out_slope)
 
 
-def fold_weight_norm(g, v):
-    """``w = g * v / ||v||`` as ``torch.nn.utils.weight_norm(dim=0)`` defines it: the norm runs over every axis but the first, which
-    is the output channel of a Conv1d ([cout, cin, k]) and the INPUT channel of a ConvTranspose1d ([cin, cout, k]).  float64."""
-    v = np.asarray(v, dtype=np.float64)
-    g = np.asarray(g, dtype=np.float64).reshape((v.shape[0],) + (1,) * (v.ndim - 1))
-    norm = np.sqrt((v * v).reshape(v.shape[0], -1).sum(axis=1)).reshape(g.shape)
-    return g * v / norm
-
-
-def _np(t):
-    return np.asarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t)
-
-
 def _layer(sd, prefix):
     """(plain float64 weight, float64 bias) of the layer ``prefix`` in any of the three spellings, or None where it is absent."""
     if prefix + ".weight" in sd:
@@ -237,8 +222,7 @@ def from_state_dict(sd, dtype=np.float32):
     if "generator" in sd and isinstance(sd["generator"], dict):
         sd = sd["generator"]
 
-    def conv(w):            # [cout, cin, k] -> [k * cin, cout]
-        return np.ascontiguousarray(w.transpose(2, 1, 0).reshape(w.shape[2] * w.shape[1], w.shape[0]), dtype=dtype)
+    conv = lambda w: conv_kernel(w, dtype)
 
     pre, post = _layer(sd, "conv_pre"), _layer(sd, "conv_post")
     if pre is None or post is None:
@@ -290,8 +274,5 @@ def from_state_dict(sd, dtype=np.float32):
 def load(path):
     """A generator checkpoint in the public layout (``torch.save`` of its ``state_dict``, bare or under ``"generator"``) -> named,
     folded arrays.  ``state_dict``s only."""
-    import torch
-    sd = torch.load(path, map_location="cpu", weights_only=True)
-    if not isinstance(sd, dict):
-        raise ValueError("'{}' does not hold a state_dict".format(path))
-    return from_state_dict(sd)
+    # (the strict loader of the three: weights_only, and a file without a dict is refused here; "generator" is unwrapped by from_state_dict)
+    return from_state_dict(vocoder_common.load_state_dict(path, weights_only=True, refuse="'{}' does not hold a state_dict"))

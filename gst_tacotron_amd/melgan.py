@@ -15,6 +15,9 @@ from typing import List
 
 import numpy as np
 
+from . import vocoder_common
+from .vocoder_common import _np, conv_kernel, fold_weight_norm      # (fold_weight_norm: part of this module's interface)
+
 
 @dataclass
 class MelGANConfig:
@@ -100,12 +103,7 @@ def synthetic_weights(cfg, seed=0, gain=1.0):
 
 
 def check_weights(cfg, weights):
-    for name, shape in manifest(cfg).items():
-        if name not in weights:
-            raise KeyError("missing weight '{}'".format(name))
-        got = tuple(np.shape(weights[name]))
-        if got != tuple(shape):
-            raise ValueError("weight '{}' has shape {}, expected {}".format(name, got, tuple(shape)))
+    vocoder_common.check_weights(manifest(cfg), weights)
 
 
 def infer_config(weights, slope=0.2):
@@ -118,20 +116,6 @@ def infer_config(weights, slope=0.2):
         n_res += 1
     return MelGANConfig(mel_dim=int(np.shape(weights["melgan/in/kernel"])[0]) // 7, base=int(np.shape(weights["melgan/out/kernel"])[0]) // 7,
                         ratios=ratios, n_res=n_res, slope=slope)
-
-
-def fold_weight_norm(g, v, transposed=False):
-    """``w = g * v / ||v||`` as ``torch.nn.utils.weight_norm(dim=0)`` defines it: the norm runs over every axis but the first, which
-    is the output channel of a Conv1d ([cout, cin, k]) and the INPUT channel of a ConvTranspose1d ([cin, cout, k], ``transposed``).
-    float64 in, float64 out."""
-    v = np.asarray(v, dtype=np.float64)
-    g = np.asarray(g, dtype=np.float64).reshape((v.shape[0],) + (1,) * (v.ndim - 1))
-    norm = np.sqrt((v * v).reshape(v.shape[0], -1).sum(axis=1)).reshape(g.shape)
-    return g * v / norm
-
-
-def _np(t):
-    return np.asarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t)
 
 
 def from_state_dict(sd, dtype=np.float32):
@@ -164,8 +148,7 @@ def from_state_dict(sd, dtype=np.float32):
     if len(seq) < 3:
         raise ValueError("not a MelGAN generator: {} convolutions".format(len(seq)))
 
-    def conv(w):            # [cout, cin, k] -> [k * cin, cout]
-        return np.ascontiguousarray(w.transpose(2, 1, 0).reshape(w.shape[2] * w.shape[1], w.shape[0]), dtype=dtype)
+    conv = lambda w: conv_kernel(w, dtype)
 
     out = {"melgan/in/kernel": conv(seq[0][1]), "melgan/in/bias": seq[0][2].astype(dtype)}
     if seq[0][1].shape[2] != 7 or seq[-1][1].shape[2] != 7 or seq[-1][1].shape[0] != 1:
@@ -198,10 +181,5 @@ def from_state_dict(sd, dtype=np.float32):
 def load(path):
     """A generator checkpoint in the public layout (``torch.save`` of its ``state_dict``, bare or under one of the usual keys)
     -> named, folded arrays."""
-    import torch
-    sd = torch.load(path, map_location="cpu")
-    for key in ("state_dict", "generator", "model_g", "netG", "model"):
-        if isinstance(sd, dict) and key in sd and isinstance(sd[key], dict):
-            sd = sd[key]
-            break
-    return from_state_dict(sd)
+    # (torch.load as torch defaults it, and whatever the file holds goes on to from_state_dict: HiFi-GAN's loader is the strict one)
+    return from_state_dict(vocoder_common.load_state_dict(path, ("state_dict", "generator", "model_g", "netG", "model")))

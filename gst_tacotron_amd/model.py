@@ -942,6 +942,48 @@ class GST_Tacotron:
         if vocoder == "hifigan" and self._hifigan is None:
             raise capi.GstTacoError(-4, "vocoder='hifigan' needs Load_HiFiGAN first")
 
+    def _load_vocoder(self, module, section, prefix, weights_or_path, config, max_frames, hop_message, infer=None, operands=None, check=False):
+        """What the three ``Load_*`` of the vocoders share: ``module`` is melgan / hifigan / waveglow, ``section`` its Hyper_Parameters
+        section, ``prefix`` its name in capi.  ``infer``: the configuration of a set of arrays where ``module.infer_config(weights)``
+        lacks an argument; ``operands``: HiFi-GAN's operand form, set between configure and the weights; ``check``: the configuration
+        has size rules of its own to run first (``cfg.check()``: WaveGlow).  Returns the configuration."""
+        if weights_or_path is None:
+            weights_or_path = (self.hp_Dict.get(section) or {}).get("Checkpoint_Path")
+            if weights_or_path is None:
+                raise ValueError("no weights given and Hyper_Parameters has no {}.Checkpoint_Path".format(section))
+        weights = module.load(weights_or_path) if isinstance(weights_or_path, (str, os.PathLike)) else weights_or_path
+        cfg = config or module.from_hp(self.hp_Dict) or (infer or module.infer_config)(weights)
+        if check:
+            cfg.check()
+        if cfg.mel_dim != self.dims.mel:
+            raise ValueError("the vocoder's mel_dim {} is not Sound.Mel_Dim {}".format(cfg.mel_dim, self.dims.mel))
+        if self.dims.audio and cfg.hop != self.dims.frame_shift:
+            raise ValueError(hop_message.format(cfg.hop, self.dims.frame_shift))
+        module.check_weights(cfg, weights)
+        if not torch.cuda.is_available():
+            raise capi.GstTacoError(-2, "no HIP device: the gfx950 kernels are the only compute path (no CPU fallback)")
+        getattr(self.ctx, prefix + "_configure")(cfg, self.ctx.cfg.max_batch, int(max_frames or self.dims.max_step))
+        if operands is not None:
+            self.ctx.hifigan_set_operands(operands)
+        getattr(self.ctx, prefix + "_load_weights")(weights)
+        with torch.cuda.device(self.device):
+            getattr(self.ctx, prefix + "_finalize")()
+        return cfg
+
+    def _vocoder_io(self, cfg, mels, mel_lengths):
+        """The mel check and the outputs of the three synthesis methods: (x, frames or None, B, T, ld, wav [B, ld], lengths [B])"""
+        x = self._dev(mels, torch.float32)
+        if x.dim() != 3 or x.shape[2] != cfg.mel_dim or x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError("mels must be [batch, frames >= 1, Mel_Dim]")
+        B, T = int(x.shape[0]), int(x.shape[1])
+        fr = self._dev(mel_lengths, torch.int32)
+        if fr is not None and tuple(fr.shape) != (B,):
+            raise ValueError("mel_lengths must be [batch]")
+        ld = T * cfg.hop
+        wav = torch.empty((B, ld), dtype=torch.float32, device=self.device)
+        lens = torch.empty((B,), dtype=torch.int32, device=self.device)
+        return x, fr, B, T, ld, wav, lens
+
     def Load_Neural_Vocoder(self, weights_or_path=None, config=None, max_frames=None):
         """Extension: loads the MelGAN generator (``gsttaco_melgan_*``, gst_tacotron_amd.melgan) into this model's context, once.
         ``weights_or_path``: named folded arrays (``melgan.synthetic_weights`` / ``melgan.from_state_dict``) or the path of a
@@ -950,24 +992,8 @@ class GST_Tacotron:
         bring (default Max_Step); the batch capacity is the model's.  Its Mel_Dim must be the model's and, where the Sound section
         is complete, its hop Sound.Frame_Shift."""
         from . import melgan
-        if weights_or_path is None:
-            weights_or_path = (self.hp_Dict.get("Vocoder_MelGAN") or {}).get("Checkpoint_Path")
-            if weights_or_path is None:
-                raise ValueError("no weights given and Hyper_Parameters has no Vocoder_MelGAN.Checkpoint_Path")
-        weights = melgan.load(weights_or_path) if isinstance(weights_or_path, (str, os.PathLike)) else weights_or_path
-        cfg = config or melgan.from_hp(self.hp_Dict) or melgan.infer_config(weights)
-        if cfg.mel_dim != self.dims.mel:
-            raise ValueError("the vocoder's mel_dim {} is not Sound.Mel_Dim {}".format(cfg.mel_dim, self.dims.mel))
-        if self.dims.audio and cfg.hop != self.dims.frame_shift:
-            raise ValueError("the vocoder's ratios multiply to {}, Sound.Frame_Shift is {}".format(cfg.hop, self.dims.frame_shift))
-        melgan.check_weights(cfg, weights)
-        if not torch.cuda.is_available():
-            raise capi.GstTacoError(-2, "no HIP device: the gfx950 kernels are the only compute path (no CPU fallback)")
-        self.ctx.melgan_configure(cfg, self.ctx.cfg.max_batch, int(max_frames or self.dims.max_step))
-        self.ctx.melgan_load_weights(weights)
-        with torch.cuda.device(self.device):
-            self.ctx.melgan_finalize()
-        self._melgan = cfg
+        self._melgan = self._load_vocoder(melgan, "Vocoder_MelGAN", "melgan", weights_or_path, config, max_frames,
+                                          "the vocoder's ratios multiply to {}, Sound.Frame_Shift is {}")
         return self
 
     def Neural_Vocoder(self, mels, mel_lengths=None):
@@ -978,16 +1004,7 @@ class GST_Tacotron:
         ``wav_lengths[b] = mel_lengths[b] * hop``; rows shorter than the vocoder's ``min_frames`` come out with length 0."""
         if self._melgan is None:
             raise capi.GstTacoError(-4, "no neural vocoder loaded (call Load_Neural_Vocoder first)")
-        x = self._dev(mels, torch.float32)
-        if x.dim() != 3 or x.shape[2] != self._melgan.mel_dim or x.shape[0] < 1 or x.shape[1] < 1:
-            raise ValueError("mels must be [batch, frames >= 1, Mel_Dim]")
-        B, T = int(x.shape[0]), int(x.shape[1])
-        fr = self._dev(mel_lengths, torch.int32)
-        if fr is not None and tuple(fr.shape) != (B,):
-            raise ValueError("mel_lengths must be [batch]")
-        ld = T * self._melgan.hop
-        wav = torch.empty((B, ld), dtype=torch.float32, device=self.device)
-        lens = torch.empty((B,), dtype=torch.int32, device=self.device)
+        x, fr, B, T, ld, wav, lens = self._vocoder_io(self._melgan, mels, mel_lengths)
         with torch.cuda.device(self.device):
             self.ctx.check(self.ctx.lib.gsttaco_melgan(self.ctx.handle, _ptr(x), _ptr(fr), B, T, _ptr(wav), _ptr(lens), ld, self._stream()))
         return wav, lens
@@ -1007,26 +1024,9 @@ class GST_Tacotron:
         ``Export_Inference`` use whatever was loaded; their outputs are float32 in [-1, 1] in every form."""
         from . import hifigan
         precision = hifigan.precision_from_hp(self.hp_Dict) if precision is None else hifigan.check_precision(precision)
-        if weights_or_path is None:
-            weights_or_path = (self.hp_Dict.get("Vocoder_HiFiGAN") or {}).get("Checkpoint_Path")
-            if weights_or_path is None:
-                raise ValueError("no weights given and Hyper_Parameters has no Vocoder_HiFiGAN.Checkpoint_Path")
-        weights = hifigan.load(weights_or_path) if isinstance(weights_or_path, (str, os.PathLike)) else weights_or_path
-        cfg = config or hifigan.from_hp(self.hp_Dict) or hifigan.infer_config(weights)
-        if cfg.mel_dim != self.dims.mel:
-            raise ValueError("the vocoder's mel_dim {} is not Sound.Mel_Dim {}".format(cfg.mel_dim, self.dims.mel))
-        if self.dims.audio and cfg.hop != self.dims.frame_shift:
-            raise ValueError("the vocoder's rates multiply to {}, Sound.Frame_Shift is {}".format(cfg.hop, self.dims.frame_shift))
-        hifigan.check_weights(cfg, weights)
-        if not torch.cuda.is_available():
-            raise capi.GstTacoError(-2, "no HIP device: the gfx950 kernels are the only compute path (no CPU fallback)")
-        self.ctx.hifigan_configure(cfg, self.ctx.cfg.max_batch, int(max_frames or self.dims.max_step))
-        if precision != "float32":
-            self.ctx.hifigan_set_operands(precision)
-        self.ctx.hifigan_load_weights(weights)
-        with torch.cuda.device(self.device):
-            self.ctx.hifigan_finalize()
-        self._hifigan = cfg
+        self._hifigan = self._load_vocoder(hifigan, "Vocoder_HiFiGAN", "hifigan", weights_or_path, config, max_frames,
+                                           "the vocoder's rates multiply to {}, Sound.Frame_Shift is {}",
+                                           operands=None if precision == "float32" else precision)
         self._hifigan_precision = precision
         return self
 
@@ -1038,16 +1038,7 @@ class GST_Tacotron:
         ``wav_lengths[b] = mel_lengths[b] * hop``; one frame is enough, a row of 0 frames comes out with length 0."""
         if self._hifigan is None:
             raise capi.GstTacoError(-4, "no HiFi-GAN loaded (call Load_HiFiGAN first)")
-        x = self._dev(mels, torch.float32)
-        if x.dim() != 3 or x.shape[2] != self._hifigan.mel_dim or x.shape[0] < 1 or x.shape[1] < 1:
-            raise ValueError("mels must be [batch, frames >= 1, Mel_Dim]")
-        B, T = int(x.shape[0]), int(x.shape[1])
-        fr = self._dev(mel_lengths, torch.int32)
-        if fr is not None and tuple(fr.shape) != (B,):
-            raise ValueError("mel_lengths must be [batch]")
-        ld = T * self._hifigan.hop
-        wav = torch.empty((B, ld), dtype=torch.float32, device=self.device)
-        lens = torch.empty((B,), dtype=torch.int32, device=self.device)
+        x, fr, B, T, ld, wav, lens = self._vocoder_io(self._hifigan, mels, mel_lengths)
         with torch.cuda.device(self.device):
             self.ctx.check(self.ctx.lib.gsttaco_hifigan(self.ctx.handle, _ptr(x), _ptr(fr), B, T, _ptr(wav), _ptr(lens), ld, self._stream()))
         return wav, lens
@@ -1061,25 +1052,9 @@ class GST_Tacotron:
         call may bring (default Max_Step); the batch capacity is the model's.  Its Mel_Dim must be the model's and, where the Sound
         section is complete, its hop Sound.Frame_Shift."""
         from . import waveglow
-        if weights_or_path is None:
-            weights_or_path = (self.hp_Dict.get("Vocoder_WaveGlow") or {}).get("Checkpoint_Path")
-            if weights_or_path is None:
-                raise ValueError("no weights given and Hyper_Parameters has no Vocoder_WaveGlow.Checkpoint_Path")
-        weights = waveglow.load(weights_or_path) if isinstance(weights_or_path, (str, os.PathLike)) else weights_or_path
-        cfg = config or waveglow.from_hp(self.hp_Dict) or waveglow.infer_config(weights, hop=int(self.hp_Dict["Sound"]["Frame_Shift"]))
-        cfg.check()
-        if cfg.mel_dim != self.dims.mel:
-            raise ValueError("the vocoder's mel_dim {} is not Sound.Mel_Dim {}".format(cfg.mel_dim, self.dims.mel))
-        if self.dims.audio and cfg.hop != self.dims.frame_shift:
-            raise ValueError("the vocoder's hop {} is not Sound.Frame_Shift {}".format(cfg.hop, self.dims.frame_shift))
-        waveglow.check_weights(cfg, weights)
-        if not torch.cuda.is_available():
-            raise capi.GstTacoError(-2, "no HIP device: the gfx950 kernels are the only compute path (no CPU fallback)")
-        self.ctx.waveglow_configure(cfg, self.ctx.cfg.max_batch, int(max_frames or self.dims.max_step))
-        self.ctx.waveglow_load_weights(weights)
-        with torch.cuda.device(self.device):
-            self.ctx.waveglow_finalize()
-        self._waveglow = cfg
+        self._waveglow = self._load_vocoder(waveglow, "Vocoder_WaveGlow", "waveglow", weights_or_path, config, max_frames,
+                                            "the vocoder's hop {} is not Sound.Frame_Shift {}",
+                                            infer=lambda w: waveglow.infer_config(w, hop=int(self.hp_Dict["Sound"]["Frame_Shift"])), check=True)
         return self
 
     def WaveGlow(self, mels, mel_lengths=None, sigma=0.6, seeds=None, z=None):
@@ -1094,14 +1069,7 @@ class GST_Tacotron:
             raise capi.GstTacoError(-4, "no flow vocoder loaded (call Load_WaveGlow first)")
         if seeds is not None and z is not None:
             raise ValueError("seeds and z are mutually exclusive")
-        x = self._dev(mels, torch.float32)
-        if x.dim() != 3 or x.shape[2] != self._waveglow.mel_dim or x.shape[0] < 1 or x.shape[1] < 1:
-            raise ValueError("mels must be [batch, frames >= 1, Mel_Dim]")
-        B, T = int(x.shape[0]), int(x.shape[1])
-        fr = self._dev(mel_lengths, torch.int32)
-        if fr is not None and tuple(fr.shape) != (B,):
-            raise ValueError("mel_lengths must be [batch]")
-        ld = T * self._waveglow.hop
+        x, fr, B, T, ld, wav, lens = self._vocoder_io(self._waveglow, mels, mel_lengths)
         dev_seeds = None
         if z is not None:
             z = self._dev(z, torch.float32)
@@ -1116,8 +1084,6 @@ class GST_Tacotron:
             if np.ndim(seeds) != 1 or len(vals) != B:
                 raise ValueError("seeds must be [batch]")
             dev_seeds = torch.from_numpy(np.array(vals, dtype=np.uint64).view(np.int64)).to(self.device)      # (the same 64 bits)
-        wav = torch.empty((B, ld), dtype=torch.float32, device=self.device)
-        lens = torch.empty((B,), dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
             self.ctx.check(self.ctx.lib.gsttaco_waveglow(self.ctx.handle, _ptr(x), _ptr(fr), B, T, ctypes.c_float(float(sigma)),
                                                          _ptr(dev_seeds), _ptr(z), _ptr(wav), _ptr(lens), ld, self._stream()))

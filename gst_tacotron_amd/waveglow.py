@@ -14,7 +14,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .melgan import fold_weight_norm
+from . import vocoder_common
+from .vocoder_common import _np, conv_kernel, fold_weight_norm
 
 MAX_LAYERS, MAX_FLOWS, MAX_GROUP = 10, 32, 16
 _SIZES = ("mel_dim", "hop", "win", "n_group", "n_flows", "n_early_every", "n_early_size", "n_layers", "n_channels")
@@ -143,12 +144,7 @@ def synthetic_weights(cfg, seed=0, gain_s=0.25):
 
 
 def check_weights(cfg, weights):
-    for name, shape in manifest(cfg).items():
-        if name not in weights:
-            raise KeyError("missing weight '{}'".format(name))
-        got = tuple(np.shape(weights[name]))
-        if got != tuple(shape):
-            raise ValueError("weight '{}' has shape {}, expected {}".format(name, got, tuple(shape)))
+    vocoder_common.check_weights(manifest(cfg), weights)
 
 
 def infer_config(weights, hop=256):
@@ -167,10 +163,6 @@ def infer_config(weights, hop=256):
                           n_early_size=size, n_layers=n_layers, n_channels=sh("waveglow/flow0/start/kernel")[1])
 
 
-def _np(t):
-    return np.asarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t)
-
-
 def from_state_dict(sd, dtype=np.float32):
     """The project's named, folded arrays of a public-layout WaveGlow ``state_dict``:
     ``upsample.weight`` [mel, mel, win] and ``upsample.bias``; per flow k ``WN.<k>.start``, ``WN.<k>.in_layers.<i>``,
@@ -187,8 +179,7 @@ def from_state_dict(sd, dtype=np.float32):
             return fold_weight_norm(sd[prefix + ".weight_g"], sd[prefix + ".weight_v"])
         raise KeyError("layer '{}' has neither weight nor weight_g / weight_v".format(prefix))
 
-    def conv(w):            # [cout, cin, k] -> [k * cin, cout]
-        return np.ascontiguousarray(w.transpose(2, 1, 0).reshape(w.shape[2] * w.shape[1], w.shape[0]), dtype=dtype)
+    conv = lambda w: conv_kernel(w, dtype)
 
     def bias(prefix):
         return np.asarray(sd[prefix + ".bias"], dtype=np.float64).astype(dtype)
@@ -237,12 +228,6 @@ def from_state_dict(sd, dtype=np.float32):
 def load(path):
     """A checkpoint file that holds a WaveGlow ``state_dict`` in the public layout (``torch.save`` of it, bare or under one of the
     usual keys) -> named, folded arrays.  A file that pickles the model object itself is refused: only ``state_dict``s are read."""
-    import torch
-    sd = torch.load(path, map_location="cpu")
-    for key in ("state_dict", "model", "waveglow"):
-        if isinstance(sd, dict) and key in sd and isinstance(sd[key], dict):
-            sd = sd[key]
-            break
-    if not isinstance(sd, dict):
-        raise ValueError("'{}' does not hold a state_dict (only state_dicts are read)".format(path))
-    return from_state_dict(sd)
+    # (torch.load as torch defaults it, as MelGAN's loader; unlike it, a file without a dict is refused here)
+    return from_state_dict(vocoder_common.load_state_dict(path, ("state_dict", "model", "waveglow"),
+                                                          refuse="'{}' does not hold a state_dict (only state_dicts are read)"))

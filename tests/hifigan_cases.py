@@ -9,36 +9,13 @@ from dataclasses import dataclass
 import numpy as np
 
 from gst_tacotron_amd import hifigan
+from vocoder_cases import _conv, _leaky, _pad16, _transposed, tile_edge_frames, tile_form      # noqa: F401
 
 MAX_ABS_MEL = 4.0
 E32_MAX = 2.0 ** -14            # a case whose float32 run strays further from float64 is ill-conditioned: changed, not excused
 
 
 # ---------------------------------------------------------------------------------------------------- the restatement
-def _leaky(x, slope):
-    return np.where(x > 0, x, x * slope)
-
-
-def _conv(x, w, b, taps, dil):
-    """x [L, cin], w [taps * cin, cout] -> [L, cout]: zero padding (taps - 1) / 2 * dil each side"""
-    cin = w.shape[0] // taps
-    L, p = x.shape[0], (taps - 1) // 2 * dil
-    xp = np.pad(x, ((p, p), (0, 0)))
-    y = np.tile(b[None, :], (L, 1))
-    for k in range(taps):
-        y = y + xp[k * dil:k * dil + L] @ w[k * cin:(k + 1) * cin]
-    return y
-
-
-def _transposed(x, w, b, r):
-    """x [L, cin], w [2r, cin, cout]: output o = i r - r/2 + k, cropped to [0, r L): two taps per sample, nothing beyond the ends"""
-    L = x.shape[0]
-    full = np.zeros(((L + 1) * r, w.shape[2]), dtype=x.dtype)
-    for k in range(2 * r):
-        full[k:k + (L - 1) * r + 1:r] += x @ w[k]
-    return full[r // 2:r // 2 + r * L] + b[None, :]
-
-
 def hifigan_row(cfg, w, x):
     """One row alone: x [frames >= 1, mel_dim] -> [frames * hop]; the dtype is x's (the weights are cast to it)."""
     dt = x.dtype
@@ -80,19 +57,10 @@ def hifigan_reference(cfg, weights, mel, frames=None, dtype=np.float64):
 
 
 # ---------------------------------------------------------------------------------------------------- the plan's constants
-def _pad16(c):
-    return (c + 15) // 16 * 16
-
-
 def plan_tiles(cfg):
     """What gsttaco_hifigan_plan reports as (kind, channels, taps, dilation, tile, form, rate) per launch at sizes whose tiles fit the
     LDS unshrunk (every case here): one launch per convolution; the N-tiles a wave item owns by padded channel count, and the time
     tile that gives four waves an item each."""
-    def tile_form(n_p):
-        ntiles = n_p // 16
-        nt = 4 if ntiles % 4 == 0 and ntiles >= 16 else (2 if ntiles % 2 == 0 else 1)
-        ngroups = ntiles // nt
-        return 64 * (1 if ngroups >= 4 else 2 if ngroups >= 2 else 4), nt
     ch, rate = cfg.channels(), 1
     out = [("in", ch[0], 7, 1) + tile_form(_pad16(ch[0])) + (1,)]
     for i, r in enumerate(cfg.rates):
@@ -106,18 +74,6 @@ def plan_tiles(cfg):
                     out.append(("conv", ch[i + 1], k, 1) + tf + (rate,))
     out.append(("out", 1, 7, 1, 256, 0, rate))
     return out
-
-
-def tile_edge_frames(tiles):
-    """One, zero and one more frame around the first and second multiple of each launch's time tile that a whole frame count
-    reaches."""
-    frames = set()
-    for *_, tile, _, rate in tiles:
-        for m in (1, 2):
-            if (m * tile) % rate == 0:
-                f = m * tile // rate
-                frames.update(v for v in (f - 1, f, f + 1) if v >= 1)
-    return sorted(frames)
 
 
 # ---------------------------------------------------------------------------------------------------- the cases

@@ -9,37 +9,22 @@ from dataclasses import dataclass
 import numpy as np
 
 from gst_tacotron_amd import melgan
+from vocoder_cases import _leaky, _pad16, _reflect, _transposed, tile_edge_frames, tile_form      # noqa: F401
 
 MAX_ABS_MEL = 4.0
 E32_MAX = 2.0 ** -14            # a case whose float32 run strays further from float64 is ill-conditioned: changed, not excused
 
 
 # ---------------------------------------------------------------------------------------------------- the restatement
-def _leaky(x, slope):
-    return np.where(x > 0, x, x * slope)
-
-
 def _conv(x, w, b, taps, dil):
-    """x [L + (taps - 1) dil, cin] (already padded), w [taps * cin, cout] -> [L, cout]"""
+    """x [L + (taps - 1) dil, cin] (already padded: MelGAN reflects, so this is not vocoder_cases._conv, which pads with zeros),
+    w [taps * cin, cout] -> [L, cout]"""
     cin = w.shape[0] // taps
     L = x.shape[0] - (taps - 1) * dil
     y = np.tile(b[None, :], (L, 1))
     for k in range(taps):
         y = y + x[k * dil:k * dil + L] @ w[k * cin:(k + 1) * cin]
     return y
-
-
-def _reflect(x, p):
-    return np.pad(x, ((p, p), (0, 0)), mode="reflect")
-
-
-def _transposed(x, w, b, r):
-    """x [L, cin], w [2r, cin, cout]: output o = i r - r/2 + k, cropped to [0, r L): two taps per sample, nothing beyond the ends"""
-    L = x.shape[0]
-    full = np.zeros(((L + 1) * r, w.shape[2]), dtype=x.dtype)
-    for k in range(2 * r):
-        full[k:k + (L - 1) * r + 1:r] += x @ w[k]
-    return full[r // 2:r // 2 + r * L] + b[None, :]
 
 
 def melgan_row(cfg, w, x):
@@ -77,18 +62,9 @@ def melgan_reference(cfg, weights, mel, frames=None, dtype=np.float64):
 
 
 # ---------------------------------------------------------------------------------------------------- the plan's constants
-def _pad16(c):
-    return (c + 15) // 16 * 16
-
-
 def plan_tiles(cfg):
     """What gsttaco_melgan_plan reports as (kind, channels, tile, form, rate) per launch at sizes whose tiles fit the LDS unshrunk
     (every case here): the N-tiles a wave item owns by padded channel count, and the time tile that gives four waves an item each."""
-    def tile_form(n_p):
-        ntiles = n_p // 16
-        nt = 4 if ntiles % 4 == 0 and ntiles >= 16 else (2 if ntiles % 2 == 0 else 1)
-        ngroups = ntiles // nt
-        return 64 * (1 if ngroups >= 4 else 2 if ngroups >= 2 else 4), nt
     ch, rate = cfg.channels(), 1
     out = [("in", ch[0]) + tile_form(_pad16(ch[0])) + (1,)]
     for i, r in enumerate(cfg.ratios):
@@ -98,18 +74,6 @@ def plan_tiles(cfg):
         out += [("res", ch[i + 1]) + tf + (rate,)] * cfg.n_res
     out.append(("out", 1, 256, 0, rate))
     return out
-
-
-def tile_edge_frames(tiles, min_frames):
-    """One, zero and one more frame around the first and second multiple of each launch's time tile that a whole frame count
-    reaches; the short ones stay in (they must come out empty)."""
-    frames = set()
-    for _, _, tile, _, rate in tiles:
-        for m in (1, 2):
-            if (m * tile) % rate == 0:
-                f = m * tile // rate
-                frames.update(v for v in (f - 1, f, f + 1) if v >= 1)
-    return sorted(frames)
 
 
 # ---------------------------------------------------------------------------------------------------- the cases

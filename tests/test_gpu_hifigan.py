@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import hifigan_cases as M
+from vocoder_harness import Vocoder
 from gst_tacotron_amd import capi, hifigan, melgan, synthetic
 
 pytestmark = pytest.mark.gpu
@@ -23,38 +24,9 @@ K = 8
 _VOCODERS = {}
 
 
-class _Vocoder:
+def _Vocoder(cfg, weights, max_batch, max_frames, finalize=True):
     """A context that holds nothing but a finalized HiFi-GAN."""
-
-    def __init__(self, cfg, weights, max_batch, max_frames, finalize=True):
-        self.cfg = cfg
-        self.ctx = capi.Context(synthetic.tiny_hp(), max_batch=2, max_tokens=8, max_ref_frames=4)
-        self.ctx.hifigan_configure(cfg, max_batch, max_frames)
-        self.ctx.hifigan_load_weights(weights)
-        if finalize:
-            self.ctx.hifigan_finalize()
-
-    def raw(self, x, fr, B, T, wav, lens, ld, stream=None):
-        import torch
-        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-        s = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
-        return self.ctx.lib.gsttaco_hifigan(self.ctx.handle, p(x), p(fr), B, T, p(wav), p(lens), ld, s)
-
-    def __call__(self, mel, frames=None, ld=None):
-        """(wav [B, ld], lengths [B]) as host arrays; the outputs start as NaN / -1, so what the call leaves unwritten shows"""
-        import torch
-        x = torch.as_tensor(np.ascontiguousarray(mel, dtype=np.float32)).cuda()
-        B, T = x.shape[:2]
-        fr = None if frames is None else torch.as_tensor(np.asarray(frames, dtype=np.int32)).cuda()
-        ld = T * self.cfg.hop if ld is None else ld
-        wav = torch.full((B, ld), float("nan"), dtype=torch.float32, device="cuda")
-        lens = torch.full((B,), -1, dtype=torch.int32, device="cuda")
-        self.ctx.check(self.raw(x, fr, B, T, wav, lens, ld))
-        torch.cuda.synchronize()
-        return wav.cpu().numpy(), lens.cpu().numpy()
-
-    def close(self):
-        self.ctx.close()
+    return Vocoder("hifigan", cfg, weights, max_batch, max_frames, finalize)
 
 
 @pytest.fixture(scope="module", autouse=True)

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import waveglow_cases as M
+from vocoder_harness import Vocoder, seeds_tensor as _seeds
 from gst_tacotron_amd import capi, melgan, synthetic, waveglow
 from oracle import rng_np
 
@@ -31,54 +32,9 @@ NOISE_TOL = 4 * NOISE_ERR_MEASURED
 _VOCODERS = {}
 
 
-def _seeds(vals):
-    import torch
-    return torch.from_numpy(np.array([int(v) & (2 ** 64 - 1) for v in vals], dtype=np.uint64).view(np.int64)).cuda()
-
-
-class _Vocoder:
+def _Vocoder(cfg, weights, max_batch, max_frames, finalize=True):
     """A context that holds nothing but a finalized flow vocoder."""
-
-    def __init__(self, cfg, weights, max_batch, max_frames, finalize=True):
-        self.cfg = cfg
-        self.ctx = capi.Context(synthetic.tiny_hp(), max_batch=2, max_tokens=8, max_ref_frames=4)
-        self.ctx.waveglow_configure(cfg, max_batch, max_frames)
-        self.ctx.waveglow_load_weights(weights)
-        if finalize:
-            self.ctx.waveglow_finalize()
-
-    def raw(self, x, fr, B, T, sigma, seeds, z, wav, lens, ld, stream=None):
-        import torch
-        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-        s = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
-        return self.ctx.lib.gsttaco_waveglow(self.ctx.handle, p(x), p(fr), B, T, ctypes.c_float(sigma), p(seeds), p(z), p(wav), p(lens), ld, s)
-
-    def noise(self, seeds, T):
-        import torch
-        sd = _seeds(seeds)
-        z = torch.full((len(seeds), T * self.cfg.hop), float("nan"), dtype=torch.float32, device="cuda")
-        s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        self.ctx.check(self.ctx.lib.gsttaco_waveglow_noise(self.ctx.handle, ctypes.c_void_p(sd.data_ptr()), len(seeds), T, ctypes.c_void_p(z.data_ptr()), s))
-        torch.cuda.synchronize()
-        return z.cpu().numpy()
-
-    def __call__(self, mel, frames=None, z=None, seeds=None, sigma=0.6, ld=None):
-        """(wav [B, ld], lengths [B]) as host arrays; the outputs start as NaN / -1, so what the call leaves unwritten shows"""
-        import torch
-        x = torch.as_tensor(np.ascontiguousarray(mel, dtype=np.float32)).cuda()
-        B, T = x.shape[:2]
-        fr = None if frames is None else torch.as_tensor(np.asarray(frames, dtype=np.int32)).cuda()
-        zd = None if z is None else torch.as_tensor(np.ascontiguousarray(z, dtype=np.float32)).cuda()
-        sd = None if seeds is None else _seeds(seeds)
-        ld = T * self.cfg.hop if ld is None else ld
-        wav = torch.full((B, ld), float("nan"), dtype=torch.float32, device="cuda")
-        lens = torch.full((B,), -1, dtype=torch.int32, device="cuda")
-        self.ctx.check(self.raw(x, fr, B, T, sigma, sd, zd, wav, lens, ld))
-        torch.cuda.synchronize()
-        return wav.cpu().numpy(), lens.cpu().numpy()
-
-    def close(self):
-        self.ctx.close()
+    return Vocoder("waveglow", cfg, weights, max_batch, max_frames, finalize)
 
 
 @pytest.fixture(scope="module", autouse=True)

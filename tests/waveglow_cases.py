@@ -9,25 +9,13 @@ from dataclasses import dataclass
 import numpy as np
 
 from gst_tacotron_amd import waveglow
+from vocoder_cases import _conv as _conv_same     # (every WaveGlow conv has an odd tap count: 3 or 1)
 
 MAX_ABS_MEL = 4.0
 E32_MAX = 2.0 ** -14            # a case whose float32 run strays further from float64 is ill-conditioned: changed, not excused
 
 
 # ---------------------------------------------------------------------------------------------------- the restatement
-def _conv_same(x, w, b, taps, dil):
-    """x [L, cin], w [taps * cin, cout], zero padding (taps // 2) * dil each side -> [L, cout]"""
-    cin = w.shape[0] // taps
-    L = x.shape[0]
-    pad = (taps // 2) * dil
-    xp = np.zeros((L + 2 * pad, cin), dtype=x.dtype)
-    xp[pad:pad + L] = x
-    y = np.tile(b[None, :], (L, 1))
-    for k in range(taps):
-        y = y + xp[k * dil:k * dil + L] @ w[k * cin:(k + 1) * cin]
-    return y
-
-
 def _upsample(x, w, b, hop):
     """x [n, mel], w [win, mel, mel]: sample q hop + p sums taps p + j hop of frames q - j; cropped to n hop samples"""
     n, mel = x.shape
