@@ -9,7 +9,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from gst_tacotron_amd import hifigan
-from vocoder_cases import _conv, _leaky, _pad16, _transposed, tile_edge_frames, tile_form      # noqa: F401
+from vocoder_cases import _conv, _leaky, _pad16, _transposed, hifigan_plan_rule, tile_edge_frames, tile_form      # noqa: F401
 
 MAX_ABS_MEL = 4.0
 E32_MAX = 2.0 ** -14            # a case whose float32 run strays further from float64 is ill-conditioned: changed, not excused
@@ -58,22 +58,10 @@ def hifigan_reference(cfg, weights, mel, frames=None, dtype=np.float64):
 
 # ---------------------------------------------------------------------------------------------------- the plan's constants
 def plan_tiles(cfg):
-    """What gsttaco_hifigan_plan reports as (kind, channels, taps, dilation, tile, form, rate) per launch at sizes whose tiles fit the
-    LDS unshrunk (every case here): one launch per convolution; the N-tiles a wave item owns by padded channel count, and the time
-    tile that gives four waves an item each."""
-    ch, rate = cfg.channels(), 1
-    out = [("in", ch[0], 7, 1) + tile_form(_pad16(ch[0])) + (1,)]
-    for i, r in enumerate(cfg.rates):
-        tf = tile_form(_pad16(ch[i + 1]))
-        out.append(("up", ch[i + 1], 2 * r, 1) + tf + (rate,))
-        rate *= r
-        for k, dils in zip(cfg.kernels, cfg.dilations):
-            for d in dils:
-                out.append(("conv", ch[i + 1], k, d) + tf + (rate,))
-                if cfg.resblock == 1:
-                    out.append(("conv", ch[i + 1], k, 1) + tf + (rate,))
-    out.append(("out", 1, 7, 1, 256, 0, rate))
-    return out
+    """What gsttaco_hifigan_plan reports as (kind, channels, taps, dilation, tile, form, rate) per launch: one launch per convolution;
+    the N-tiles a wave item owns by padded channel count, and the time tile that gives four waves an item each, halved while the
+    launch's LDS does not fit (vocoder_cases.hifigan_plan_rule)."""
+    return [(s["kind"], s["channels"], s["taps"], s["dilation"], s["tile"], s["form"], s["rate"]) for s in hifigan_plan_rule(cfg)]
 
 
 # ---------------------------------------------------------------------------------------------------- the cases

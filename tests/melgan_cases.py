@@ -9,7 +9,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from gst_tacotron_amd import melgan
-from vocoder_cases import _leaky, _pad16, _reflect, _transposed, tile_edge_frames, tile_form      # noqa: F401
+from vocoder_cases import _leaky, _pad16, _reflect, _transposed, melgan_plan_rule, tile_edge_frames, tile_form      # noqa: F401
 
 MAX_ABS_MEL = 4.0
 E32_MAX = 2.0 ** -14            # a case whose float32 run strays further from float64 is ill-conditioned: changed, not excused
@@ -63,17 +63,10 @@ def melgan_reference(cfg, weights, mel, frames=None, dtype=np.float64):
 
 # ---------------------------------------------------------------------------------------------------- the plan's constants
 def plan_tiles(cfg):
-    """What gsttaco_melgan_plan reports as (kind, channels, tile, form, rate) per launch at sizes whose tiles fit the LDS unshrunk
-    (every case here): the N-tiles a wave item owns by padded channel count, and the time tile that gives four waves an item each."""
-    ch, rate = cfg.channels(), 1
-    out = [("in", ch[0]) + tile_form(_pad16(ch[0])) + (1,)]
-    for i, r in enumerate(cfg.ratios):
-        tf = tile_form(_pad16(ch[i + 1]))
-        out.append(("up", ch[i + 1]) + tf + (rate,))
-        rate *= r
-        out += [("res", ch[i + 1]) + tf + (rate,)] * cfg.n_res
-    out.append(("out", 1, 256, 0, rate))
-    return out
+    """What gsttaco_melgan_plan reports as (kind, channels, tile, form, rate) per launch: the N-tiles a wave item owns by padded
+    channel count, and the time tile that gives four waves an item each, halved while the launch's LDS does not fit
+    (vocoder_cases.melgan_plan_rule)."""
+    return [(s["kind"], s["channels"], s["tile"], s["form"], s["rate"]) for s in melgan_plan_rule(cfg)]
 
 
 # ---------------------------------------------------------------------------------------------------- the cases

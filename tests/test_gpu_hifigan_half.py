@@ -16,6 +16,7 @@ import pytest
 
 import hifigan_cases as M
 import hifigan_half_cases as H
+from vocoder_harness import Vocoder
 from gst_tacotron_amd import capi, hifigan, synthetic
 
 pytestmark = pytest.mark.gpu
@@ -31,52 +32,12 @@ BEYOND = 1e3                    # what every buffer holds beyond a row's length:
 _VOCODERS = {}
 
 
-class _Vocoder:
-    """A context that holds nothing but a HiFi-GAN; ``precision`` None makes no gsttaco_hifigan_set_operands call at all."""
+class _Vocoder(Vocoder):
+    """A context that holds nothing but a HiFi-GAN; ``precision`` None makes no gsttaco_hifigan_set_operands call at all.  The call,
+    ``raw`` and the one-launch-alone route (``stage`` / ``buffer``) are tests/vocoder_harness.py's."""
 
     def __init__(self, cfg, weights, max_batch, max_frames, precision=None, finalize=True):
-        self.cfg, self.max_batch, self.max_frames = cfg, max_batch, max_frames
-        self.ctx = capi.Context(synthetic.tiny_hp(), max_batch=2, max_tokens=8, max_ref_frames=4)
-        self.ctx.hifigan_configure(cfg, max_batch, max_frames)
-        if precision is not None:
-            self.ctx.hifigan_set_operands(precision)
-        self.ctx.hifigan_load_weights(weights)
-        if finalize:
-            self.ctx.hifigan_finalize()
-
-    @staticmethod
-    def _p(t):
-        return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-    @staticmethod
-    def _s(stream=None):
-        import torch
-        return ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
-
-    def raw(self, x, fr, B, T, wav, lens, ld, stream=None):
-        return self.ctx.lib.gsttaco_hifigan(self.ctx.handle, self._p(x), self._p(fr), B, T, self._p(wav), self._p(lens), ld, self._s(stream))
-
-    def stage(self, i, x, fr, B, T, wav, ld):
-        self.ctx.check(self.ctx.lib.gsttaco_hifigan_debug_stage(self.ctx.handle, i, self._p(x), self._p(fr), B, T, self._p(wav), ld, self._s()))
-
-    def buffer(self, k, tensor, write):
-        self.ctx.hifigan_debug_buffer(k, tensor, write, self._s())
-
-    def __call__(self, mel, frames=None, ld=None):
-        """(wav [B, ld], lengths [B]) as host arrays; the outputs start as NaN / -1, so what the call leaves unwritten shows"""
-        import torch
-        x = torch.as_tensor(np.ascontiguousarray(mel, dtype=np.float32)).cuda()
-        B, T = x.shape[:2]
-        fr = None if frames is None else torch.as_tensor(np.asarray(frames, dtype=np.int32)).cuda()
-        ld = T * self.cfg.hop if ld is None else ld
-        wav = torch.full((B, ld), float("nan"), dtype=torch.float32, device="cuda")
-        lens = torch.full((B,), -1, dtype=torch.int32, device="cuda")
-        self.ctx.check(self.raw(x, fr, B, T, wav, lens, ld))
-        torch.cuda.synchronize()
-        return wav.cpu().numpy(), lens.cpu().numpy()
-
-    def close(self):
-        self.ctx.close()
+        super().__init__("hifigan", cfg, weights, max_batch, max_frames, finalize, operands=precision)
 
 
 @pytest.fixture(scope="module", autouse=True)

@@ -1,6 +1,7 @@
-"""The context wrapper the three vocoders' GPU tests share (tests/test_gpu_melgan.py, test_gpu_hifigan.py, test_gpu_waveglow.py;
-tools/vocoder_bits.py runs the case tables through it too): a context that holds nothing but one finalized vocoder, called with host
-arrays, its outputs prefilled with NaN / -1 so that what a call leaves unwritten shows."""
+"""The context wrapper the three vocoders' GPU tests share (tests/test_gpu_melgan.py, test_gpu_hifigan.py, test_gpu_waveglow.py,
+test_gpu_hifigan_half.py, test_gpu_vocoder_surface.py; tools/vocoder_bits.py runs the case tables through it too): a context that
+holds nothing but one finalized vocoder, called with host arrays, its outputs prefilled with NaN / -1 so that what a call leaves
+unwritten shows; and HiFi-GAN's one-launch-alone route (``stage`` / ``buffer``)."""
 import ctypes
 
 import numpy as np
@@ -23,7 +24,7 @@ class Vocoder:
     (x, fr, B, T, wav, lens, ld), and for waveglow (x, fr, B, T, sigma, seeds, z, wav, lens, ld); it returns the code."""
 
     def __init__(self, prefix, cfg, weights, max_batch, max_frames, finalize=True, operands=None):
-        self.prefix, self.cfg = prefix, cfg
+        self.prefix, self.cfg, self.max_batch, self.max_frames = prefix, cfg, max_batch, max_frames
         self.ctx = capi.Context(synthetic.tiny_hp(), max_batch=2, max_tokens=8, max_ref_frames=4)
         getattr(self.ctx, prefix + "_configure")(cfg, max_batch, max_frames)
         if operands is not None:            # hifigan: the operand form, chosen between configure and finalize
@@ -44,6 +45,17 @@ class Vocoder:
             return self.ctx.lib.gsttaco_waveglow(self.ctx.handle, _p(x), _p(fr), B, T, ctypes.c_float(sigma), _p(seeds), _p(z), _p(wav), _p(lens), ld, s)
         wav, lens, ld = rest
         return getattr(self.ctx.lib, "gsttaco_" + self.prefix)(self.ctx.handle, _p(x), _p(fr), B, T, _p(wav), _p(lens), ld, s)
+
+    def stage(self, i, x, fr, B, T, wav, ld):
+        """hifigan: launch i of the plan alone (gsttaco_hifigan_debug_stage) on the workspace as it stands"""
+        import torch
+        s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        self.ctx.check(self.ctx.lib.gsttaco_hifigan_debug_stage(self.ctx.handle, i, _p(x), _p(fr), B, T, _p(wav), ld, s))
+
+    def buffer(self, k, tensor, write):
+        """hifigan: the float32 device ``tensor`` into (``write``) or out of workspace buffer k (gsttaco_hifigan_debug_buffer)"""
+        import torch
+        self.ctx.hifigan_debug_buffer(k, tensor, write, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
 
     def noise(self, seeds, T):
         """waveglow: z [len(seeds), T * hop] as gsttaco_waveglow_noise draws it"""
